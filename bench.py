@@ -13,6 +13,12 @@ step.  Rank 0 prints ONE JSON line.
 `python -m torch.distributed.run --nproc-per-node N`, rendezvous on 127.0.0.1); launched by torchrun
 (WORLD_SIZE set) it is one of the ranks.  With the nccl backend it refuses to run with fewer visible
 GPUs than ranks.  The line carries `dist` = what the process group itself reports (backend, world size).
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the line (with the
+roofline priced from the committed PMC profiles).  `--full` adds everything else, each leg still skippable
+with its --no-* option: roofline.dominant (a per-op pass), small_batch, side_kernels, variants,
+streaming_cfg5 and cpu_baseline.  `--dump-outputs DIR` writes what the last timed step handed its caller,
+one float32 DIR/<name>.npy per output tensor (inputs and weights are seeded: two builds compare 1:1).
 """
 from __future__ import annotations
 
@@ -555,6 +561,27 @@ def summary_of(line) -> dict:
     return {k: v for k, v in s.items() if v is not None}
 
 
+DUMP_LIMIT_BYTES = 60_000_000     # under 64 MB with the .npy headers and crop_index.npy
+
+
+def dump_outputs(path, arrays) -> None:
+    """--dump-outputs: every output tensor of the last timed step (rank 0's engine outputs) as float32 <path>/<name>.npy.  All of
+    them are per crop (dim 0); above DUMP_LIMIT_BYTES the same fixed, seeded sample of crops is kept from each of them, and its
+    indices are written to crop_index.npy."""
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = len(next(iter(arrays.values())))
+        keep = max(1, int(n * DUMP_LIMIT_BYTES / total))
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["crop_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(path / f"{k}.npy", np.ascontiguousarray(a))
+
+
 def spawn_ranks(args) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks of this same script, one per GPU."""
     import socket
@@ -600,6 +627,11 @@ def main():
     ap.add_argument("--check-gather", action="store_true",
                     help="N>1: after the timed region rank 0 recomputes every rank's batch and checks the gathered rows "
                          "bitwise against them (and every rank checks its own rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline also run roofline.dominant, small_batch, side_kernels, variants, streaming_cfg5 and "
+                         "cpu_baseline (the --no-* options above skip single legs of a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as float32 DIR/<name>.npy (at most 64 MB)")
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":
         return cpu_worker(sys.argv[2:])
     args = ap.parse_args()
@@ -683,6 +715,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     model.check_status()       # poco_status: a timed-out in-kernel wait in any of the timed forwards would void the number (raises)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     step_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)]
     ev_ms = float(np.mean(step_ms))
     ev_med = float(np.median(step_ms))
@@ -704,7 +738,8 @@ def main():
     if rank == 0:
         value = world * B * args.steps / elapsed
         roof, ex = roofline_block(args.variant, B, flops_per_crop, ev_ms)
-        if world == 1 and not args.no_dominant:
+        full = world == 1 and args.full
+        if full and not args.no_dominant:
             roof["dominant"] = dominant_kernel(model, batch, B, args.lanes, ex)
         line = {
             "metric": "person-crops/sec (224x224) POCO-CLIFF bs=64" if args.variant.endswith("cliff")
@@ -733,16 +768,16 @@ def main():
         if gather_check is not None:
             line["dist"]["gather_check"] = ("ok: all gathered rows bitwise equal to the per-rank forwards" if gather_check
                                             else "FAILED")
-        if world == 1 and not args.no_side:
+        if full and not args.no_side:
             line["small_batch"] = small_batch_leg(model, args.variant, device)
             line["side_kernels"] = side_kernels(device)
-        if world == 1 and not args.no_variants and args.variant == "hrnet_w48_cls-cliff" and B == 64:
+        if full and not args.no_variants and args.variant == "hrnet_w48_cls-cliff" and B == 64:
             # BASELINE configs #3 (ResNet-50 wording) and #2 in the same driver line
             line["variants"] = {"resnet50-cliff_b64": variant_leg("resnet50-cliff", 64, device),
                                 "hrnet_w32-pare_b32": variant_leg("hrnet_w32-pare", 32, device)}
-        if world == 1 and not args.no_stream:
+        if full and not args.no_stream:
             line["streaming_cfg5"] = streaming_leg(args.variant, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.variant, B)
             if "streaming_cfg5" in line:
                 try:

@@ -152,7 +152,7 @@ def test_demo_video_two_ranks_matches_one_process(tmp_path, cuda):
 def test_bench_line_contract(cuda):
     """The ONE JSON line bench.py prints: every field of the driver contract, roofline with a fresh (or explicitly stale) traffic
     source, per-step event statistics, and the CPU baseline + streaming legs on request only."""
-    r = _run(["bench.py", "--steps", "5", "--warmup", "2", "--variant", "resnet50-cliff", "--no-stream", "--no-cpu-baseline"])
+    r = _run(["bench.py", "--full", "--steps", "5", "--warmup", "2", "--variant", "resnet50-cliff", "--no-stream", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -169,3 +169,24 @@ def test_bench_line_contract(cuda):
     ev = d["step_ms_events"]
     assert ev["min"] <= ev["median"] <= ev["max"] and abs(ev["mean"] - d["ms_per_step"]) / ev["mean"] < 0.05
     assert "cpu_baseline" not in d and "streaming_cfg5" not in d
+    assert "dominant" in rf and "small_batch" in d and "side_kernels" in d          # the --full legs that were not switched off
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_outputs(tmp_path, cuda):
+    """A plain run times exactly --steps steps and carries none of the --full legs; --dump-outputs writes what the last timed step
+    computed, equal to a forward of the same seeded engine on the same seeded batch."""
+    import bench
+    r = _run(["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--variant", "resnet50-cliff", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _json_line(r.stdout)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and len(d["summary"]) > 0
+    assert not {"small_batch", "side_kernels", "variants", "streaming_cfg5", "cpu_baseline"} & set(d) and "dominant" not in d["roofline"]
+    m = bench.build_model("resnet50-cliff", 64, cuda)
+    ref = m(util.cuda_batch(synth.synth_batch(64, 1234), cuda), want_segm=False)
+    names = {k for k, v in ref.items() if isinstance(v, torch.Tensor)}
+    assert {p.stem for p in tmp_path.glob("*.npy")} == names
+    for k in names:
+        a = np.load(tmp_path / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == tuple(ref[k].shape), k
+        b = ref[k].cpu().numpy()
+        assert np.abs(a - b).max() <= 1e-5 * max(1.0, float(np.abs(b).max())), k

@@ -11,10 +11,10 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # ONLY=<short tag> (w48cliff | resnet50cliff | w32pare): re-take the kernel stats / PMC passes of one variant, keep the rest
 [ -n "$ONLY" ] || {
-python $R/bench.py 2>$OUT/bench_w48.err | tail -1 > $OUT/${TAG}_bench_hrnet_w48_cls-cliff.json
-python $R/bench.py --variant resnet50-cliff --batch 64 --no-stream --no-side 2>/dev/null | tail -1 > $OUT/${TAG}_bench_resnet50-cliff.json
-python $R/bench.py --variant hrnet_w32-pare --batch 32 --no-stream --no-side 2>/dev/null | tail -1 > $OUT/${TAG}_bench_hrnet_w32-pare.json
-python $R/bench.py --no-graph --no-cpu-baseline --no-stream --no-side --no-variants 2>/dev/null | tail -1 > $OUT/${TAG}_bench_hrnet_w48_cls-cliff_nograph.json
+python $R/bench.py --full 2>$OUT/bench_w48.err | tail -1 > $OUT/${TAG}_bench_hrnet_w48_cls-cliff.json
+python $R/bench.py --full --variant resnet50-cliff --batch 64 --no-stream --no-side 2>/dev/null | tail -1 > $OUT/${TAG}_bench_resnet50-cliff.json
+python $R/bench.py --full --variant hrnet_w32-pare --batch 32 --no-stream --no-side 2>/dev/null | tail -1 > $OUT/${TAG}_bench_hrnet_w32-pare.json
+python $R/bench.py --full --no-graph --no-cpu-baseline --no-stream --no-side --no-variants 2>/dev/null | tail -1 > $OUT/${TAG}_bench_hrnet_w48_cls-cliff_nograph.json
 }
 prof_variant() {   # variant batch short-tag
   V=$1; B=$2; T=$3
