@@ -4,10 +4,11 @@
                    --mode folder --image_folder <dir> --output_folder out --smpl data/smpl/SMPL_NEUTRAL.npz
 
 Same flags as the reference where they concern the regressor (--cfg --ckpt --mode --image_folder
---vid_file --output_folder --batch_size --no_render --no_kinematic_uncert --inf_model).  Detector /
-tracker / renderer are third-party and out of scope: person boxes come from
+--vid_file --output_folder --batch_size --no_render --no_kinematic_uncert --inf_model --sideview --no_uncert_color).  Detector /
+tracker are third-party and out of scope: person boxes come from
 --detections (json {image name: [[cx,cy,w,h],...]}, the format multi_person_tracker produces) or
-default to one centred box; results are written as .npz next to what the reference would render.
+default to one centred box; results are written as .npz.  --render (opt-in; the reference renders by default) draws the
+uncertainty-coloured meshes on the GPU (poco_amd/render.py) into the PNGs the reference writes.
 --mode video expects --vid_file to be a folder of extracted frames (the reference shells out to
 ffmpeg first, demo.py:71; ffmpeg/cv2 are not part of this image).
 """
@@ -29,7 +30,12 @@ def parse_args(argv=None):
     p.add_argument("--batch_size", type=int, default=64, help="batch size of POCO")
     p.add_argument("--tracker_batch_size", type=int, default=12)
     p.add_argument("--detector", type=str, default="yolo")
-    p.add_argument("--no_render", action="store_true", help="(rendering is out of scope; always off)")
+    p.add_argument("--no_render", action="store_true", help="disable rendering (wins over --render)")
+    p.add_argument("--render", action="store_true",
+                   help="draw the uncertainty-coloured meshes over the input (GPU): folder mode <out>/poco_results/<image>.png, "
+                        "video mode <out>/tmp_images_output/%%06d.png + uncertainty.log; needs `faces` in the --smpl file")
+    p.add_argument("--sideview", action="store_true", help="with --render: add the Ry(270) view to the right of each picture")
+    p.add_argument("--no_uncert_color", action="store_true", help="with --render: plain grey meshes instead of the uncertainty colour")
     p.add_argument("--no_kinematic_uncert", action="store_false",
                    help="Do not use SMPL Kinematic for uncert (same store_false semantics as the reference)")
     p.add_argument("--smooth", action="store_true", help="one-euro smoothing of each track (video mode)")
@@ -52,6 +58,22 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
+def render_enabled(args) -> bool:
+    """--render is opt-in; --no_render keeps its meaning and wins."""
+    return bool(getattr(args, "render", False)) and not getattr(args, "no_render", False)
+
+
+def _check_render_assets(args) -> None:
+    """--render draws the body model's triangles: refuse a --smpl file without `faces` before any GPU work."""
+    import numpy as np
+    if not (isinstance(args.smpl, str) and os.path.isfile(args.smpl)):
+        sys.exit(f"--render: body-model file not found: {args.smpl}")
+    with np.load(args.smpl) as z:
+        if "faces" not in z.files:
+            sys.exit(f"--render: {args.smpl} has no `faces` array (convert the SMPL .pkl with tools/convert_smpl.py, which "
+                     "keeps its triangles)")
+
+
 def _spawn_ranks(args) -> int:
     """`demo.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU."""
     import socket
@@ -70,6 +92,8 @@ def _spawn_ranks(args) -> int:
 def main(args):
     if args.mode in ("webcam",):
         sys.exit("webcam mode needs a capture device + renderer: out of scope")
+    if render_enabled(args):
+        _check_render_assets(args)
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")

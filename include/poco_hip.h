@@ -246,6 +246,42 @@ int poco_crop_normalize_f64(const unsigned char* d_frame, int H, int W, const do
 int poco_crop_normalize_multi(const unsigned char* const* d_frames, int nframes, const int* d_frame_idx, int H, int W,
                               const float* d_boxes, int N, double bbox_scale, int res, float* d_out, void* stream);
 
+/* ---- demo renderer: the uncertainty-coloured SMPL overlay of demo.py --render ----------------------------------------------
+ * Replaces pyrender's offscreen render (pocolib/utils/vibe_renderer.py:33-57,88-151) as pocolib/core/tester.py:248-345 (folder
+ * mode) and :482-580 (video mode) call it; csrc/render.hip.  Draws P posed meshes over an RGB uint8 frame in place.
+ *   Geometry (vibe_renderer.py:33-57,88-151): vertex v of person p becomes q = R * Rx(180 deg) * v, R = h_rot3x3 (row-major) or
+ *     the identity (the side view passes Ry(270 deg), tester.py:335-348).  The weak-perspective camera (sx, sy, tx, ty) = orig_cam
+ *     projects through the matrix of vibe_renderer.py:49-56: col = W/2 (1 + sx (q_x + tx)), row = H/2 (1 - sy (q_y - ty)), rows
+ *     from the top; no perspective divide, so screen-space barycentrics are exact.  Pixel (r, c) is one sample at its centre
+ *     (c + 0.5, r + 0.5).  Fragments with |q_z| > 1 are discarded (GL clipping, NDC z = -q_z).  Inside one person the larger q_z
+ *     (nearer) wins, ties go to the lower triangle index.  Fill rule: a centre on an edge belongs to the triangle it would lie in
+ *     after a nudge by (+eps, +eps^2) - an edge shared by two triangles owns each of its centres exactly once.
+ *   People: each has its own camera, so there is no common depth (the reference renders them one pass each and pastes): painter's
+ *     order, person p + 1 covers person p wherever both cover a pixel.  The caller orders them (folder mode: detection order,
+ *     tester.py:276; video mode: ascending orig_cam[1], stable, demo_utils.py:307-313).
+ *   Shading: pyrender's metallic-roughness shader for this scene (vibe_renderer.py:74-86: ambient 0.3, three directional lights
+ *     of intensity 1 along -z, so l = v = h = +z).  c = clamp(n'_z, 0, 1), n' = the renormalised interpolated vertex normal after
+ *     R * Rx; vertex normals = area-weighted sums of the incident faces' normals (gathered, not atomically summed).  material 0
+ *     (pyrender's default for a vertex-coloured trimesh): metallic m = 0.2, roughness rho = 0.8; material != 0 (the plain grey of
+ *     tester.py:288-290): m = 0, rho = 1.  alpha = rho^2, f0 = F = 0.04 (1 - m) + b m, c_diff = 0.96 b (1 - m),
+ *     D = alpha^2 / (pi (c^2 (alpha^2 - 1) + 1)^2), G = (2c / (c + sqrt(alpha^2 + (1 - alpha^2) c^2)))^2,
+ *     colour = 3 c ((1 - F) c_diff / pi + F G D / (4 c^2 + 0.001)) + 0.3 b, written as round(255 clamp(colour^(1/2.2), 0, 1)).
+ *   Composite (valid_mask, vibe_renderer.py:139-141): pixels no person covers keep their bytes exactly.
+ * Limits: P <= 1024, F < 2^22 (the 64-bit visibility key (P - 1 - p) << 54 | bits(1 - q_z) << 22 | triangle), V <= 2^24,
+ * H, W <= 16384.  Fidelity to pyrender's pixels is unpinned (single sample, area-weighted normals, view vector +z). */
+typedef struct poco_renderer* poco_renderer_t;
+/* h_faces int32 [F,3] (host) of meshes with V vertices: validated (indices in [0, V)), a vertex -> face CSR is built, both are
+ * uploaded.  Needs the GPU after validation; the handle owns a visibility buffer that grows with the largest frame rendered. */
+int poco_renderer_create(const int32_t* h_faces, int F, int V, poco_renderer_t* out);
+/* Draw P people over d_frame uint8 [H,W,3] RGB (in place).  d_verts fp32 [P,V,3] (the engine's smpl_vertices as they are),
+ * d_params fp32 [P,8] per person (sx, sy, tx, ty, r, g, b, material), r g b = base colour in [0,1].  h_rot3x3: NULL = identity.
+ * d_frag_count: NULL, or int32 [H,W] that receives the number of fragments per pixel that pass coverage and clipping (a test hook
+ * for the fill rule).  Enqueued on `stream` (a memset + three launches): no allocation unless the frame or P*V is larger than
+ * any before, no synchronisation. */
+int poco_renderer_render(poco_renderer_t r, unsigned char* d_frame, int H, int W, const float* d_verts, int P,
+                         const float* d_params, const float* h_rot3x3, int* d_frag_count, void* stream);
+void poco_renderer_destroy(poco_renderer_t r);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

@@ -177,3 +177,17 @@ void launch_crop_normalize_multi(const unsigned char* const* frames, int nframes
 // poco_outputs_t.record: [rotmat 216 | betas 10 | cam 3 | var 24 | post-processed confidence 1] per crop (254 floats)
 void launch_pack_record(const float* rot, int rot_stride, const float* betas, int betas_stride, const float* cam, int cam_stride,
                         const float* var, int var_stride, float* rec, int cliff, int kinematic, float thr, int B, hipStream_t s);
+
+// ---- demo renderer (render.hip) --------------------------------------------------------------------------
+// Per person: RENDER_PARAMS floats (sx, sy, tx, ty, r, g, b, material) = include/poco_hip.h poco_renderer_render's d_params.
+constexpr int RENDER_PARAMS = 8;
+// q = m * v (row-major 3x3): the caller's rotation times Rx(180 deg), applied to vertices and normals.
+struct RenderXform {
+  float m[9];
+};
+// verts [P,V,3]; faces [F,3]; csr_off [V+1] / csr_face: the faces incident to each vertex, ascending; pos / nrm [P*V] scratch;
+// vis [H*W] must hold all ones (no fragment) on entry; count [H*W] (nullable): +1 per fragment that passes coverage and clipping;
+// frame uint8 [H,W,3], overwritten where a person covers a pixel centre.
+void launch_render(const float* verts, int P, int V, const int* faces, int F, const int* csr_off, const int* csr_face,
+                   const RenderXform& xf, const float* params, int H, int W, float4* pos, float4* nrm, unsigned long long* vis,
+                   int* count, unsigned char* frame, hipStream_t s);

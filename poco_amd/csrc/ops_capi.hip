@@ -357,3 +357,108 @@ extern "C" int poco_op_rot6d(const float* d_in, float* d_rotmat, int B, void* st
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- demo renderer (csrc/render.hip) ------------------------------------------------------------------------------------
+struct poco_renderer {
+  int F = 0, V = 0;
+  int* faces = nullptr;                    // [F,3]
+  int* csr_off = nullptr;                  // [V+1]
+  int* csr_face = nullptr;                 // [3F]
+  unsigned long long* vis = nullptr;       // [vis_cap] visibility keys, grown on demand
+  size_t vis_cap = 0;
+  float4* scratch = nullptr;               // [2 * scratch_cap]: screen position / depth, then unit normals, per (person, vertex)
+  size_t scratch_cap = 0;
+  ~poco_renderer() {
+    for (void* p : {(void*)faces, (void*)csr_off, (void*)csr_face, (void*)vis, (void*)scratch})
+      if (p) (void)hipFree(p);
+  }
+};
+
+static constexpr int RENDER_MAX_PEOPLE = 1024;          // 10 bits of the visibility key
+static constexpr int RENDER_MAX_FACES = (1 << 22) - 1;  // 22 bits of the visibility key
+static constexpr int RENDER_MAX_VERTS = 1 << 24;
+static constexpr int RENDER_MAX_SIDE = 16384;
+
+extern "C" int poco_renderer_create(const int32_t* h_faces, int F, int V, poco_renderer_t* out) {
+  if (!out) { poco_set_error("poco_renderer_create: null handle pointer"); return POCO_ERR_ARG; }
+  *out = nullptr;
+  if (!h_faces || F < 1 || F > RENDER_MAX_FACES || V < 1 || V > RENDER_MAX_VERTS) {
+    poco_set_error("poco_renderer_create: bad arguments (need faces, 1 <= F < 2^22, 1 <= V <= 2^24)");
+    return POCO_ERR_ARG;
+  }
+  std::vector<int> off(V + 1, 0);
+  for (size_t k = 0; k < (size_t)F * 3; ++k) {
+    const int v = h_faces[k];
+    if (v < 0 || v >= V) {
+      poco_set_error("poco_renderer_create: face " + std::to_string(k / 3) + " has vertex index " + std::to_string(v) +
+                     " outside [0, " + std::to_string(V) + ")");
+      return POCO_ERR_ARG;
+    }
+    ++off[v + 1];
+  }
+  for (int v = 0; v < V; ++v) off[v + 1] += off[v];
+  std::vector<int> fill(off.begin(), off.end() - 1), inc((size_t)F * 3);
+  for (int f = 0; f < F; ++f)                     // ascending face index per vertex: the normal sum has a fixed order
+    for (int j = 0; j < 3; ++j) inc[fill[h_faces[3 * f + j]]++] = f;
+  auto* r = new poco_renderer;
+  r->F = F;
+  r->V = V;
+  auto up = [](int** d, const int* h, size_t n) -> hipError_t {
+    hipError_t e = hipMalloc(d, n * sizeof(int));
+    return e != hipSuccess ? e : hipMemcpy(*d, h, n * sizeof(int), hipMemcpyHostToDevice);
+  };
+  hipError_t e = up(&r->faces, h_faces, (size_t)F * 3);
+  if (e == hipSuccess) e = up(&r->csr_off, off.data(), off.size());
+  if (e == hipSuccess) e = up(&r->csr_face, inc.data(), inc.size());
+  if (e != hipSuccess) {
+    delete r;
+    poco_set_error(std::string("poco_renderer_create: ") + hipGetErrorString(e));
+    return POCO_ERR_HIP;
+  }
+  *out = r;
+  return POCO_OK;
+}
+
+extern "C" int poco_renderer_render(poco_renderer_t r, unsigned char* d_frame, int H, int W, const float* d_verts, int P,
+                                    const float* d_params, const float* h_rot3x3, int* d_frag_count, void* stream) {
+  if (!r || !d_frame || H < 1 || W < 1 || H > RENDER_MAX_SIDE || W > RENDER_MAX_SIDE || P < 0 || P > RENDER_MAX_PEOPLE ||
+      (P > 0 && (!d_verts || !d_params))) {
+    poco_set_error("poco_renderer_render: bad arguments (need a handle, a frame of 1..16384 x 1..16384, 0 <= P <= 1024 and, "
+                   "for P > 0, vertices and parameters)");
+    return POCO_ERR_ARG;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t npix = (size_t)H * W;
+  if (d_frag_count) POCO_HIP_CHECK(hipMemsetAsync(d_frag_count, 0, npix * sizeof(int), s));
+  if (P == 0) return POCO_OK;
+  const size_t nvert = (size_t)P * r->V;
+  // growth frees the old buffer: hipFree waits for the device, so a render still in flight on another stream finishes first
+  if (npix > r->vis_cap) {
+    if (r->vis) (void)hipFree(r->vis);
+    r->vis = nullptr;
+    r->vis_cap = 0;
+    POCO_HIP_CHECK(hipMalloc(&r->vis, npix * sizeof(unsigned long long)));
+    r->vis_cap = npix;
+  }
+  if (nvert > r->scratch_cap) {
+    if (r->scratch) (void)hipFree(r->scratch);
+    r->scratch = nullptr;
+    r->scratch_cap = 0;
+    POCO_HIP_CHECK(hipMalloc(&r->scratch, 2 * nvert * sizeof(float4)));
+    r->scratch_cap = nvert;
+  }
+  // q = R * Rx(180 deg) * v: Rx(180 deg) = diag(1, -1, -1) negates the 2nd and 3rd columns of R (exactly)
+  RenderXform xf;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const float rij = h_rot3x3 ? h_rot3x3[3 * i + j] : (i == j ? 1.f : 0.f);
+      xf.m[3 * i + j] = j == 0 ? rij : -rij;
+    }
+  POCO_HIP_CHECK(hipMemsetAsync(r->vis, 0xFF, npix * sizeof(unsigned long long), s));
+  launch_render(d_verts, P, r->V, r->faces, r->F, r->csr_off, r->csr_face, xf, d_params, H, W, r->scratch, r->scratch + nvert,
+                r->vis, d_frag_count, d_frame, s);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" void poco_renderer_destroy(poco_renderer_t r) { delete r; }

@@ -1,7 +1,8 @@
 """POCOTester for the MI355X engine: batch assembly + post-processing of
 pocolib/core/tester.py:153-245 (folder mode) and :362-479 (per-track video mode), without the
-third-party detector / tracker / renderer (out of scope: SURVEY.md 2 rows 2,27).  Detections are an
-input: {image name: [[cx, cy, w, h], ...]} (what multi_person_tracker hands to the reference).
+third-party detector / tracker (out of scope: SURVEY.md 2 rows 2,27).  Detections are an
+input: {image name: [[cx, cy, w, h], ...]} (what multi_person_tracker hands to the reference).  With --render the
+uncertainty-coloured meshes are drawn on the GPU (poco_amd/render.py; tester.py:248-345 and :482-580).
 
 Per image the crops are produced on the GPU (poco_crop_normalize) from the decoded frame, so the
 reference's per-detection cv2.warpAffine + per-crop H2D copy (tester.py:182-203) disappears."""
@@ -74,11 +75,31 @@ class POCOTester:
         self.model = POCO(**kw, pretrained=args.ckpt, inf_model=getattr(args, "inf_model", "best"),
                           max_batch=max(int(args.batch_size), 1), smpl=args.smpl, device=str(self.device),
                           keep_state_dict=False).finalize()     # (state_dict() re-reads the checkpoint file on demand)
-        self.faces = None                       # triangle list for --save_obj, if the body-model file carries one
+        self.faces = None                       # triangle list for --save_obj / --render, if the body-model file carries one
         if isinstance(args.smpl, str) and os.path.isfile(args.smpl):
             with np.load(args.smpl) as z:
                 if "faces" in z.files:
                     self.faces = np.asarray(z["faces"], np.int64)
+        self._renderer = None
+
+    # ---- --render ---------------------------------------------------------------------------------------------------
+    @property
+    def render_on(self) -> bool:
+        """--render is opt-in; --no_render wins (demo.py render_enabled)."""
+        return bool(getattr(self.args, "render", False)) and not getattr(self.args, "no_render", False)
+
+    def render_frame(self, frame: torch.Tensor, verts, orig_cam, var, side_bg: int) -> torch.Tensor:
+        """The picture of one frame: people (in painter's order) drawn over the device frame `frame` (in place), with
+        --sideview the Ry(270) view on a canvas of value side_bg to its right; --no_uncert_color = plain grey."""
+        from . import render
+        if self.faces is None:
+            raise RuntimeError(f"--render: {self.args.smpl} has no `faces` array")
+        V = int(np.asarray(verts).shape[-2])
+        if self._renderer is None or self._renderer.V != V:
+            self._renderer = render.Renderer(self.faces, V, self.device)
+        return render.render_people(self._renderer, frame, verts, orig_cam, var, self.backbone,
+                                    uncert_color=not getattr(self.args, "no_uncert_color", False),
+                                    sideview=bool(getattr(self.args, "sideview", False)), side_bg=side_bg)
 
     def _save_meshes(self, folder: str, verts: np.ndarray, names):
         from .postproc import write_obj
@@ -116,12 +137,14 @@ class POCOTester:
         return res
 
     @torch.no_grad()
-    def iter_frame_results(self, items, bbox_scale: float = 1.0):
+    def iter_frame_results(self, items, bbox_scale: float = 1.0, keep_frames: bool = False):
         """items: iterable of (frame uint8 [H,W,3] RGB, detections [n,4]); yields one result dict (or None for a frame without
         detections) per item, in order.  The reference runs one forward per image (pocolib/core/tester.py:168-213); crops are
         independent of each other, so here the crops of CONSECUTIVE frames share forwards of up to `batch_size` crops (a photo
         folder with one person per image would otherwise sit in the launch-bound B = 1 regime) and the
-        rows are handed back per frame.  At most `batch_size` crops and their frames are held at a time."""
+        rows are handed back per frame.  At most `batch_size` crops and their frames are held at a time.
+        keep_frames (--render): yields (result, the frame's device copy or None) pairs instead, so the picture is drawn on the
+        frame the crops were cut from."""
         from collections import deque
         bs = self.model.max_batch
         queue = deque()                    # frames in arrival order: {"dets", "W", "H", "parts", "todo"}
@@ -151,15 +174,18 @@ class POCOTester:
         def drain():
             while queue and queue[0]["todo"] == 0:
                 e = queue.popleft()
-                yield None if not e["parts"] else {k: np.concatenate([p[k] for p in e["parts"]], 0) for k in e["parts"][0]}
+                res = None if not e["parts"] else {k: np.concatenate([p[k] for p in e["parts"]], 0) for k in e["parts"][0]}
+                yield (res, e["frame"]) if keep_frames else res
 
         for frame, dets in items:
             raw = np.asarray(dets)
             raw = raw.reshape(-1, 4) if raw.size else np.zeros((0, 4), np.float32)
-            e = {"dets": raw, "W": frame.shape[1], "H": frame.shape[0], "parts": [], "todo": len(raw)}
+            e = {"dets": raw, "W": frame.shape[1], "H": frame.shape[0], "parts": [], "todo": len(raw), "frame": None}
             queue.append(e)
             if len(raw):
                 fr = torch.from_numpy(np.ascontiguousarray(frame)).to(self.device)
+                if keep_frames:
+                    e["frame"] = fr
                 lo = 0
                 while lo < len(raw):
                     k = min(bs - npend, len(raw) - lo)
@@ -300,6 +326,11 @@ class POCOTester:
             s = float(min(H, W))
             return np.array([[W / 2.0, H / 2.0, s, s]], dtype=np.float32)
 
+        render_on = self.render_on
+        img_dir = os.path.join(output_path, "poco_results")          # reference demo.py:95
+        if render_on:
+            os.makedirs(img_dir, exist_ok=True)
+
         def write(n, r):
             np.savez_compressed(os.path.join(output_path, os.path.splitext(n)[0] + "_poco.npz"), **r)
             if getattr(self.args, "save_obj", False):          # tester.py:300-303
@@ -335,10 +366,15 @@ class POCOTester:
                     yield img, d
 
             writes = deque()
-            for (pos, n), r in zip(picked, self.iter_frame_results(items(), bbox_scale)):
+            for (pos, n), r in zip(picked, self.iter_frame_results(items(), bbox_scale, keep_frames=render_on)):
                 n_img += 1
+                if render_on:
+                    r, fr = r
                 if r is not None:
                     writes.append(wr_pool.submit(write, n, r))
+                    if render_on:                                 # tester.py:248-345: detection order, white side canvas
+                        pic = self.render_frame(fr, r["verts"], r["orig_cam"], r["var"], side_bg=255).cpu().numpy()
+                        writes.append(wr_pool.submit(_write_png, os.path.join(img_dir, os.path.splitext(n)[0] + ".png"), pic))
                 while len(writes) > ahead:
                     writes.popleft().result()
             for w in writes:
@@ -397,6 +433,8 @@ def _run_on_video_folder(self, frame_folder: str, tracking_path: Optional[str], 
             for pid, r in results.items():
                 sub = f"{int(pid):04d}" if str(pid).lstrip("-").isdigit() else str(pid)
                 self._save_meshes(os.path.join(output_path, "meshes", sub), r["verts"], [f"{int(f):06d}" for f in r["frame_ids"]])
+        if self.render_on:                                             # demo.py:147-150 -> tester.py:482-580, rank 0 only
+            self._render_video(results, frame_folder, names, load, output_path)
     finally:
         if world > 1:               # the other ranks wait here: release them also when the write fails
             tdist.barrier()
@@ -448,7 +486,55 @@ def _merge_rank_results(self, local_raw: dict, tracking: dict, W: int, H: int) -
     return {pid: out[pid] for pid in tracking}
 
 
+def _write_png(path: str, img: np.ndarray) -> None:
+    from PIL import Image
+    Image.fromarray(img).save(path)
+
+
+def _render_video(self, results: dict, frame_folder: str, names, load, output_path: str) -> None:
+    """render_results of tester.py:482-580: every frame of the folder with the people the tracks place in it, in ascending
+    orig_cam[1] (demo_utils.py:307-313, ties in track order), black side canvas, <output>/tmp_images_output/%06d.png, and the
+    lines of <output>/uncertainty.log (tester.py:547-550)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .render import video_order
+    out_dir = os.path.join(output_path, "tmp_images_output")
+    os.makedirs(out_dir, exist_ok=True)
+    per_frame = [[] for _ in names]
+    for pid, r in results.items():
+        for k, f in enumerate(r["frame_ids"]):
+            if 0 <= int(f) < len(names):
+                per_frame[int(f)].append((pid, k))
+    sideview = bool(getattr(self.args, "sideview", False))
+    log_lines = []
+    with ThreadPoolExecutor(max(1, min(8, (os.cpu_count() or 2) // 2))) as pool:
+        writes = []
+        for fi, name in enumerate(names):
+            fr = torch.from_numpy(np.ascontiguousarray(load(fi))).to(self.device)
+            people = per_frame[fi]
+            if people:
+                cams = np.stack([results[pid]["orig_cam"][k] for pid, k in people])
+                people = [people[i] for i in video_order(cams)]
+                pic = self.render_frame(fr, np.stack([results[pid]["verts"][k] for pid, k in people]),
+                                        np.stack([results[pid]["orig_cam"][k] for pid, k in people]),
+                                        np.stack([results[pid]["var"][k] for pid, k in people]), side_bg=0)
+                for pid, k in people:
+                    g = float(np.clip(results[pid]["var_global"][k], 0, 0.99))
+                    who = f"{int(pid):02d}" if str(pid).lstrip("-").isdigit() else str(pid)
+                    log_lines.append(f"img_f:{os.path.join(frame_folder, name)} person:{who} var:{g:.3f}")
+            else:
+                pic = torch.cat([fr, torch.zeros_like(fr)], 1) if sideview else fr
+            writes.append(pool.submit(_write_png, os.path.join(out_dir, f"{fi:06d}.png"), pic.cpu().numpy()))
+            while len(writes) > 16:
+                writes.pop(0).result()
+        for w in writes:
+            w.result()
+    with open(os.path.join(output_path, "uncertainty.log"), "a") as f:
+        for ln in log_lines:
+            print(ln, file=f)
+
+
 POCOTester.run_on_video_folder = _run_on_video_folder
+POCOTester._render_video = _render_video
 POCOTester._merge_rank_results = _merge_rank_results
 
 

@@ -1,0 +1,121 @@
+"""Time the demo renderer (poco_renderer_render: memset + vertex, raster and shade launches) with HIP events at 1920 x 1080 for
+1, 4 and 16 SMPL-sized meshes (6890 vertices, 13776 faces, procedurally generated: a deformed torus grid), one JSON line per case.
+
+    python tools/bench_render.py [--iters 50] [--folder 32]
+--folder N: also the folder-mode wall time per image of demo.py on N synthetic 1080p images (one person each, resnet50-cliff
+synthetic checkpoint) without and with --render (PNG encoding on the host included)."""
+import argparse
+import json
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from poco_amd import render  # noqa: E402
+
+V_SMPL, F_SMPL = 6890, 13776
+
+
+def smpl_sized_mesh():
+    """A closed 65 x 106 torus grid (6890 vertices, 13780 triangles, 4 dropped -> 13776) squashed into a body-sized shape."""
+    n, m = 106, 65
+    u = np.linspace(0, 2 * np.pi, n, endpoint=False)
+    v = np.linspace(0, 2 * np.pi, m, endpoint=False)
+    U, Vv = np.meshgrid(u, v, indexing="ij")
+    x = (0.25 + 0.08 * np.cos(Vv)) * np.cos(U)
+    z = (0.25 + 0.08 * np.cos(Vv)) * np.sin(U) * 0.6
+    y = 0.08 * np.sin(Vv) + 0.9 * np.sin(U / 2) ** 2 - 0.45
+    verts = np.stack([x, y * 2.0, z], -1).reshape(-1, 3).astype(np.float32)
+    faces = []
+    for i in range(n):
+        for j in range(m):
+            a, b, c, d = i * m + j, ((i + 1) % n) * m + j, i * m + (j + 1) % m, ((i + 1) % n) * m + (j + 1) % m
+            faces += [(a, b, d), (a, d, c)]
+    faces = np.array(faces[:F_SMPL], np.int32)
+    assert verts.shape[0] == V_SMPL and faces.shape[0] == F_SMPL
+    return verts, faces
+
+
+def people(P, H, W, verts, seed=0):
+    """P copies spread over the frame (a grid of cells), each about 0.8 of its cell tall, slightly rotated per person."""
+    r = np.random.default_rng(seed)
+    g = int(np.ceil(np.sqrt(P)))
+    vs, cams = [], []
+    for p in range(P):
+        a = r.uniform(-0.5, 0.5)
+        R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]], np.float32)
+        vs.append(verts @ R.T)
+        s = 0.8 / g
+        cx, cy = (p % g + 0.5) / g * 2 - 1, (p // g + 0.5) / g * 2 - 1        # cell centre in NDC
+        cams.append([s * H / W, s, cx / (s * H / W), -cy / s])
+    return np.stack(vs), np.array(cams, np.float32)
+
+
+def bench(iters):
+    dev = torch.device("cuda:0")
+    H, W = 1080, 1920
+    verts, faces = smpl_sized_mesh()
+    R = render.Renderer(faces, V_SMPL, dev)
+    for P in (1, 4, 16):
+        vs, cams = people(P, H, W, verts)
+        cols = np.array([render.vertex_color(np.full(24, 0.3 + 0.04 * p, np.float32), "hrnet_w48_cls-cliff") for p in range(P)])
+        mats = np.zeros(P, np.float32)
+        dv = torch.from_numpy(vs).to(dev)
+        frame = torch.zeros(H, W, 3, dtype=torch.uint8, device=dev)
+        cnt = torch.zeros(H, W, dtype=torch.int32, device=dev)
+        R.render(frame, dv, cams, cols, mats, frag_count=cnt)
+        frags, covered = int(cnt.sum()), int((cnt > 0).sum())
+        for _ in range(5):
+            R.render(frame, dv, cams, cols, mats)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            R.render(frame, dv, cams, cols, mats)
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / iters
+        print(json.dumps({"bench": "render", "H": H, "W": W, "people": P, "verts": V_SMPL, "faces": F_SMPL, "fragments": frags,
+                          "covered_px": covered, "ms": round(ms, 4), "iters": iters}), flush=True)
+
+
+def folder(n):
+    import demo
+    from PIL import Image
+    from poco_amd import synth
+    from tests import util
+    tmp = Path(tempfile.mkdtemp(prefix="poco_render_"))
+    w = util.synth_weights("resnet50-cliff")
+    torch.save({"state_dict": {"model." + k: torch.from_numpy(v) for k, v in w.items()}}, tmp / "ckpt.pt")
+    smpl = synth.synth_smpl(7)
+    smpl["faces"] = smpl_sized_mesh()[1]
+    np.savez(tmp / "smpl.npz", **smpl)
+    imgs = tmp / "imgs"
+    imgs.mkdir()
+    r = np.random.default_rng(0)
+    for i in range(n):
+        Image.fromarray(r.integers(0, 256, (1080, 1920, 3), dtype=np.uint8)).save(imgs / f"im{i:05d}.png")
+    from poco_amd.tester import POCOTester
+    for extra in ([], ["--render"], ["--render", "--sideview"]):
+        a = demo.parse_args(["--cfg", "configs/demo_poco_cliff_resnet50.yaml", "--ckpt", str(tmp / "ckpt.pt"), "--mode", "folder",
+                             "--image_folder", str(imgs), "--output_folder", str(tmp / "out"), "--batch_size", "16",
+                             "--smpl", str(tmp / "smpl.npz"), *extra])
+        t = POCOTester(a)
+        t.run_on_image_folder(str(imgs), None, str(tmp / "out"))          # warm-up (allocator, file cache)
+        st = t.run_on_image_folder(str(imgs), None, str(tmp / "out"))
+        print(json.dumps({"bench": "folder_render", "images": n, "H": 1080, "W": 1920, "flags": " ".join(extra) or "(none)",
+                          "ms_per_image": round(1000 * st["seconds"] / n, 2)}), flush=True)
+        del t
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--folder", type=int, default=0)
+    args = ap.parse_args()
+    bench(args.iters)
+    if args.folder:
+        folder(args.folder)
