@@ -1,0 +1,73 @@
+"""eval.py - the reference's evaluation entry point (eval.py, pocolib/core/trainer.py:298-403) on the MI355X engine.
+
+    python eval.py --cfg configs/demo_poco_cliff.yaml --ckpt data/poco_cliff.pt --smpl data/smpl/SMPL_NEUTRAL.npz \\
+                   --j_regressor data/J_regressor_h36m.npy --dataset 3dpw_test.npz [--img_dir DIR]
+
+Prints MPJPE, PA-MPJPE, V2V, the uncertainty / pose-error correlation and N, and writes evaluation_results_<name>.npz (numeric
+arrays; the reference joblib-dumps a dict).  The metrics are computed on the GPU (poco_amd/evaluate.py, csrc/eval_metrics.hip):
+per crop nothing is copied to the host between the forward and the final reduction.  Not computed: Var-MPJPE / Variance (they
+need the training-time accumulators), gendered SMPL models, multi-GPU evaluation (DESIGN.md "Evaluation").
+"""
+import argparse
+import os
+import sys
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--cfg", type=str, required=True, help="config file that defines model hyperparams")
+    p.add_argument("--ckpt", type=str, required=True, help="checkpoint path (.pt/.ckpt/.pth or run dir)")
+    p.add_argument("--inf_model", type=str, default="best")
+    p.add_argument("--smpl", type=str, default="data/smpl/SMPL_NEUTRAL.npz", help="SMPL body model as .npz (tools/convert_smpl.py)")
+    p.add_argument("--j_regressor", type=str, required=True, help="J_regressor_h36m.npy: float [17, 6890]")
+    p.add_argument("--dataset", type=str, required=True,
+                   help="the reference's dataset .npz: imgname, center, scale and pose + shape (SMPL ground truth) or S (joint "
+                        "ground truth); optional img [N,3,224,224] normalised crops, orig_shape, gender, person_id")
+    p.add_argument("--img_dir", type=str, default=None, help="folder the imgname entries are relative to (without `img` crops)")
+    p.add_argument("--dataset_name", default="3dpw", choices=["3dpw", "h36m-p2", "mpi-inf-3dhp"],
+                   help="selects the joint map: 17 joints for mpi-inf-3dhp, 14 otherwise")
+    p.add_argument("--batch_size", type=int, default=64)
+    p.add_argument("--save_results", action="store_true", help="also store pred_jnts3D / gt_jnts3D per sample")
+    p.add_argument("--output_folder", type=str, default="out")
+    p.add_argument("--no_kinematic_uncert", action="store_false",
+                   help="Do not use SMPL Kinematic for uncert (same store_false semantics as demo.py)")
+    return p.parse_args(argv)
+
+
+def check_dataset_file(path: str) -> str:
+    """Refuse a dataset file without ground truth before any GPU work; returns 'smpl' or 'joints'."""
+    import numpy as np
+    from poco_amd.evaluate import check_dataset_keys
+    if not os.path.isfile(path):
+        sys.exit(f"dataset file not found: {path}")
+    with np.load(path, allow_pickle=False) as z:
+        try:
+            return check_dataset_keys(z.files)
+        except ValueError as e:
+            sys.exit(f"{path}: {e}")
+
+
+def main(args):
+    check_dataset_file(args.dataset)
+    if not os.path.isfile(args.j_regressor):
+        sys.exit(f"joint regressor not found: {args.j_regressor}")
+    import numpy as np
+    from poco_amd import evaluate
+    from poco_amd.tester import POCOTester
+    try:
+        ds = evaluate.EvalDataset(args.dataset, args.img_dir, args.dataset_name)
+    except ValueError as e:
+        sys.exit(str(e))
+    J = np.load(args.j_regressor).astype(np.float32)
+    tester = POCOTester(args)                       # builds the engine from --cfg / --ckpt / --smpl exactly as demo.py does
+    res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
+                            kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
+    for line in evaluate.report_lines(res):
+        print(line)
+    out = os.path.join(args.output_folder, f"evaluation_results_{args.dataset_name}.npz")
+    evaluate.save_npz(out, res, args.dataset_name)
+    return res
+
+
+if __name__ == "__main__":
+    main(parse_args())

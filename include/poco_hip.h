@@ -225,6 +225,11 @@ int poco_bench_part_attention(const float* d_heat, int heat_cs, const float* d_f
 int poco_op_lc2d_pose(const float* d_x, const float* d_w, float* d_pose6d, int B, void* stream);
 /* rot6d_to_rotmat == pocolib/utils/geometry.py:247-261: d_in [B,24,3,2] (144 floats per crop) -> d_rotmat [B,24,3,3]. */
 int poco_op_rot6d(const float* d_in, float* d_rotmat, int B, void* stream);
+/* batch_rodrigues == pocolib/utils/geometry.py:207-244 (through quat_to_rotmat, with the reference's `theta + 1e-8` inside the
+ * norm; not a textbook Rodrigues): d_axis_angle [N,3] -> d_rotmat [N,3,3].  Evaluated in fp64, stored as fp32.  The same device
+ * function gives poco_evaluator_step its pose distance; this entry turns a ground-truth axis-angle pose [B,72] (N = 24 B) into
+ * the rotation matrices poco_smpl_lbs takes.  Enqueued on `stream`. */
+int poco_op_rodrigues(const float* d_axis_angle, float* d_rotmat, int N, void* stream);
 
 /* GPU-side crop + normalise: replaces the per-detection CPU loop cv2.getAffineTransform -> cv2.warpAffine(INTER_LINEAR,
  * BORDER_CONSTANT) -> ToTensor -> Normalize + per-crop H2D copy of pocolib/core/tester.py:182-203 and
@@ -281,6 +286,58 @@ int poco_renderer_create(const int32_t* h_faces, int F, int V, poco_renderer_t* 
 int poco_renderer_render(poco_renderer_t r, unsigned char* d_frame, int H, int W, const float* d_verts, int P,
                          const float* d_params, const float* h_rot3x3, int* d_frag_count, void* stream);
 void poco_renderer_destroy(poco_renderer_t r);
+
+/* ---- evaluator: MPJPE, PA-MPJPE, V2V and the uncertainty / pose-error correlation of eval.py ---------------------------------
+ * Replaces the host side of pocolib/core/trainer.py:298-336 (validation_step) and :365-391 (validation_epoch_end):
+ * get_jnts_from_mesh, mpjpe_error, pampjpe_error (one np.linalg.svd per crop, in Python), vert_error, calculate_distance_pose,
+ * calculate_pearson_coff (pocolib/utils/eval_utils.py:11-118,154-165), POCOUtils.prepare_uncert (poco_utils.py:21-25,62-94) and
+ * SaveResults.accumulate_* (save_results.py:45-82); csrc/eval_metrics.hip.  Created once, stepped per batch, finished per run.
+ *   Per crop (all sums and the Procrustes solve in fp64, stored as fp32):
+ *     joints   = J_regressor @ vertices (eval_utils.py:66-69; base_dataset.py:359-360 for the ground truth), rows h_joint_map
+ *                (constants.py:95-96 H36M_TO_J14 / H36M_TO_J17), minus row `pelvis` (eval_utils.py:70-73);
+ *     MPJPE    = |pred - gt| per joint and its mean (eval_utils.py:99-102);
+ *     PA-MPJPE = the same after the similarity transform s R x + t of the predicted onto the ground-truth joints
+ *                (eval_utils.py:11-59,84-97): R = argmax over SO(3) of tr(R K), K = X1 X2^T, found as Horn's quaternion (largest
+ *                eigenvector of a symmetric 4x4, cyclic Jacobi, a fixed number of sweeps) - the rotation the reference's SVD and Z
+ *                sign fix select; s = tr(R K) / var1.  var1 = 0 gives Inf / NaN in the crop's PA fields, nothing else;
+ *     V2V      = mean vertex distance (eval_utils.py:104-118), 0 with joint ground truth;
+ *     pose distance [24] = mean squared difference of pred_pose and batch_rodrigues(gt_pose) per SMPL joint (eval_utils.py:154-160);
+ *     processed uncertainty [24] = var_pose averaged over its trailing axes (innermost first), then, with `kinematic`,
+ *                var[i] += var[parent(i)] for i = 1..23 (poco_utils.py:21-25,67-70,89-90), in fp32 like the host.
+ *   Record of crop n = POCO_EVAL_RECORD_FLOATS fp32 (joint slots m >= M are 0):
+ *     [0] MPJPE  [1] PA-MPJPE  [2] V2V  [3] 0  [4..36) MPJPE per joint  [36..68) PA-MPJPE per joint  [68..92) pose distance
+ *     [92..116) processed uncertainty  [116..212) predicted joints, pelvis-relative [32,3]  [212..308) ground-truth joints [32,3]
+ *     [308..404) predicted joints, not pelvis-relative [32,3]  [404..416) 0
+ *   Summary = 8 doubles, reduced on the device in fp64 in a fixed order: [0] N  [1] 1000 mean MPJPE  [2] 1000 mean PA-MPJPE
+ *     [3] 1000 mean V2V (trainer.py:375-376)  [4] Pearson r of (pose distance, processed uncertainty) over all crops and selected
+ *     joints, centred: means first, then the three centred sums, clipped to [-1, 1] (scipy.stats.pearsonr, eval_utils.py:162-165)
+ *     [5] number of pairs  [6], [7] 0.
+ * One evaluator is used from one stream at a time (its partial-sum scratch is reused in stream order). */
+#define POCO_EVAL_MAX_JOINTS 32
+#define POCO_EVAL_RECORD_FLOATS 416
+typedef struct poco_evaluator* poco_evaluator_t;
+/* h_J_regressor fp32 [J,V] (host; dense or sparse - exact zeros are dropped, the rest is kept as CSR by row), 1 <= J <= 32,
+ * 1 <= V <= 2^22; h_joint_map int32 [M], 1 <= M <= J, entries and `pelvis` in [0, J); h_sel_uncert int32 [num_sel] = the SMPL
+ * joints that enter the correlation (sel_uncert_part, save_results.py:19; entries in [0, 24); num_sel = 0: all 24); kinematic =
+ * POCO.KINEMATIC_UNCERT; capacity = records the evaluator can hold (1 .. 2^24).  Host only, like poco_create: everything is
+ * validated here; the first step uploads the tables and allocates the records (1664 bytes each) and the scratch. */
+int poco_evaluator_create(const float* h_J_regressor, int J, int V, const int32_t* h_joint_map, int M, int pelvis,
+                          const int32_t* h_sel_uncert, int num_sel, int kinematic, int64_t capacity, poco_evaluator_t* out);
+/* Records of B crops at records[first .. first + B), first += B.  d_pred_vertices [B,V,3] (smpl_vertices), exactly one of
+ * d_gt_vertices [B,V,3] (3DPW: joints regressed from it, V2V) and d_gt_joints [B,M,3] (H36M / MPI-INF-3DHP: used as they are),
+ * d_pred_pose [B,24,3,3], d_gt_pose [B,72] axis-angle, d_var_pose [B,24,var_t1,var_t2] (the engine's [B,24]: var_t1 = var_t2 = 1).
+ * Argument errors - a null handle or pointer, B <= 0, both or neither ground truth, first + B > capacity - return POCO_ERR_ARG
+ * before any GPU work and leave the records as they were.  Enqueued on `stream` (two launches per 256 crops), safe right behind
+ * poco_forward on the same stream: no synchronisation and, after the first step, no allocation. */
+int poco_evaluator_step(poco_evaluator_t e, int B, const float* d_pred_vertices, const float* d_gt_vertices,
+                        const float* d_gt_joints, const float* d_pred_pose, const float* d_gt_pose, const float* d_var_pose,
+                        int var_t1, int var_t2, void* stream);
+/* Reduce the N records written so far into h_summary8 (host, 8 doubles) and, if h_records is not NULL, copy the records to it
+ * (host fp32 [records_cap, POCO_EVAL_RECORD_FLOATS], records_cap >= N).  Synchronises `stream`.  N = 0 is POCO_ERR_STATE. */
+int poco_evaluator_finish(poco_evaluator_t e, double* h_summary8, float* h_records, int64_t records_cap, void* stream);
+/* Rewind: the next step writes record 0. */
+int poco_evaluator_reset(poco_evaluator_t e);
+void poco_evaluator_destroy(poco_evaluator_t e);
 
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /

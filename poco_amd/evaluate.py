@@ -1,0 +1,256 @@
+"""Evaluation on the GPU (eval.py): a binding of poco_evaluator_* (include/poco_hip.h, csrc/eval_metrics.hip) and the loop of
+pocolib/core/trainer.py:298-336,365-391 on this engine.  Per crop nothing goes to the host between the forward and
+Evaluator.finish(): the metrics are computed from the model's device outputs into device records.
+
+The reference evaluates with numpy on the host (pocolib/utils/eval_utils.py: one np.linalg.svd per crop); tests/eval_np.py
+restates that and is the yardstick of tests/test_eval_*.py."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from ._lib import PocoHipError, check, lib
+
+H36M_TO_J17 = [6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10, 0, 7, 9]      # constants.py:95
+H36M_TO_J14 = H36M_TO_J17[:14]                                               # constants.py:96
+J24_TO_J17 = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 18, 14, 16, 17]       # constants.py:98
+J24_TO_J14 = J24_TO_J17[:14]                                                 # constants.py:99
+DATASET_NAMES = ("3dpw", "h36m-p2", "mpi-inf-3dhp")
+MAX_JOINTS = 32
+RECORD_FLOATS = 416
+# record offsets (include/poco_hip.h)
+R_MPJPE, R_PA, R_V2V, R_MPJPE_J, R_PA_J, R_POSE, R_UNC, R_PRED, R_GT, R_NONREL = 0, 1, 2, 4, 36, 68, 92, 116, 212, 308
+
+
+def joint_map(dataset_name: str):
+    """eval_utils.py:65: 17 joints for mpi-inf-3dhp, 14 otherwise."""
+    return H36M_TO_J17 if dataset_name == "mpi-inf-3dhp" else H36M_TO_J14
+
+
+def _bind():
+    L = lib()
+    if getattr(L, "_eval_bound", False):
+        return L
+    L.poco_evaluator_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int64, C.POINTER(C.c_void_p)]
+    L.poco_evaluator_step.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+    L.poco_evaluator_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.poco_evaluator_reset.argtypes = [C.c_void_p]
+    L.poco_evaluator_destroy.argtypes = [C.c_void_p]
+    L.poco_evaluator_destroy.restype = None
+    L._eval_bound = True
+    return L
+
+
+def _dev(t: Optional[torch.Tensor], what: str, tail) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise PocoHipError(f"Evaluator.step: {what} must be a CUDA tensor")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.to(torch.float32).contiguous()
+    if tuple(t.shape[1:]) != tuple(tail):
+        raise PocoHipError(f"Evaluator.step: {what} must be [B, {', '.join(map(str, tail))}], got {tuple(t.shape)}")
+    return t
+
+
+class Evaluator:
+    """Device-side metric accumulator.
+
+        ev = Evaluator(J_regressor_h36m, joint_map("3dpw"), capacity=len(dataset))
+        ev.step(model(batch), gt_pose, gt_vertices=verts)        # per batch, enqueued on the current stream
+        res = ev.finish()                                        # val_mpjpe, val_pampjpe, val_v2v, val_corr + per-sample arrays
+    """
+
+    def __init__(self, J_regressor, jmap: Sequence[int], capacity: int, pelvis: int = 0, sel_uncert_part: Optional[Sequence[int]] = None,
+                 kinematic: bool = True, device=None):
+        self.J_regressor = np.ascontiguousarray(np.asarray(J_regressor, np.float32))
+        if self.J_regressor.ndim != 2:
+            raise PocoHipError("Evaluator: J_regressor must be [J, V]")
+        self.J, self.V = (int(x) for x in self.J_regressor.shape)
+        self.map = np.ascontiguousarray(np.asarray(jmap, np.int32).reshape(-1))
+        self.M = int(self.map.shape[0])
+        self.sel = np.ascontiguousarray(np.asarray(list(range(24)) if sel_uncert_part is None else sel_uncert_part, np.int32).reshape(-1))
+        self.capacity, self.count = int(capacity), 0
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self._h = C.c_void_p()
+        check(_bind().poco_evaluator_create(self.J_regressor.ctypes.data, self.J, self.V, self.map.ctypes.data, self.M, int(pelvis),
+                                            self.sel.ctypes.data if self.sel.size else None, int(self.sel.size), int(bool(kinematic)),
+                                            self.capacity, C.byref(self._h)), "poco_evaluator_create")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().poco_evaluator_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, pred: Dict[str, torch.Tensor], gt_pose: torch.Tensor, gt_vertices: Optional[torch.Tensor] = None,
+             gt_joints: Optional[torch.Tensor] = None) -> None:
+        """pred = the model's output dict (smpl_vertices [B,V,3], pred_pose [B,24,3,3], var_pose [B,24] or with up to two
+        trailing axes); gt_pose [B,72] axis-angle; exactly one of gt_vertices [B,V,3] and gt_joints [B,M,3].  Enqueued on the
+        current stream: no synchronisation, nothing copied to the host."""
+        pv = _dev(pred["smpl_vertices"], "smpl_vertices", (self.V, 3))
+        B = int(pv.shape[0])
+        pp = _dev(pred["pred_pose"], "pred_pose", (24, 3, 3))
+        var = pred["var_pose"]
+        if not (torch.is_tensor(var) and var.is_cuda and 2 <= var.dim() <= 4 and var.shape[1] == 24):
+            raise PocoHipError("Evaluator.step: var_pose must be a CUDA tensor [B,24], [B,24,a] or [B,24,a,b]")
+        var = _dev(var, "var_pose", var.shape[1:])
+        t1, t2 = (1, 1) if var.dim() == 2 else ((1, int(var.shape[2])) if var.dim() == 3 else (int(var.shape[2]), int(var.shape[3])))
+        gp = _dev(gt_pose, "gt_pose", (72,))
+        gv = _dev(gt_vertices, "gt_vertices", (self.V, 3))
+        gj = _dev(gt_joints, "gt_joints", (self.M, 3))
+        for t in (pp, var, gp, gv, gj):
+            if t is not None and t.shape[0] != B:
+                raise PocoHipError("Evaluator.step: batch sizes differ")
+        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        with torch.cuda.device(self.device):
+            check(lib().poco_evaluator_step(self._h, B, p(pv), p(gv), p(gj), p(pp), p(gp), p(var), t1, t2,
+                                            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "poco_evaluator_step")
+        self.count += B
+
+    def reset(self) -> None:
+        check(lib().poco_evaluator_reset(self._h), "poco_evaluator_reset")
+        self.count = 0
+
+    def finish(self, save_results: bool = False, return_records: bool = False) -> Dict[str, object]:
+        """Summary under the reference's log names (trainer.py:397-403) plus the per-sample arrays of
+        SaveResults.evaluation_results (save_results.py:23-43): mpjpe / pampjpe [N,M], v2v [N], corr_x / corr_y (flattened over
+        the selected joints), and with save_results pred_jnts3D / gt_jnts3D [N,M,3].  Synchronises the current stream."""
+        summ = np.zeros(8, np.float64)
+        rec = np.empty((self.count, RECORD_FLOATS), np.float32)
+        with torch.cuda.device(self.device):
+            check(lib().poco_evaluator_finish(self._h, summ.ctypes.data, rec.ctypes.data, rec.shape[0],
+                                              C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "poco_evaluator_finish")
+        M = self.M
+        out = {"N": int(summ[0]), "val_mpjpe": float(summ[1]), "val_pampjpe": float(summ[2]), "val_v2v": float(summ[3]),
+               "val_corr": float(summ[4]), "summary": summ,
+               "mpjpe": rec[:, R_MPJPE_J:R_MPJPE_J + M].copy(), "pampjpe": rec[:, R_PA_J:R_PA_J + M].copy(), "v2v": rec[:, R_V2V].copy(),
+               "corr_x": rec[:, R_POSE:R_POSE + 24][:, self.sel].reshape(-1), "corr_y": rec[:, R_UNC:R_UNC + 24][:, self.sel].reshape(-1)}
+        if save_results:
+            out["pred_jnts3D"] = rec[:, R_PRED:R_PRED + 3 * MAX_JOINTS].reshape(-1, MAX_JOINTS, 3)[:, :M].copy()
+            out["gt_jnts3D"] = rec[:, R_GT:R_GT + 3 * MAX_JOINTS].reshape(-1, MAX_JOINTS, 3)[:, :M].copy()
+        if return_records:
+            out["records"] = rec
+        return out
+
+
+# ---- datasets ------------------------------------------------------------------------------------------------------------------
+def check_dataset_keys(files) -> str:
+    """'smpl' (pose + shape: 3DPW-style, ground-truth vertices through SMPL) or 'joints' (S: H36M / MPI-INF-3DHP).  A file with
+    neither is refused (base_dataset.py:54-147 reads the same keys)."""
+    files = set(files)
+    missing = [k for k in ("imgname", "center", "scale") if k not in files]
+    if missing:
+        raise ValueError(f"dataset file lacks {missing}")
+    if "pose" in files and "shape" in files:
+        return "smpl"
+    if "S" in files:
+        return "joints"
+    raise ValueError("dataset file has neither `pose` + `shape` (SMPL ground truth) nor `S` (joint ground truth)")
+
+
+class EvalDataset:
+    """The reference's dataset .npz (base_dataset.py:54-147): imgname, center [N,2], scale [N] (bbox size / 200), and pose [N,72]
+    + shape [N,10] or S [N,24,3|4]; optional gender, person_id, orig_shape [N,2] (h, w) and img [N,3,224,224] = already normalised
+    crops.  Without `img` the images are read from img_dir and cropped on the GPU with the demo's crop (poco_amd/tester.py)."""
+
+    def __init__(self, path: str, img_dir: Optional[str] = None, dataset_name: str = "3dpw", bbox_scale: float = 1.0):
+        if dataset_name not in DATASET_NAMES:
+            raise ValueError(f"dataset_name must be one of {DATASET_NAMES}")
+        z = np.load(path, allow_pickle=False)
+        self.gt_form = check_dataset_keys(z.files)
+        self.name, self.img_dir, self.bbox_scale = dataset_name, img_dir, float(bbox_scale)
+        self.imgname = [str(x) for x in z["imgname"]]
+        self.center = np.asarray(z["center"], np.float32).reshape(-1, 2)
+        self.scale = np.asarray(z["scale"], np.float32).reshape(-1)
+        n = len(self.imgname)
+        self.pose = np.asarray(z["pose"], np.float32).reshape(n, 72) if "pose" in z.files else np.zeros((n, 72), np.float32)
+        self.shape = np.asarray(z["shape"], np.float32).reshape(n, 10) if "shape" in z.files else None
+        self.joints = None
+        if self.gt_form == "joints":
+            jm = J24_TO_J17 if dataset_name == "mpi-inf-3dhp" else J24_TO_J14       # base_dataset.py:379
+            self.joints = np.ascontiguousarray(np.asarray(z["S"], np.float32)[:, jm, :3])
+        self.img = z["img"] if "img" in z.files else None
+        self.orig_shape = np.asarray(z["orig_shape"], np.float32).reshape(n, 2) if "orig_shape" in z.files else None
+        if self.img is None and not (img_dir and os.path.isdir(img_dir)):
+            raise ValueError("the dataset file has no `img` crops: --img_dir must name the folder its imgname entries are relative to")
+        for k in ("gender", "person_id"):
+            setattr(self, k, np.asarray(z[k]) if k in z.files else None)
+
+    def __len__(self) -> int:
+        return len(self.imgname)
+
+    def batch(self, lo: int, hi: int, device) -> Dict[str, torch.Tensor]:
+        """Model inputs of samples [lo, hi) (the dict of tester.py:205-212) on the device."""
+        from .tester import calculate_bbox_info, calculate_focal_length, crop_normalize
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)   # noqa: E731
+        center, scale = self.center[lo:hi], self.scale[lo:hi]
+        if self.img is not None:
+            img = t(self.img[lo:hi])
+            shapes = self.orig_shape[lo:hi] if self.orig_shape is not None else np.tile([[224.0, 224.0]], (hi - lo, 1))
+        else:
+            from PIL import Image
+            crops, shapes = [], []
+            for i in range(lo, hi):
+                fr = np.array(Image.open(os.path.join(self.img_dir, self.imgname[i])).convert("RGB"))
+                side = float(self.scale[i]) * 200.0
+                box = torch.tensor([[self.center[i, 0], self.center[i, 1], side, side]], dtype=torch.float32, device=device)
+                crops.append(crop_normalize(torch.from_numpy(np.ascontiguousarray(fr)).to(device), box, self.bbox_scale))
+                shapes.append(fr.shape[:2])
+            img, shapes = torch.cat(crops), np.asarray(shapes, np.float32)
+        info = np.stack([calculate_bbox_info(c, s, hw) for c, s, hw in zip(center, scale, shapes)])
+        focal = np.array([calculate_focal_length(h, w) for h, w in shapes], np.float32)
+        return {"img": img, "bbox_info": t(info), "focal_length": t(focal), "scale": t(scale), "center": t(center),
+                "orig_shape": t(shapes)}
+
+
+@torch.no_grad()
+def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
+             sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_records: bool = False) -> Dict[str, object]:
+    """trainer.py:298-336 over a whole dataset: forward, then the metrics of every batch (the ragged last one included) on the
+    device.  SMPL ground truth: gt_vertices = POCO.smpl_lbs(shape, poco_op_rodrigues(pose)) (base_dataset.py:353-366, neutral
+    model), also on the device.  Returns Evaluator.finish() plus `imgname`."""
+    from . import ops
+    dev = model.device
+    ev = Evaluator(J_regressor, joint_map(dataset.name), capacity=len(dataset), sel_uncert_part=sel_uncert_part, kinematic=kinematic,
+                   device=dev)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+    for lo in range(0, len(dataset), batch_size):
+        hi = min(lo + batch_size, len(dataset))
+        out = model(dataset.batch(lo, hi, dev), want_segm=False)
+        gt_pose = t(dataset.pose[lo:hi])
+        if dataset.gt_form == "smpl":
+            gt_verts, _ = model.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))
+            ev.step(out, gt_pose, gt_vertices=gt_verts)
+        else:
+            ev.step(out, gt_pose, gt_joints=t(dataset.joints[lo:hi]))
+    res = ev.finish(save_results=save_results, return_records=return_records)
+    model.check_status()
+    res["imgname"] = np.asarray(dataset.imgname)
+    ev.close()
+    return res
+
+
+def report_lines(res: Dict[str, object]):
+    """The lines of trainer.py:386-391 this port computes."""
+    return [f"MPJPE: {res['val_mpjpe']}", f"PA-MPJPE: {res['val_pampjpe']}", f"V2V (mm): {res['val_v2v']}",
+            f"Uncert Error Correlation: {res['val_corr']}", f"N: {res['N']}"]
+
+
+def save_npz(path: str, res: Dict[str, object], dataset_name: str) -> None:
+    """evaluation_results_<name>.npz: the numeric arrays of save_results.py:84-92 (the reference joblib-dumps a dict)."""
+    keep = {k: v for k, v in res.items() if isinstance(v, np.ndarray) and k not in ("records", "summary") and v.dtype.kind in "fiu"}
+    keep.update({k: np.float64(res[k]) for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")})
+    keep["N"] = np.int64(res["N"])
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    np.savez(path, **keep)

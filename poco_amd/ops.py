@@ -106,3 +106,14 @@ def rot6d(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty((B, 24, 3, 3), device=x.device)
     check(lib().poco_op_rot6d(fptr(x.contiguous()), fptr(out), B, current_stream()), "poco_op_rot6d")
     return out
+
+
+def rodrigues(aa: torch.Tensor) -> torch.Tensor:
+    """batch_rodrigues (geometry.py:207-244): axis-angle [..., 3] -> rotation matrices [..., 3, 3]; [B,72] gives [B,24,3,3]."""
+    assert aa.is_cuda and aa.dtype == torch.float32 and aa.shape[-1] % 3 == 0 and aa.numel() > 0
+    a = aa.contiguous().view(-1, 3)
+    out = torch.empty((a.shape[0], 3, 3), device=aa.device)
+    check(lib().poco_op_rodrigues(fptr(a), fptr(out), a.shape[0], current_stream()), "poco_op_rodrigues")
+    if aa.shape[-1] == 3:
+        return out.view(*aa.shape[:-1], 3, 3)
+    return out.view(*aa.shape[:-1], aa.shape[-1] // 3, 3, 3)

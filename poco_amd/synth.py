@@ -183,6 +183,23 @@ def synth_smpl(seed: int = 7, num_verts: int = NUM_VERTS) -> Dict[str, np.ndarra
     }
 
 
+def synth_j_regressor_h36m(seed: int = 11, num_verts: int = NUM_VERTS, nnz: int = 24) -> np.ndarray:
+    """A stand-in for data/J_regressor_h36m.npy (not redistributable): float32 [17, V], `nnz` non-zeros per row (fewer if the
+    mesh is smaller), every row sums to one.  The weights are a peaked Dirichlet draw, so each joint sits near one or two
+    vertices and the 17 joints spread over the body like the template does (NOT anatomically placed)."""
+    r = np.random.default_rng([seed, num_verts])
+    m = np.zeros((17, num_verts))
+    k = min(nnz, num_verts)
+    for i in range(17):
+        m[i, r.choice(num_verts, k, replace=False)] = r.dirichlet(np.full(k, 0.1))
+    m32 = m.astype(np.float32)
+    # rows sum to one in float32 as well as it can be said: put the rounding residue on the largest weight
+    for i in range(17):
+        j = int(np.argmax(m32[i]))
+        m32[i, j] = np.float32(m32[i, j] + (1.0 - m32[i].astype(np.float64).sum()))
+    return m32
+
+
 # --------------------------------------------------------------------------------------------
 # Input batches (contract: pocolib/core/tester.py:178-212, pocolib/utils/image_utils.py:171-187)
 # --------------------------------------------------------------------------------------------
