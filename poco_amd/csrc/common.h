@@ -73,18 +73,24 @@ inline ConvCfg conv_cfg_from(const int* c) { return ConvCfg{c[0], c[1], c[2], c[
 // Channel offset `co` of a slice inside a wider buffer -> float offset (co/16)*W*16 + co%16.
 inline size_t l16_chan_off(int co, int W) { return (size_t)(co >> 4) * W * 16 + (co & 15); }
 
+// The further layouts of a conv's weights, one per algorithm family that reads them in an order of its own (each nullable: the
+// engine packs a layout only for the ops that may run its algorithm).  The plain fragment order every conv has is ConvDesc::wfrag.
+struct ConvWeights {
+  const float* wino = nullptr;      // 3x3 stride-1 only: Winograd F(2x2,3x3)-transformed weights (ALG 3 / 4)
+  const float* wino4 = nullptr;     // 3x3 stride-1 only: F(4x4,3x3) weight fragments, 36 positions (ALG 7)
+  const float* wino4p = nullptr;    // the same weights in the LDS order of ALG 8 (conv_wino4p.hip)
+  const float* wino4w = nullptr;    // the same weights in the LDS order of ALG 13 (conv_wino4w.hip)
+  const float* wino4g = nullptr;    // 3x3 stride-1 convs on small planes: per-position GEMM fragments of ALG 11 (conv_wino4g.hip)
+  const float* split_f16 = nullptr; // EXPERIMENT (ALG 12, gemm1x1h.hip): hi / lo fp16 halves of the 1x1 weights
+};
+
 struct ConvDesc {
   // activations: L16 (see above), each buffer may be a channel slice of a wider buffer
   const float* in;  int in_cs,  in_co;    // channel stride (channels per pixel of the buffer), offset
   const float* res; int res_cs, res_co;   // optional residual (same spatial shape as the output)
   float*       out; int out_cs, out_co;
   const float* wfrag;                     // weights in MFMA fragment order (see conv_pack_weights)
-  const float* wfrag_wino;                // 3x3 stride-1 only: Winograd-transformed weights (ALG 3), nullable
-  const float* wfrag_wino4 = nullptr;     // 3x3 stride-1 only: F(4x4,3x3) weight fragments, 36 positions (ALG 7), nullable
-  const float* wfrag_wino4p = nullptr;    // the same weights in the LDS order of ALG 8 (conv_wino4p.hip), nullable
-  const float* wfrag_wino4w = nullptr;    // the same weights in the LDS order of ALG 13 (conv_wino4w.hip), nullable
-  const float* wfrag_wino4g = nullptr;    // 3x3 stride-1 convs on planes <= 8x8: per-position GEMM fragments of ALG 11 (conv_wino4g.hip)
-  const float* wfrag_h = nullptr;         // EXPERIMENT (ALG 12, gemm1x1h.hip): hi / lo fp16 halves of the 1x1 weights, nullable
+  ConvWeights w;                          // ... and in the orders of the algorithms that need their own, each nullable
   float* scratch = nullptr;               // ALG 11: V + M staging (conv_wino4g_scratch_floats), owned by the caller
   size_t scratch_floats = 0;
   float* sk_scratch = nullptr;            // ALG 14 (gemm1x1sk.hip): flags + partial accumulators (gemm1x1sk_scratch_floats), zeroed once by the owner

@@ -752,7 +752,7 @@ void conv_wino_transform_weights(const float* w_oihw, int Cout, int Cin, std::ve
 }
 
 int conv_wino_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
-  if (d.ks != 3 || d.stride != 1 || !d.wfrag_wino) {
+  if (d.ks != 3 || d.stride != 1 || !d.w.wino) {
     poco_set_error("conv(winograd): needs a 3x3 stride-1 conv with transformed weights");
     return POCO_ERR_ARG;
   }
@@ -767,7 +767,7 @@ int conv_wino_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) 
     if (lds4 > 160 * 1024 || (size_t)cfg.WM * cfg.NT * 4 * 64 > (size_t)2 * 16 * cfg.NT * 64) { poco_set_error("conv(winograd/half): LDS budget exceeded"); return POCO_ERR_ARG; }
     WinoParams p;
     p.in = d.in + l16_chan_off(d.in_co, d.W); p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr; p.out = d.out + l16_chan_off(d.out_co, d.W);
-    p.ufrag = reinterpret_cast<const float4*>(d.wfrag_wino); p.bias = d.bias;
+    p.ufrag = reinterpret_cast<const float4*>(d.w.wino); p.bias = d.bias;
     p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
     p.H = d.H; p.W = d.W; p.nC16 = d.Cin / 16; p.nT16 = d.Cout / 16;
     p.R = cfg.R; p.NI = cfg.NI; p.S = g.S; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.planeF4 = g.planeF4;
@@ -821,7 +821,7 @@ int conv_wino_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) 
   if (lds > 160 * 1024) { poco_set_error("conv(winograd): LDS budget exceeded"); return POCO_ERR_ARG; }
   WinoParams p;
   p.in = d.in + l16_chan_off(d.in_co, d.W); p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr; p.out = d.out + l16_chan_off(d.out_co, d.W);
-    p.ufrag = reinterpret_cast<const float4*>(d.wfrag_wino); p.bias = d.bias;
+    p.ufrag = reinterpret_cast<const float4*>(d.w.wino); p.bias = d.bias;
   p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
   p.H = d.H; p.W = d.W; p.nC16 = d.Cin / 16; p.nT16 = d.Cout / 16;
   p.R = cfg.R; p.NI = cfg.NI; p.S = g.S; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.planeF4 = g.planeF4;

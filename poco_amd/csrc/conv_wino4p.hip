@@ -804,7 +804,7 @@ int conv_wino4p_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
   W4PLayout L;
   FlatGeo fg{};
   const bool flat = cfg.NI == 0;
-  if (!w4p_geo(d, cfg, &g, &L, &fg) || !d.wfrag_wino4p) {
+  if (!w4p_geo(d, cfg, &g, &L, &fg) || !d.w.wino4p) {
     poco_set_error("conv(winograd 4x4, specialised waves): needs ks = 3, stride 1, NT 1..3, WM = 2, WN = 4, R % 4 == 0, "
                    "NI*(R/4)*ceil(W/4) <= 32 tiles (or R = 4, NI = 0: flat items), a patch of <= 1024 slots that fits the LDS next "
                    "to the U ring, and the ALG 8 weight fragments");
@@ -815,7 +815,7 @@ int conv_wino4p_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
   p.in = d.in + l16_chan_off(d.in_co, d.W);
   p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr;
   p.out = d.out + l16_chan_off(d.out_co, d.W);
-  p.ufrag = reinterpret_cast<const float4*>(d.wfrag_wino4p); p.bias = d.bias;
+  p.ufrag = reinterpret_cast<const float4*>(d.w.wino4p); p.bias = d.bias;
   p.B = d.B; p.H = d.H; p.W = d.W; p.nC4 = d.Cin / 4; p.nT16 = d.Cout / 16;
   p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
   p.R = g.R; p.NI = g.NI; p.S = g.S; p.nbands = g.nbands; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.rawF4 = g.rawF4;

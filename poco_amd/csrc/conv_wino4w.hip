@@ -817,7 +817,7 @@ int conv_wino4w_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
   W4WLayout L;
   FlatGeo fg{};
   const bool flat = cfg.NI == 0;
-  if (!w4w_geo(d, cfg, &g, &L, &fg) || !d.wfrag_wino4w) {
+  if (!w4w_geo(d, cfg, &g, &L, &fg) || !d.w.wino4w) {
     poco_set_error("conv(winograd 4x4, whole-position waves): needs ks = 3, stride 1, NT 1..3, WM = 2, WN = 1, R % 4 == 0, "
                    "NI*(R/4)*ceil(W/4) <= 32 tiles (or R = 4 MS, NI = 0: flat items), a patch of <= 1024 slots, tensors below 2^30 elements and the ALG 13 weight fragments");
     return POCO_ERR_ARG;
@@ -828,7 +828,7 @@ int conv_wino4w_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
   p.in = d.in + l16_chan_off(d.in_co, d.W);
   p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr;
   p.out = d.out + l16_chan_off(d.out_co, d.W);
-  p.ufrag = reinterpret_cast<const float4*>(d.wfrag_wino4w); p.bias = d.bias;
+  p.ufrag = reinterpret_cast<const float4*>(d.w.wino4w); p.bias = d.bias;
   p.B = d.B; p.H = d.H; p.W = d.W; p.nC4 = d.Cin / 4; p.nT16 = d.Cout / 16;
   p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
   p.R = g.R; p.NI = g.NI; p.S = g.S; p.nbands = g.nbands; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.rawF4 = g.rawF4;

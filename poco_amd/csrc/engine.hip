@@ -74,12 +74,7 @@ struct Op {
   int Cin = 0, Cout = 0, ks = 1, stride = 1, actfn = 0, res_after = 0, relu_from = 0;
   float* wdev = nullptr;
   float* bdev = nullptr;
-  float* wdev_wino = nullptr;   // 3x3 stride-1 convs: Winograd-transformed weights (ALG 3)
-  float* wdev_wino4p = nullptr; // the same in the LDS order of ALG 8
-  float* wdev_wino4w = nullptr; // ... and in the quad order of ALG 13 (conv_wino4w.hip)
-  float* wdev_wino4g = nullptr; // planes <= 8x8: per-position GEMM fragments of ALG 11 (conv_wino4g.hip)
-  float* wdev_h = nullptr;      // POCO_SPLIT_F16=1 only: hi / lo fp16 halves of a plain 1x1 conv's weights (ALG 12 experiment)
-  float* wdev_wino4 = nullptr;  // 3x3 stride-1 convs on planes >= 28x28: F(4x4,3x3) fragments (ALG 7)
+  ConvWeights w;                // the layouts of the Winograd forms the op may run (conv_algs) / of the split_f16 experiment
   float* wdev2 = nullptr;       // OP_CHAIN: the second 1x1 conv (next block's conv1)
   float* bdev2 = nullptr;
   // fuse
@@ -190,7 +185,7 @@ struct Engine {
   int num_lanes = 4;      // 1 = run everything on the caller's stream
   hipStream_t lane_stream[4] = {};   // side lanes 1..3 (lane 0 is the caller's stream)
   hipEvent_t ev_fork = nullptr, ev_join[4] = {};
-  std::vector<hipEvent_t> ev_dep;   // one per op with a cross-lane dependency (Op::wait_lane)
+  std::vector<hipEvent_t> ev_dep;   // one per op with a cross-lane dependency (Op::wait_mask)
   // SMPL / flow device models
   SmplDev smpl{};
   int a_coef = -1, a_A = -1, a_j24 = -1, a_verts = -1, a_j49 = -1, a_attn_scratch = -1, a_camt = -1, a_fullt = -1, a_j2d = -1;
@@ -249,6 +244,23 @@ static void op_accesses(const Engine& e, const Op& op, std::vector<OpAccess>* rd
   add(wr, op.out, conv ? op.Cout : (op.type == OP_FUSE ? op.C : ALL));
   add(wr, op.out2, ALL);
   for (const Op& su : op.sub) op_accesses(e, su, rd, wr);
+}
+
+// Which Winograd forms a conv op may run: the ONE statement of the rule.  Builder::conv packs exactly the weight layouts of the forms
+// it names, poco_set_conv_cfg refuses every other one (whatever else its validation says).
+struct ConvAlgs { bool wino, wino4, wino4p, wino4w, wino4g; };   // ALG 3 / 4, 7, 8, 13, 11
+static ConvAlgs conv_algs(const EngineOpts& o, int H, int W, int ks, int stride, int actfn) {
+  ConvAlgs a{};
+  if (ks != 3 || stride != 1 || actfn > 1) return a;      // 3x3 stride-1 convs with no activation or a plain ReLU
+  const int lo = std::min(H, W), hi = std::max(H, W);
+  a.wino = true;                                           // F(2x2,3x3): any plane
+  // F(4x4,3x3) in LDS: 56x56 / 28x28 planes, 14x14 (16 tiles per image, 31 % padding), 7x7 with ALG 13 only (option w4_min_plane <= 14)
+  a.wino4w = lo >= o.w4_min_plane;
+  a.wino4p = a.wino4w && lo >= 14;
+  a.wino4 = a.wino4w && lo >= 28;
+  // F(4x4,3x3) as 36 position GEMMs with V / M staged in memory (scratch sized for max_batch; poco_forward refuses larger batches)
+  a.wino4g = hi <= o.wg_max_plane && H * W > 1;
+  return a;
 }
 
 struct Builder {
@@ -357,7 +369,7 @@ struct Builder {
   }
 
   // BN(eval) folded into per-channel scale/shift:  y = conv*scale + shift
-  void bn_fold(const std::string& bn, const HostParam* conv_bias, int Cout, std::vector<float>& scale,
+  void bn_fold(const std::string& bn, const std::vector<float>* conv_bias, int Cout, std::vector<float>& scale,
                std::vector<float>& shift) {
     scale.assign(Cout, 1.f);
     shift.assign(Cout, 0.f);
@@ -372,49 +384,120 @@ struct Builder {
         const double s = (double)g->data[c] / std::sqrt((double)v->data[c] + (double)BN_EPS);
         scale[c] = (float)s;
         shift[c] = (float)((double)b->data[c] - (double)m->data[c] * s);
-        if (conv_bias) shift[c] = (float)((double)shift[c] + (double)conv_bias->data[c] * s);
+        if (conv_bias) shift[c] = (float)((double)shift[c] + (double)(*conv_bias)[c] * s);
       }
     } else if (conv_bias && !declare) {
-      for (int c = 0; c < Cout; ++c) shift[c] = conv_bias->data[c];
+      for (int c = 0; c < Cout; ++c) shift[c] = (*conv_bias)[c];
     }
   }
 
-  // conv (+bias) + BN + act (+ residual).  `in` may be a channel slice; returns the output act
-  // (or writes into `into` at channel offset).  kperm: optional K-column permutation for Linear
-  // layers whose input vector is laid out differently from the reference's torch.cat.
-  int conv(const std::string& name, const std::string& convp, const std::string& bnp, Ref in, int Cin_real,
-           int Cout, int ks, int stride, int actfn, bool has_bias, Ref res = Ref(), int res_after = 0,
-           Ref into = Ref(), const std::vector<int>* kperm = nullptr, int Cin_padded = 0, bool is_linear = false,
-           bool direct = false, const HostParam* w_direct = nullptr, const HostParam* b_direct = nullptr) {
-    const Act ain = e.acts[in.act];
-    const int Cin = Cin_padded ? Cin_padded : Cin_real;
+  // ---- merged weights -------------------------------------------------------------------------
+  // Several convs run as ONE launch: their merged weight [Cout, K, ks, ks] with the BN scales folded in and the merged shift are
+  // built here on the host and handed to conv() in a ConvSpec.  The arithmetic is fixed: a weight is (float)((double)scale[o] * w),
+  // a shift is summed in double in source order and rounded once.
+  struct Merged {
+    std::vector<float> w, b;
+    bool have = false;      // false in declare mode and when a tensor is missing
+    bool stacked = false;   // made by stack_rows
+  };
+  struct MergeSrc {         // one member: <conv>.weight (+ .bias), BN <bn>.* ("" = none), C = its input (concat_k) / output (stack_rows) channels
+    std::string conv, bn;
+    int C;
+    bool bias = false;
+  };
+  // K concatenation:  sum_j bn_j(conv_j(x_j))  =  [s_0 W_0 | s_1 W_1 | ...] . [x_0 ; x_1 ; ...] + sum_j shift_j
+  Merged concat_k(const std::vector<MergeSrc>& srcs, int Cout, int ks) {
+    const int taps = ks * ks;
+    int K = 0, koff = 0;
+    for (const MergeSrc& m : srcs) K += m.C;
+    Merged r;
+    r.have = !declare;
+    if (r.have) r.w.assign((size_t)Cout * K * taps, 0.f);
+    std::vector<double> bsum(Cout, 0.0);
+    for (const MergeSrc& m : srcs) {
+      const HostParam* w = P(m.conv + ".weight", {Cout, m.C, ks, ks});
+      std::vector<float> scale, shift;
+      bn_fold(m.bn, nullptr, Cout, scale, shift);
+      r.have = r.have && w;
+      for (int o = 0; r.have && o < Cout; ++o) {
+        for (int k = 0; k < m.C * taps; ++k)
+          r.w[((size_t)o * K + koff) * taps + k] = (float)((double)scale[o] * w->data[(size_t)o * m.C * taps + k]);
+        bsum[o] += (double)shift[o];
+      }
+      koff += m.C;
+    }
+    for (double v : bsum) r.b.push_back((float)v);
+    return r;
+  }
+  // Row stacking: layers that read the SAME input (in_shape: [Cin] or [Cin, ks, ks]) as one layer over the concatenated output rows
+  Merged stack_rows(const std::vector<MergeSrc>& srcs, const std::vector<int64_t>& in_shape) {
+    size_t per = 1;
+    for (int64_t d : in_shape) per *= (size_t)d;
+    Merged r;
+    r.have = !declare;
+    r.stacked = true;
+    for (const MergeSrc& m : srcs) {
+      std::vector<int64_t> wshape = {m.C};
+      wshape.insert(wshape.end(), in_shape.begin(), in_shape.end());
+      const HostParam* w = P(m.conv + ".weight", wshape);
+      const HostParam* cb = m.bias ? P(m.conv + ".bias", {m.C}) : nullptr;
+      std::vector<float> scale, shift;
+      bn_fold(m.bn, cb ? &cb->data : nullptr, m.C, scale, shift);
+      r.have = r.have && w && (cb || !m.bias);
+      for (size_t k = 0; r.have && k < m.C * per; ++k) r.w.push_back((float)((double)scale[k / per] * w->data[k]));
+      r.b.insert(r.b.end(), shift.begin(), shift.end());
+    }
+    return r;
+  }
+
+  // conv (+bias) + BN + act (+ residual).  The weights are the parameters <conv>.weight (+ .bias if `bias`; [Cout, Cin] if `linear`,
+  // an nn.Linear) with the BN <bn>.* ("" = none) folded in, or a `merged` weight the caller built.  `in` may be a channel slice; the
+  // output is a fresh activation or the channel slice `into`; `res` is added before the activation (res_after: after it).
+  // kperm / Cin_padded (Linear layers whose input vector is laid out differently from the reference's torch.cat): K column k of the
+  // weight goes to column kperm[k] (< 0: dropped, another GEMM handles it) of Cin_padded columns.
+  struct ConvSpec {
+    std::string name, conv, bn;   // op name ("" = `conv`), parameter prefixes
+    Ref in, res, into;
+    int Cin = 0, Cout = 0, ks = 1, stride = 1;
+    int act = 0, relu_from = 0;   // 0 none, 1 ReLU, 2 sigmoid, 3 ReLU on the output channels >= relu_from only
+    int res_after = 0, Cin_padded = 0;
+    bool bias = false, linear = false;
+    const std::vector<int>* kperm = nullptr;
+    const Merged* merged = nullptr;
+    double flops = 0;             // per crop (0 = from the geometry)
+  };
+  int conv(const ConvSpec& s) {
+    const Act ain = e.acts[s.in.act];
+    const int Cin = s.Cin_padded ? s.Cin_padded : s.Cin, Cout = s.Cout, ks = s.ks;
     const int pad = (ks - 1) / 2;
-    const int Ho = (ain.H + 2 * pad - ks) / stride + 1, Wo = (ain.W + 2 * pad - ks) / stride + 1;
+    const int Ho = (ain.H + 2 * pad - ks) / s.stride + 1, Wo = (ain.W + 2 * pad - ks) / s.stride + 1;
     const int Cout16 = (Cout + 15) / 16 * 16;
-    std::vector<int64_t> wshape = is_linear ? std::vector<int64_t>{Cout, Cin_real}
-                                            : std::vector<int64_t>{Cout, Cin_real, ks, ks};
-    const HostParam* w = direct ? w_direct : P(convp + ".weight", wshape);
-    const HostParam* cb = direct ? b_direct : (has_bias ? P(convp + ".bias", {Cout}) : nullptr);
+    const std::vector<float>*w = nullptr, *cb = nullptr;
+    if (s.merged) {
+      if (s.merged->have) { w = &s.merged->w; cb = &s.merged->b; }
+    } else {
+      const HostParam* pw = P(s.conv + ".weight", s.linear ? std::vector<int64_t>{Cout, s.Cin} : std::vector<int64_t>{Cout, s.Cin, ks, ks});
+      const HostParam* pb = s.bias ? P(s.conv + ".bias", {Cout}) : nullptr;
+      if (pw) w = &pw->data;
+      if (pb) cb = &pb->data;
+    }
     std::vector<float> scale, shift;
-    bn_fold(bnp, cb, Cout, scale, shift);
+    bn_fold(s.bn, cb, Cout, scale, shift);
     Op op;
-    op.type = OP_CONV; op.name = name;
-    op.in = in; op.res = res; op.res_after = res_after;
-    op.Cin = Cin; op.Cout = Cout16; op.ks = ks; op.stride = stride; op.actfn = actfn;
-    op.flops = 2.0 * Ho * Wo * (double)Cout * Cin_real * ks * ks;
-    int out_act;
-    if (into.act >= 0) { out_act = into.act; op.out = into; }
-    else { out_act = new_act(Cout16, Ho, Wo); op.out = R(out_act); }
+    op.type = OP_CONV; op.name = s.name.empty() ? s.conv : s.name;
+    op.in = s.in; op.res = s.res; op.res_after = s.res_after;
+    op.Cin = Cin; op.Cout = Cout16; op.ks = ks; op.stride = s.stride; op.actfn = s.act; op.relu_from = s.relu_from;
+    op.flops = s.flops > 0 ? s.flops : 2.0 * Ho * Wo * (double)Cout * s.Cin * ks * ks;
+    op.out = s.into.act >= 0 ? s.into : R(new_act(Cout16, Ho, Wo));
     if (!declare && w) {
       std::vector<float> wsrc;
-      const float* wp = w->data.data();
-      if (kperm || Cin != Cin_real) {        // re-lay the K columns (Linear layers only: ks == 1)
+      const float* wp = w->data();
+      if (s.kperm || Cin != s.Cin) {        // re-lay the K columns (Linear layers only: ks == 1)
         wsrc.assign((size_t)Cout * Cin, 0.f);
         for (int o = 0; o < Cout; ++o)
-          for (int k = 0; k < Cin_real; ++k) {
-            const int dst = kperm ? (*kperm)[k] : k;
-            if (dst < 0) continue;      // column handled by another (split) GEMM
-            wsrc[(size_t)o * Cin + dst] = wp[(size_t)o * Cin_real + k];
+          for (int k = 0; k < s.Cin; ++k) {
+            const int dst = s.kperm ? (*s.kperm)[k] : k;
+            if (dst >= 0) wsrc[(size_t)o * Cin + dst] = wp[(size_t)o * s.Cin + k];
           }
         wp = wsrc.data();
       }
@@ -424,55 +507,59 @@ struct Builder {
       std::copy(shift.begin(), shift.end(), sh.begin());
       op.wdev = upload(packed);
       op.bdev = upload(sh);
+      // one more layout per Winograd form the op may run (every packer: OIHW weights x scale -> its fragment order)
+      auto layout = [&](bool on, size_t floats, void (*pack)(const float*, const float*, int, int, int, float*)) -> const float* {
+        if (!on) return nullptr;
+        std::vector<float> buf(floats);
+        pack(wp, scale.data(), Cout, Cin, Cout16, buf.data());
+        return upload(buf);
+      };
 #if POCO_EXPERIMENTS
-      if (e.opts.split_f16 && ks == 1 && !is_linear && Cin % 32 == 0 && ain.H * ain.W >= 16 && !kperm) {
-        std::vector<float> ph(gemm1x1h_packed_floats(Cin, Cout16));
-        gemm1x1h_pack_weights(wp, scale.data(), Cout, Cin, Cout16, ph.data());
-        op.wdev_h = upload(ph);
-      }
+      op.w.split_f16 = layout(e.opts.split_f16 && ks == 1 && !s.linear && Cin % 32 == 0 && ain.H * ain.W >= 16 && !s.kperm && !(s.merged && s.merged->stacked),
+                              gemm1x1h_packed_floats(Cin, Cout16), gemm1x1h_pack_weights);
 #endif
-      if (ks == 3 && stride == 1 && !is_linear) {
+      const ConvAlgs alg = conv_algs(e.opts, ain.H, ain.W, ks, s.stride, s.act);
+      if (alg.wino) {
         std::vector<float> wt, pu(conv_packed_weight_floats(Cin, Cout16, 4));
         conv_wino_transform_weights(wp, Cout, Cin, &wt);
         conv_pack_weights(wt.data(), scale.data(), Cout, Cin, 4, Cout16, pu.data());
-        op.wdev_wino = upload(pu);
-        if (ain.H >= e.opts.w4_min_plane && ain.W >= e.opts.w4_min_plane) {          // F(4x4,3x3): 56x56 / 28x28 planes, 14x14 (16 tiles per image, 31 % padding), 7x7 with ALG 13 only
-          std::vector<float> pu4(conv_wino4_packed_floats(Cin, Cout16));
-          if (ain.H >= 28 && ain.W >= 28) {
-            conv_wino4_pack_weights(wp, scale.data(), Cout, Cin, Cout16, pu4.data());
-            op.wdev_wino4 = upload(pu4);
-          }
-          if (ain.H >= 14 && ain.W >= 14) {
-            pu4.resize(conv_wino4p_packed_floats(Cin, Cout16));                           // other order (+ slack for the streamed requests)
-            conv_wino4p_pack_weights(wp, scale.data(), Cout, Cin, Cout16, pu4.data());
-            op.wdev_wino4p = upload(pu4);
-          }
-          pu4.resize(conv_wino4w_packed_floats(Cin, Cout16));                             // ALG 13: whole-position waves (+ slack)
-          conv_wino4w_pack_weights(wp, scale.data(), Cout, Cin, Cout16, pu4.data());
-          op.wdev_wino4w = upload(pu4);
-        }
-        if (ain.H <= e.opts.wg_max_plane && ain.W <= e.opts.wg_max_plane && ain.H * ain.W > 1 && actfn <= 1) {      // 7x7 planes: F(4x4,3x3) as 36 position GEMMs (ALG 11)
-          std::vector<float> pg(conv_wino4g_packed_floats(Cin, Cout16));
-          conv_wino4g_pack_weights(wp, scale.data(), Cout, Cin, Cout16, pg.data());
-          op.wdev_wino4g = upload(pg);
-          e.wino4g_scratch_need = std::max(e.wino4g_scratch_need, conv_wino4g_scratch_floats(e.max_batch, ain.H, ain.W, Cin, Cout16));
-        }
+        op.w.wino = upload(pu);
       }
+      op.w.wino4 = layout(alg.wino4, conv_wino4_packed_floats(Cin, Cout16), conv_wino4_pack_weights);
+      op.w.wino4p = layout(alg.wino4p, conv_wino4p_packed_floats(Cin, Cout16), conv_wino4p_pack_weights);      // (+ slack for the streamed requests)
+      op.w.wino4w = layout(alg.wino4w, conv_wino4w_packed_floats(Cin, Cout16), conv_wino4w_pack_weights);
+      op.w.wino4g = layout(alg.wino4g, conv_wino4g_packed_floats(Cin, Cout16), conv_wino4g_pack_weights);
+      if (alg.wino4g) e.wino4g_scratch_need = std::max(e.wino4g_scratch_need, conv_wino4g_scratch_floats(e.max_batch, ain.H, ain.W, Cin, Cout16));
     }
+    const int out_act = op.out.act;
     push(std::move(op));
     return out_act;
   }
 
-  int conv_bn(const std::string& pfx_conv, const std::string& pfx_bn, int in, int Cin, int Cout, int ks, int stride,
-              int relu, int res = -1, bool bias = false, int res_after = 0, Ref into = Ref()) {
-    return conv(pfx_conv, pfx_conv, pfx_bn, R(in), Cin, Cout, ks, stride, relu ? 1 : 0, bias,
-                res >= 0 ? R(res) : Ref(), res_after, into);
+  // short forms: conv + BN (+ ReLU), no conv bias ...
+  static ConvSpec bn_spec(const std::string& convp, const std::string& bnp, Ref in, int Cin, int Cout, int ks, int stride, int relu) {
+    ConvSpec s;
+    s.conv = convp; s.bn = bnp; s.in = in; s.Cin = Cin; s.Cout = Cout; s.ks = ks; s.stride = stride; s.act = relu ? 1 : 0;
+    return s;
+  }
+  int conv_bn(const std::string& convp, const std::string& bnp, int in, int Cin, int Cout, int ks, int stride, int relu, int res = -1) {
+    ConvSpec s = bn_spec(convp, bnp, R(in), Cin, Cout, ks, stride, relu);
+    if (res >= 0) s.res = R(res);
+    return conv(s);
+  }
+  // ... and an nn.Linear (or a 1x1 conv) with bias, no BN
+  static ConvSpec fc_spec(const std::string& convp, Ref in, int Cin, int Cout, int act, bool linear = true) {
+    ConvSpec s;
+    s.conv = convp; s.in = in; s.Cin = Cin; s.Cout = Cout; s.act = act; s.bias = true; s.linear = linear;
+    return s;
   }
 
   // ---- blocks --------------------------------------------------------------------------------
   int basic_block(const std::string& p, int x, int C, Ref into = Ref()) {           // hrnet.py:42-58
     int y = conv_bn(p + ".conv1", p + ".bn1", x, C, C, 3, 1, 1);
-    return conv_bn(p + ".conv2", p + ".bn2", y, C, C, 3, 1, 1, x, false, 0, into);
+    ConvSpec c2 = bn_spec(p + ".conv2", p + ".bn2", R(y), C, C, 3, 1, 1);
+    c2.res = R(x); c2.into = into;
+    return conv(c2);
   }
   // `cat` >= 0 (stride-1 block with a projection shortcut): x lives in channels [planes, planes + Cin) of the act `cat`.
   // conv2 then writes its output into channels [0, planes) of the same act and
@@ -480,43 +567,29 @@ struct Builder {
   // runs as ONE 1x1 conv over the planes + Cin channels: the 4*planes-wide tensor is written once instead of written
   // by the shortcut conv, re-read as a residual and written again (at 56x56 that is 2 x 205 MB per 64 crops).
   int bottleneck(const std::string& p, int x, int Cin, int planes, int stride, bool down, int cat = -1) {   // :79-99
+    const int Cout = planes * 4;
+    // [s3*W3 | sd*Wd] and b3 + bd of a block with a projection shortcut (the two weights are declared ahead of the BN tensors)
+    auto merged_shortcut = [&]() {
+      P(p + ".conv3.weight", {Cout, planes, 1, 1});
+      P(p + ".downsample.0.weight", {Cout, Cin, 1, 1});
+      return concat_k({{p + ".conv3", p + ".bn3", planes}, {p + ".downsample.0", p + ".downsample.1", Cin}}, Cout, 1);
+    };
     if (cat >= 0) {
-      const int Cout = planes * 4;
-      const int t1 = conv(p + ".conv1", p + ".conv1", p + ".bn1", R(cat, planes), Cin, planes, 1, 1, 1, false);
-      conv(p + ".conv2", p + ".conv2", p + ".bn2", R(t1), planes, planes, 3, 1, 1, false, Ref(), 0, R(cat, 0));
-      const HostParam* w3 = P(p + ".conv3.weight", {Cout, planes, 1, 1});
-      const HostParam* wd = P(p + ".downsample.0.weight", {Cout, Cin, 1, 1});
-      std::vector<float> s3, b3, sd, bd;
-      bn_fold(p + ".bn3", nullptr, Cout, s3, b3);
-      bn_fold(p + ".downsample.1", nullptr, Cout, sd, bd);
-      HostParam wm, bm;
-      const bool have = !declare && w3 && wd;
-      if (have) {
-        const int K = planes + Cin;
-        wm.shape = {Cout, K, 1, 1};
-        wm.data.resize((size_t)Cout * K);
-        bm.shape = {Cout};
-        bm.data.resize(Cout);
-        for (int o = 0; o < Cout; ++o) {
-          for (int k = 0; k < planes; ++k) wm.data[(size_t)o * K + k] = (float)((double)s3[o] * w3->data[(size_t)o * planes + k]);
-          for (int k = 0; k < Cin; ++k) wm.data[(size_t)o * K + planes + k] = (float)((double)sd[o] * wd->data[(size_t)o * Cin + k]);
-          bm.data[o] = (float)((double)b3[o] + (double)bd[o]);
-        }
-      }
-      return conv(p + ".conv3+downsample", "", "", R(cat, 0), planes + Cin, Cout, 1, 1, 1, true, Ref(), 0, Ref(), nullptr, 0,
-                  false, true, have ? &wm : nullptr, have ? &bm : nullptr);
+      const int t1 = conv(bn_spec(p + ".conv1", p + ".bn1", R(cat, planes), Cin, planes, 1, 1, 1));
+      ConvSpec c2 = bn_spec(p + ".conv2", p + ".bn2", R(t1), planes, planes, 3, 1, 1);
+      c2.into = R(cat, 0);
+      conv(c2);
+      const Merged m = merged_shortcut();
+      ConvSpec c3;
+      c3.name = p + ".conv3+downsample"; c3.in = R(cat, 0); c3.Cin = planes + Cin; c3.Cout = Cout; c3.act = 1; c3.merged = &m;
+      return conv(c3);
     }
     int y = conv_bn(p + ".conv1", p + ".bn1", x, Cin, planes, 1, 1, 1);
     y = conv_bn(p + ".conv2", p + ".bn2", y, planes, planes, 3, stride, 1);
-    if (down && stride == 2 && dual && !in_parallel && (planes * 4) % 64 == 0) {
+    if (down && stride == 2 && dual && !in_parallel && Cout % 64 == 0) {
       // bn3(conv3(t)) + bn_d(conv_d(x, stride 2)) as one GEMM over [t ; x(2y,2x)] (launch_gemm1x1_dual): no separate
       // shortcut tensor, no residual read
-      const int Cout = planes * 4;
-      const HostParam* w3 = P(p + ".conv3.weight", {Cout, planes, 1, 1});
-      const HostParam* wd = P(p + ".downsample.0.weight", {Cout, Cin, 1, 1});
-      std::vector<float> s3, b3, sd, bd;
-      bn_fold(p + ".bn3", nullptr, Cout, s3, b3);
-      bn_fold(p + ".downsample.1", nullptr, Cout, sd, bd);
+      const Merged m = merged_shortcut();
       const Act at = e.acts[y];
       Op op;
       op.type = OP_DUAL1X1; op.name = p + ".conv3+downsample";
@@ -524,24 +597,17 @@ struct Builder {
       const int o = new_act(Cout, at.H, at.W);
       op.out = R(o);
       op.flops = 2.0 * at.H * at.W * (double)Cout * (planes + Cin);
-      if (!declare && w3 && wd) {
-        const int K = planes + Cin;
-        std::vector<float> wm((size_t)Cout * K), bm(Cout), ones(Cout, 1.f);
-        for (int c = 0; c < Cout; ++c) {
-          for (int k = 0; k < planes; ++k) wm[(size_t)c * K + k] = (float)((double)s3[c] * w3->data[(size_t)c * planes + k]);
-          for (int k = 0; k < Cin; ++k) wm[(size_t)c * K + planes + k] = (float)((double)sd[c] * wd->data[(size_t)c * Cin + k]);
-          bm[c] = (float)((double)b3[c] + (double)bd[c]);
-        }
-        std::vector<float> packed(conv_packed_weight_floats(K, Cout, 1));
-        conv_pack_weights(wm.data(), ones.data(), Cout, K, 1, Cout, packed.data());
-        op.wdev = upload(packed); op.bdev = upload(bm);
+      if (m.have) {
+        std::vector<float> packed(conv_packed_weight_floats(planes + Cin, Cout, 1));
+        conv_pack_weights(m.w.data(), nullptr, Cout, planes + Cin, 1, Cout, packed.data());
+        op.wdev = upload(packed); op.bdev = upload(m.b);
       }
       push(std::move(op));
       return o;
     }
     int r = x;
-    if (down) r = conv_bn(p + ".downsample.0", p + ".downsample.1", x, Cin, planes * 4, 1, stride, 0);
-    return conv_bn(p + ".conv3", p + ".bn3", y, planes, planes * 4, 1, 1, 1, r);
+    if (down) r = conv_bn(p + ".downsample.0", p + ".downsample.1", x, Cin, Cout, 1, stride, 0);
+    return conv_bn(p + ".conv3", p + ".bn3", y, planes, Cout, 1, 1, 1, r);
   }
 
   // conv3 + residual + ReLU of block `pa` chained with conv1 + ReLU of block `pb` (planes = 64; csrc/bneck_chain.hip):
@@ -625,10 +691,8 @@ struct Builder {
   struct SubConv { std::string convp, bnp; int Cout; int relu; };
   int conv_multi(const std::string& name, const std::vector<SubConv>& subs, Ref in, int Cin, int ks, int stride,
                  std::vector<int>* offsets, Ref into = Ref()) {
-    const Act ain = e.acts[in.act];
-    const int pad = (ks - 1) / 2;
-    const int Ho = (ain.H + 2 * pad - ks) / stride + 1, Wo = (ain.W + 2 * pad - ks) / stride + 1;
     int Ctot = 0, relu_from = -1;
+    std::vector<MergeSrc> srcs;
     offsets->clear();
     for (const SubConv& sc : subs) {
       if (sc.Cout % 16) { ok = false; e.err += "conv_multi: member widths must be multiples of 16; "; }
@@ -636,35 +700,14 @@ struct Builder {
       if (!sc.relu && relu_from >= 0) { ok = false; e.err += "conv_multi: ReLU members must come last; "; }
       offsets->push_back(Ctot + (into.act >= 0 ? into.co : 0));
       Ctot += sc.Cout;
+      srcs.push_back({sc.convp, sc.bnp, sc.Cout});
     }
-    const size_t per = (size_t)Cin * ks * ks;
-    std::vector<float> wcat, scat, hcat;
-    bool have = !declare;
-    for (const SubConv& sc : subs) {
-      const HostParam* w = P(sc.convp + ".weight", {sc.Cout, Cin, ks, ks});
-      std::vector<float> scale, shift;
-      bn_fold(sc.bnp, nullptr, sc.Cout, scale, shift);
-      if (declare || !w) { have = false; continue; }
-      wcat.insert(wcat.end(), w->data.begin(), w->data.begin() + (size_t)sc.Cout * per);
-      scat.insert(scat.end(), scale.begin(), scale.end());
-      hcat.insert(hcat.end(), shift.begin(), shift.end());
-    }
-    Op op;
-    op.type = OP_CONV; op.name = name;
-    op.in = in; op.Cin = Cin; op.Cout = Ctot; op.ks = ks; op.stride = stride;
-    op.actfn = relu_from < 0 ? 0 : (relu_from == 0 ? 1 : 3);
-    op.relu_from = std::max(relu_from, 0);
-    op.flops = 2.0 * Ho * Wo * (double)Ctot * Cin * ks * ks;
-    const int out_act = into.act >= 0 ? into.act : new_act(Ctot, Ho, Wo);
-    op.out = into.act >= 0 ? into : R(out_act);
-    if (have) {
-      std::vector<float> packed(conv_packed_weight_floats(Cin, Ctot, ks));
-      conv_pack_weights(wcat.data(), scat.data(), Ctot, Cin, ks, Ctot, packed.data());
-      op.wdev = upload(packed);
-      op.bdev = upload(hcat);
-    }
-    push(std::move(op));
-    return out_act;
+    const Merged m = stack_rows(srcs, {Cin, ks, ks});
+    ConvSpec c;
+    c.name = name; c.in = in; c.Cin = Cin; c.Cout = Ctot; c.ks = ks; c.stride = stride; c.into = into; c.merged = &m;
+    c.act = relu_from < 0 ? 0 : (relu_from == 0 ? 1 : 3);
+    c.relu_from = std::max(relu_from, 0);
+    return conv(c);
   }
 
   // HighResolutionModule.forward, hrnet.py:248-266.  last_into: write branch-0 output into a wider
@@ -673,7 +716,7 @@ struct Builder {
   // branch chains form ONE parallel region (lane i = sum_i, then the 8 convs of branch i): one join less per
   // module, and a lane's sum overlaps the other lanes' first convs.
   bool region_open = false;
-  // K-merge (round 3; `kmerge`, POCO_NO_KMERGE=1 restores the separate form): the sum of the lowest-resolution branch T = nb-1,
+  // K-merge (round 3; option `kmerge`, kmerge=0 restores the separate form): the sum of the lowest-resolution branch T = nb-1,
   //     y_T = relu(x_T + sum_{j<T} bn_j(conv_j(t_j)))        (t_j = running tensor of down path j -> T before its last conv),
   // is ONE stride-2 3x3 conv over the channel concatenation [t_{T-2} | ... | t_0 | x_{T-1}] with the BN-folded weights
   // concatenated along K, the summed shifts as bias, x_T as the residual and the ReLU in the epilogue: T launches and the
@@ -713,7 +756,7 @@ struct Builder {
     // need no synchronisation at all (round 2 joined all lanes after the chains and again after the first fuse convs and spread the
     // fuse convs round-robin over the lanes): a lane that finishes its chain early does its fuse convs while the slowest chain is
     // still running, and behind the slowest chain only its own fuse convs remain before the join in front of the sums.
-    // W48-CLIFF 64 crops 4508 -> 4654 crops/s (+3.2 %), PARE 32 crops +3.3 %, W48 16 crops +6.5 % (same box, POCO_NO_XDEP=1 against default).
+    // W48-CLIFF 64 crops 4508 -> 4654 crops/s (+3.2 %), PARE 32 crops +3.3 %, W48 16 crops +6.5 % (same box, option xdep=0 against default).
     const bool dag = xdep && !region_seq;
     auto BL = [&](int i) { return i < (int)lmap.size() ? lmap[i] - '0' : i; };
     if (!dag) end_parallel();
@@ -768,9 +811,10 @@ struct Builder {
           const bool lastk = (k == i - j - 1);
           const bool to_kc = merged && kc >= 0 && k == i - j - 2;
           const std::string qq = fl(i, j) + "." + std::to_string(k);
-          const int y = conv(qq + ".0", qq + ".0", qq + ".1", t, ch[j], lastk ? ch[i] : ch[j], 3, 2, lastk ? 0 : 1, false,
-                             Ref(), 0, to_kc ? R(kc, kc_off[j]) : Ref());
-          t = to_kc ? R(kc, kc_off[j]) : R(y);
+          ConvSpec c = bn_spec(qq + ".0", qq + ".1", t, ch[j], lastk ? ch[i] : ch[j], 3, 2, lastk ? 0 : 1);
+          if (to_kc) c.into = R(kc, kc_off[j]);
+          const int y = conv(c);
+          t = to_kc ? c.into : R(y);
         }
         terms[i][j] = {t, 0};
       }
@@ -801,42 +845,25 @@ struct Builder {
     std::vector<int> order;
     for (int j = T - 2; j >= 0; --j) order.push_back(j);
     order.push_back(T - 1);
-    int K = 0;
-    for (int j : order) K += ch[j];
-    const int Cout = ch[T];
-    HostParam wm, bm;
-    wm.shape = {Cout, K, 3, 3};
-    bm.shape = {Cout};
-    bool have = !declare;
-    std::vector<double> bsum(Cout, 0.0);
-    if (have) wm.data.assign((size_t)Cout * K * 9, 0.f);
-    int koff = 0;
+    std::vector<MergeSrc> srcs;
     for (int j : order) {
       const std::string q = fl(T, j) + "." + std::to_string(T - j - 1);
-      const HostParam* w = P(q + ".0.weight", {Cout, ch[j], 3, 3});
-      std::vector<float> scale, shift;
-      bn_fold(q + ".1", nullptr, Cout, scale, shift);
-      if (declare || !w) have = false;
-      if (have) {
-        for (int o = 0; o < Cout; ++o) {
-          for (int c = 0; c < ch[j]; ++c)
-            for (int t = 0; t < 9; ++t)
-              wm.data[((size_t)o * K + koff + c) * 9 + t] = (float)((double)scale[o] * w->data[((size_t)o * ch[j] + c) * 9 + t]);
-          bsum[o] += (double)shift[o];
-        }
-      }
-      koff += ch[j];
+      srcs.push_back({q + ".0", q + ".1", ch[j]});
     }
-    if (have) { bm.data.resize(Cout); for (int o = 0; o < Cout; ++o) bm.data[o] = (float)bsum[o]; }
-    return conv(p + ".fuse" + std::to_string(T) + "+down", "", "", in, K, Cout, 3, 2, 1, true, res, 0, Ref(), nullptr, 0, false, true,
-                have ? &wm : nullptr, have ? &bm : nullptr);
+    const Merged m = concat_k(srcs, ch[T], 3);
+    ConvSpec c;
+    c.name = p + ".fuse" + std::to_string(T) + "+down"; c.in = in; c.Cout = ch[T]; c.ks = 3; c.stride = 2; c.act = 1; c.res = res; c.merged = &m;
+    for (const MergeSrc& sr : srcs) c.Cin += sr.C;
+    return conv(c);
   }
 
   // stem + layer1 + transitions + stages 2-4 (hrnet.py:466-497 / hrnet_cls.py:438-469)
   std::vector<int> hrnet_trunk(const std::string& p, int w, Ref final_out0 = Ref(), bool open_after = false) {
     int x = stem(p, 3, 224);
     const int cat = kcat ? new_act(128, 56, 56) : -1;      // [layer1.0 conv2 output | stem output], see bottleneck()
-    x = conv_bn(p + "conv2", p + "bn2", x, 64, 64, 3, 2, 1, -1, false, 0, kcat ? R(cat, 64) : Ref());
+    ConvSpec c2 = bn_spec(p + "conv2", p + "bn2", R(x), 64, 64, 3, 2, 1);
+    if (kcat) c2.into = R(cat, 64);
+    x = conv(c2);
     x = layer1(p + "layer1.", x, cat, 4);
     std::vector<int> ys = {x};
     std::vector<int> prev_ch = {256};
@@ -1043,7 +1070,7 @@ bool build_graph(Engine& e, bool declare) {
     const bool up_lanes = e.opts.up_lanes;
     std::vector<int> ys = b.hrnet_trunk(bp, 32, Builder::R(feat480, 0), /*open_after=*/up_lanes);
     // hrnet.py:515-519: bilinear x2 (align_corners) + conv3x3 + BN + ReLU chains, channel concat.  The three chains are
-    // independent: each one continues on the lane that ran its branch's fuse sum of the last module (POCO_NO_UP_LANES=1: one
+    // independent: each one continues on the lane that ran its branch's fuse sum of the last module (option up_lanes=0: one
     // after the other on one stream, the round-2 form)
     const int chs[4] = {32, 64, 128, 256};
     const int offs[4] = {0, 32, 96, 224};
@@ -1061,9 +1088,9 @@ bool build_graph(Engine& e, bool declare) {
         b.push(std::move(up));
         const std::string q = bp + "upsample_stage_" + std::to_string(br + 1) + ".";
         const bool lastt = (t == br - 1);
-        y = b.conv(q + std::to_string(1 + 4 * t), q + std::to_string(1 + 4 * t), q + std::to_string(2 + 4 * t),
-                   Builder::R(u), chs[br], chs[br], 3, 1, 1, false, Ref(), 0,
-                   lastt ? Builder::R(feat480, offs[br]) : Ref());
+        Builder::ConvSpec c = Builder::bn_spec(q + std::to_string(1 + 4 * t), q + std::to_string(2 + 4 * t), Builder::R(u), chs[br], chs[br], 3, 1, 1);
+        if (lastt) c.into = Builder::R(feat480, offs[br]);
+        y = b.conv(c);
       }
     }
     if (up_open) b.end_parallel();
@@ -1091,9 +1118,13 @@ bool build_graph(Engine& e, bool declare) {
     for (int i = 0; i < 3; ++i) {
       const std::string q = bp + "downsamp_modules." + std::to_string(i);
       // hrnet_cls.py:475-477:  incre(y_{i+1}) + ReLU(BN(conv_s2(y)))   -> residual added after the ReLU
-      y = b.conv_bn(q + ".0", q + ".1", y, hc[i] * 4, hc[i + 1] * 4, 3, 2, 1, inc[i + 1], true, 1);
+      Builder::ConvSpec c = Builder::bn_spec(q + ".0", q + ".1", Builder::R(y), hc[i] * 4, hc[i + 1] * 4, 3, 2, 1);
+      c.bias = true; c.res = Builder::R(inc[i + 1]); c.res_after = 1;
+      y = b.conv(c);
     }
-    y = b.conv_bn(bp + "final_layer.0", bp + "final_layer.1", y, 1024, 2048, 1, 1, 1, -1, true);
+    Builder::ConvSpec fin = Builder::bn_spec(bp + "final_layer.0", bp + "final_layer.1", Builder::R(y), 1024, 2048, 1, 1, 1);
+    fin.bias = true;
+    y = b.conv(fin);
     Op ap; ap.type = OP_AVGPOOL; ap.name = bp + "avgpool"; ap.in = Builder::R(y); ap.out = Builder::R(xc, 0);
     b.push(std::move(ap));
     b.P(bp + "classifier.weight", {1000, 2048}, 0);
@@ -1153,40 +1184,25 @@ bool build_graph(Engine& e, bool declare) {
     }
     b.push(std::move(bc));
     add_copy(b, hp + "bbox_info", Builder::X(X_BBOX), Builder::R(xc, XC_BBOX), 3);
-    std::vector<int> perm(2208);
-    for (int k = 0; k < 2048; ++k) perm[k] = k;
-    for (int k = 0; k < 3; ++k) perm[2048 + k] = XC_BBOX + k;
-    for (int k = 0; k < 157; ++k) perm[2051 + k] = XC_STATE + k;
     // decpose/decshape/deccam fused into one [157,1024] matrix: declared separately, stacked here
-    const HostParam* dp = b.P(hp + "decpose.weight", {144, 1024});
-    const HostParam* dpb = b.P(hp + "decpose.bias", {144});
-    const HostParam* ds = b.P(hp + "decshape.weight", {10, 1024});
-    const HostParam* dsb = b.P(hp + "decshape.bias", {10});
-    const HostParam* dc = b.P(hp + "deccam.weight", {3, 1024});
-    const HostParam* dcb = b.P(hp + "deccam.bias", {3});
-    HostParam decW, decB;
-    const bool have_dec = !declare && dp && ds && dc && dpb && dsb && dcb;
-    if (have_dec) {
-      decW.shape = {157, 1024}; decB.shape = {157};
-      decW.data = dp->data; decW.data.insert(decW.data.end(), ds->data.begin(), ds->data.end());
-      decW.data.insert(decW.data.end(), dc->data.begin(), dc->data.end());
-      decB.data = dpb->data; decB.data.insert(decB.data.end(), dsb->data.begin(), dsb->data.end());
-      decB.data.insert(decB.data.end(), dcb->data.begin(), dcb->data.end());
-    }
+    const Builder::Merged dec = b.stack_rows({{hp + "decpose", "", 144, true}, {hp + "decshape", "", 10, true}, {hp + "deccam", "", 3, true}}, {1024});
     // fc1 is linear and [feat, bbox] never change over the 3 iterations (cliff_head.py:103-113): its
     // 2048-column feature part (+bias) is evaluated once, each iteration only adds the 176-column
     // [bbox | pose | shape | cam] part on top (residual epilogue).
+    // (reference column order [feat 2048 | bbox 3 | state 157] -> columns of xc; the state part is addressed from column 2048)
     std::vector<int> perm_feat(2208, -1), perm_state(2208, -1);
     for (int k = 0; k < 2048; ++k) perm_feat[k] = k;
-    for (int k = 2048; k < 2208; ++k) perm_state[k] = perm[k] - 2048;
-    int h0 = b.conv(hp + "fc1.feat", hp + "fc1", "", Builder::R(xc, 0), 2208, 1024, 1, 1, 0, true, Ref(), 0, Ref(),
-                    &perm_feat, 2048, true);
-    (fuse ? mlp_sub : e.ops).back().flops = 2.0 * 1024 * 2048;
+    for (int k = 0; k < 3; ++k) perm_state[2048 + k] = XC_BBOX - 2048 + k;
+    for (int k = 0; k < 157; ++k) perm_state[2051 + k] = XC_STATE - 2048 + k;
+    Builder::ConvSpec fc1 = Builder::fc_spec(hp + "fc1", Builder::R(xc, 0), 2208, 1024, 0);
+    fc1.name = hp + "fc1.feat"; fc1.kperm = &perm_feat; fc1.Cin_padded = 2048; fc1.flops = 2.0 * 1024 * 2048;
+    int h0 = b.conv(fc1);
     const int u = b.new_act(448, 1, 1, true);       // [sigmoid(featNet(feat)) 216 | pad | sigmoid(poseNet(R)) 216 | pad] (poco_head.py:122-141)
+    Builder::ConvSpec feat_net = Builder::fc_spec(up + "uncert_fc_featNet", Builder::R(xc, 0), 2048, 216, 2);
+    feat_net.into = Builder::R(u, 0);
     if (fuse) {
       b.cur_stage = 3;
-      b.conv(up + "uncert_fc_featNet", up + "uncert_fc_featNet", "", Builder::R(xc, 0), 2048, 216, 1, 1, 2, true, Ref(), 0,
-             Builder::R(u, 0), nullptr, 0, true);
+      b.conv(feat_net);
       b.cur_stage = 6;
       add_copy(b, "out.uncert_feat", Builder::R(xc, 0), Builder::X(Y_UFEAT), 2048);
     }
@@ -1194,23 +1210,26 @@ bool build_graph(Engine& e, bool declare) {
     for (int it = 0; it < 3; ++it) {
       const std::string sfx = "#" + std::to_string(it);
       b.cur_stage = 1 + 3 * it;
-      int h1 = b.conv(hp + "fc1.state" + sfx, hp + "fc1", "", Builder::R(xc, 2048), 2208, 1024, 1, 1, 0, false, Builder::R(h0), 0,
-                      Ref(), &perm_state, XC_DIM - 2048, true);
-      (fuse ? mlp_sub : e.ops).back().flops = 2.0 * 1024 * 160;
+      fc1.name = hp + "fc1.state" + sfx; fc1.in = Builder::R(xc, 2048); fc1.bias = false; fc1.res = Builder::R(h0);
+      fc1.kperm = &perm_state; fc1.Cin_padded = XC_DIM - 2048; fc1.flops = 2.0 * 1024 * 160;
+      int h1 = b.conv(fc1);
       b.cur_stage = 2 + 3 * it;
-      h2 = b.conv(hp + "fc2" + sfx, hp + "fc2", "", Builder::R(h1), 1024, 1024, 1, 1, 0, true, Ref(), 0, Ref(),
-                  nullptr, 0, true);
+      Builder::ConvSpec fc2 = Builder::fc_spec(hp + "fc2", Builder::R(h1), 1024, 1024, 0);
+      fc2.name = hp + "fc2" + sfx;
+      h2 = b.conv(fc2);
       // fused decoder: state += dec(h2)  (in place on the state slice of xc)
       b.cur_stage = 3 + 3 * it;
-      b.conv(hp + "dec" + sfx, "", "", Builder::R(h2), 1024, 157, 1, 1, 0, true, Builder::R(xc, XC_STATE), 0,
-             Builder::R(xc, XC_STATE), nullptr, 0, true, true, have_dec ? &decW : nullptr, have_dec ? &decB : nullptr);
+      Builder::ConvSpec d;
+      d.name = hp + "dec" + sfx; d.in = Builder::R(h2); d.Cin = 1024; d.Cout = 157; d.linear = true; d.merged = &dec;
+      d.res = d.into = Builder::R(xc, XC_STATE);
+      b.conv(d);
     }
     int rot = b.new_act(224, 1, 1, true);
     b.cur_stage = 10;
     { Op op; op.type = OP_ROT6D; op.name = hp + "rot6d"; op.in = Builder::R(xc, XC_STATE); op.out = Builder::R(rot);
       op.out2 = Builder::X(Y_POSE); b.push(std::move(op)); }
     // the tail is two independent chains of small kernels: SMPL-LBS + camera on one lane, the output copies and the confidence
-    // MLP on another (POCO_NO_TAIL_LANES=1: one stream)
+    // MLP on another (option tail_lanes=0: one stream)
     if (!fuse && b.tail_lanes) { b.begin_parallel(9); b.lane(1); }
     add_copy(b, "out.pred_pose6d", Builder::R(xc, XC_STATE), Builder::X(Y_POSE6D), 144);
     add_copy(b, "out.pred_shape", Builder::R(xc, XC_STATE + 144), Builder::X(Y_SHAPE), 10);
@@ -1231,13 +1250,13 @@ bool build_graph(Engine& e, bool declare) {
     build_tail(b, Builder::R(xc, XC_STATE + 144), Builder::R(rot), Builder::R(xc, XC_STATE + 154), true);
     if (b.tail_lanes) b.lane(1);
     // poco_head 'feat-pose-net' (poco_head.py:122-141): sigmoid(featNet(feat)) || sigmoid(poseNet(R)) -> fc1 -> sigmoid
-    if (!fuse)
-      b.conv(up + "uncert_fc_featNet", up + "uncert_fc_featNet", "", Builder::R(xc, 0), 2048, 216, 1, 1, 2, true, Ref(), 0,
-             Builder::R(u, 0), nullptr, 0, true);
-    b.conv(up + "uncert_fc_poseNet", up + "uncert_fc_poseNet", "", Builder::R(rot), 216, 216, 1, 1, 2, true, Ref(), 0,
-           Builder::R(u, 216), nullptr, 224, true);
-    int var = b.conv(up + "uncert_fc1", up + "uncert_fc1", "", Builder::R(u), 432, 24, 1, 1, 2, true, Ref(), 0, Ref(),
-                     nullptr, 448, true);
+    if (!fuse) b.conv(feat_net);
+    Builder::ConvSpec pose_net = Builder::fc_spec(up + "uncert_fc_poseNet", Builder::R(rot), 216, 216, 2);
+    pose_net.into = Builder::R(u, 216); pose_net.Cin_padded = 224;
+    b.conv(pose_net);
+    Builder::ConvSpec ufc1 = Builder::fc_spec(up + "uncert_fc1", Builder::R(u), 432, 24, 2);
+    ufc1.Cin_padded = 448;
+    int var = b.conv(ufc1);
     add_copy(b, "out.var_pose", Builder::R(var), Builder::X(Y_VAR), 24);
     add_record(b, Builder::R(var), true);
     if (b.tail_lanes) b.end_parallel();
@@ -1250,10 +1269,10 @@ bool build_graph(Engine& e, bool declare) {
     };
     if (b.tail_lanes) { b.begin_parallel(9); b.lane(0); }
     int kp = branch("keypoint_deconv_layers");
-    int heat = b.conv(hp + "keypoint_final_layer", hp + "keypoint_final_layer", "", Builder::R(kp), 128, 25, 1, 1, 0, true);
+    int heat = b.conv(Builder::fc_spec(hp + "keypoint_final_layer", Builder::R(kp), 128, 25, 0, /*linear=*/false));
     if (b.tail_lanes) b.lane(1);
     int sm = branch("smpl_deconv_layers");
-    int cs = b.conv(hp + "smpl_final_layer", hp + "smpl_final_layer", "", Builder::R(sm), 128, 64, 1, 1, 0, true);
+    int cs = b.conv(Builder::fc_spec(hp + "smpl_final_layer", Builder::R(sm), 128, 64, 0, /*linear=*/false));
     if (b.tail_lanes) b.end_parallel();
     int xu = b.new_act(XU_DIM, 1, 1, true);
     int flat = b.new_act(1536, 1, 1, true);
@@ -1269,19 +1288,10 @@ bool build_graph(Engine& e, bool declare) {
       if (!declare && w) op.wdev = b.upload(w->data);
       b.push(std::move(op)); }
     // shape_mlp (10) and cam_mlp (3) stacked into one [13,1536] matrix (pare_head.py:902-906)
-    const HostParam* sw = b.P(hp + "shape_mlp.weight", {10, 1536});
-    const HostParam* sb = b.P(hp + "shape_mlp.bias", {10});
-    const HostParam* cw = b.P(hp + "cam_mlp.weight", {3, 1536});
-    const HostParam* cb = b.P(hp + "cam_mlp.bias", {3});
-    HostParam scW, scB;
-    const bool have_sc = !declare && sw && sb && cw && cb;
-    if (have_sc) {
-      scW.shape = {13, 1536}; scB.shape = {13};
-      scW.data = sw->data; scW.data.insert(scW.data.end(), cw->data.begin(), cw->data.end());
-      scB.data = sb->data; scB.data.insert(scB.data.end(), cb->data.begin(), cb->data.end());
-    }
-    int sc13 = b.conv(hp + "shape_cam_mlp", "", "", Builder::R(flat), 1536, 13, 1, 1, 0, true, Ref(), 0, Ref(), nullptr, 0,
-                      true, true, have_sc ? &scW : nullptr, have_sc ? &scB : nullptr);
+    const Builder::Merged sc = b.stack_rows({{hp + "shape_mlp", "", 10, true}, {hp + "cam_mlp", "", 3, true}}, {1536});
+    Builder::ConvSpec scs;
+    scs.name = hp + "shape_cam_mlp"; scs.in = Builder::R(flat); scs.Cin = 1536; scs.Cout = 13; scs.linear = true; scs.merged = &sc;
+    int sc13 = b.conv(scs);
     e.acts[sc13].persistent = true;
     { Op op; op.type = OP_ROT6D; op.name = hp + "rot6d"; op.in = Builder::R(pose6d); op.out = Builder::R(xu, 3072);
       op.out2 = Builder::X(Y_POSE); b.push(std::move(op)); }
@@ -1302,10 +1312,10 @@ bool build_graph(Engine& e, bool declare) {
     build_tail(b, Builder::R(sc13, 0), Builder::R(xu, 3072), Builder::R(sc13, 10), false);
     if (b.tail_lanes) b.lane(1);
     // poco_head 'feat-pose' (poco_head.py:134-141): sigmoid(fc2(sigmoid(fc1([feat; R]))))
-    int h = b.conv(up + "uncert_fc1", up + "uncert_fc1", "", Builder::R(xu), 3288, 512, 1, 1, 2, true, Ref(), 0, Ref(),
-                   nullptr, XU_DIM, true);
-    int var = b.conv(up + "uncert_fc2", up + "uncert_fc2", "", Builder::R(h), 512, 24, 1, 1, 2, true, Ref(), 0, Ref(),
-                     nullptr, 0, true);
+    Builder::ConvSpec ufc1 = Builder::fc_spec(up + "uncert_fc1", Builder::R(xu), 3288, 512, 2);
+    ufc1.Cin_padded = XU_DIM;
+    int h = b.conv(ufc1);
+    int var = b.conv(Builder::fc_spec(up + "uncert_fc2", Builder::R(h), 512, 24, 2));
     add_copy(b, "out.var_pose", Builder::R(var), Builder::X(Y_VAR), 24);
     add_record(b, Builder::R(var), false);
     if (b.tail_lanes) b.end_parallel();
@@ -1435,6 +1445,39 @@ inline float* aptr(Engine& e, const Ref& r) {
 inline float* sptr(Engine& e, int act) { const Act& a = e.acts[act]; return e.ws + a.off; }
 inline int astride(Engine& e, const Ref& r) { return e.acts[r.act].C; }   // valid for vector acts (H=W=1)
 
+// The geometry of a conv op at batch B (no pointers: valid before finalize): what the launch, the default configuration and the
+// validation of a configuration see
+ConvDesc conv_desc_of(const Engine& e, const Op& op, int B) {
+  const Act& ai = e.acts[op.in.act];
+  ConvDesc d{};
+  d.B = B; d.H = ai.H; d.W = ai.W; d.Cin = op.Cin; d.Cout = op.Cout; d.ks = op.ks; d.stride = op.stride;
+  d.in_cs = ai.C; d.out_cs = e.acts[op.out.act].C;
+  d.act = op.actfn; d.res_after_act = op.res_after; d.relu_from = op.relu_from;
+  return d;
+}
+
+// An OP_COPY / OP_BCAST / OP_ROT6D op as a row job: a sub-op of the fused regressor (mlp_chain.hip) or a launch of its own.
+// A missing input is an error; an output the caller did not ask for leaves J->dst NULL (the job is skipped).
+int row_job_of(Engine& e, const Op& op, const IO& io, MlpRowJob* J) {
+  *J = MlpRowJob{};
+  J->n = op.n;
+  if (op.type == OP_ROT6D) {
+    J->kind = MLP_ROW_ROT6D;
+    J->dst2 = ext_out(io, op.out2.ext); J->dst2_rs = 216;
+  } else if (op.type == OP_BCAST) {
+    J->kind = MLP_ROW_BCAST; J->src = op.wdev;
+  } else if (op.type == OP_COPY) {
+    J->kind = MLP_ROW_COPY;
+  } else { poco_set_error("forward: " + op.name + " is not a row job"); return POCO_ERR_STATE; }
+  if (op.in.ext) {
+    J->src = ext_in(io, op.in.ext); J->src_rs = op.n;
+    if (!J->src) { poco_set_error("forward: missing input for " + op.name); return POCO_ERR_ARG; }
+  } else if (op.in.act >= 0) { J->src = aptr(e, op.in); J->src_rs = astride(e, op.in); }
+  if (op.out.ext) { J->dst = ext_out(io, op.out.ext); J->dst_rs = op.n; }
+  else { J->dst = aptr(e, op.out); J->dst_rs = astride(e, op.out); }
+  return POCO_OK;
+}
+
 int run_op(Engine& e, Op& op, int B, const IO& io, hipStream_t s) {
   switch (op.type) {
     case OP_STEM: {
@@ -1446,19 +1489,16 @@ int run_op(Engine& e, Op& op, int B, const IO& io, hipStream_t s) {
     case OP_CONV: {
       const Act& ai = e.acts[op.in.act];
       const Act& ao = e.acts[op.out.act];
-      ConvDesc d{};
-      d.in = aptr(e, op.in); d.in_cs = ai.C; d.in_co = 0;
+      ConvDesc d = conv_desc_of(e, op, B);
+      d.in = aptr(e, op.in);
       if (op.res.act >= 0) { d.res = aptr(e, op.res); d.res_cs = e.acts[op.res.act].C; }
-      d.out = aptr(e, op.out); d.out_cs = ao.C; d.out_co = 0;
-      d.wfrag = op.wdev; d.bias = op.bdev; d.wfrag_wino = op.wdev_wino; d.wfrag_wino4 = op.wdev_wino4; d.wfrag_wino4p = op.wdev_wino4p; d.wfrag_wino4w = op.wdev_wino4w;
-      d.wfrag_wino4g = op.wdev_wino4g; d.scratch = e.wino4g_scratch[op.lane & 3]; d.scratch_floats = e.wino4g_scratch_need;
+      d.out = aptr(e, op.out);
+      d.wfrag = op.wdev; d.bias = op.bdev; d.w = op.w;
+      d.scratch = e.wino4g_scratch[op.lane & 3]; d.scratch_floats = e.wino4g_scratch_need;
       d.sk_scratch = e.sk_scratch[op.lane & 3]; d.sk_scratch_floats = d.sk_scratch ? gemm1x1sk_scratch_floats() : 0; d.sk_err_host = e.mlp_err_host; d.sk_max_spins = (unsigned)e.opts.debug_wait_spins;
-      d.B = B; d.H = ai.H; d.W = ai.W; d.Cin = op.Cin; d.Cout = op.Cout; d.ks = op.ks; d.stride = op.stride;
-      d.act = op.actfn; d.res_after_act = op.res_after; d.relu_from = op.relu_from;
       auto it = op.cfg.find(B);
       if (it == op.cfg.end()) it = op.cfg.emplace(B, conv_default_cfg(d)).first;
-      if (op.wdev_h && (op.in.co & 31) == 0) {          // split-fp16 experiment: every plain 1x1 conv runs on ALG 12
-        d.wfrag_h = op.wdev_h;
+      if (op.w.split_f16 && (op.in.co & 31) == 0) {          // split-fp16 experiment: every plain 1x1 conv runs on ALG 12
         const int nT16 = op.Cout / 16;
         const long Pout = (long)B * ((ai.H - 1) / op.stride + 1) * ((ai.W - 1) / op.stride + 1);
         const bool tiled = Pout >= 2048 && nT16 >= 4;      // 128 x 128 block tiles (LDS-staged, converted once per block)
@@ -1476,7 +1516,7 @@ int run_op(Engine& e, Op& op, int B, const IO& io, hipStream_t s) {
           Op& nx = e.ops[k + 1];
           auto nit = nx.cfg.find(B);
           if (nx.type == OP_CONV && nx.phase == op.phase && nx.lane == op.lane && nx.in.act == op.out.act && nx.in.co == 0 &&
-              op.out.co == 0 && nit != nx.cfg.end() && nit->second.ALG == 11 && nx.wdev_wino4g && ao.C == op.Cout &&
+              op.out.co == 0 && nit != nx.cfg.end() && nit->second.ALG == 11 && nx.w.wino4g && ao.C == op.Cout &&
               conv_wino4g_can_chain(ai.H, ai.W, op.Cout, nx.Cin) &&
               std::max(op.Cin, op.Cout) == std::max(nx.Cin, nx.Cout)) {      // both convs split the lane's scratch into V | M the same way
             d.wg_emit_next = 1;
@@ -1527,9 +1567,15 @@ int run_op(Engine& e, Op& op, int B, const IO& io, hipStream_t s) {
     case OP_LC2D:
       launch_lc2d_pose(aptr(e, op.in), astride(e, op.in), op.wdev, aptr(e, op.out), B, s);
       return POCO_OK;
+    case OP_COPY:
+    case OP_BCAST:
     case OP_ROT6D: {
-      float* y = ext_out(io, op.out2.ext);
-      launch_rot6d(aptr(e, op.in), astride(e, op.in), aptr(e, op.out), astride(e, op.out), y, 216, B, s);
+      MlpRowJob J;
+      const int rc = row_job_of(e, op, io, &J);
+      if (rc != POCO_OK || !J.dst) return rc;
+      if (J.kind == MLP_ROW_COPY) launch_copy_rows(J.src, J.src_rs, J.dst, J.dst_rs, J.n, B, s);
+      else if (J.kind == MLP_ROW_BCAST) launch_broadcast_rows(J.src, J.dst, J.dst_rs, J.n, B, s);
+      else launch_rot6d(J.src, J.src_rs, J.dst, J.dst_rs, J.dst2, J.dst2_rs, B, s);
       return POCO_OK;
     }
     case OP_CHAIN: {
@@ -1569,21 +1615,9 @@ int run_op(Engine& e, Op& op, int B, const IO& io, hipStream_t s) {
           ++st.nlayers;
         } else {
           if (nr >= MLP_MAX_ROWS) { poco_set_error("forward: " + op.name + ": too many row jobs"); return POCO_ERR_STATE; }
-          MlpRowJob J{};
-          if (su.type == OP_ROT6D) {
-            J.kind = MLP_ROW_ROT6D;
-            J.src = aptr(e, su.in); J.src_rs = astride(e, su.in);
-            J.dst = aptr(e, su.out); J.dst_rs = astride(e, su.out);
-            J.dst2 = ext_out(io, su.out2.ext); J.dst2_rs = 216;
-          } else if (su.type == OP_BCAST) {
-            J.kind = MLP_ROW_BCAST; J.src = su.wdev; J.dst = aptr(e, su.out); J.dst_rs = astride(e, su.out); J.n = su.n;
-          } else if (su.type == OP_COPY) {
-            J.kind = MLP_ROW_COPY; J.n = su.n;
-            if (su.in.ext) { J.src = ext_in(io, su.in.ext); J.src_rs = su.n; if (!J.src) { poco_set_error("forward: missing input for " + su.name); return POCO_ERR_ARG; } }
-            else { J.src = aptr(e, su.in); J.src_rs = astride(e, su.in); }
-            if (su.out.ext) { J.dst = ext_out(io, su.out.ext); J.dst_rs = su.n; if (!J.dst) continue; }   // output not requested
-            else { J.dst = aptr(e, su.out); J.dst_rs = astride(e, su.out); }
-          } else { poco_set_error("forward: " + su.name + " cannot be a sub-op of the fused regressor"); return POCO_ERR_STATE; }
+          MlpRowJob J;
+          if (int rc = row_job_of(e, su, io, &J)) return rc;
+          if (!J.dst) continue;
           p.row[nr++] = J;
           ++st.nrows;
         }
@@ -1591,19 +1625,6 @@ int run_op(Engine& e, Op& op, int B, const IO& io, hipStream_t s) {
       p.nstages = last + 1;
       return launch_mlp_chain(p, e.opts.mlp_blocks, s);
     }
-    case OP_COPY: {
-      const float* src; int sstride;
-      if (op.in.ext) { src = ext_in(io, op.in.ext); sstride = op.n; if (!src) { poco_set_error("forward: missing input for " + op.name); return POCO_ERR_ARG; } }
-      else { src = aptr(e, op.in); sstride = astride(e, op.in); }
-      float* dst; int dstride;
-      if (op.out.ext) { dst = ext_out(io, op.out.ext); dstride = op.n; if (!dst) return POCO_OK; }   // output not requested
-      else { dst = aptr(e, op.out); dstride = astride(e, op.out); }
-      launch_copy_rows(src, sstride, dst, dstride, op.n, B, s);
-      return POCO_OK;
-    }
-    case OP_BCAST:
-      launch_broadcast_rows(op.wdev, aptr(e, op.out), astride(e, op.out), op.n, B, s);
-      return POCO_OK;
     case OP_SMPL: {
       SmplIO sio{};
       sio.betas = aptr(e, e.smpl_betas); sio.betas_stride = astride(e, e.smpl_betas);
@@ -1967,26 +1988,30 @@ extern "C" int poco_profile_ops(poco_handle_t h, int B, const poco_inputs_t* in,
   const int n = (int)e->ops.size();
   if (cap < n) { poco_set_error("poco_profile_ops: buffer too small"); return POCO_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
-  std::vector<hipEvent_t> ev(n + 1);
-  for (auto& x : ev) POCO_HIP_CHECK(hipEventCreate(&x));
+  std::vector<hipEvent_t> ev(n + 1, nullptr);
   std::vector<double> acc(n, 0.0);
   IO io{&in_l, &out_l};
-  for (int it = 0; it < iters + 1; ++it) {
-    for (int l = 0; l < 4; ++l) e->wg_ready_act[l] = -1;
-    POCO_HIP_CHECK(hipEventRecord(ev[0], s));
-    for (int i = 0; i < n; ++i) {
-      int rc = run_op(*e, e->ops[i], B, io, s);
-      if (rc != POCO_OK) return rc;
-      POCO_HIP_CHECK(hipEventRecord(ev[i + 1], s));
+  auto measure = [&]() -> int {
+    for (auto& x : ev) POCO_HIP_CHECK(hipEventCreate(&x));
+    for (int it = 0; it < iters + 1; ++it) {
+      for (int l = 0; l < 4; ++l) e->wg_ready_act[l] = -1;
+      POCO_HIP_CHECK(hipEventRecord(ev[0], s));
+      for (int i = 0; i < n; ++i) {
+        int rc = run_op(*e, e->ops[i], B, io, s);
+        if (rc != POCO_OK) return rc;
+        POCO_HIP_CHECK(hipEventRecord(ev[i + 1], s));
+      }
+      POCO_HIP_CHECK(hipStreamSynchronize(s));
+      if (int rc = poco_status(h)) return rc;      // a timed-out wait makes the times (and outputs) of this pass meaningless
+      if (it == 0) continue;   // warm-up
+      for (int i = 0; i < n; ++i) { float ms = 0; POCO_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); acc[i] += ms; }
     }
-    POCO_HIP_CHECK(hipStreamSynchronize(s));
-    if (int rc = poco_status(h)) return rc;      // a timed-out wait makes the times (and outputs) of this pass meaningless
-    if (it == 0) continue;   // warm-up
-    for (int i = 0; i < n; ++i) { float ms = 0; POCO_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); acc[i] += ms; }
-  }
-  for (int i = 0; i < n; ++i) ms_per_op[i] = (float)(acc[i] / iters);
-  for (auto& x : ev) (void)hipEventDestroy(x);
-  return POCO_OK;
+    return POCO_OK;
+  };
+  const int rc = measure();
+  for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);      // on every path
+  for (int i = 0; rc == POCO_OK && i < n; ++i) ms_per_op[i] = (float)(acc[i] / iters);
+  return rc;
 }
 
 extern "C" size_t poco_workspace_bytes(poco_handle_t h) { return h ? H(h)->ws_floats * sizeof(float) : 0; }
@@ -1999,20 +2024,20 @@ extern "C" int poco_set_conv_cfg(poco_handle_t h, int op_index, int B, const int
     poco_set_error("poco_set_conv_cfg: bad arguments");
     return POCO_ERR_ARG;
   }
-  // validate against this op's geometry at batch B (a table entry measured at another batch size may not fit)
+  // validate against this op's geometry at batch B (a table entry measured at another batch size may not fit) and against the
+  // Winograd forms the op carries (or will carry after finalize) weights for
   const Op& op = e->ops[op_index];
-  const Act& ai = e->acts[op.in.act];
-  ConvDesc d{};
-  d.B = B; d.H = ai.H; d.W = ai.W; d.Cin = op.Cin; d.Cout = op.Cout; d.ks = op.ks; d.stride = op.stride;
-  d.in_cs = ai.C; d.out_cs = e->acts[op.out.act].C; d.act = op.actfn;
+  const ConvDesc d = conv_desc_of(*e, op, B);
   const ConvCfg c = conv_cfg_from(cfg7);
   const size_t lds = conv_lds_bytes(d, c);
-  if (B < 1 || lds == 0 || lds > 160 * 1024 || ((c.ALG == 3 || c.ALG == 4) && (op.wdev_wino == nullptr && e->finalized)) ||
-      ((c.ALG == 3 || c.ALG == 4) && (op.actfn == 3 || op.actfn == 2)) ||
-      (c.ALG == 7 && ((op.wdev_wino4 == nullptr && e->finalized) || ai.H < 28 || ai.W < 28 || op.actfn >= 2)) ||
-      (c.ALG == 8 && ((op.wdev_wino4p == nullptr && e->finalized) || ai.H < 14 || ai.W < 14 || op.actfn >= 2)) ||
-      (c.ALG == 13 && ((op.wdev_wino4w == nullptr && e->finalized) || ai.H < e->opts.w4_min_plane || ai.W < e->opts.w4_min_plane || op.actfn >= 2)) ||
-      (c.ALG == 11 && ((op.wdev_wino4g == nullptr && e->finalized) || ai.H > e->opts.wg_max_plane || ai.W > e->opts.wg_max_plane || ai.H * ai.W <= 1 || op.actfn >= 2))) {     // (its scratch is sized for max_batch; poco_forward refuses larger batches)
+  const ConvAlgs ok = conv_algs(e->opts, d.H, d.W, d.ks, d.stride, d.act);
+  // (ALG 3 / 4 BEFORE finalize: held against the activation only, as it always was - conv_lds_bytes does not look at the kernel size
+  // for them, so such an entry is accepted here for a conv that is not 3x3 stride-1 and refused by its launch.  Kept: closing it
+  // changes which table entries an engine accepts)
+  const bool wino_ok = e->finalized ? ok.wino : conv_algs(e->opts, d.H, d.W, 3, 1, d.act).wino;
+  const bool no_weights = ((c.ALG == 3 || c.ALG == 4) && !wino_ok) || (c.ALG == 7 && !ok.wino4) || (c.ALG == 8 && !ok.wino4p) ||
+                          (c.ALG == 13 && !ok.wino4w) || (c.ALG == 11 && !ok.wino4g);
+  if (B < 1 || lds == 0 || lds > 160 * 1024 || no_weights) {
     poco_set_error("poco_set_conv_cfg: configuration does not fit op '" + op.name + "' at this batch size");
     return POCO_ERR_ARG;
   }
@@ -2032,13 +2057,7 @@ extern "C" int poco_get_conv_cfg(poco_handle_t h, int op_index, int B, int* cfg7
   ConvCfg c;
   auto it = op.cfg.find(B);
   if (it != op.cfg.end()) c = it->second;
-  else {
-    const Act& ai = e->acts[op.in.act];
-    ConvDesc d{};
-    d.B = B; d.H = ai.H; d.W = ai.W; d.Cin = op.Cin; d.Cout = op.Cout; d.ks = op.ks; d.stride = op.stride;
-    d.in_cs = ai.C; d.out_cs = e->acts[op.out.act].C; d.act = op.actfn;
-    c = conv_default_cfg(d);
-  }
+  else c = conv_default_cfg(conv_desc_of(*e, op, B));
   const int v[7] = {c.MT, c.NT, c.WM, c.WN, c.R, c.NI, c.ALG};
   for (int k = 0; k < 7; ++k) cfg7[k] = v[k];
   return POCO_OK;

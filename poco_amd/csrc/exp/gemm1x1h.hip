@@ -7,7 +7,7 @@
 // Same operand roles, K walk and epilogue as gemm1x1.hip (ALG 6).  Lane layout of the K = 32 MFMA (tools/probes/
 // mfma_f16_probe.hip): lane (r = l % 16, q = l / 16) holds the 8 consecutive k = 8 q .. 8 q + 7 of row / column r, i.e. for the
 // pixel operand the channels 8 q .. 8 q + 7 of a 32-channel slice = 32 contiguous bytes of fp32 in the L16 layout.
-// Enabled only by POCO_SPLIT_F16=1 (bench.py --split-f16) for the plain 1x1 convs with Cin % 32 == 0; gated by the stress
+// Enabled only by the poco_create_ex option split_f16=1 (bench.py --split-f16) for the plain 1x1 convs with Cin % 32 == 0; gated by the stress
 // fixtures at 1e-3 (tests/test_model_gpu.py::test_split_f16_experiment_passes_the_gate).
 #include "conv_mfma_types.h"
 
@@ -347,7 +347,7 @@ bool gemm1x1h_cfg_valid(const ConvDesc& d, const ConvCfg& cfg) {
 }
 
 int gemm1x1h_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
-  if (!gemm1x1h_cfg_valid(d, cfg) || !d.wfrag_h) {
+  if (!gemm1x1h_cfg_valid(d, cfg) || !d.w.split_f16) {
     poco_set_error("gemm1x1h (split-fp16 experiment): ALG 12 needs ks = 1, Cin % 32 == 0, (MT,NT) in {2,4}x{2,4}, WM*WN <= 8 and its hi/lo weight fragments");
     return POCO_ERR_ARG;
   }
@@ -362,7 +362,7 @@ int gemm1x1h_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
   p.in = d.in + l16_chan_off(d.in_co, d.W);
   p.res = d.res ? d.res + l16_chan_off(d.res_co, p.Wo) : nullptr;
   p.out = d.out + l16_chan_off(d.out_co, p.Wo);
-  p.wfrag = reinterpret_cast<const float4*>(d.wfrag_h); p.bias = d.bias;
+  p.wfrag = reinterpret_cast<const float4*>(d.w.split_f16); p.bias = d.bias;
   p.P = d.B * p.Ho * p.Wo; p.nC32 = d.Cin / 32; p.nT16 = d.Cout / 16; p.WM = cfg.WM; p.WN = cfg.WN;
   p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16;
   p.res_rs = d.res_cs * p.Wo; p.out_rs = d.out_cs * p.Wo; p.out_ss = p.Wo * 16;

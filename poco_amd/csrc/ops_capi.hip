@@ -54,7 +54,7 @@ static int conv_common(const float* d_in, int B, int H, int W, int Cin, const fl
     std::vector<float> ph(gemm1x1h_packed_floats(Cin, Cout16));
     gemm1x1h_pack_weights(h_w, h_scale, Cout, Cin, Cout16, ph.data());
     POCO_HIP_CHECK(dwh.upload(ph));
-    d.wfrag_h = dwh.p;
+    d.w.split_f16 = dwh.p;
   }
 #endif
   if (ks == 3 && stride == 1) {
@@ -62,30 +62,30 @@ static int conv_common(const float* d_in, int B, int H, int W, int Cin, const fl
     conv_wino_transform_weights(h_w, Cout, Cin, &wt);
     conv_pack_weights(wt.data(), h_scale, Cout, Cin, 4, Cout16, pu.data());
     POCO_HIP_CHECK(dwu.upload(pu));
-    d.wfrag_wino = dwu.p;
+    d.w.wino = dwu.p;
     if (cfg7 && cfg7[6] == 7) {                   // F(4x4,3x3): 36-position fragments
       std::vector<float> pu4(conv_wino4_packed_floats(Cin, Cout16));
       conv_wino4_pack_weights(h_w, h_scale, Cout, Cin, Cout16, pu4.data());
       POCO_HIP_CHECK(dwu4.upload(pu4));
-      d.wfrag_wino4 = dwu4.p;
+      d.w.wino4 = dwu4.p;
     }
     if (cfg7 && cfg7[6] == 8) {                   // the same fragments in the LDS order of the specialised-wave kernel
       std::vector<float> pu4(conv_wino4p_packed_floats(Cin, Cout16));
       conv_wino4p_pack_weights(h_w, h_scale, Cout, Cin, Cout16, pu4.data());
       POCO_HIP_CHECK(dwu4p.upload(pu4));
-      d.wfrag_wino4p = dwu4p.p;
+      d.w.wino4p = dwu4p.p;
     }
     if (cfg7 && cfg7[6] == 13) {                  // ... and in the quad order of the whole-position kernel
       std::vector<float> pu4(conv_wino4w_packed_floats(Cin, Cout16));
       conv_wino4w_pack_weights(h_w, h_scale, Cout, Cin, Cout16, pu4.data());
       POCO_HIP_CHECK(dwu4w.upload(pu4));
-      d.wfrag_wino4w = dwu4w.p;
+      d.w.wino4w = dwu4w.p;
     }
     if (cfg7 && cfg7[6] == 11) {                  // F(4x4,3x3) as 36 position GEMMs: per-position fragments + V / M staging
       std::vector<float> pg(conv_wino4g_packed_floats(Cin, Cout16));
       conv_wino4g_pack_weights(h_w, h_scale, Cout, Cin, Cout16, pg.data());
       POCO_HIP_CHECK(dwu4g.upload(pg));
-      d.wfrag_wino4g = dwu4g.p;
+      d.w.wino4g = dwu4g.p;
       d.scratch_floats = conv_wino4g_scratch_floats(B, H, W, Cin, Cout16);
       POCO_HIP_CHECK(hipMalloc(&dscr.p, d.scratch_floats * sizeof(float)));
       d.scratch = dscr.p;
@@ -198,12 +198,12 @@ extern "C" int poco_tune_conv(int B, int H, int W, int Cin, int Cout, int ks, in
   POCO_HIP_CHECK(hipMalloc(&dout.p, nout * sizeof(float)));
   ConvDesc d{};
   d.in = din.p; d.in_cs = Cin; d.out = dout.p; d.out_cs = Cout; d.wfrag = dw.p; d.bias = db.p;
-  d.wfrag_wino = dwu.p; d.wfrag_wino4 = dwu4.p; d.wfrag_wino4p = dwu4.p; d.wfrag_wino4w = dwu4.p;     // timing only: random fragments serve all orders
+  d.w.wino = dwu.p; d.w.wino4 = dwu4.p; d.w.wino4p = dwu4.p; d.w.wino4w = dwu4.p;     // timing only: random fragments serve all orders
   if (any11 && ks == 3 && stride == 1 && H <= 16 && W <= 16) {
     std::vector<float> hg(conv_wino4g_packed_floats(Cin, Cout));
     for (auto& v : hg) v = rnd() * ws;
     POCO_HIP_CHECK(dwu4g.upload(hg));
-    d.wfrag_wino4g = dwu4g.p;
+    d.w.wino4g = dwu4g.p;
     d.scratch_floats = conv_wino4g_scratch_floats(B, H, W, Cin, Cout);
     POCO_HIP_CHECK(hipMalloc(&dscr.p, d.scratch_floats * sizeof(float)));
     d.scratch = dscr.p;
@@ -229,7 +229,7 @@ extern "C" int poco_tune_conv(int B, int H, int W, int Cin, int Cout, int ks, in
     for (auto& v : hw2) v = rnd() * ws;
     gemm1x1h_pack_weights(hw2.data(), nullptr, Cout, Cin, Cout, ph.data());
     POCO_HIP_CHECK(dwh.upload(ph));
-    d.wfrag_h = dwh.p;
+    d.w.split_f16 = dwh.p;
   }
 #endif
   d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout; d.ks = ks; d.stride = stride; d.act = 1;
