@@ -5,8 +5,10 @@
 
 Prints MPJPE, PA-MPJPE, V2V, the uncertainty / pose-error correlation and N, and writes evaluation_results_<name>.npz (numeric
 arrays; the reference joblib-dumps a dict).  The metrics are computed on the GPU (poco_amd/evaluate.py, csrc/eval_metrics.hip):
-per crop nothing is copied to the host between the forward and the final reduction.  Not computed: Var-MPJPE / Variance (they
-need the training-time accumulators), gendered SMPL models, multi-GPU evaluation (DESIGN.md "Evaluation").
+per crop nothing is copied to the host between the forward and the final reduction.  --likelihood adds the Var-MPJPE and Variance
+lines of the reference and the held-out flow NLL - the likelihood of the ground-truth pose under the model's own RealNVP, the
+quantity the uncertainty was trained on (csrc/eval_likelihood.hip, DESIGN.md "Likelihood").  Not computed: gendered SMPL models,
+multi-GPU evaluation (DESIGN.md "Evaluation").
 """
 import argparse
 import os
@@ -31,6 +33,9 @@ def parse_args(argv=None):
     p.add_argument("--output_folder", type=str, default="out")
     p.add_argument("--no_kinematic_uncert", action="store_false",
                    help="Do not use SMPL Kinematic for uncert (same store_false semantics as demo.py)")
+    p.add_argument("--likelihood", action="store_true",
+                   help="also print Var-MPJPE, Variance and the held-out flow NLL (needs `pose` in the dataset and "
+                        "flow_head.cond_layer in the checkpoint)")
     return p.parse_args(argv)
 
 
@@ -47,8 +52,23 @@ def check_dataset_file(path: str) -> str:
             sys.exit(f"{path}: {e}")
 
 
+def check_likelihood_inputs(args) -> None:
+    """--likelihood: refuse a dataset without `pose` and a checkpoint without the flow's context layer before any GPU work."""
+    import numpy as np
+    from poco_amd.checkpoint import read_checkpoint
+    with np.load(args.dataset, allow_pickle=False) as z:
+        if "pose" not in z.files:
+            sys.exit(f"{args.dataset}: --likelihood needs `pose` (the flow scores the ground-truth pose)")
+    keys = {(k[len("model."):] if k.startswith("model.") else k) for k in read_checkpoint(args.ckpt, args.inf_model)}
+    missing = [k for k in ("flow_head.cond_layer.weight", "flow_head.cond_layer.bias") if k not in keys]
+    if missing:
+        sys.exit(f"{args.ckpt}: --likelihood needs {missing} (the checkpoint has no flow context layer)")
+
+
 def main(args):
     check_dataset_file(args.dataset)
+    if args.likelihood:
+        check_likelihood_inputs(args)
     if not os.path.isfile(args.j_regressor):
         sys.exit(f"joint regressor not found: {args.j_regressor}")
     import numpy as np
@@ -61,8 +81,9 @@ def main(args):
     J = np.load(args.j_regressor).astype(np.float32)
     tester = POCOTester(args)                       # builds the engine from --cfg / --ckpt / --smpl exactly as demo.py does
     res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
-                            kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
-    for line in evaluate.report_lines(res):
+                            kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
+                            likelihood=args.likelihood)
+    for line in (evaluate.likelihood_lines(res) if args.likelihood else []) + evaluate.report_lines(res):
         print(line)
     out = os.path.join(args.output_folder, f"evaluation_results_{args.dataset_name}.npz")
     evaluate.save_npz(out, res, args.dataset_name)

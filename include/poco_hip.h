@@ -111,6 +111,9 @@ int poco_create(const char* variant, int max_batch, int num_flow_layers, poco_ha
  *                                            ~3 s) / the first n launches of the fused regressor time out on purpose
  *   flow_ctx_rows = <n>                      context rows poco_realnvp*'s scratch is planned for at finalize (default max_batch)
  *   record_kinematic = 0|1, record_thr = <f> post-processing of poco_outputs_t.record's confidence (defaults 1, 0.40)
+ *   mask_params_id = <ids>, exclude_uncert_idx = <ids>   POCO.MASK_PARAMS_ID / POCO.EXCLUDE_UNCERT_IDX as the yaml spells them ("1-4-7";
+ *                                            default "" as in the shipped configs): the forward does not read them, poco_flow_nll refuses
+ *                                            an engine that has either (a masked flow also tolerates the flow_head.mask_params buffer)
  * Unknown keys are an error. */
 int poco_create_ex(const char* variant, int max_batch, int num_flow_layers, const char* options, poco_handle_t* out);
 void poco_destroy(poco_handle_t h);
@@ -187,6 +190,33 @@ int poco_realnvp(poco_handle_t h, int N, const float* d_x, const float* d_ctx, f
  * materialised.  d_ctx [ceil(N/rep), 512]; row r uses d_ctx[r / rep].  rep = 1 is poco_realnvp. */
 int poco_realnvp_rep(poco_handle_t h, int N, const float* d_x, const float* d_ctx, int rep, float* d_out, int forward,
                      void* stream);
+
+/* ---- the flow likelihood of the ground truth: held-out NLL of eval.py --likelihood -------------------------------------------------
+ * Replaces the training-time branch of flow_head.forward (pocolib/models/head/nf_head.py:78-123) and the loss line
+ * pocolib/losses/losses.py:342-347 at evaluation time; csrc/eval_likelihood.hip.  The forward never runs any of this. */
+/* context_feats = cond_layer(uncert_feat) (nf_head.py:82): d_uncert_feat [B, poco_uncert_feat_dim] -> d_ctx [B,512], on the engine's
+ * small-M GEMM (csrc/linear_mfma.hip; it keeps its partial sums in LDS, so there is no scratch to plan).  flow_head.cond_layer.{weight,
+ * bias} stay required=0 and are uploaded at poco_finalize when the checkpoint has them; without them this is POCO_ERR_STATE naming
+ * the missing tensor.  A null pointer, B < 1 or B > max_batch is POCO_ERR_ARG.  Enqueued on `stream`: no allocation, no synchronisation. */
+int poco_flow_context(poco_handle_t h, int B, const float* d_uncert_feat, float* d_ctx, void* stream);
+/* Per crop: bar = |pred_pose - batch_rodrigues(gt_pose)| / (var_pose + 1e-9) (nf_head.py:89-101; sigma repeated over the 3x3; R_gt by
+ * the device function of poco_op_rodrigues), log_phi = flow.log_prob(bar.reshape(-1, 9), context repeated over the 24 joints)
+ * (nf_head.py:105-112), log sigma = log(var_pose) (losses.py:346).  d_pred_pose [B,24,3,3], d_gt_pose [B,72] axis-angle, d_var_pose
+ * [B,24], d_ctx [B,512] (poco_flow_context), d_valid [B] int32 = has_smpl (NULL: every crop), d_out [B, POCO_FLOW_NLL_RECORD_FLOATS]:
+ *     [0] valid (1 or 0)  [1] sum over the 24 joints of (log sigma - log phi), in joint order, fp64, stored as fp32  [2..8) 0
+ *     [8..32) log phi  [32..56) log sigma  [56..80) mean over the 3x3 of bar
+ * The record of an invalid crop is all zero (the reference drops such crops, nf_head.py:88-95).  Three launches on `stream` -
+ * residual rows, the two launches of poco_realnvp_rep with rep = 24, epilogue - into scratch planned at poco_finalize for max_batch
+ * crops: no allocation, no synchronisation, no host round trip.  POCO_ERR_ARG before any GPU work: a null handle or pointer, B < 1,
+ * B > max_batch (or more crops than option flow_ctx_rows planned the flow scratch for), and an engine created with mask_params_id
+ * or exclude_uncert_idx (nf_head.py:54-59,90-91,117-118: refused, not approximated). */
+#define POCO_FLOW_NLL_RECORD_FLOATS 80
+int poco_flow_nll(poco_handle_t h, int B, const float* d_pred_pose, const float* d_gt_pose, const float* d_var_pose,
+                  const float* d_ctx, const int32_t* d_valid, float* d_out, void* stream);
+/* Reduce N records (device, any number of poco_flow_nll calls laid end to end) in one block, fp64, fixed order, into h_summary4 (host):
+ *     [0] valid crops  [1] mean log phi  [2] mean log sigma  [3] loss_nf = mean over valid crops x 24 joints of (log sigma - log phi)
+ * = losses.py:346 with nf_loss_weight = 1.  No valid crop: [0] = 0 and NaN means.  Synchronises `stream`.  N < 1 or N > 2^24 is POCO_ERR_ARG. */
+int poco_flow_nll_reduce(poco_handle_t h, int64_t N, const float* d_records, double* h_summary4, void* stream);
 
 /* ---- stand-alone operators (parity tests, tuner, micro-benchmarks) -------------------------- */
 
@@ -335,6 +365,13 @@ int poco_evaluator_step(poco_evaluator_t e, int B, const float* d_pred_vertices,
 /* Reduce the N records written so far into h_summary8 (host, 8 doubles) and, if h_records is not NULL, copy the records to it
  * (host fp32 [records_cap, POCO_EVAL_RECORD_FLOATS], records_cap >= N).  Synchronises `stream`.  N = 0 is POCO_ERR_STATE. */
 int poco_evaluator_finish(poco_evaluator_t e, double* h_summary8, float* h_records, int64_t records_cap, void* stream);
+/* Var-MPJPE and Variance of pocolib/core/trainer.py:374,377-378,389-390 over the records written so far, which are only read:
+ *     u_i = mean over the 24 joints of the processed uncertainty of crop i (POCOUtils.accumulate_uncert('val', ...) returns
+ *           prepare_uncert(var_pose).mean(1), poco_utils.py:151-169,265-281)
+ *     h_summary2[0] = Var-MPJPE = mean_i(MPJPE_i / (u_i + 1e-9))     [1] = Variance = mean_i(u_i)
+ * in fp64 from the stored fp32 fields, in metres (the reference does not scale these two by 1000).  One block, fixed order.
+ * Synchronises `stream`.  No step yet is POCO_ERR_STATE. */
+int poco_evaluator_uncert_summary(poco_evaluator_t e, double* h_summary2, void* stream);
 /* Rewind: the next step writes record 0. */
 int poco_evaluator_reset(poco_evaluator_t e);
 void poco_evaluator_destroy(poco_evaluator_t e);

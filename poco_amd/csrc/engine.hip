@@ -121,6 +121,7 @@ struct EngineOpts {
   int debug_mlp_timeouts = 0;  // ... and: the first n launches of the fused regressor leave one block out of their first grid barrier, i.e. time out
   int rec_kinematic = 1;   // poco_outputs_t.record: kinematic accumulation of the per-joint uncertainty (KINEMATIC_UNCERT)
   float rec_thr = 0.40f;   // ... and the sensitivity threshold of get_global_uncert (poco_utils.py:50)
+  std::string mask_params_id, exclude_uncert_idx;   // POCO.MASK_PARAMS_ID / EXCLUDE_UNCERT_IDX: recorded so that poco_flow_nll can refuse them
 };
 
 static bool parse_opts(const char* str, EngineOpts* o, std::string* err) {
@@ -160,6 +161,8 @@ static bool parse_opts(const char* str, EngineOpts* o, std::string* err) {
     else if (k == "debug_mlp_timeouts") o->debug_mlp_timeouts = std::max(0, atoi(v.c_str()));
     else if (k == "record_kinematic") o->rec_kinematic = on;
     else if (k == "record_thr") o->rec_thr = (float)atof(v.c_str());
+    else if (k == "mask_params_id") o->mask_params_id = eq == std::string::npos ? "" : v;
+    else if (k == "exclude_uncert_idx") o->exclude_uncert_idx = eq == std::string::npos ? "" : v;
     else { *err = "unknown engine option '" + k + "'"; return false; }
   }
   for (char c : o->branch_lanes)
@@ -199,6 +202,12 @@ struct Engine {
   size_t wino4g_scratch_need = 0;
   float* flow_scratch = nullptr;          // step A of the flow (context GEMM): planned at finalize for opts.flow_ctx_rows context rows
   size_t flow_scratch_floats = 0;
+  // the flow's context layer (nf_head.py:82) and the scratch of poco_flow_nll, planned at finalize for max_batch crops
+  const float* cond_frag = nullptr;       // flow_head.cond_layer.weight in conv_pack_weights(ks = 1) order; null: not in the checkpoint
+  const float* cond_bias = nullptr;
+  float* nll_rows = nullptr;              // [max_batch * 24][9] residual rows
+  float* nll_logphi = nullptr;            // [max_batch * 24]
+  double* nll_summary = nullptr;          // [4], poco_flow_nll_reduce
   int uncert_feat_dim = 0;
   float* sk_scratch[4] = {};          // ALG 14 (stream-K 1x1 GEMM): flags + partials, one buffer per lane
   unsigned* mlp_sync = nullptr;       // OP_MLP: grid-barrier counters (device) ...
@@ -216,6 +225,7 @@ struct Engine {
     for (void* p : dev_allocs) (void)hipFree(p);
     if (ws) (void)hipFree(ws);
     if (flow_scratch) (void)hipFree(flow_scratch);
+    for (void* q : {(void*)nll_rows, (void*)nll_logphi, (void*)nll_summary}) if (q) (void)hipFree(q);
     if (mlp_sync) (void)hipFree(mlp_sync);
     for (float* q : sk_scratch) if (q) (void)hipFree(q);
     if (mlp_err_host) (void)hipHostFree(mlp_err_host);
@@ -980,9 +990,17 @@ void build_flow(Builder& b, int in_ctx) {
   Engine& e = b.e;
   const int L = 2 * e.flow_layers, D = 9, H = 64, ctx = 512, K0 = D + ctx;
   // cond_layer is evaluated and discarded by the reference at inference (nf_head.py:82,129-136):
-  // declared (so checkpoints load strictly) but never launched in forward.
-  b.P("flow_head.cond_layer.weight", {ctx, in_ctx}, 0);
-  b.P("flow_head.cond_layer.bias", {ctx}, 0);
+  // declared (so checkpoints load strictly) but never launched in forward.  When the checkpoint has it, it is uploaded for
+  // poco_flow_context (the evaluation-time likelihood, poco_flow_nll).
+  const HostParam* cw = b.P("flow_head.cond_layer.weight", {ctx, in_ctx}, 0);
+  const HostParam* cb = b.P("flow_head.cond_layer.bias", {ctx}, 0);
+  if (!e.opts.mask_params_id.empty() && e.opts.exclude_uncert_idx.empty()) b.P("flow_head.mask_params", {24}, 0);   // nf_head.py:56-59
+  if (!b.declare && cw && cb) {
+    std::vector<float> cf(conv_packed_weight_floats(in_ctx, ctx, 1));
+    conv_pack_weights(cw->data.data(), nullptr, ctx, in_ctx, 1, ctx, cf.data());
+    e.cond_frag = b.upload(cf);
+    e.cond_bias = b.upload(cb->data);
+  }
   const HostParam* mask = b.P("flow_head.flow.mask", {L, D}, 0);
   const int NM = L * 2;                                   // MLPs: index li*2 + net (net 0 = s, 1 = t)
   std::vector<float> wpack((size_t)NM * 24 * 256), b1((size_t)NM * H), b2((size_t)NM * 16, 0.f), wctx((size_t)NM * H * ctx),
@@ -1776,6 +1794,10 @@ extern "C" int poco_finalize(poco_handle_t h) {
     const int rows = e->opts.flow_ctx_rows > 0 ? e->opts.flow_ctx_rows : e->max_batch;
     e->flow_scratch_floats = realnvp_scratch_floats(e->flow, rows);
     POCO_HIP_CHECK(hipMalloc(&e->flow_scratch, e->flow_scratch_floats * sizeof(float)));
+    // poco_flow_nll: the residual rows and their log_prob for max_batch crops (27 KB at 32 crops), next to the flow scratch
+    POCO_HIP_CHECK(hipMalloc(&e->nll_rows, (size_t)e->max_batch * 24 * 9 * sizeof(float)));
+    POCO_HIP_CHECK(hipMalloc(&e->nll_logphi, (size_t)e->max_batch * 24 * sizeof(float)));
+    POCO_HIP_CHECK(hipMalloc(&e->nll_summary, 4 * sizeof(double)));
   }
   POCO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->mlp_err_host), 64, hipHostMallocMapped));
   *e->mlp_err_host = 0;
@@ -2112,4 +2134,74 @@ extern "C" int poco_realnvp_rep(poco_handle_t h, int N, const float* d_x, const 
 extern "C" int poco_realnvp(poco_handle_t h, int N, const float* d_x, const float* d_ctx, float* d_out, int forward,
                             void* stream) {
   return poco_realnvp_rep(h, N, d_x, d_ctx, 1, d_out, forward, stream);
+}
+
+// ---- the flow likelihood of the ground truth (kernels: csrc/eval_likelihood.hip) ------------------------------------------------
+// Everything that can be refused on the host is refused before the state is looked at, so a binding learns about a bad call without a GPU.
+static const char* flow_cond_missing(const Engine* e) {
+  if (e->finalized) return e->cond_frag ? nullptr : "flow_head.cond_layer.weight";
+  if (!e->params.count("flow_head.cond_layer.weight")) return "flow_head.cond_layer.weight";
+  if (!e->params.count("flow_head.cond_layer.bias")) return "flow_head.cond_layer.bias";
+  return nullptr;
+}
+
+extern "C" int poco_flow_context(poco_handle_t h, int B, const float* d_uncert_feat, float* d_ctx, void* stream) {
+  Engine* e = H(h);
+  if (!e || !d_uncert_feat || !d_ctx || B < 1 || B > e->max_batch) {
+    poco_set_error("poco_flow_context: bad arguments (need a handle, both pointers and 1 <= B <= max_batch)");
+    return POCO_ERR_ARG;
+  }
+  if (const char* t = flow_cond_missing(e)) {
+    poco_set_error(std::string("poco_flow_context: the checkpoint had no ") + t);
+    return POCO_ERR_STATE;
+  }
+  if (!e->finalized) { poco_set_error("poco_flow_context: engine not finalized"); return POCO_ERR_STATE; }
+  ConvDesc d{};
+  d.in = d_uncert_feat; d.in_cs = e->uncert_feat_dim; d.out = d_ctx; d.out_cs = 512;
+  d.wfrag = e->cond_frag; d.bias = e->cond_bias;
+  d.B = B; d.H = 1; d.W = 1; d.Cin = e->uncert_feat_dim; d.Cout = 512; d.ks = 1; d.stride = 1; d.act = 0;
+  return conv_launch(d, ConvCfg{1, 1, 8, 1, 1, 1, 5}, (hipStream_t)stream);     // linear_mfma, K split over 8 waves: the row count is <= max_batch
+}
+
+extern "C" int poco_flow_nll(poco_handle_t h, int B, const float* d_pred_pose, const float* d_gt_pose, const float* d_var_pose,
+                             const float* d_ctx, const int32_t* d_valid, float* d_out, void* stream) {
+  Engine* e = H(h);
+  if (!e) { poco_set_error("poco_flow_nll: null handle"); return POCO_ERR_ARG; }
+  if (!e->opts.mask_params_id.empty() || !e->opts.exclude_uncert_idx.empty()) {
+    poco_set_error("poco_flow_nll: MASK_PARAMS_ID / EXCLUDE_UNCERT_IDX flows (nf_head.py:54-59,90-91,117-118) are not built; the shipped "
+                   "configurations have neither");
+    return POCO_ERR_ARG;
+  }
+  if (!d_pred_pose || !d_gt_pose || !d_var_pose || !d_ctx || !d_out || B < 1 || B > e->max_batch) {
+    poco_set_error("poco_flow_nll: bad arguments (need pred_pose, gt_pose, var_pose, ctx, out and 1 <= B <= max_batch = " +
+                   std::to_string(e->max_batch) + ")");
+    return POCO_ERR_ARG;
+  }
+  if (!e->finalized || !e->has_flow) { poco_set_error("poco_flow_nll: engine not finalized or flow_head.flow.* tensors not loaded"); return POCO_ERR_STATE; }
+  if (realnvp_scratch_floats(e->flow, B) > e->flow_scratch_floats) {
+    poco_set_error("poco_flow_nll: " + std::to_string(B) + " crops, the flow scratch was planned for flow_ctx_rows = " +
+                   std::to_string(e->opts.flow_ctx_rows) + " context rows");
+    return POCO_ERR_ARG;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  launch_flow_residual(d_pred_pose, d_gt_pose, d_var_pose, e->nll_rows, B, s);
+  if (int rc = launch_realnvp(e->flow, e->nll_rows, d_ctx, 24, e->nll_logphi, B * 24, 0, e->flow_scratch, s)) return rc;
+  launch_flow_nll_epilogue(e->nll_rows, e->nll_logphi, d_var_pose, d_valid, d_out, B, s);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_flow_nll_reduce(poco_handle_t h, int64_t N, const float* d_records, double* h_summary4, void* stream) {
+  Engine* e = H(h);
+  if (!e || !d_records || !h_summary4 || N < 1 || N > (1ll << 24)) {
+    poco_set_error("poco_flow_nll_reduce: bad arguments (need a handle, records, a summary of 4 doubles and 1 <= N <= 2^24)");
+    return POCO_ERR_ARG;
+  }
+  if (!e->finalized || !e->nll_summary) { poco_set_error("poco_flow_nll_reduce: engine not finalized or flow_head.flow.* tensors not loaded"); return POCO_ERR_STATE; }
+  const hipStream_t s = (hipStream_t)stream;
+  launch_flow_nll_reduce(d_records, N, e->nll_summary, s);
+  POCO_HIP_CHECK(hipGetLastError());
+  POCO_HIP_CHECK(hipMemcpyAsync(h_summary4, e->nll_summary, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  POCO_HIP_CHECK(hipStreamSynchronize(s));
+  return POCO_OK;
 }

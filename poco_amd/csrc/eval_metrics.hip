@@ -18,6 +18,8 @@
 // The processed uncertainty alone is fp32, in the order of poco_amd/postproc.py, so that it equals the host's values.
 // No atomics: every output word has one writer and every sum a fixed order - two runs give the same bits.
 #include "common.h"
+#include "kernels.h"
+#include "rodrigues.h"
 #include "../../include/poco_hip.h"
 
 #include <algorithm>
@@ -40,25 +42,6 @@ static_assert(R_NONREL + EV_MAXJ * 3 <= EV_REC, "record layout");
 
 // get_smpl_skeleton() of pocolib/utils/kp_utils.py:881-908 as parent per joint
 __constant__ int EV_SMPL_PARENT[24] = {-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21};
-
-// batch_rodrigues + quat_to_rotmat (geometry.py:207-244) of one axis-angle vector: the norm is taken of theta + 1e-8, the vector
-// is divided by that norm, the quaternion (cos(a/2), sin(a/2) n) is renormalised and expanded.  fp64 inside, R row-major.
-__device__ __forceinline__ void rodrigues_f64(const float* __restrict__ aa, double* R) {
-  const double tx = aa[0], ty = aa[1], tz = aa[2];
-  const double ex = tx + 1e-8, ey = ty + 1e-8, ez = tz + 1e-8;
-  const double angle = sqrt(ex * ex + ey * ey + ez * ez);
-  const double nx = tx / angle, ny = ty / angle, nz = tz / angle;
-  const double half = angle * 0.5;
-  const double c = cos(half), s = sin(half);
-  double w = c, x = s * nx, y = s * ny, z = s * nz;
-  const double qn = sqrt(w * w + x * x + y * y + z * z);
-  w /= qn; x /= qn; y /= qn; z /= qn;
-  const double w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
-  const double wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
-  R[0] = w2 + x2 - y2 - z2; R[1] = 2 * xy - 2 * wz;   R[2] = 2 * wy + 2 * xz;
-  R[3] = 2 * wz + 2 * xy;   R[4] = w2 - x2 + y2 - z2; R[5] = 2 * yz - 2 * wx;
-  R[6] = 2 * xz - 2 * wy;   R[7] = 2 * wx + 2 * yz;   R[8] = w2 - x2 - y2 + z2;
-}
 
 __global__ __launch_bounds__(256) void rodrigues_kernel(const float* __restrict__ aa, float* __restrict__ rot, int N) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -449,7 +432,7 @@ static int evaluator_upload(poco_evaluator* e) {
   POCO_HIP_CHECK(up(&e->d_map, e->map));
   POCO_HIP_CHECK(up(&e->d_sel, e->sel));
   POCO_HIP_CHECK(hipMalloc(&e->d_part, (size_t)e->sub * e->S * EV_PSTRIDE * sizeof(double)));
-  POCO_HIP_CHECK(hipMalloc(&e->d_summary, 8 * sizeof(double)));
+  POCO_HIP_CHECK(hipMalloc(&e->d_summary, (8 + 2) * sizeof(double)));   // [8..10): poco_evaluator_uncert_summary
   POCO_HIP_CHECK(hipMalloc(&e->d_rec, (size_t)e->capacity * EV_REC * sizeof(float)));
   e->on_device = true;
   return POCO_OK;
@@ -502,6 +485,19 @@ extern "C" int poco_evaluator_finish(poco_evaluator_t e, double* h_summary8, flo
   POCO_HIP_CHECK(hipMemcpyAsync(h_summary8, e->d_summary, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
   if (h_records)
     POCO_HIP_CHECK(hipMemcpyAsync(h_records, e->d_rec, (size_t)e->first * EV_REC * sizeof(float), hipMemcpyDeviceToHost, s));
+  POCO_HIP_CHECK(hipStreamSynchronize(s));
+  return POCO_OK;
+}
+
+// Var-MPJPE and Variance (trainer.py:374,377-378; kernel in eval_likelihood.hip): a second reduction over the same records, which it only reads
+extern "C" int poco_evaluator_uncert_summary(poco_evaluator_t e, double* h_summary2, void* stream) {
+  if (!e || !h_summary2) { poco_set_error("poco_evaluator_uncert_summary: bad arguments (need a handle and a summary of 2 doubles)"); return POCO_ERR_ARG; }
+  if (e->first < 1) { poco_set_error("poco_evaluator_uncert_summary: no crop has been stepped"); return POCO_ERR_STATE; }
+  if (int rc = evaluator_upload(e)) return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  launch_eval_uncert_summary(e->d_rec, EV_REC, R_MPJPE, R_UNC, e->first, e->d_summary + 8, s);
+  POCO_HIP_CHECK(hipGetLastError());
+  POCO_HIP_CHECK(hipMemcpyAsync(h_summary2, e->d_summary + 8, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   POCO_HIP_CHECK(hipStreamSynchronize(s));
   return POCO_OK;
 }

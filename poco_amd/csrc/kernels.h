@@ -164,6 +164,18 @@ size_t realnvp_scratch_floats(const FlowDev& f, int ctx_rows);
 int launch_realnvp(const FlowDev& f, const float* x, const float* ctx, int rep, float* out, int N, int forward, float* scratch,
                    hipStream_t s);
 
+// ---- flow likelihood and the evaluator's uncertainty summaries (eval_likelihood.hip) -------------------------------------
+constexpr int FLOW_NLL_REC = 80;   // include/poco_hip.h POCO_FLOW_NLL_RECORD_FLOATS
+// rows [B*24, 9] = |pred_pose - batch_rodrigues(gt_pose)| / (var_pose + 1e-9)   (nf_head.py:89-105)
+void launch_flow_residual(const float* pred_pose, const float* gt_pose, const float* var_pose, float* rows, int B, hipStream_t s);
+// records [B, 80] from the rows, their log_prob and var_pose; valid [B] int32 (nullable = all): an invalid crop's record is zero
+void launch_flow_nll_epilogue(const float* rows, const float* logphi, const float* var_pose, const int* valid, float* out, int B,
+                              hipStream_t s);
+// {valid crops, mean log phi, mean log sigma, loss_nf} (losses.py:346) of N records, fp64, one block
+void launch_flow_nll_reduce(const float* rec, long long N, double* d_summary4, hipStream_t s);
+// {Var-MPJPE, Variance} (trainer.py:374-378) of N evaluator records of `stride` floats, fp64, one block
+void launch_eval_uncert_summary(const float* rec, int stride, int off_mpjpe, int off_unc, long long N, double* d_summary2, hipStream_t s);
+
 // ---- preprocessing (kernels_misc.hip) --------------------------------------------------------------------
 // frame: uint8 [H,W,3] RGB (device); boxes: [N,4] = (cx, cy, w, h) in pixels (float32 or float64); out: [N,3,res,res] fp32
 // NCHW = ToTensor + Normalize of the uint8 crop cv2.warpAffine(getAffineTransform(box * scale -> res x res)) makes, byte-exact.

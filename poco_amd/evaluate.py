@@ -39,6 +39,7 @@ def _bind():
                                         C.c_int64, C.POINTER(C.c_void_p)]
     L.poco_evaluator_step.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
     L.poco_evaluator_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.poco_evaluator_uncert_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.poco_evaluator_reset.argtypes = [C.c_void_p]
     L.poco_evaluator_destroy.argtypes = [C.c_void_p]
     L.poco_evaluator_destroy.restype = None
@@ -122,6 +123,16 @@ class Evaluator:
         check(lib().poco_evaluator_reset(self._h), "poco_evaluator_reset")
         self.count = 0
 
+    def uncert_summary(self) -> Dict[str, float]:
+        """val_mpjpe_var = mean_i(MPJPE_i / (mean_24(processed uncertainty_i) + 1e-9)) and val_var = mean_i(mean_24(...))
+        (trainer.py:374,377-378; metres, not scaled by 1000) over the records written so far, reduced on the device; the records
+        are only read.  Synchronises the current stream."""
+        summ = np.zeros(2, np.float64)
+        with torch.cuda.device(self.device):
+            check(_bind().poco_evaluator_uncert_summary(self._h, summ.ctypes.data, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                  "poco_evaluator_uncert_summary")
+        return {"val_mpjpe_var": float(summ[0]), "val_var": float(summ[1])}
+
     def finish(self, save_results: bool = False, return_records: bool = False) -> Dict[str, object]:
         """Summary under the reference's log names (trainer.py:397-403) plus the per-sample arrays of
         SaveResults.evaluation_results (save_results.py:23-43): mpjpe / pampjpe [N,M], v2v [N], corr_x / corr_y (flattened over
@@ -141,6 +152,51 @@ class Evaluator:
             out["gt_jnts3D"] = rec[:, R_GT:R_GT + 3 * MAX_JOINTS].reshape(-1, MAX_JOINTS, 3)[:, :M].copy()
         if return_records:
             out["records"] = rec
+        return out
+
+
+NLL_RECORD_FLOATS = 80
+N_VALID, N_SUM, N_LOGPHI, N_LOGSIGMA, N_BAR = 0, 1, 8, 32, 56      # record offsets of poco_flow_nll (include/poco_hip.h)
+
+
+class LikelihoodAccumulator:
+    """Device-side accumulator of the flow likelihood (POCO.flow_nll), stepped next to an Evaluator on the same stream.
+
+        lk = LikelihoodAccumulator(model, capacity=len(dataset))
+        lk.step(model(batch), gt_pose, valid=has_smpl)           # per batch, enqueued on the current stream
+        res = lk.finish()                                        # val_nll, val_log_phi, val_log_sigma + [N,24] arrays
+    """
+
+    def __init__(self, model, capacity: int):
+        if int(capacity) < 1:
+            raise PocoHipError("LikelihoodAccumulator: capacity must be at least 1")
+        self.model, self.capacity, self.count = model, int(capacity), 0
+        self.records = torch.zeros(self.capacity, NLL_RECORD_FLOATS, device=model.device, dtype=torch.float32)
+
+    def step(self, pred: Dict[str, torch.Tensor], gt_pose: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
+        """Records of B crops at records[count .. count + B).  More crops than the capacity holds is an error and leaves the
+        records as they were.  Nothing is copied to the host."""
+        B = int(pred["pred_pose"].shape[0])
+        if self.count + B > self.capacity:
+            raise PocoHipError(f"LikelihoodAccumulator.step: {self.count} + {B} crops exceed the capacity of {self.capacity}")
+        self.model.flow_nll(pred, gt_pose, valid, out=self.records[self.count:self.count + B])
+        self.count += B
+
+    def reset(self) -> None:
+        self.count = 0
+
+    def finish(self, return_records: bool = False) -> Dict[str, object]:
+        """val_nll = loss_nf of losses.py:346 (nf_loss_weight = 1) over the valid crops, val_log_phi / val_log_sigma = the means of
+        its two terms, and per crop log_phi / log_sigma / bar_pose [N,24] and nll_valid [N].  Synchronises the current stream."""
+        if self.count < 1:
+            raise PocoHipError("LikelihoodAccumulator.finish: no crop has been stepped")
+        summ = self.model.flow_nll_summary(self.records[:self.count])
+        rec = self.records[:self.count].cpu().numpy()
+        out = {"nll_N": int(summ[0]), "val_log_phi": float(summ[1]), "val_log_sigma": float(summ[2]), "val_nll": float(summ[3]),
+               "log_phi": rec[:, N_LOGPHI:N_LOGPHI + 24].copy(), "log_sigma": rec[:, N_LOGSIGMA:N_LOGSIGMA + 24].copy(),
+               "bar_pose": rec[:, N_BAR:N_BAR + 24].copy(), "nll_valid": rec[:, N_VALID].astype(np.int32)}
+        if return_records:
+            out["nll_records"] = rec
         return out
 
 
@@ -174,7 +230,8 @@ class EvalDataset:
         self.center = np.asarray(z["center"], np.float32).reshape(-1, 2)
         self.scale = np.asarray(z["scale"], np.float32).reshape(-1)
         n = len(self.imgname)
-        self.pose = np.asarray(z["pose"], np.float32).reshape(n, 72) if "pose" in z.files else np.zeros((n, 72), np.float32)
+        self.has_pose = "pose" in z.files
+        self.pose = np.asarray(z["pose"], np.float32).reshape(n, 72) if self.has_pose else np.zeros((n, 72), np.float32)
         self.shape = np.asarray(z["shape"], np.float32).reshape(n, 10) if "shape" in z.files else None
         self.joints = None
         if self.gt_form == "joints":
@@ -216,25 +273,36 @@ class EvalDataset:
 
 @torch.no_grad()
 def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
-             sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_records: bool = False) -> Dict[str, object]:
+             sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_records: bool = False,
+             likelihood: bool = False) -> Dict[str, object]:
     """trainer.py:298-336 over a whole dataset: forward, then the metrics of every batch (the ragged last one included) on the
     device.  SMPL ground truth: gt_vertices = POCO.smpl_lbs(shape, poco_op_rodrigues(pose)) (base_dataset.py:353-366, neutral
-    model), also on the device.  Returns Evaluator.finish() plus `imgname`."""
+    model), also on the device.  Returns Evaluator.finish() plus `imgname`.  likelihood=True (needs `pose` in the dataset and
+    cond_layer in the checkpoint): also the held-out flow NLL of every batch on the same stream (LikelihoodAccumulator: val_nll,
+    val_log_phi, val_log_sigma, log_phi / log_sigma / bar_pose [N,24]) and Evaluator.uncert_summary() (val_mpjpe_var, val_var)."""
     from . import ops
     dev = model.device
     ev = Evaluator(J_regressor, joint_map(dataset.name), capacity=len(dataset), sel_uncert_part=sel_uncert_part, kinematic=kinematic,
                    device=dev)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+    if likelihood and not dataset.has_pose:
+        raise ValueError("likelihood=True needs a dataset with `pose` (the flow scores the ground-truth pose)")
+    lk = LikelihoodAccumulator(model, capacity=len(dataset)) if likelihood else None
     for lo in range(0, len(dataset), batch_size):
         hi = min(lo + batch_size, len(dataset))
         out = model(dataset.batch(lo, hi, dev), want_segm=False)
         gt_pose = t(dataset.pose[lo:hi])
+        if lk is not None:
+            lk.step(out, gt_pose)
         if dataset.gt_form == "smpl":
             gt_verts, _ = model.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))
             ev.step(out, gt_pose, gt_vertices=gt_verts)
         else:
             ev.step(out, gt_pose, gt_joints=t(dataset.joints[lo:hi]))
     res = ev.finish(save_results=save_results, return_records=return_records)
+    if lk is not None:
+        res.update(ev.uncert_summary())
+        res.update(lk.finish())
     model.check_status()
     res["imgname"] = np.asarray(dataset.imgname)
     ev.close()
@@ -247,10 +315,17 @@ def report_lines(res: Dict[str, object]):
             f"Uncert Error Correlation: {res['val_corr']}", f"N: {res['N']}"]
 
 
+def likelihood_lines(res: Dict[str, object]):
+    """The two lines of trainer.py:389-390 report_lines leaves out, and the held-out flow NLL (losses.py:346) with its two terms."""
+    return [f"Var-MPJPE: {res['val_mpjpe_var']}", f"Variance: {res['val_var']}",
+            f"Flow NLL: {res['val_nll']} (log sigma {res['val_log_sigma']}, log phi {res['val_log_phi']}, crops {res['nll_N']})"]
+
+
 def save_npz(path: str, res: Dict[str, object], dataset_name: str) -> None:
     """evaluation_results_<name>.npz: the numeric arrays of save_results.py:84-92 (the reference joblib-dumps a dict)."""
     keep = {k: v for k, v in res.items() if isinstance(v, np.ndarray) and k not in ("records", "summary") and v.dtype.kind in "fiu"}
     keep.update({k: np.float64(res[k]) for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")})
     keep["N"] = np.int64(res["N"])
+    keep.update({k: np.float64(res[k]) for k in ("val_nll", "val_log_phi", "val_log_sigma", "val_mpjpe_var", "val_var") if k in res})
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     np.savez(path, **keep)

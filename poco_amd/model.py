@@ -76,6 +76,9 @@ def _bind():
     L.poco_smpl_lbs.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
     L.poco_realnvp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.poco_realnvp_rep.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.poco_flow_context.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.poco_flow_nll.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    L.poco_flow_nll_reduce.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 
@@ -116,6 +119,10 @@ class POCO:
         if isinstance(engine_options, dict):
             engine_options = ",".join(f"{k}={int(v) if isinstance(v, bool) else v}" for k, v in engine_options.items())
         self.engine_options = engine_options or ""
+        # MASK_PARAMS_ID / EXCLUDE_UNCERT_IDX do not enter the forward; the engine records them so that flow_nll can refuse such a flow
+        for key, val in (("mask_params_id", mask_params_id), ("exclude_uncert_idx", exclude_uncert_idx)):
+            if val:
+                self.engine_options += ("," if self.engine_options else "") + f"{key}={val}"
         self.max_graphs = int(max_graphs)
         check(self._L.poco_create_ex(backbone.encode(), self.max_batch, self.num_flow_layers, self.engine_options.encode(),
                                      C.byref(self._h)), "poco_create_ex")
@@ -464,3 +471,60 @@ class POCO:
     def realnvp_forward(self, z: torch.Tensor, ctx: torch.Tensor, rep: int = 1) -> torch.Tensor:
         """RealNVP.forward_p(z [N,9], x_cond) (real_nvp.py:25-38)."""
         return self._realnvp(z, ctx, rep, 1)
+
+    # ---- the flow likelihood of the ground truth (include/poco_hip.h poco_flow_*) ----------------------------------------------
+    FLOW_NLL_RECORD_FLOATS = 80
+
+    def _f32(self, t: torch.Tensor, what: str, tail) -> torch.Tensor:
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise PocoHipError(f"{what} must be a CUDA tensor")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            t = t.to(torch.float32).contiguous()
+        if tuple(t.shape[1:]) != tuple(tail):
+            raise PocoHipError(f"{what} must be [B, {', '.join(map(str, tail))}], got {tuple(t.shape)}")
+        return t
+
+    def flow_context(self, uncert_feat: torch.Tensor) -> torch.Tensor:
+        """context_feats = flow_head.cond_layer(uncert_feat) (nf_head.py:82): [B, uncert_feat_dim] -> [B,512].  Enqueued on the
+        current stream.  Raises if the checkpoint had no cond_layer."""
+        self.finalize()
+        uf = self._f32(uncert_feat, "uncert_feat", (self._L.poco_uncert_feat_dim(self._h),))
+        ctx = torch.empty(uf.shape[0], 512, device=self.device, dtype=torch.float32)
+        check(self._L.poco_flow_context(self._h, int(uf.shape[0]), uf.data_ptr(), ctx.data_ptr(), _stream()), "poco_flow_context")
+        return ctx
+
+    def flow_nll(self, pred: Dict[str, torch.Tensor], gt_pose: torch.Tensor, valid: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The likelihood of the ground-truth pose under the model's flow, per crop (the training-time branch of
+        flow_head.forward, nf_head.py:84-123, and the terms of losses.py:346).  pred = the model's output dict (pred_pose,
+        var_pose, uncert_feat), gt_pose [B,72] axis-angle, valid [B] = has_smpl (None: every crop).  Returns [B,80] records:
+        [0] valid, [1] sum_j(log sigma - log phi), [8..32) log phi, [32..56) log sigma, [56..80) mean_9(bar); `out` = a
+        contiguous float32 [B,80] CUDA tensor to write them into.  Enqueued on the current stream, nothing goes to the host."""
+        pp = self._f32(pred["pred_pose"], "pred_pose", (24, 3, 3))
+        B = int(pp.shape[0])
+        var = self._f32(pred["var_pose"], "var_pose", (24,))
+        gp = self._f32(gt_pose, "gt_pose", (72,))
+        ctx = self.flow_context(pred["uncert_feat"])
+        if valid is not None:
+            if not (torch.is_tensor(valid) and valid.is_cuda):
+                raise PocoHipError("valid must be a CUDA tensor")
+            valid = valid.to(torch.int32).contiguous().view(-1)
+        if out is None:
+            out = torch.empty(B, self.FLOW_NLL_RECORD_FLOATS, device=self.device, dtype=torch.float32)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, self.FLOW_NLL_RECORD_FLOATS)):
+            raise PocoHipError(f"out must be a contiguous float32 CUDA tensor [{B}, {self.FLOW_NLL_RECORD_FLOATS}]")
+        for t in (var, gp, ctx, valid):
+            if t is not None and t.shape[0] != B:
+                raise PocoHipError("flow_nll: batch sizes differ")
+        check(self._L.poco_flow_nll(self._h, B, pp.data_ptr(), gp.data_ptr(), var.data_ptr(), ctx.data_ptr(),
+                                    None if valid is None else valid.data_ptr(), out.data_ptr(), _stream()), "poco_flow_nll")
+        return out
+
+    def flow_nll_summary(self, records: torch.Tensor) -> np.ndarray:
+        """poco_flow_nll_reduce over [N,80] device records: (valid crops, mean log phi, mean log sigma, loss_nf) as float64.
+        Synchronises the current stream."""
+        self.finalize()
+        rec = self._f32(records, "records", (self.FLOW_NLL_RECORD_FLOATS,))
+        summ = np.zeros(4, np.float64)
+        check(self._L.poco_flow_nll_reduce(self._h, int(rec.shape[0]), rec.data_ptr(), summ.ctypes.data, _stream()), "poco_flow_nll_reduce")
+        return summ
