@@ -231,6 +231,65 @@ int poco_op_conv2d(const float* d_in, int B, int H, int W, int Cin, const float*
                    const float* h_scale, const float* h_shift, int Cout, int ks, int stride,
                    const float* d_res, int relu, float* d_out, const int* cfg7, void* stream);
 
+/* The same conv on VIEWS, with every epilogue form - the operand form the engine uses: each activation is the channel slice
+ * [co, co + width) of a wider L16 buffer with `cs` channels per pixel (concat buffers, merged-conv outputs read in place).
+ * poco_op_conv2d is the dense special case (in_cs = Cin, res_cs = out_cs = Cout, offsets 0, act = relu).
+ *   d_in  = base of a buffer [B,H,in_cs/16,W,16], the conv reads channels [in_co, in_co + Cin);
+ *   d_res = base of [B,Ho,res_cs/16,Wo,16] (nullable), channels [res_co, res_co + Cout);
+ *   d_out = base of [B,Ho,out_cs/16,Wo,16], the conv writes channels [out_co, out_co + Cout) and nothing else.
+ *   act: 0 none, 1 ReLU, 2 sigmoid, 3 ReLU on the output channels >= relu_from only (several convs of one input merged along
+ *   Cout, the members without a ReLU first: csrc/engine.hip conv_multi); relu_from a multiple of 16 in [0, Cout].
+ *   res_after_act: 1 = the residual is added after the activation instead of before it ("out += residual; relu",
+ *   hrnet.py:42-58, is the 0 form).
+ * The entry adds the channel offsets to the pointers as the engine does (csrc/common.h l16_chan_off) and fills the descriptor
+ * with the buffers' strides.  Before any GPU work, POCO_ERR_ARG with a message for: a null d_in / h_weight / d_out; act outside
+ * 0..3; a bad relu_from; a stride smaller than offset + width; strides / offsets that are no multiples of 16 (planes: an L16
+ * slice) or of 4 (H = W = 1 rows, the regressor's state vector; ALG 11 needs 16 there too).  A form the chosen ALG refuses
+ * (the Winograd kernels: act 2 and 3) is POCO_ERR_ARG from the launcher.  Synchronises `stream`. */
+int poco_op_conv2d_ex(const float* d_in, int B, int H, int W, int Cin, int in_cs, int in_co, const float* h_weight,
+                      const float* h_scale, const float* h_shift, int Cout, int ks, int stride, const float* d_res,
+                      int res_cs, int res_co, int act, int relu_from, int res_after_act, float* d_out, int out_cs,
+                      int out_co, const int* cfg7, void* stream);
+
+/* ---- backbone side kernels and fused launches on their own (parity tests) ---------------------------------------------------
+ * All activations L16; a device pointer is at the FIRST CHANNEL of its slice, `*_cs` = channels per pixel of the buffer it lies
+ * in (a multiple of 16, >= the slice width).  Host weights are OIHW with per-channel scale / shift (nullable: 1 / 0), folded and
+ * packed exactly as the engine's builder does.  Argument errors are POCO_ERR_ARG before any GPU work; each entry synchronises
+ * `stream` before it returns. */
+/* Tail of one Bottleneck chained with the head of the next, planes = 64 (hrnet.py:79-99, resnet.py:101-121):
+ *   y = ReLU(bn3(conv3(t)) + res)  [.,256],   u = ReLU(bn1(conv1(y)))  [.,64];   t [B,H,W,64], res [B,H,W,256].
+ * h_w3 [256,64,1,1], h_w1 [64,256,1,1]. */
+int poco_op_bneck_chain(const float* d_t, int t_cs, const float* d_res, int res_cs, float* d_y, int y_cs, float* d_u,
+                        int u_cs, const float* h_w3, const float* h_scale3, const float* h_shift3, const float* h_w1,
+                        const float* h_scale1, const float* h_shift1, int B, int H, int W, void* stream);
+/* 16-pixel sub-tiles the persistent grid of poco_op_bneck_chain holds at once: with more, its waves walk several. */
+int poco_op_bneck_chain_resident_tiles(void);
+/* Projection-shortcut Bottleneck tail as one GEMM over two sources (resnet.py:101-121, layer2-4 .0):
+ *   out = act( bn3(conv3(a)) + bn_d(conv_d(b)) ),  conv_d = 1x1 at stride2 (1|2): b is sampled at (stride2 y, stride2 x).
+ * a [B,Ho,Wo,Ca], b [B,H2,W2,Cb], out [B,Ho,Wo,Cout], Cout a multiple of 64; h_wa [Cout,Ca,1,1], h_wb [Cout,Cb,1,1].
+ * wave_layout = 100 NI + 10 WM + WN (0 = the default: one wave per block), WM WN <= 8, NI (load schedule) in {0,1,3,4,5,6};
+ * any other value is POCO_ERR_ARG.  act 0 | 1. */
+int poco_op_conv1x1_dual(const float* d_a, int a_cs, int Ca, const float* d_b, int b_cs, int Cb, int H2, int W2,
+                         int stride2, const float* h_wa, const float* h_scale_a, const float* h_shift_a,
+                         const float* h_wb, const float* h_scale_b, const float* h_shift_b, float* d_out, int out_cs,
+                         int Cout, int B, int Ho, int Wo, int act, int wave_layout, void* stream);
+/* HRNet fuse (hrnet.py:257-264): out = [ReLU]( sum_k src_k[b, y >> shift_k, x >> shift_k, :] ), n = 1..4 terms (host arrays of n
+ * device pointers, strides, shifts 0..3 = nearest-neighbour upsampling by 2^shift; H, W multiples of 2^shift), C channels. */
+int poco_op_fuse_sum(int n, const float* const* d_src, const int* src_cs, const int* shift, float* d_out, int out_cs,
+                     int B, int H, int W, int C, int relu, void* stream);
+/* F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) (hrnet.py:440): [B,H,W,C] -> [B,2H,2W,C], dense. */
+int poco_op_bilinear_up2x(const float* d_in, float* d_out, int B, int H, int W, int C, void* stream);
+/* nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (resnet.py:206; padding never wins): [B,H,W,C] dense -> a slice of out_cs. */
+int poco_op_maxpool3x3s2(const float* d_in, float* d_out, int B, int H, int W, int C, int out_cs, void* stream);
+/* Global average pool (hrnet_cls.py:482, cliff_head.py:96): [B,H,W,C] dense L16 -> d_dst[b * dst_stride + c] (dst_stride a
+ * multiple of 4, >= C). */
+int poco_op_avgpool(const float* d_in, float* d_dst, int B, int H, int W, int C, int dst_stride, void* stream);
+/* Stem conv + BN + ReLU from the image: ks = 3 (hrnet.py:467-469) or 7 (resnet.py:203-205), stride 2, pad (ks-1)/2, 3 -> 64.
+ * d_img [B,3,H,W] NCHW, h_weight [64,3,ks,ks], d_out [B,Ho,4,Wo,16] L16 dense.  use_mfma 1 = the implicit-GEMM form where it
+ * covers the shape (output width 112), else - and with 0 - the packed-FMA form: the answer is the same. */
+int poco_op_stem_conv(const float* d_img, const float* h_weight, const float* h_scale, const float* h_shift, float* d_out,
+                      int B, int H, int W, int ks, int use_mfma, void* stream);
+
 /* Time `iters` launches of the same conv (+ReLU) with hipEvents; ms_out = mean ms per launch.
  * cfg_used7 (nullable) receives the tile configuration that ran: SEVEN ints {MT,NT,WM,WN,R,NI,ALG} (csrc/common.h
  * CONV_CFG_INTS) - the caller's array must hold 7. */

@@ -160,8 +160,8 @@ int launch_bneck_chain(const float* t, int t_cs, const float* res, int res_cs, f
   p.t_rs = t_cs * W; p.res_rs = res_cs * W; p.y_rs = y_cs * W; p.u_rs = u_cs * W;
   p.t_ss = p.res_ss = p.y_ss = p.u_ss = W * 16;
   p.dW = make_fastdiv(W);
-  const int grid = std::min(256, (p.ntiles + 7) / 8);
-  hipLaunchKernelGGL(bneck_chain_kernel, dim3(grid), dim3(512), CH_LDS, s, p);
+  const int grid = std::min(BNECK_CHAIN_MAX_BLOCKS, (p.ntiles + BNECK_CHAIN_WAVES - 1) / BNECK_CHAIN_WAVES);
+  hipLaunchKernelGGL(bneck_chain_kernel, dim3(grid), dim3(BNECK_CHAIN_WAVES * 64), CH_LDS, s, p);
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }

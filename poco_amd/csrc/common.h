@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -114,6 +115,36 @@ size_t conv_packed_weight_floats(int Cin, int Cout16, int ks);
 // Cout16 >= Cout is Cout rounded up to a multiple of 16 (extra channels are zero).
 void conv_pack_weights(const float* w_oihw, const float* scale /*nullable*/, int Cout, int Cin,
                        int ks, int Cout16, float* dst);
+// K concatenation of `nsrc` convs that share their output channels (engine: Builder::concat_k; poco_op_conv1x1_dual):
+//   sum_j (scale_j * conv_j(x_j) + shift_j)  =  [s_0 W_0 | s_1 W_1 | ...] . [x_0 ; x_1 ; ...] + sum_j shift_j
+// w[j] is OIHW [Cout, C[j], ks, ks], scale[j] / shift[j] are [Cout].  The arithmetic is fixed: a merged weight is
+// (float)((double)scale * w), a merged shift is summed in double in source order and rounded once.
+inline void conv_concat_k_weights(const float* const* w, const float* const* scale, const float* const* shift, const int* C,
+                                  int nsrc, int Cout, int ks, std::vector<float>* wout, std::vector<float>* bout) {
+  const int taps = ks * ks;
+  int K = 0, koff = 0;
+  for (int j = 0; j < nsrc; ++j) K += C[j];
+  wout->assign((size_t)Cout * K * taps, 0.f);
+  std::vector<double> bsum(Cout, 0.0);
+  for (int j = 0; j < nsrc; ++j) {
+    for (int o = 0; o < Cout; ++o) {
+      for (int k = 0; k < C[j] * taps; ++k)
+        (*wout)[((size_t)o * K + koff) * taps + k] = (float)((double)scale[j][o] * w[j][(size_t)o * C[j] * taps + k]);
+      bsum[o] += (double)shift[j][o];
+    }
+    koff += C[j];
+  }
+  bout->clear();
+  for (double v : bsum) bout->push_back((float)v);
+}
+// Stem conv weights (Cin = 3, Cout = 64): OIHW [64,3,ks,ks] x scale[64] -> tap-major [ks*ks*3][64] (launch_stem_conv).
+inline void stem_pack_weights(const float* w_oihw, const float* scale, int ks, std::vector<float>* dst) {
+  dst->assign((size_t)ks * ks * 3 * 64, 0.f);
+  for (int co = 0; co < 64; ++co)
+    for (int c = 0; c < 3; ++c)
+      for (int t = 0; t < ks * ks; ++t)
+        (*dst)[((size_t)t * 3 + c) * 64 + co] = w_oihw[((size_t)co * 3 + c) * ks * ks + t] * scale[co];
+}
 // Heuristic tile choice.
 ConvCfg conv_default_cfg(const ConvDesc& d);
 // Validate + launch.  Returns POCO_OK or an error code (message via poco_set_error).

@@ -417,26 +417,21 @@ struct Builder {
   };
   // K concatenation:  sum_j bn_j(conv_j(x_j))  =  [s_0 W_0 | s_1 W_1 | ...] . [x_0 ; x_1 ; ...] + sum_j shift_j
   Merged concat_k(const std::vector<MergeSrc>& srcs, int Cout, int ks) {
-    const int taps = ks * ks;
-    int K = 0, koff = 0;
-    for (const MergeSrc& m : srcs) K += m.C;
     Merged r;
     r.have = !declare;
-    if (r.have) r.w.assign((size_t)Cout * K * taps, 0.f);
-    std::vector<double> bsum(Cout, 0.0);
-    for (const MergeSrc& m : srcs) {
+    std::vector<std::vector<float>> scale(srcs.size()), shift(srcs.size());
+    std::vector<const float*> wp, sp, bp;
+    std::vector<int> C;
+    for (size_t j = 0; j < srcs.size(); ++j) {
+      const MergeSrc& m = srcs[j];
       const HostParam* w = P(m.conv + ".weight", {Cout, m.C, ks, ks});
-      std::vector<float> scale, shift;
-      bn_fold(m.bn, nullptr, Cout, scale, shift);
+      bn_fold(m.bn, nullptr, Cout, scale[j], shift[j]);
       r.have = r.have && w;
-      for (int o = 0; r.have && o < Cout; ++o) {
-        for (int k = 0; k < m.C * taps; ++k)
-          r.w[((size_t)o * K + koff) * taps + k] = (float)((double)scale[o] * w->data[(size_t)o * m.C * taps + k]);
-        bsum[o] += (double)shift[o];
-      }
-      koff += m.C;
+      wp.push_back(w ? w->data.data() : nullptr); sp.push_back(scale[j].data()); bp.push_back(shift[j].data());
+      C.push_back(m.C);
     }
-    for (double v : bsum) r.b.push_back((float)v);
+    if (r.have) conv_concat_k_weights(wp.data(), sp.data(), bp.data(), C.data(), (int)srcs.size(), Cout, ks, &r.w, &r.b);   // (common.h)
+    else r.b.assign(Cout, 0.f);
     return r;
   }
   // Row stacking: layers that read the SAME input (in_shape: [Cin] or [Cin, ks, ks]) as one layer over the concatenated output rows
@@ -676,11 +671,8 @@ struct Builder {
     int out = new_act(64, Ho, Ho);
     op.out = R(out);
     if (!declare && w) {
-      std::vector<float> wt((size_t)ks * ks * 3 * 64);
-      for (int co = 0; co < 64; ++co)
-        for (int c = 0; c < 3; ++c)
-          for (int t = 0; t < ks * ks; ++t)
-            wt[((size_t)t * 3 + c) * 64 + co] = w->data[((size_t)co * 3 + c) * ks * ks + t] * scale[co];
+      std::vector<float> wt;
+      stem_pack_weights(w->data.data(), scale.data(), ks, &wt);      // (common.h)
       op.wdev = upload(wt);
       op.bdev = upload(shift);
     }

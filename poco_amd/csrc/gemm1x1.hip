@@ -268,6 +268,14 @@ int gemm1x1_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
   return POCO_ERR_ARG;
 }
 
+bool gemm1x1_dual_layout(int wave_layout, int* WM, int* WN, int* NI) {
+  *WM = *WN = *NI = 1;
+  if (wave_layout == 0) return true;
+  if (wave_layout < 0) return false;
+  *WM = (wave_layout / 10) % 10; *WN = wave_layout % 10; *NI = wave_layout >= 100 ? wave_layout / 100 : 1;
+  return *WM >= 1 && *WN >= 1 && *WM * *WN <= 8 && (*NI == 1 || (*NI >= 3 && *NI <= 6));
+}
+
 // out = act( [Wa | Wb] . [a ; b(stride2)] + bias ): the K-concatenated form of  bn3(conv3(a)) + bn_d(conv_d(b))  for the
 // stride-2 Bottlenecks of ResNet-50 (resnet.py:101-121, layer2-4 .0): a [B,Ho,Wo,Ca of a_cs] is conv2's output, b
 // [B,H2,W2,Cb of b_cs] the block input, sampled at (2y, 2x).  wfrag: conv_pack_weights(ks = 1) over Ca + Cb input channels.
@@ -291,7 +299,10 @@ int launch_gemm1x1_dual(const float* a, int a_cs, int Ca, const float* b, int b_
   // tile 7x4, depth 2, one wave per block, default load schedule: the fastest of the wave layouts / schedules probed per
   // ResNet-50 stage at B = 64 (tools/dual_probe.sh builds with -DG1_DUAL_EXP to repeat that sweep)
   int WM = 1, WN = 1, NI = 1;
-  if (wave_layout > 0) { WM = std::max(1, (wave_layout / 10) % 10); WN = std::max(1, wave_layout % 10); NI = wave_layout >= 100 ? wave_layout / 100 : 1; if (WM * WN > 8 || !(NI == 1 || (NI >= 3 && NI <= 6))) { WM = WN = NI = 1; } }
+  if (!gemm1x1_dual_layout(wave_layout, &WM, &WN, &NI)) {
+    poco_set_error("gemm1x1_dual: wave_layout = 100 NI + 10 WM + WN needs WM, WN >= 1, WM * WN <= 8 and NI in {0, 1, 3, 4, 5, 6} (0 = one wave per block)");
+    return POCO_ERR_ARG;
+  }
 #ifdef G1_DUAL_EXP
   static const char* ov = getenv("POCO_G1_DUAL");         // "WM,WN,NI": timing probe, probe builds only
   if (ov) {

@@ -16,10 +16,14 @@ bool launch_stem_conv_mfma(const float* img_nchw, const float* w, const float* s
                            hipStream_t s);
 // 3x3 stride-2 pad-1 max pool, NHWC (resnet.py:206).
 // conv3 + residual + ReLU of one Bottleneck chained with conv1 + ReLU of the next (bneck_chain.hip)
+constexpr int BNECK_CHAIN_MAX_BLOCKS = 256, BNECK_CHAIN_WAVES = 8;   // persistent grid: beyond blocks x waves 16-pixel sub-tiles a wave walks several
 int launch_bneck_chain(const float* t, int t_cs, const float* res, int res_cs, float* y, int y_cs, float* u, int u_cs,
                        const float* w3, const float* b3, const float* w1, const float* b1, int B, int H, int W,
                        hipStream_t s);
 // K-concatenated projection shortcut with a strided second source (gemm1x1.hip)
+// wave_layout = 100 NI + 10 WM + WN: WM x WN waves per block (each >= 1, at most 8 in all), NI = load schedule 1 | 3..6 (0 = 1);
+// wave_layout 0 = one wave per block, hipcc's load order.  False = not a layout (launch_gemm1x1_dual then returns POCO_ERR_ARG).
+bool gemm1x1_dual_layout(int wave_layout, int* WM, int* WN, int* NI);
 int launch_gemm1x1_dual(const float* a, int a_cs, int Ca, const float* b, int b_cs, int Cb, int H2, int W2, int stride2,
                         const float* wfrag, const float* bias, float* out, int out_cs, int Cout, int B, int Ho, int Wo, int act,
                         hipStream_t stream, int wave_layout = 0);   // wave_layout = 100 NI + 10 WM + WN (0 = one wave per block, hipcc's load order)

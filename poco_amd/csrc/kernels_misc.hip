@@ -210,13 +210,17 @@ __global__ void avgpool_kernel(const float4* __restrict__ in, float* __restrict_
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * C4) return;
   const int c = i % C4, b = i / C4;
+  // a partial sum per image row, then the sum of the rows: one running fp32 sum over a 56 x 56 plane of post-ReLU (all
+  // positive) values drifts by ~2e-6 relative (measured 2.4e-6), the two-level sum by ~2e-7
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int y = 0; y < H; ++y) {
     const float4* p = in + L16_F4((size_t)b * H + y, 0, c, W, C4 >> 2);
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int x = 0; x < W; ++x) {
       const float4 v = p[(size_t)x * 4];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+      r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w;
     }
+    s.x += r.x; s.y += r.y; s.z += r.z; s.w += r.w;
   }
   const float inv = 1.f / (float)(H * W);
   *reinterpret_cast<float4*>(dst + (size_t)b * dst_stride + c * 4) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);

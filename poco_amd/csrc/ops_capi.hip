@@ -3,6 +3,7 @@
 #include "../../include/poco_hip.h"
 #include "common.h"
 
+#include <algorithm>
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -26,19 +27,43 @@ struct DevBuf {
 };
 }  // namespace
 
+// The operand form of a conv: every activation a channel slice [co, co + width) of a buffer with `cs` channels per pixel, and the
+// epilogue (ConvDesc::act / relu_from / res_after_act).  poco_op_conv2d is the dense case, poco_op_conv2d_ex exposes all of it.
+struct ConvView {
+  int in_cs, in_co, res_cs, res_co, out_cs, out_co;
+  int act, relu_from, res_after_act;
+};
+
+// Host-side validation of a view, before any GPU work.  `alg`: the ALG of the caller's configuration (-1 = heuristic).
+static int conv_view_check(const char* who, const void* d_in, const void* h_w, const void* d_out, const void* d_res, int B, int H,
+                           int W, int Cin, int Cout, int ks, int stride, const ConvView& v, int alg) {
+  auto bad = [&](const std::string& m) { poco_set_error(std::string(who) + ": " + m); return POCO_ERR_ARG; };
+  if (!d_in || !h_w || !d_out) return bad("null pointer");
+  if (B < 1 || H < 1 || W < 1 || Cin < 16 || Cout < 16) return bad("B, H, W must be >= 1 and Cin, Cout >= 16");
+  if (Cout % 16) return bad("Cout must be a multiple of 16 (the engine pads; the bare op does not)");
+  if (!(ks == 1 || ks == 3) || !(stride == 1 || stride == 2)) return bad("ks must be 1|3 and stride 1|2");
+  if (v.act < 0 || v.act > 3) return bad("act must be 0 (none), 1 (ReLU), 2 (sigmoid) or 3 (ReLU from relu_from)");
+  if (v.relu_from < 0 || (v.relu_from & 15) || v.relu_from > Cout) return bad("relu_from must be a multiple of 16 in [0, Cout]");
+  if (v.res_after_act != 0 && v.res_after_act != 1) return bad("res_after_act must be 0 or 1");
+  // what conv_launch admits: multiples of 4 (ALG 11 / 12: of 16).  On a plane the L16 layout itself needs whole 16-channel slices
+  // (l16_chan_off of any other offset is no channel slice); only vectors (H = W = 1: plain [B][C] rows) can use the multiples of 4.
+  const int gran = (H == 1 && W == 1 && alg != 11 && alg != 12) ? 4 : 16;
+  const int all = v.in_cs | v.in_co | v.out_cs | v.out_co | (d_res ? (v.res_cs | v.res_co) : 0);
+  if (v.in_co < 0 || v.out_co < 0 || (d_res && v.res_co < 0) || (all & (gran - 1)))
+    return bad("channel strides / offsets must be non-negative multiples of " + std::to_string(gran) +
+               (gran == 4 ? " (rows, H = W = 1)" : " (L16 planes; ALG 11)"));
+  if (v.in_cs < v.in_co + Cin) return bad("in_cs is smaller than in_co + Cin");
+  if (v.out_cs < v.out_co + Cout) return bad("out_cs is smaller than out_co + Cout");
+  if (d_res && v.res_cs < v.res_co + Cout) return bad("res_cs is smaller than res_co + Cout");
+  return POCO_OK;
+}
+
 static int conv_common(const float* d_in, int B, int H, int W, int Cin, const float* h_w,
                        const float* h_scale, const float* h_shift, int Cout, int ks, int stride,
-                       const float* d_res, int relu, float* d_out, const int* cfg7, int iters,
-                       float* ms_out, hipStream_t stream) {
-  if (!d_in || !h_w || !d_out) {
-    poco_set_error("conv2d: null pointer");
-    return POCO_ERR_ARG;
-  }
-  const int Cout16 = (Cout + 15) / 16 * 16;
-  if (Cout16 != Cout) {
-    poco_set_error("conv2d op: Cout must be a multiple of 16 (the engine pads; the bare op does not)");
-    return POCO_ERR_ARG;
-  }
+                       const float* d_res, const ConvView& v, float* d_out, const int* cfg7, int iters,
+                       float* ms_out, hipStream_t stream, const char* who = "conv2d") {
+  if (int rc = conv_view_check(who, d_in, h_w, d_out, d_res, B, H, W, Cin, Cout, ks, stride, v, (cfg7 && cfg7[0] > 0) ? cfg7[6] : -1)) return rc;
+  const int Cout16 = Cout;
   std::vector<float> packed(conv_packed_weight_floats(Cin, Cout16, ks));
   conv_pack_weights(h_w, h_scale, Cout, Cin, ks, Cout16, packed.data());
   std::vector<float> shift(Cout16, 0.f);
@@ -88,6 +113,7 @@ static int conv_common(const float* d_in, int B, int H, int W, int Cin, const fl
       d.w.wino4g = dwu4g.p;
       d.scratch_floats = conv_wino4g_scratch_floats(B, H, W, Cin, Cout16);
       POCO_HIP_CHECK(hipMalloc(&dscr.p, d.scratch_floats * sizeof(float)));
+      POCO_HIP_CHECK(hipMemsetAsync(dscr.p, 0xFF, d.scratch_floats * sizeof(float), stream));   // NaN: the engine never initialises this staging either
       d.scratch = dscr.p;
     }
   }
@@ -96,16 +122,20 @@ static int conv_common(const float* d_in, int B, int H, int W, int Cin, const fl
     if (!sk_err) { POCO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sk_err), 64, hipHostMallocMapped)); *sk_err = 0; }
     d.sk_scratch_floats = gemm1x1sk_scratch_floats();
     POCO_HIP_CHECK(hipMalloc(&dsk.p, d.sk_scratch_floats * sizeof(float)));
-    POCO_HIP_CHECK(hipMemset(dsk.p, 0, (size_t)SK_MAX_WAVES * sizeof(float)));
+    POCO_HIP_CHECK(hipMemsetAsync(dsk.p, 0xFF, d.sk_scratch_floats * sizeof(float), stream));    // partial accumulators: NaN (never initialised by the engine)
+    POCO_HIP_CHECK(hipMemsetAsync(dsk.p, 0, (size_t)SK_MAX_WAVES * sizeof(float), stream));      // flags: zero, as the owner must leave them (both on the kernels' stream)
     d.sk_scratch = dsk.p;
     d.sk_err_host = sk_err;
   }
-  d.in = d_in; d.in_cs = Cin; d.in_co = 0;
-  d.res = d_res; d.res_cs = Cout; d.res_co = 0;
-  d.out = d_out; d.out_cs = Cout; d.out_co = 0;
+  // the engine's form (run_op / conv_desc_of): pointers at the first channel of each slice (aptr), offsets 0, strides of the buffers
+  const int pad = (ks - 1) / 2;
+  const int Wo = (W + 2 * pad - ks) / stride + 1;
+  d.in = d_in + l16_chan_off(v.in_co, W); d.in_cs = v.in_cs; d.in_co = 0;
+  d.res = d_res ? d_res + l16_chan_off(v.res_co, Wo) : nullptr; d.res_cs = d_res ? v.res_cs : v.out_cs; d.res_co = 0;
+  d.out = d_out + l16_chan_off(v.out_co, Wo); d.out_cs = v.out_cs; d.out_co = 0;
   d.wfrag = dw.p; d.bias = db.p;
   d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout16;
-  d.ks = ks; d.stride = stride; d.act = relu; d.res_after_act = 0;
+  d.ks = ks; d.stride = stride; d.act = v.act; d.res_after_act = v.res_after_act; d.relu_from = v.relu_from;
   ConvCfg cfg = conv_default_cfg(d);
   if (cfg7 && cfg7[0] > 0) cfg = conv_cfg_from(cfg7);
   int rc = conv_launch(d, cfg, stream);
@@ -134,8 +164,18 @@ extern "C" int poco_op_conv2d(const float* d_in, int B, int H, int W, int Cin, c
                               const float* h_scale, const float* h_shift, int Cout, int ks, int stride,
                               const float* d_res, int relu, float* d_out, const int* cfg7,
                               void* stream) {
-  return conv_common(d_in, B, H, W, Cin, h_weight, h_scale, h_shift, Cout, ks, stride, d_res, relu,
+  const ConvView dense{Cin, 0, Cout, 0, Cout, 0, relu, 0, 0};
+  return conv_common(d_in, B, H, W, Cin, h_weight, h_scale, h_shift, Cout, ks, stride, d_res, dense,
                      d_out, cfg7, 0, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_conv2d_ex(const float* d_in, int B, int H, int W, int Cin, int in_cs, int in_co, const float* h_weight,
+                                 const float* h_scale, const float* h_shift, int Cout, int ks, int stride, const float* d_res,
+                                 int res_cs, int res_co, int act, int relu_from, int res_after_act, float* d_out, int out_cs,
+                                 int out_co, const int* cfg7, void* stream) {
+  const ConvView v{in_cs, in_co, res_cs, res_co, out_cs, out_co, act, relu_from, res_after_act};
+  return conv_common(d_in, B, H, W, Cin, h_weight, h_scale, h_shift, Cout, ks, stride, d_res, v, d_out, cfg7, 0, nullptr,
+                     (hipStream_t)stream, "conv2d_ex");
 }
 
 extern "C" int poco_bench_conv2d(const float* d_in, int B, int H, int W, int Cin, const float* h_weight,
@@ -148,7 +188,8 @@ extern "C" int poco_bench_conv2d(const float* d_in, int B, int H, int W, int Cin
     cfg_used7[0] = c.MT; cfg_used7[1] = c.NT; cfg_used7[2] = c.WM;
     cfg_used7[3] = c.WN; cfg_used7[4] = c.R;  cfg_used7[5] = c.NI; cfg_used7[6] = c.ALG;
   }
-  return conv_common(d_in, B, H, W, Cin, h_weight, nullptr, nullptr, Cout, ks, stride, nullptr, 1, d_out,
+  const ConvView dense{Cin, 0, Cout, 0, Cout, 0, 1, 0, 0};
+  return conv_common(d_in, B, H, W, Cin, h_weight, nullptr, nullptr, Cout, ks, stride, nullptr, dense, d_out,
                      cfg7, iters, ms_out, (hipStream_t)stream);
 }
 
@@ -216,7 +257,7 @@ extern "C" int poco_tune_conv(int B, int H, int W, int Cin, int Cout, int ks, in
     if (!sk_err) { POCO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sk_err), 64, hipHostMallocMapped)); *sk_err = 0; }
     d.sk_scratch_floats = gemm1x1sk_scratch_floats();
     POCO_HIP_CHECK(hipMalloc(&dsk.p, d.sk_scratch_floats * sizeof(float)));
-    POCO_HIP_CHECK(hipMemset(dsk.p, 0, (size_t)SK_MAX_WAVES * sizeof(float)));
+    POCO_HIP_CHECK(hipMemsetAsync(dsk.p, 0, (size_t)SK_MAX_WAVES * sizeof(float), stream));
     d.sk_scratch = dsk.p;
     d.sk_err_host = sk_err;
   }
@@ -356,6 +397,159 @@ extern "C" int poco_op_rot6d(const float* d_in, float* d_rotmat, int B, void* st
   launch_rot6d(d_in, 144, d_rotmat, 216, nullptr, 0, B, (hipStream_t)stream);
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
+}
+
+// ---- backbone side kernels and fused launches on their own (tests/test_engine_kernels_gpu.py) -------------------------------
+// Every entry validates on the host before any GPU work, launches on `stream` and synchronises it before it returns (the
+// temporary weight buffers live only that long).  Activations are L16; a pointer is at the first channel of its slice (aptr()).
+namespace {
+int op_bad(const char* who, const std::string& m) { poco_set_error(std::string(who) + ": " + m); return POCO_ERR_ARG; }
+// a slice of `width` channels inside a buffer of `cs` channels per pixel
+bool slice_ok(int cs, int width) { return cs >= width && (cs & 15) == 0; }
+// the kernels move float4: every activation pointer must be 16-byte aligned
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int op_finish(const char* who, hipStream_t s) {
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) { poco_set_error(std::string(who) + ": " + hipGetErrorString(e)); return POCO_ERR_HIP; }
+  return POCO_OK;
+}
+std::vector<float> ones_or(const float* p, int n, float dflt) {
+  std::vector<float> v(n, dflt);
+  if (p) v.assign(p, p + n);
+  return v;
+}
+}  // namespace
+
+extern "C" int poco_op_bneck_chain_resident_tiles(void) { return BNECK_CHAIN_MAX_BLOCKS * BNECK_CHAIN_WAVES; }
+
+extern "C" int poco_op_bneck_chain(const float* d_t, int t_cs, const float* d_res, int res_cs, float* d_y, int y_cs, float* d_u,
+                                   int u_cs, const float* h_w3, const float* h_scale3, const float* h_shift3, const float* h_w1,
+                                   const float* h_scale1, const float* h_shift1, int B, int H, int W, void* stream) {
+  const char* who = "bneck_chain";
+  if (!d_t || !d_res || !d_y || !d_u || !h_w3 || !h_w1) return op_bad(who, "null pointer");
+  if (B < 1 || H < 1 || W < 1 || (long)B * H * W >= (1L << 26)) return op_bad(who, "needs B, H, W >= 1 and fewer than 2^26 pixels");
+  if (!slice_ok(t_cs, 64) || !slice_ok(u_cs, 64) || !slice_ok(res_cs, 256) || !slice_ok(y_cs, 256))
+    return op_bad(who, "channel strides must be multiples of 16, t_cs / u_cs >= 64 and res_cs / y_cs >= 256");
+  if ((long)B * H * W * std::max(std::max(t_cs, u_cs), std::max(res_cs, y_cs)) >= (1L << 31)) return op_bad(who, "buffer of 2^31 floats or more");
+  // packed the way Builder::chain_op packs them
+  std::vector<float> p3(conv_packed_weight_floats(64, 256, 1)), p1(conv_packed_weight_floats(256, 64, 1));
+  conv_pack_weights(h_w3, h_scale3, 256, 64, 1, 256, p3.data());
+  conv_pack_weights(h_w1, h_scale1, 64, 256, 1, 64, p1.data());
+  DevBuf w3, b3, w1, b1;
+  POCO_HIP_CHECK(w3.upload(p3));
+  POCO_HIP_CHECK(b3.upload(ones_or(h_shift3, 256, 0.f)));
+  POCO_HIP_CHECK(w1.upload(p1));
+  POCO_HIP_CHECK(b1.upload(ones_or(h_shift1, 64, 0.f)));
+  const int rc = launch_bneck_chain(d_t, t_cs, d_res, res_cs, d_y, y_cs, d_u, u_cs, w3.p, b3.p, w1.p, b1.p, B, H, W, (hipStream_t)stream);
+  const int rs = op_finish(who, (hipStream_t)stream);
+  return rc != POCO_OK ? rc : rs;
+}
+
+extern "C" int poco_op_conv1x1_dual(const float* d_a, int a_cs, int Ca, const float* d_b, int b_cs, int Cb, int H2, int W2,
+                                    int stride2, const float* h_wa, const float* h_scale_a, const float* h_shift_a,
+                                    const float* h_wb, const float* h_scale_b, const float* h_shift_b, float* d_out, int out_cs,
+                                    int Cout, int B, int Ho, int Wo, int act, int wave_layout, void* stream) {
+  const char* who = "conv1x1_dual";
+  if (!d_a || !d_b || !d_out || !h_wa || !h_wb) return op_bad(who, "null pointer");
+  if (B < 1 || Ho < 1 || Wo < 1 || H2 < 1 || W2 < 1 || Ca < 16 || Cb < 16 || Cout < 64) return op_bad(who, "empty shape");
+  if ((Ca | Cb) % 16 || Cout % 64) return op_bad(who, "Ca, Cb must be multiples of 16 and Cout a multiple of 64");
+  if (stride2 != 1 && stride2 != 2) return op_bad(who, "stride2 must be 1 or 2");
+  if ((H2 - 1) / stride2 + 1 != Ho || (W2 - 1) / stride2 + 1 != Wo) return op_bad(who, "the second source's plane does not give Ho x Wo at stride2");
+  if (!slice_ok(a_cs, Ca) || !slice_ok(b_cs, Cb) || !slice_ok(out_cs, Cout)) return op_bad(who, "channel strides must be multiples of 16 and at least the slice width");
+  if (act != 0 && act != 1) return op_bad(who, "act must be 0 or 1");
+  {                                // the launcher refuses an unknown layout too; asked here so that it happens before any GPU work
+    int WM, WN, NI;
+    if (!gemm1x1_dual_layout(wave_layout, &WM, &WN, &NI))
+      return op_bad(who, "wave_layout = 100 NI + 10 WM + WN needs WM, WN >= 1, WM * WN <= 8 and NI in {0, 1, 3, 4, 5, 6}");
+  }
+  if ((long)B * Ho * Wo * std::max(a_cs, out_cs) >= (1L << 31) || (long)B * H2 * W2 * b_cs >= (1L << 31)) return op_bad(who, "buffer of 2^31 floats or more");
+  // merged and packed the way Builder::bottleneck packs conv3+downsample
+  const std::vector<float> sa = ones_or(h_scale_a, Cout, 1.f), sb = ones_or(h_scale_b, Cout, 1.f);
+  const std::vector<float> ba = ones_or(h_shift_a, Cout, 0.f), bb = ones_or(h_shift_b, Cout, 0.f);
+  const float* w[2] = {h_wa, h_wb};
+  const float* sc[2] = {sa.data(), sb.data()};
+  const float* sh[2] = {ba.data(), bb.data()};
+  const int C[2] = {Ca, Cb};
+  std::vector<float> mw, mb;
+  conv_concat_k_weights(w, sc, sh, C, 2, Cout, 1, &mw, &mb);
+  std::vector<float> packed(conv_packed_weight_floats(Ca + Cb, Cout, 1));
+  conv_pack_weights(mw.data(), nullptr, Cout, Ca + Cb, 1, Cout, packed.data());
+  DevBuf dw, db;
+  POCO_HIP_CHECK(dw.upload(packed));
+  POCO_HIP_CHECK(db.upload(mb));
+  const int rc = launch_gemm1x1_dual(d_a, a_cs, Ca, d_b, b_cs, Cb, H2, W2, stride2, dw.p, db.p, d_out, out_cs, Cout, B, Ho, Wo, act,
+                                     (hipStream_t)stream, wave_layout);
+  const int rs = op_finish(who, (hipStream_t)stream);
+  return rc != POCO_OK ? rc : rs;
+}
+
+extern "C" int poco_op_fuse_sum(int n, const float* const* d_src, const int* src_cs, const int* shift, float* d_out, int out_cs,
+                                int B, int H, int W, int C, int relu, void* stream) {
+  const char* who = "fuse_sum";
+  if (!d_src || !src_cs || !shift || !d_out) return op_bad(who, "null pointer");
+  if (n < 1 || n > 4) return op_bad(who, "1 to 4 terms");
+  if (B < 1 || H < 1 || W < 1 || C < 16 || (C & 15)) return op_bad(who, "needs B, H, W >= 1 and C a multiple of 16");
+  if (!slice_ok(out_cs, C)) return op_bad(who, "out_cs must be a multiple of 16 and at least C");
+  if ((long)B * H * W * out_cs >= (1L << 31)) return op_bad(who, "buffer of 2^31 floats or more");
+  FuseArgs fa{};
+  fa.n = n;
+  for (int k = 0; k < n; ++k) {
+    if (!d_src[k]) return op_bad(who, "null term");
+    if (shift[k] < 0 || shift[k] > 3 || (H & ((1 << shift[k]) - 1)) || (W & ((1 << shift[k]) - 1)))
+      return op_bad(who, "a term's shift must be 0..3 and H, W multiples of 2^shift");
+    if (!slice_ok(src_cs[k], C)) return op_bad(who, "a term's channel stride must be a multiple of 16 and at least C");
+    fa.src[k] = d_src[k]; fa.shift[k] = shift[k]; fa.src_cs[k] = src_cs[k];
+  }
+  launch_fuse_sum(fa, d_out, B, H, W, C, out_cs, relu ? 1 : 0, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_bilinear_up2x(const float* d_in, float* d_out, int B, int H, int W, int C, void* stream) {
+  const char* who = "bilinear_up2x";
+  if (!d_in || !d_out) return op_bad(who, "null pointer");
+  if (B < 1 || H < 1 || W < 1 || C < 16 || (C & 15)) return op_bad(who, "needs B, H, W >= 1 and C a multiple of 16");
+  if ((long)B * 4 * H * W * C >= (1L << 31)) return op_bad(who, "buffer of 2^31 floats or more");
+  launch_bilinear_up2x(d_in, d_out, B, H, W, C, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_maxpool3x3s2(const float* d_in, float* d_out, int B, int H, int W, int C, int out_cs, void* stream) {
+  const char* who = "maxpool3x3s2";
+  if (!d_in || !d_out) return op_bad(who, "null pointer");
+  if (B < 1 || H < 1 || W < 1 || C < 16 || (C & 15)) return op_bad(who, "needs B, H, W >= 1 and C a multiple of 16");
+  if (!slice_ok(out_cs, C)) return op_bad(who, "out_cs must be a multiple of 16 and at least C");
+  if ((long)B * H * W * C >= (1L << 31) || (long)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * out_cs >= (1L << 31)) return op_bad(who, "buffer of 2^31 floats or more");
+  launch_maxpool3x3s2(d_in, d_out, B, H, W, C, out_cs, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_avgpool(const float* d_in, float* d_dst, int B, int H, int W, int C, int dst_stride, void* stream) {
+  const char* who = "avgpool";
+  if (!d_in || !d_dst) return op_bad(who, "null pointer");
+  if (B < 1 || H < 1 || W < 1 || C < 16 || (C & 15)) return op_bad(who, "needs B, H, W >= 1 and C a multiple of 16");
+  if (dst_stride < C || (dst_stride & 3)) return op_bad(who, "dst_stride must be a multiple of 4 and at least C");
+  if (!aligned16(d_in) || !aligned16(d_dst)) return op_bad(who, "d_in and d_dst must be 16-byte aligned (float4 loads / stores)");
+  if ((long)B * H * W * C >= (1L << 31) || (long)B * dst_stride >= (1L << 31)) return op_bad(who, "buffer of 2^31 floats or more");
+  launch_avgpool(d_in, d_dst, B, H, W, C, dst_stride, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_stem_conv(const float* d_img, const float* h_weight, const float* h_scale, const float* h_shift,
+                                 float* d_out, int B, int H, int W, int ks, int use_mfma, void* stream) {
+  const char* who = "stem_conv";
+  if (!d_img || !h_weight || !d_out) return op_bad(who, "null pointer");
+  if (ks != 3 && ks != 7) return op_bad(who, "ks must be 3 or 7");
+  if (use_mfma != 0 && use_mfma != 1) return op_bad(who, "use_mfma must be 0 or 1");
+  if (B < 1 || H < 1 || W < 1 || (long)B * 3 * H * W >= (1L << 31) || (long)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * 64 >= (1L << 31))
+    return op_bad(who, "needs B, H, W >= 1 and fewer than 2^31 floats per tensor");
+  std::vector<float> wt;
+  stem_pack_weights(h_weight, ones_or(h_scale, 64, 1.f).data(), ks, &wt);     // as Builder::stem packs them
+  DevBuf dw, db;
+  POCO_HIP_CHECK(dw.upload(wt));
+  POCO_HIP_CHECK(db.upload(ones_or(h_shift, 64, 0.f)));
+  launch_stem_conv(d_img, dw.p, db.p, d_out, B, H, W, ks, (hipStream_t)stream, use_mfma);
+  return op_finish(who, (hipStream_t)stream);
 }
 
 // ---- demo renderer (csrc/render.hip) ------------------------------------------------------------------------------------

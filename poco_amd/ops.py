@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import check, current_stream, fptr, lib
+from ._lib import PocoHipError, check, current_stream, fptr, lib
 
 
 def _cfg(cfg):
@@ -29,6 +29,117 @@ def from_l16(y: torch.Tensor) -> torch.Tensor:
     return y.permute(0, 1, 3, 2, 4).reshape(B, H, W, C16 * 16).contiguous()
 
 
+# ---- poisoned wide buffers (tests): what a kernel must not write keeps a bit pattern, what it must not read is NaN ----------
+POISON_BITS = 0x5A5AA5A5          # a finite float (1.54e16): "nobody may write here"; compared bitwise
+
+
+class Wide:
+    """An L16 activation buffer [B,H,cs/16,W,16] inside one allocation with a guard band of `guard_rows` image rows of the buffer
+    (cs * W floats each) before and after it.  fill = "nan" (inputs: everything outside the slice the kernel may read is NaN, so
+    foreign memory that enters the arithmetic - even times a zero weight - shows in the result) or "poison" (outputs: POISON_BITS
+    everywhere the kernel must not write; the slice it must write is NaN, so an unwritten element shows too)."""
+
+    def __init__(self, B, H, W, cs, device, fill, guard_rows=1):
+        assert fill in ("nan", "poison") and cs % 4 == 0 and (cs % 16 == 0 or H * W == 1)
+        self.B, self.H, self.W, self.cs = B, H, W, cs
+        self.guard = guard_rows * cs * W
+        n = B * H * W * cs
+        self.flat = torch.empty(n + 2 * self.guard, device=device, dtype=torch.float32)
+        if fill == "nan":
+            self.flat.fill_(float("nan"))
+        else:
+            self.flat.view(torch.int32).fill_(POISON_BITS)
+        self.body = self.flat[self.guard:self.guard + n]
+
+    def _mask_or_view(self, co, C):
+        if self.H * self.W == 1:                       # rows: plain [B][cs], offsets in multiples of 4
+            return self.body.view(self.B, self.cs)[:, co:co + C]
+        assert co % 16 == 0 and C % 16 == 0
+        return self.body.view(self.B, self.H, self.cs // 16, self.W, 16)[:, :, co // 16:(co + C) // 16]
+
+    def put(self, co, x_nhwc):
+        """Write an NHWC tensor into channels [co, co + C)."""
+        C = x_nhwc.shape[-1]
+        if self.H * self.W == 1:
+            self._mask_or_view(co, C).copy_(x_nhwc.reshape(self.B, C))
+        else:
+            self._mask_or_view(co, C).copy_(to_l16(x_nhwc.contiguous()))
+        return self
+
+    def fill(self, co, C, value):
+        self._mask_or_view(co, C).fill_(value)
+        return self
+
+    def get(self, co, C):
+        """Channels [co, co + C) as NHWC."""
+        v = self._mask_or_view(co, C)
+        if self.H * self.W == 1:
+            return v.reshape(self.B, 1, 1, C).contiguous()
+        return from_l16(v.contiguous())
+
+    def outside_bits(self, co, C):
+        """int32 bits of every element of the allocation outside channels [co, co + C): guard bands and neighbouring channels."""
+        keep = torch.ones_like(self.flat, dtype=torch.bool)
+        kb = keep[self.guard:self.guard + self.body.numel()]
+        if self.H * self.W == 1:
+            kb.view(self.B, self.cs)[:, co:co + C] = False
+        else:
+            kb.view(self.B, self.H, self.cs // 16, self.W, 16)[:, :, co // 16:(co + C) // 16] = False
+        return self.flat.view(torch.int32)[keep]
+
+    def untouched(self, co, C):
+        """True if nothing outside channels [co, co + C) was written (bitwise)."""
+        return bool((self.outside_bits(co, C) == POISON_BITS).all())
+
+    def ptr(self, co=0):
+        """Device pointer of the first channel of the slice at `co` (csrc/common.h l16_chan_off), as the engine's aptr()."""
+        off = (co >> 4) * self.W * 16 + (co & 15)
+        return C.c_void_p(self.body.data_ptr() + 4 * off)
+
+    def base(self):
+        return C.c_void_p(self.body.data_ptr())
+
+
+def _out_hw(H, W, ks, stride):
+    pad = (ks - 1) // 2
+    return (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+
+
+def conv2d_view(x: torch.Tensor, weight: np.ndarray, scale=None, shift=None, stride=1, residual=None, *, in_cs=None, in_co=0,
+                res_cs=None, res_co=0, out_cs=None, out_co=0, act=0, relu_from=0, res_after_act=0, cfg=None):
+    """poco_op_conv2d_ex: the conv on channel slices of wider L16 buffers, with every epilogue form (include/poco_hip.h).
+    x [B,H,W,Cin] / residual [B,Ho,Wo,Cout] NHWC cuda tensors are placed at channel offset in_co / res_co of poisoned buffers with
+    in_cs / res_cs channels; residual = "input" makes the input buffer double as the residual (BasicBlock conv2: needs Cin == Cout,
+    stride 1).  Returns (out NHWC [B,Ho,Wo,Cout] = channels [out_co, out_co + Cout) of the output buffer, that buffer as a Wide):
+    the caller checks `wide.untouched(out_co, Cout)` and that `out` holds no NaN."""
+    assert x.is_cuda and x.dtype == torch.float32
+    B, H, W, Cin = x.shape
+    Cout, Cin2, ks, ks2 = weight.shape
+    assert Cin2 == Cin and ks == ks2
+    Ho, Wo = _out_hw(H, W, ks, stride)
+    in_cs = Cin if in_cs is None else in_cs
+    out_cs = Cout if out_cs is None else out_cs
+    res_cs = Cout if res_cs is None else res_cs
+    win = Wide(B, H, W, in_cs, x.device, "nan").put(in_co, x)
+    if isinstance(residual, str):
+        assert residual == "input" and Cin == Cout and stride == 1
+        wres, res_cs, res_co = win, in_cs, in_co
+    elif residual is not None:
+        wres = Wide(B, Ho, Wo, res_cs, x.device, "nan").put(res_co, residual)
+    else:
+        wres = None
+    wout = Wide(B, Ho, Wo, out_cs, x.device, "poison").fill(out_co, Cout, float("nan"))
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    scale = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+    shift = None if shift is None else np.ascontiguousarray(shift, dtype=np.float32)
+    cptr, _keep = _cfg(cfg)
+    rc = lib().poco_op_conv2d_ex(win.base(), B, H, W, Cin, in_cs, in_co, fptr(weight), fptr(scale), fptr(shift), Cout, ks, stride,
+                                 C.c_void_p(0) if wres is None else wres.base(), res_cs, res_co, int(act), int(relu_from),
+                                 int(res_after_act), wout.base(), out_cs, out_co, cptr, current_stream())
+    check(rc, "poco_op_conv2d_ex")
+    return wout.get(out_co, Cout), wout
+
+
 def conv2d_nhwc(x: torch.Tensor, weight: np.ndarray, scale=None, shift=None, stride=1, residual=None,
                 relu=False, cfg=None) -> torch.Tensor:
     """x [B,H,W,Cin] cuda fp32 NHWC; weight OIHW numpy fp32 (host). Returns NHWC output."""
@@ -36,13 +147,13 @@ def conv2d_nhwc(x: torch.Tensor, weight: np.ndarray, scale=None, shift=None, str
     B, H, W, Cin = x.shape
     Cout, Cin2, ks, ks2 = weight.shape
     assert Cin2 == Cin and ks == ks2
-    pad = (ks - 1) // 2
-    Ho = (H + 2 * pad - ks) // stride + 1
-    Wo = (W + 2 * pad - ks) // stride + 1
+    Ho, Wo = _out_hw(H, W, ks, stride)
     # the operator works on the library's L16 layout; Cin/Cout are padded to multiples of 16 inside the op,
     # so NHWC tensors are converted here (tests / tuning only - the engine never leaves L16)
     assert Cin % 16 == 0 and Cout % 16 == 0, "conv2d_nhwc: channel counts must be multiples of 16"
-    out = torch.empty((B, Ho, Cout // 16, Wo, 16), device=x.device, dtype=torch.float32)
+    # the output starts as NaN between poisoned guard bands: an element the kernel leaves unwritten stays NaN in the result (the
+    # caching allocator would otherwise hand back the previous, correct answer), a store outside the tensor raises below
+    wout = Wide(B, Ho, Wo, Cout, x.device, "poison").fill(0, Cout, float("nan"))
     weight = np.ascontiguousarray(weight, dtype=np.float32)
     scale = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
     shift = None if shift is None else np.ascontiguousarray(shift, dtype=np.float32)
@@ -50,9 +161,11 @@ def conv2d_nhwc(x: torch.Tensor, weight: np.ndarray, scale=None, shift=None, str
     xl = to_l16(x)
     rl = None if residual is None else to_l16(residual)
     rc = lib().poco_op_conv2d(fptr(xl), B, H, W, Cin, fptr(weight), fptr(scale), fptr(shift), Cout, ks,
-                              stride, fptr(rl), int(relu), fptr(out), cptr, current_stream())
+                              stride, fptr(rl), int(relu), wout.base(), cptr, current_stream())
     check(rc, "poco_op_conv2d")
-    return from_l16(out)
+    if not wout.untouched(0, Cout):
+        raise PocoHipError("poco_op_conv2d wrote outside its output tensor (guard band changed)")
+    return wout.get(0, Cout)
 
 
 def bench_conv2d(x: torch.Tensor, weight: np.ndarray, stride=1, cfg=None, iters=20):
@@ -117,3 +230,110 @@ def rodrigues(aa: torch.Tensor) -> torch.Tensor:
     if aa.shape[-1] == 3:
         return out.view(*aa.shape[:-1], 3, 3)
     return out.view(*aa.shape[:-1], aa.shape[-1] // 3, 3, 3)
+
+
+# ---- backbone side kernels and fused launches on their own (include/poco_hip.h; tests/test_engine_kernels_gpu.py) -----------
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def bneck_chain(t, res, w3, scale3, shift3, w1, scale1, shift1, *, t_cs=64, t_co=0, res_cs=256, res_co=0, y_cs=256, y_co=0,
+                u_cs=64, u_co=0):
+    """y = ReLU(bn3(conv3(t)) + res), u = ReLU(bn1(conv1(y))) (poco_op_bneck_chain): t [B,H,W,64], res [B,H,W,256] NHWC, each
+    operand a slice at *_co of a poisoned buffer with *_cs channels.  Returns (y, u, y buffer, u buffer)."""
+    B, H, W, _ = t.shape
+    wt = Wide(B, H, W, t_cs, t.device, "nan").put(t_co, t)
+    wr = Wide(B, H, W, res_cs, t.device, "nan").put(res_co, res)
+    wy = Wide(B, H, W, y_cs, t.device, "poison").fill(y_co, 256, float("nan"))
+    wu = Wide(B, H, W, u_cs, t.device, "poison").fill(u_co, 64, float("nan"))
+    w3, scale3, shift3, w1, scale1, shift1 = map(_f32, (w3, scale3, shift3, w1, scale1, shift1))
+    check(lib().poco_op_bneck_chain(wt.ptr(t_co), t_cs, wr.ptr(res_co), res_cs, wy.ptr(y_co), y_cs, wu.ptr(u_co), u_cs, fptr(w3),
+                                    fptr(scale3), fptr(shift3), fptr(w1), fptr(scale1), fptr(shift1), B, H, W, current_stream()),
+          "poco_op_bneck_chain")
+    return wy.get(y_co, 256), wu.get(u_co, 64), wy, wu
+
+
+def bneck_chain_resident_tiles() -> int:
+    return int(lib().poco_op_bneck_chain_resident_tiles())
+
+
+def conv1x1_dual(a, b, wa, scale_a, shift_a, wb, scale_b, shift_b, stride2=2, act=1, wave_layout=0, *, a_cs=None, a_co=0,
+                 b_cs=None, b_co=0, out_cs=None, out_co=0):
+    """act(bn3(conv3(a)) + bn_d(conv_d(b, stride2))) as one GEMM (poco_op_conv1x1_dual): a [B,Ho,Wo,Ca], b [B,H2,W2,Cb] NHWC.
+    Returns (out NHWC, output buffer)."""
+    B, Ho, Wo, Ca = a.shape
+    _, H2, W2, Cb = b.shape
+    Cout = wa.shape[0]
+    a_cs, b_cs, out_cs = a_cs or Ca, b_cs or Cb, out_cs or Cout
+    wa_ = Wide(B, Ho, Wo, a_cs, a.device, "nan").put(a_co, a)
+    wb_ = Wide(B, H2, W2, b_cs, a.device, "nan").put(b_co, b)
+    wo = Wide(B, Ho, Wo, out_cs, a.device, "poison").fill(out_co, Cout, float("nan"))
+    wa, scale_a, shift_a, wb, scale_b, shift_b = map(_f32, (wa, scale_a, shift_a, wb, scale_b, shift_b))
+    check(lib().poco_op_conv1x1_dual(wa_.ptr(a_co), a_cs, Ca, wb_.ptr(b_co), b_cs, Cb, H2, W2, stride2, fptr(wa), fptr(scale_a),
+                                     fptr(shift_a), fptr(wb), fptr(scale_b), fptr(shift_b), wo.ptr(out_co), out_cs, Cout, B, Ho, Wo,
+                                     int(act), int(wave_layout), current_stream()), "poco_op_conv1x1_dual")
+    return wo.get(out_co, Cout), wo
+
+
+def fuse_sum(terms, shifts, relu, *, src_cs=None, src_co=None, out_cs=None, out_co=0):
+    """[ReLU](sum_k term_k upsampled by 2^shift_k) (poco_op_fuse_sum): terms = NHWC tensors [B, H >> s, W >> s, C].
+    Returns (out NHWC [B,H,W,C], output buffer)."""
+    n = len(terms)
+    Cc = terms[0].shape[-1]
+    B = terms[0].shape[0]
+    H, W = max(t.shape[1] << s for t, s in zip(terms, shifts)), max(t.shape[2] << s for t, s in zip(terms, shifts))
+    src_cs = list(src_cs or [Cc] * n)
+    src_co = list(src_co or [0] * n)
+    out_cs = out_cs or Cc
+    ws = [Wide(B, t.shape[1], t.shape[2], cs, t.device, "nan").put(co, t) for t, cs, co in zip(terms, src_cs, src_co)]
+    wo = Wide(B, H, W, out_cs, terms[0].device, "poison").fill(out_co, Cc, float("nan"))
+    ptrs = (C.c_void_p * n)(*[w.ptr(co).value for w, co in zip(ws, src_co)])
+    check(lib().poco_op_fuse_sum(n, ptrs, (C.c_int * n)(*src_cs), (C.c_int * n)(*shifts), wo.ptr(out_co), out_cs, B, H, W, Cc,
+                                 int(relu), current_stream()), "poco_op_fuse_sum")
+    return wo.get(out_co, Cc), wo
+
+
+def bilinear_up2x(x):
+    """x2 bilinear, align_corners=True (poco_op_bilinear_up2x): NHWC [B,H,W,C] -> ([B,2H,2W,C], output buffer)."""
+    B, H, W, Cc = x.shape
+    wi = Wide(B, H, W, Cc, x.device, "nan").put(0, x)
+    wo = Wide(B, 2 * H, 2 * W, Cc, x.device, "poison").fill(0, Cc, float("nan"))
+    check(lib().poco_op_bilinear_up2x(wi.ptr(), wo.ptr(), B, H, W, Cc, current_stream()), "poco_op_bilinear_up2x")
+    return wo.get(0, Cc), wo
+
+
+def maxpool3x3s2(x, *, out_cs=None, out_co=0):
+    """3x3 stride-2 pad-1 max pool (poco_op_maxpool3x3s2): NHWC -> (NHWC [B,Ho,Wo,C], output buffer)."""
+    B, H, W, Cc = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    out_cs = out_cs or Cc
+    wi = Wide(B, H, W, Cc, x.device, "nan").put(0, x)
+    wo = Wide(B, Ho, Wo, out_cs, x.device, "poison").fill(out_co, Cc, float("nan"))
+    check(lib().poco_op_maxpool3x3s2(wi.ptr(), wo.ptr(out_co), B, H, W, Cc, out_cs, current_stream()), "poco_op_maxpool3x3s2")
+    return wo.get(out_co, Cc), wo
+
+
+def avgpool(x, *, dst_stride=None, dst_off=0):
+    """Global average pool (poco_op_avgpool): NHWC [B,H,W,C] -> ([B,C] = columns [dst_off, dst_off + C) of rows of dst_stride
+    floats, the destination as a Wide of 1x1 planes)."""
+    B, H, W, Cc = x.shape
+    dst_stride = dst_stride or Cc
+    wi = Wide(B, H, W, Cc, x.device, "nan").put(0, x)
+    wo = Wide(B, 1, 1, dst_stride, x.device, "poison").fill(dst_off, Cc, float("nan"))
+    check(lib().poco_op_avgpool(wi.ptr(), wo.ptr(dst_off), B, H, W, Cc, dst_stride, current_stream()), "poco_op_avgpool")
+    return wo.get(dst_off, Cc).reshape(B, Cc), wo
+
+
+def stem_conv(img, weight, scale, shift, use_mfma=1):
+    """Stem conv + BN + ReLU (poco_op_stem_conv): img [B,3,H,W] NCHW cuda, weight [64,3,ks,ks] -> (NHWC [B,Ho,Wo,64], buffer)."""
+    B, _, H, W = img.shape
+    ks = weight.shape[-1]
+    Ho, Wo = _out_hw(H, W, ks, 2)
+    n = img.numel()
+    g = -(-3 * W // 64) * 64                                 # guard: NaN around the image, at least one row of all channels (keeps 256-byte alignment)
+    flat = torch.full((n + 2 * g,), float("nan"), device=img.device)
+    flat[g:g + n] = img.reshape(-1)
+    wo = Wide(B, Ho, Wo, 64, img.device, "poison").fill(0, 64, float("nan"))
+    check(lib().poco_op_stem_conv(C.c_void_p(flat.data_ptr() + 4 * g), fptr(_f32(weight)), fptr(_f32(scale)), fptr(_f32(shift)),
+                                  wo.ptr(), B, H, W, ks, int(use_mfma), current_stream()), "poco_op_stem_conv")
+    return wo.get(0, 64), wo

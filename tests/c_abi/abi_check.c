@@ -34,6 +34,15 @@ int main(int argc, char** argv) {
   tune_fn tune = (tune_fn)dlsym(so, "poco_tune_conv");
   status_fn status = (status_fn)dlsym(so, "poco_status");
   if (!tune || !status) return 4;
+  {
+    /* the stand-alone operators of the view conv and the backbone side kernels (additions to ABI 4) */
+    const char* ops[] = {"poco_op_conv2d", "poco_op_conv2d_ex", "poco_op_bneck_chain", "poco_op_bneck_chain_resident_tiles",
+                         "poco_op_conv1x1_dual", "poco_op_fuse_sum", "poco_op_bilinear_up2x", "poco_op_maxpool3x3s2",
+                         "poco_op_avgpool", "poco_op_stem_conv"};
+    size_t k;
+    for (k = 0; k < sizeof ops / sizeof ops[0]; ++k)
+      if (!dlsym(so, ops[k])) { fprintf(stderr, "missing %s\n", ops[k]); return 28; }
+  }
   if (!last_error || !create || !destroy || !num_tensors || !tensor_info || !load_tensor || !forward || !create_ex || !version) return 4;
   if (version() != POCO_ABI_VERSION) { fprintf(stderr, "library ABI %d, header ABI %d\n", version(), POCO_ABI_VERSION); return 15; }
 

@@ -543,17 +543,18 @@ def test_graph_replay_matches_eager(cuda):
 
 
 def test_smpl_lbs_op(cuda):
-    """poco_smpl_lbs vs the float64 numpy restatement; identity pose + zero betas -> template."""
+    """poco_smpl_lbs vs the float64 numpy restatement; identity pose + zero betas -> template.  B = 1, 63, 64, 65, 129 besides the
+    11 of old: the skin kernel stages 64 crops per block (one short, exact, one over, two blocks and one crop)."""
     from oracle import poco_ref, smpl_np
-    m = util.make_engine("resnet50-cliff", max_batch=16)
+    m = util.make_engine("resnet50-cliff", max_batch=129)
     smpl = synth.synth_smpl(7)
     r = np.random.default_rng(5)
-    B = 11
-    betas = r.standard_normal((B, 10)).astype(np.float32)
-    R = poco_ref.rot6d_to_rotmat(torch.from_numpy(r.standard_normal((B * 24, 6)).astype(np.float32))).reshape(B, 24, 3, 3)
-    v64, j64 = smpl_np.smpl_lbs_np(smpl, betas, R.numpy())
-    v, j = m.smpl_lbs(torch.from_numpy(betas).to(cuda), R.to(cuda))
-    assert np.abs(_np(v) - v64).max() < 2e-5 and np.abs(_np(j) - j64).max() < 2e-5
+    for B in (11, 1, 63, 64, 65, 129):
+        betas = r.standard_normal((B, 10)).astype(np.float32)
+        R = poco_ref.rot6d_to_rotmat(torch.from_numpy(r.standard_normal((B * 24, 6)).astype(np.float32))).reshape(B, 24, 3, 3)
+        v64, j64 = smpl_np.smpl_lbs_np(smpl, betas, R.numpy())
+        v, j = m.smpl_lbs(torch.from_numpy(betas).to(cuda), R.to(cuda))
+        assert np.abs(_np(v) - v64).max() < 2e-5 and np.abs(_np(j) - j64).max() < 2e-5, B
     eye = torch.eye(3).repeat(2, 24, 1, 1).to(cuda)
     v0, _ = m.smpl_lbs(torch.zeros(2, 10, device=cuda), eye)
     assert np.abs(_np(v0) - smpl["v_template"][None]).max() < 1e-6
