@@ -42,27 +42,8 @@ struct ConvCfg {
   int WN;      // waves along output channels  (block = WM*WN waves)
   int R;       // output rows per slab
   int NI;      // slabs (row bands / whole images) per block
-  int ALG;     // 0: register-staged single LDS buffer; 1: LDS-DMA double-buffered (patch + weights);
-               // 2: ALG 1 persistent over tiles; 3: Winograd F(2x2,3x3) (MT ignored, NT in {1,2}, R even);
-               // 4: Winograd, half-position waves + pipelined transform (WN = 2 halves, WM <= 4, NT <= 3)
-               // 5: small-M linear (H = W = 1, ks = 1): K split over WM waves per 16 outputs (linear_mfma.hip)
-               // 7: Winograd F(4x4,3x3) for planes >= 28x28 (conv_wino4.hip): NT 1..3, WM = 2 tile
-               //    groups, WN = 4 position quarters, R = output rows per slab (multiple of 4), NI slabs (<= 32 tiles)
-               // 8: ALG 7's arithmetic and geometry with specialised waves (conv_wino4p.hip): 8 MFMA waves + 4 producer
-               //    waves (LDS-DMA + input transform, V staged in LDS); same cfg fields as ALG 7
-               // 13: F(4x4,3x3) with WHOLE-POSITION MFMA waves (conv_wino4w.hip; round 5): a block = 2 NT MFMA waves (all 36 positions of
-               //    one 16-tile group x one n-tile each, register-only output transform: no exchange) + 2 producer waves, slice pipeline
-               //    continuous across items; NT 1..3, WM = 2, WN = 1, R / NI as ALG 8 (flat items: R = 4, NI = 0)
-               // 6: 1x1 conv (stride 1|2) as a register-direct GEMM, no LDS / barriers (gemm1x1.hip):
-               //    (MT,NT) in {(2,4),(4,2),(4,4),(7,2),(7,4),(8,2)}, R = operand prefetch depth (2|3), NI = load schedule 1..6
-               // 9: ALG 6 with coalesced global traffic: pixel / output tiles turned into the MFMA lane order through
-               //    wave-private LDS (gemm1x1t.hip): (MT,NT) in {(4,4),(7,2),(7,4),(8,2)}, R = NI = 1
-               // 12: EXPERIMENT, -DPOCO_EXPERIMENTS=1 builds only (python -m poco_amd.build --experiments), never chosen by the table:
-               //     1x1 conv in split fp16 (exp/gemm1x1h.hip)
-               // 11: Winograd F(4x4,3x3) as 36 position GEMMs with V / M staged in memory, for planes <= 16x16 (conv_wino4g.hip):
-               //    three launches (input transform, GEMM, output transform); (MT,NT) in {(2,4),(4,2),(4,4),(8,2)}, R = depth 2|3
-               // 10: 3x3 conv (stride 1|2) as a register-direct gather GEMM over K = 9*Cin, no LDS / barriers (gemm3x3.hip):
-               //    (MT,NT) in {(2,4),(4,2..4),(7,2..4),(8,2)}, R = operand prefetch depth (2|3), NI = load schedule 1|3|6
+  int ALG;     // the algorithm, 0..14: one row of the table in conv_mfma.hip (conv_alg), which says what each one is and how it reads
+               // the fields above
 };
 constexpr int CONV_CFG_INTS = 7;   // ints per configuration in the C ABI / tuning table
 inline ConvCfg conv_cfg_from(const int* c) { return ConvCfg{c[0], c[1], c[2], c[3], c[4], c[5], c[6]}; }
@@ -74,16 +55,27 @@ inline ConvCfg conv_cfg_from(const int* c) { return ConvCfg{c[0], c[1], c[2], c[
 // Channel offset `co` of a slice inside a wider buffer -> float offset (co/16)*W*16 + co%16.
 inline size_t l16_chan_off(int co, int W) { return (size_t)(co >> 4) * W * 16 + (co & 15); }
 
-// The further layouts of a conv's weights, one per algorithm family that reads them in an order of its own (each nullable: the
-// engine packs a layout only for the ops that may run its algorithm).  The plain fragment order every conv has is ConvDesc::wfrag.
-struct ConvWeights {
-  const float* wino = nullptr;      // 3x3 stride-1 only: Winograd F(2x2,3x3)-transformed weights (ALG 3 / 4)
-  const float* wino4 = nullptr;     // 3x3 stride-1 only: F(4x4,3x3) weight fragments, 36 positions (ALG 7)
-  const float* wino4p = nullptr;    // the same weights in the LDS order of ALG 8 (conv_wino4p.hip)
-  const float* wino4w = nullptr;    // the same weights in the LDS order of ALG 13 (conv_wino4w.hip)
-  const float* wino4g = nullptr;    // 3x3 stride-1 convs on small planes: per-position GEMM fragments of ALG 11 (conv_wino4g.hip)
-  const float* split_f16 = nullptr; // EXPERIMENT (ALG 12, gemm1x1h.hip): hi / lo fp16 halves of the 1x1 weights
+// The orders a conv's weights are packed in, one per algorithm family that reads them in an order of its own.  Every conv has the
+// plain fragment order (ConvDesc::wfrag, conv_pack_weights); the further ones are nullable: the engine packs a layout only for
+// the ops that may run an algorithm that reads it (conv_alg(ALG)->layout).
+enum ConvWLayout {
+  CONV_W_PLAIN,       // ConvDesc::wfrag; its slot in ConvWeights stays empty
+  CONV_W_WINO,        // 3x3 stride-1 only: Winograd F(2x2,3x3)-transformed weights (ALG 3 / 4)
+  CONV_W_WINO4,       // 3x3 stride-1 only: F(4x4,3x3) weight fragments, 36 positions (ALG 7)
+  CONV_W_WINO4P,      // the same weights in the LDS order of ALG 8 (conv_wino4p.hip)
+  CONV_W_WINO4W,      // the same weights in the LDS order of ALG 13 (conv_wino4w.hip)
+  CONV_W_WINO4G,      // 3x3 stride-1 convs on small planes: per-position GEMM fragments of ALG 11 (conv_wino4g.hip)
+  CONV_W_SPLIT_F16,   // EXPERIMENT (ALG 12, gemm1x1h.hip): hi / lo fp16 halves of the 1x1 weights
+  CONV_W_COUNT
 };
+struct ConvWeights { const float* of[CONV_W_COUNT] = {}; };
+// Size (floats) and packer (host: OIHW weights x per-output-channel scale -> the layout's order) of each layout but the plain one,
+// whose two take the kernel size as well.  {null, null}: the layout is not part of this build.
+struct ConvWLayoutOps {
+  size_t (*floats)(int Cin, int Cout16);
+  void (*pack)(const float* w_oihw, const float* scale /*nullable*/, int Cout, int Cin, int Cout16, float* dst);
+};
+const ConvWLayoutOps& conv_w_layout(int layout);
 
 struct ConvDesc {
   // activations: L16 (see above), each buffer may be a channel slice of a wider buffer
@@ -147,9 +139,21 @@ inline void stem_pack_weights(const float* w_oihw, const float* scale, int ks, s
 }
 // Heuristic tile choice.
 ConvCfg conv_default_cfg(const ConvDesc& d);
+// What the host has to know about one algorithm: the rows of the table in conv_mfma.hip.
+enum ConvScratch { CONV_SCRATCH_NONE, CONV_SCRATCH_WG /* ConvDesc::scratch */, CONV_SCRATCH_SK /* ConvDesc::sk_scratch */, CONV_SCRATCH_KINDS };
+struct ConvAlg {
+  int alg;               // ConvCfg::ALG
+  ConvWLayout layout;    // the weights it reads
+  bool wino;             // a Winograd form: 3x3 stride-1 convs with no activation or a plain ReLU only (refuses act 2 / 3)
+  int gran;              // channel strides / offsets of the activation slices must be multiples of this
+  ConvScratch scratch;   // the caller-owned scratch it needs
+  size_t (*lds_bytes)(const ConvDesc& d, const ConvCfg& cfg);      // 0 = the configuration is invalid for the conv
+  int (*launch)(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream);
+};
+const ConvAlg* conv_alg(int ALG);      // null: no such algorithm
 // Validate + launch.  Returns POCO_OK or an error code (message via poco_set_error).
 int conv_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream);
-// LDS bytes a configuration needs (0 if invalid).
+// LDS bytes a configuration needs (0 if invalid, an unknown ALG included).
 size_t conv_lds_bytes(const ConvDesc& d, const ConvCfg& cfg);
 
 // ---- small-M linear layers (linear_mfma.hip), ALG 5 -------------------------------------------------
@@ -214,7 +218,8 @@ int conv_wino4w_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
 
 // ---- Winograd F(2x2,3x3) variant (conv_wino.hip) --------------------------------------------------
 #include <vector>
-// [Cout][Cin][16] transformed filters (G g G^T, float64 on the host); pack with conv_pack_weights(ks=4).
-void conv_wino_transform_weights(const float* w_oihw, int Cout, int Cin, std::vector<float>* out);
+// the layout ALG 3 / 4 read: [Cout][Cin][16] transformed filters (G g G^T, float64 on the host) in the order of conv_pack_weights(ks = 4)
+size_t conv_wino_packed_floats(int Cin, int Cout16);
+void conv_wino_pack_weights(const float* w_oihw, const float* scale, int Cout, int Cin, int Cout16, float* dst);
 size_t conv_wino_lds_bytes(const ConvDesc& d, const ConvCfg& cfg);
 int conv_wino_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream);

@@ -93,25 +93,9 @@ static size_t lds_bytes_for(const ConvDesc& d, const ConvCfg& cfg, const Geometr
   return (size_t)4 * g.planeF4 * sizeof(float4);
 }
 
-size_t conv_lds_bytes(const ConvDesc& d, const ConvCfg& cfg) {
-  if (cfg.ALG == 5) return linear_cfg_valid(d, cfg) ? (size_t)cfg.WM * 4 * 64 * sizeof(float4) : 0;
-  if (cfg.ALG == 6) return gemm1x1_cfg_valid(d, cfg) ? 16 : 0;      // no LDS; non-zero = "valid" for the callers
-  if (cfg.ALG == 9) return gemm1x1t_lds_bytes(d, cfg);
-  if (cfg.ALG == 14) return gemm1x1sk_cfg_valid(d, cfg) ? 16 : 0;   // no LDS; non-zero = "valid" for the callers
-  if (cfg.ALG == 10) return gemm3x3_cfg_valid(d, cfg) ? 16 : 0;     // no LDS; non-zero = "valid" for the callers
-  if (cfg.ALG == 11) return conv_wino4g_cfg_valid(d, cfg) ? 16 : 0;
-#if POCO_EXPERIMENTS
-  if (cfg.ALG == 12) return gemm1x1h_cfg_valid(d, cfg) ? 16 : 0;
-#else
-  if (cfg.ALG == 12) return 0;
-#endif
-  if (cfg.ALG == 7) return conv_wino4_lds_bytes(d, cfg);
-  if (cfg.ALG == 8) return conv_wino4p_lds_bytes(d, cfg);
-  if (cfg.ALG == 13) return conv_wino4w_lds_bytes(d, cfg);
-  if (cfg.ALG == 3 || cfg.ALG == 4) return conv_wino_lds_bytes(d, cfg);
+static size_t staged_lds_bytes(const ConvDesc& d, const ConvCfg& cfg) {
   Geometry g;
-  if (!geometry(d, cfg, &g)) return 0;
-  return lds_bytes_for(d, cfg, g);
+  return geometry(d, cfg, &g) ? lds_bytes_for(d, cfg, g) : 0;
 }
 
 ConvCfg conv_default_cfg(const ConvDesc& d) {
@@ -182,29 +166,8 @@ ConvCfg conv_default_cfg(const ConvDesc& d) {
   return best;
 }
 
-int conv_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
-  if (cfg.ALG == 5) return linear_launch(d, cfg, stream);
-  if (cfg.ALG == 6) return gemm1x1_launch(d, cfg, stream);
-  if (cfg.ALG == 9) return gemm1x1t_launch(d, cfg, stream);
-  if (cfg.ALG == 14) return gemm1x1sk_launch(d, cfg, stream);
-  if (cfg.ALG == 10) return gemm3x3_launch(d, cfg, stream);
-  if (cfg.ALG == 11) return conv_wino4g_launch(d, cfg, stream);
-#if POCO_EXPERIMENTS
-  if (cfg.ALG == 12) return gemm1x1h_launch(d, cfg, stream);
-#else
-  if (cfg.ALG == 12) { poco_set_error("conv: ALG 12 (split-fp16 experiment) is not part of this build (python -m poco_amd.build --experiments)"); return POCO_ERR_ARG; }
-#endif
-  if (cfg.ALG == 7) return conv_wino4_launch(d, cfg, stream);
-  if (cfg.ALG == 8) return conv_wino4p_launch(d, cfg, stream);
-  if (cfg.ALG == 13) return conv_wino4w_launch(d, cfg, stream);
-  if (cfg.ALG == 3 || cfg.ALG == 4) {
-    if (d.Cin % 16 || d.Cout % 16 || ((d.in_cs | d.in_co | d.out_cs | d.out_co | d.res_cs | d.res_co) & 3)) {
-      poco_set_error("conv: channel counts/strides must be multiples of 16/4");
-      return POCO_ERR_ARG;
-    }
-    if (d.act == 3 || d.act == 2) { poco_set_error("conv: the Winograd kernels support no activation or ReLU only"); return POCO_ERR_ARG; }
-    return conv_wino_launch(d, cfg, stream);
-  }
+// ALG 0, 1, 2: the LDS-staged kernels of this file
+static int staged_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
   if (!(d.ks == 1 || d.ks == 3) || !(d.stride == 1 || d.stride == 2)) {
     poco_set_error("conv: ks must be 1|3 and stride 1|2");
     return POCO_ERR_ARG;
@@ -234,10 +197,6 @@ int conv_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
   const size_t lds = lds_bytes_for(d, cfg, g);
   if (cfg.ALG >= 1 && (g.planeF4 / 64 + nwaves - 1) / nwaves > DMA_MAXG) {
     poco_set_error("conv: halo patch too large for the LDS-DMA variant");
-    return POCO_ERR_ARG;
-  }
-  if (cfg.ALG < 0 || cfg.ALG > 3) {
-    poco_set_error("conv: unknown ALG");
     return POCO_ERR_ARG;
   }
   if (lds > 160 * 1024) {
@@ -289,4 +248,95 @@ int conv_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
   if (d.ks == 1 && d.stride == 2) return conv_launch_k1s2(cfg.ALG, cfg.MT, cfg.NT, kp, grid, nthreads, lds, stream);
   if (d.ks == 3 && d.stride == 1) return conv_launch_k3s1(cfg.ALG, cfg.MT, cfg.NT, kp, grid, nthreads, lds, stream);
   return conv_launch_k3s2(cfg.ALG, cfg.MT, cfg.NT, kp, grid, nthreads, lds, stream);
+}
+
+// ---- the algorithms -------------------------------------------------------------------------------------------------------------
+const ConvWLayoutOps& conv_w_layout(int layout) {
+  static const ConvWLayoutOps ops[CONV_W_COUNT] = {
+      {nullptr, nullptr},                                         // CONV_W_PLAIN (conv_packed_weight_floats / conv_pack_weights)
+      {conv_wino_packed_floats, conv_wino_pack_weights},
+      {conv_wino4_packed_floats, conv_wino4_pack_weights},
+      {conv_wino4p_packed_floats, conv_wino4p_pack_weights},      // (+ slack for the streamed requests)
+      {conv_wino4w_packed_floats, conv_wino4w_pack_weights},
+      {conv_wino4g_packed_floats, conv_wino4g_pack_weights},
+#if POCO_EXPERIMENTS
+      {gemm1x1h_packed_floats, gemm1x1h_pack_weights},      // (else null: not part of this build)
+#endif
+  };
+  return ops[layout];
+}
+
+namespace {
+
+// A kernel without LDS says "valid" with a non-zero size: the callers (poco_set_conv_cfg, the tuner) read 0 as invalid.
+template <bool (*VALID)(const ConvDesc&, const ConvCfg&)>
+size_t no_lds(const ConvDesc& d, const ConvCfg& cfg) { return VALID(d, cfg) ? 16 : 0; }
+size_t linear_lds_bytes(const ConvDesc& d, const ConvCfg& cfg) { return linear_cfg_valid(d, cfg) ? (size_t)cfg.WM * 4 * 64 * sizeof(float4) : 0; }
+#if !POCO_EXPERIMENTS      // ALG 12 keeps its row in the shipped library: never valid, and its launch says why
+size_t alg12_absent_lds(const ConvDesc&, const ConvCfg&) { return 0; }
+int alg12_absent_launch(const ConvDesc&, const ConvCfg&, hipStream_t) {
+  poco_set_error("conv: ALG 12 (split-fp16 experiment) is not part of this build (python -m poco_amd.build --experiments)");
+  return POCO_ERR_ARG;
+}
+#endif
+
+}  // namespace
+
+const ConvAlg* conv_alg(int ALG) {
+  constexpr ConvScratch NONE = CONV_SCRATCH_NONE;
+  // One row per ConvCfg::ALG: {ALG, weight layout, Winograd form, channel granularity, scratch, lds_bytes, launch}.
+  static const ConvAlg rows[] = {
+      {0, CONV_W_PLAIN, false, 4, NONE, staged_lds_bytes, staged_launch},      // register-staged single LDS buffer
+      {1, CONV_W_PLAIN, false, 4, NONE, staged_lds_bytes, staged_launch},      // LDS-DMA double-buffered (patch + weights)
+      {2, CONV_W_PLAIN, false, 4, NONE, staged_lds_bytes, staged_launch},      // ALG 1 persistent over tiles
+      // Winograd F(2x2,3x3) (MT ignored, NT in {1,2}, R even)
+      {3, CONV_W_WINO, true, 4, NONE, conv_wino_lds_bytes, conv_wino_launch},
+      // Winograd, half-position waves + pipelined transform (WN = 2 halves, WM <= 4, NT <= 3)
+      {4, CONV_W_WINO, true, 4, NONE, conv_wino_lds_bytes, conv_wino_launch},
+      // small-M linear (H = W = 1, ks = 1): K split over WM waves per 16 outputs (linear_mfma.hip)
+      {5, CONV_W_PLAIN, false, 4, NONE, linear_lds_bytes, linear_launch},
+      // 1x1 conv (stride 1|2) as a register-direct GEMM, no LDS / barriers (gemm1x1.hip):
+      // (MT,NT) in {(2,4),(4,2),(4,4),(7,2),(7,4),(8,2)}, R = operand prefetch depth (2|3), NI = load schedule 1..6
+      {6, CONV_W_PLAIN, false, 4, NONE, no_lds<gemm1x1_cfg_valid>, gemm1x1_launch},
+      // Winograd F(4x4,3x3) for planes >= 28x28 (conv_wino4.hip): NT 1..3, WM = 2 tile groups, WN = 4 position quarters,
+      // R = output rows per slab (multiple of 4), NI slabs (<= 32 tiles)
+      {7, CONV_W_WINO4, true, 4, NONE, conv_wino4_lds_bytes, conv_wino4_launch},
+      // ALG 7's arithmetic and geometry with specialised waves (conv_wino4p.hip): 8 MFMA waves + 4 producer waves (LDS-DMA + input
+      // transform, V staged in LDS); same cfg fields as ALG 7
+      {8, CONV_W_WINO4P, true, 4, NONE, conv_wino4p_lds_bytes, conv_wino4p_launch},
+      // ALG 6 with coalesced global traffic: pixel / output tiles turned into the MFMA lane order through wave-private LDS
+      // (gemm1x1t.hip): (MT,NT) in {(4,4),(7,2),(7,4),(8,2)}, R = NI = 1
+      {9, CONV_W_PLAIN, false, 4, NONE, gemm1x1t_lds_bytes, gemm1x1t_launch},
+      // 3x3 conv (stride 1|2) as a register-direct gather GEMM over K = 9*Cin, no LDS / barriers (gemm3x3.hip):
+      // (MT,NT) in {(2,4),(4,2..4),(7,2..4),(8,2)}, R = operand prefetch depth (2|3), NI = load schedule 1|3|6
+      {10, CONV_W_PLAIN, false, 4, NONE, no_lds<gemm3x3_cfg_valid>, gemm3x3_launch},
+      // Winograd F(4x4,3x3) as 36 position GEMMs with V / M staged in memory, for planes <= 16x16 (conv_wino4g.hip): three launches
+      // (input transform, GEMM, output transform); (MT,NT) in {(2,4),(4,2),(4,4),(8,2)}, R = depth 2|3
+      {11, CONV_W_WINO4G, true, 16, CONV_SCRATCH_WG, no_lds<conv_wino4g_cfg_valid>, conv_wino4g_launch},
+      // EXPERIMENT, -DPOCO_EXPERIMENTS=1 builds only (python -m poco_amd.build --experiments), never chosen by the table:
+      // 1x1 conv in split fp16 (exp/gemm1x1h.hip)
+#if POCO_EXPERIMENTS
+      {12, CONV_W_SPLIT_F16, false, 16, NONE, no_lds<gemm1x1h_cfg_valid>, gemm1x1h_launch},
+#else
+      {12, CONV_W_SPLIT_F16, false, 16, NONE, alg12_absent_lds, alg12_absent_launch},
+#endif
+      // F(4x4,3x3) with WHOLE-POSITION MFMA waves (conv_wino4w.hip; round 5): a block = 2 NT MFMA waves (all 36 positions of one
+      // 16-tile group x one n-tile each, register-only output transform: no exchange) + 2 producer waves, slice pipeline continuous
+      // across items; NT 1..3, WM = 2, WN = 1, R / NI as ALG 8 (flat items: R = 4, NI = 0)
+      {13, CONV_W_WINO4W, true, 4, NONE, conv_wino4w_lds_bytes, conv_wino4w_launch},
+      {14, CONV_W_PLAIN, false, 4, CONV_SCRATCH_SK, no_lds<gemm1x1sk_cfg_valid>, gemm1x1sk_launch},      // stream-K 1x1 GEMM (gemm1x1sk.hip)
+  };
+  for (const ConvAlg& a : rows)
+    if (a.alg == ALG) return &a;
+  return nullptr;
+}
+
+size_t conv_lds_bytes(const ConvDesc& d, const ConvCfg& cfg) {
+  const ConvAlg* a = conv_alg(cfg.ALG);
+  return a ? a->lds_bytes(d, cfg) : 0;
+}
+int conv_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
+  if (const ConvAlg* a = conv_alg(cfg.ALG)) return a->launch(d, cfg, stream);
+  poco_set_error("conv: unknown ALG");
+  return POCO_ERR_ARG;
 }

@@ -737,7 +737,7 @@ size_t conv_wino_lds_bytes(const ConvDesc& d, const ConvCfg& cfg) {
 
 // U = G g G^T per (co, ci), float64 on the host, written as a [Cout][Cin][16] "16-tap" filter that
 // conv_pack_weights(ks = 4) lays out in fragment order.
-void conv_wino_transform_weights(const float* w_oihw, int Cout, int Cin, std::vector<float>* out) {
+static void conv_wino_transform_weights(const float* w_oihw, int Cout, int Cin, std::vector<float>* out) {
   static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
   out->assign((size_t)Cout * Cin * 16, 0.f);
   for (size_t oc = 0; oc < (size_t)Cout * Cin; ++oc) {
@@ -751,8 +751,20 @@ void conv_wino_transform_weights(const float* w_oihw, int Cout, int Cin, std::ve
   }
 }
 
+size_t conv_wino_packed_floats(int Cin, int Cout16) { return conv_packed_weight_floats(Cin, Cout16, 4); }
+void conv_wino_pack_weights(const float* w_oihw, const float* scale, int Cout, int Cin, int Cout16, float* dst) {
+  std::vector<float> wt;
+  conv_wino_transform_weights(w_oihw, Cout, Cin, &wt);
+  conv_pack_weights(wt.data(), scale, Cout, Cin, 4, Cout16, dst);
+}
+
 int conv_wino_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
-  if (d.ks != 3 || d.stride != 1 || !d.w.wino) {
+  if (d.Cin % 16 || d.Cout % 16 || ((d.in_cs | d.in_co | d.out_cs | d.out_co | d.res_cs | d.res_co) & 3)) {
+    poco_set_error("conv: channel counts/strides must be multiples of 16/4");
+    return POCO_ERR_ARG;
+  }
+  if (d.act == 3 || d.act == 2) { poco_set_error("conv: the Winograd kernels support no activation or ReLU only"); return POCO_ERR_ARG; }
+  if (d.ks != 3 || d.stride != 1 || !d.w.of[CONV_W_WINO]) {
     poco_set_error("conv(winograd): needs a 3x3 stride-1 conv with transformed weights");
     return POCO_ERR_ARG;
   }
@@ -767,7 +779,7 @@ int conv_wino_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) 
     if (lds4 > 160 * 1024 || (size_t)cfg.WM * cfg.NT * 4 * 64 > (size_t)2 * 16 * cfg.NT * 64) { poco_set_error("conv(winograd/half): LDS budget exceeded"); return POCO_ERR_ARG; }
     WinoParams p;
     p.in = d.in + l16_chan_off(d.in_co, d.W); p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr; p.out = d.out + l16_chan_off(d.out_co, d.W);
-    p.ufrag = reinterpret_cast<const float4*>(d.w.wino); p.bias = d.bias;
+    p.ufrag = reinterpret_cast<const float4*>(d.w.of[CONV_W_WINO]); p.bias = d.bias;
     p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
     p.H = d.H; p.W = d.W; p.nC16 = d.Cin / 16; p.nT16 = d.Cout / 16;
     p.R = cfg.R; p.NI = cfg.NI; p.S = g.S; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.planeF4 = g.planeF4;
@@ -821,7 +833,7 @@ int conv_wino_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) 
   if (lds > 160 * 1024) { poco_set_error("conv(winograd): LDS budget exceeded"); return POCO_ERR_ARG; }
   WinoParams p;
   p.in = d.in + l16_chan_off(d.in_co, d.W); p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr; p.out = d.out + l16_chan_off(d.out_co, d.W);
-    p.ufrag = reinterpret_cast<const float4*>(d.w.wino); p.bias = d.bias;
+    p.ufrag = reinterpret_cast<const float4*>(d.w.of[CONV_W_WINO]); p.bias = d.bias;
   p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
   p.H = d.H; p.W = d.W; p.nC16 = d.Cin / 16; p.nT16 = d.Cout / 16;
   p.R = cfg.R; p.NI = cfg.NI; p.S = g.S; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.planeF4 = g.planeF4;

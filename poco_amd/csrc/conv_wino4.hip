@@ -367,7 +367,7 @@ size_t conv_wino4_lds_bytes(const ConvDesc& d, const ConvCfg& cfg) {
 
 int conv_wino4_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
   W4Geo g;
-  if (!w4geo(d, cfg, &g) || !d.w.wino4) {
+  if (!w4geo(d, cfg, &g) || !d.w.of[CONV_W_WINO4]) {
     poco_set_error("conv(winograd 4x4): needs ks = 3, stride 1, NT 1..3, WM = 2, WN = 4, R % 4 == 0, NI*(R/4)*ceil(W/4) <= 32 tiles and the ALG 7 weight fragments");
     return POCO_ERR_ARG;
   }
@@ -376,7 +376,7 @@ int conv_wino4_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream)
   p.in = d.in + l16_chan_off(d.in_co, d.W);
   p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr;
   p.out = d.out + l16_chan_off(d.out_co, d.W);
-  p.ufrag = reinterpret_cast<const float4*>(d.w.wino4); p.bias = d.bias;
+  p.ufrag = reinterpret_cast<const float4*>(d.w.of[CONV_W_WINO4]); p.bias = d.bias;
   p.B = d.B; p.H = d.H; p.W = d.W; p.nC4 = d.Cin / 4; p.nT16 = d.Cout / 16;
   p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
   p.R = g.R; p.NI = g.NI; p.S = g.S; p.nbands = g.nbands; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.rawF4 = g.rawF4;

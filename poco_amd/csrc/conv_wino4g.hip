@@ -348,7 +348,7 @@ int conv_wino4g_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
     return POCO_ERR_ARG;
   }
   const size_t need = conv_wino4g_scratch_floats(d.B, d.H, d.W, d.Cin, d.Cout);
-  if (!d.w.wino4g || !d.scratch || d.scratch_floats < need) {
+  if (!d.w.of[CONV_W_WINO4G] || !d.scratch || d.scratch_floats < need) {
     poco_set_error("conv(winograd 4x4 as GEMM): ALG 11 needs its per-position weight fragments and a scratch buffer for V and M");
     return POCO_ERR_ARG;
   }
@@ -372,7 +372,7 @@ int conv_wino4g_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
     poco_set_error("conv(winograd 4x4 as GEMM): the fused tail needs tiles-per-image dividing 16");
     return POCO_ERR_ARG;
   }
-  p.ufrag = reinterpret_cast<const float4*>(d.w.wino4g); p.bias = d.bias;
+  p.ufrag = reinterpret_cast<const float4*>(d.w.of[CONV_W_WINO4G]); p.bias = d.bias;
   p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
   p.act = d.act; p.res_after_act = d.res_after_act;
   p.WM = cfg.WM; p.WN = cfg.WN;

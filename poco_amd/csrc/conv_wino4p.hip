@@ -804,7 +804,7 @@ int conv_wino4p_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
   W4PLayout L;
   FlatGeo fg{};
   const bool flat = cfg.NI == 0;
-  if (!w4p_geo(d, cfg, &g, &L, &fg) || !d.w.wino4p) {
+  if (!w4p_geo(d, cfg, &g, &L, &fg) || !d.w.of[CONV_W_WINO4P]) {
     poco_set_error("conv(winograd 4x4, specialised waves): needs ks = 3, stride 1, NT 1..3, WM = 2, WN = 4, R % 4 == 0, "
                    "NI*(R/4)*ceil(W/4) <= 32 tiles (or R = 4, NI = 0: flat items), a patch of <= 1024 slots that fits the LDS next "
                    "to the U ring, and the ALG 8 weight fragments");
@@ -812,43 +812,18 @@ int conv_wino4p_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
   }
   if (d.act == 3 || d.act == 2) { poco_set_error("conv(winograd 4x4): activation must be none or ReLU"); return POCO_ERR_ARG; }
   W4PParams p{};
-  p.in = d.in + l16_chan_off(d.in_co, d.W);
-  p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr;
-  p.out = d.out + l16_chan_off(d.out_co, d.W);
-  p.ufrag = reinterpret_cast<const float4*>(d.w.wino4p); p.bias = d.bias;
-  p.B = d.B; p.H = d.H; p.W = d.W; p.nC4 = d.Cin / 4; p.nT16 = d.Cout / 16;
-  p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
-  p.R = g.R; p.NI = g.NI; p.S = g.S; p.nbands = g.nbands; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.rawF4 = g.rawF4;
-  p.tiles_per_slab = g.tps;
-  p.act = d.act; p.res_after_act = d.res_after_act;
-  p.uoff = L.uoff; p.voff = L.voff; p.xoff = L.xoff;
-  p.dPW = make_fastdiv(g.PW); p.dSlab = make_fastdiv(g.PR * g.PW); p.dBands = make_fastdiv(g.nbands);
-  p.dTX = make_fastdiv(g.TX); p.dTslab = make_fastdiv(g.tps);
-  p.nblocks_m = flat ? g.S : (g.S + g.NI - 1) / g.NI; p.nb_n = (p.nT16 + cfg.NT - 1) / cfg.NT;
+  w4p_fill_params(d, cfg, g, fg, d.w.of[CONV_W_WINO4P], L.uoff, L.voff, p);
+  p.xoff = L.xoff;
   p.dNbn = make_fastdiv(p.nb_n);
   // measured (tools/ninner_solo.py, tools/conv_traffic.py): 480 -> 128 @ 56x56 -4 % and 715 -> 479 MB per launch; the short-K shapes
   // (14x14 192 -> 192, 28x28 96 -> 96) +1 ... +2 % - their patch is small next to the L2 and the extra division sits on the item start
   p.ninner = p.nb_n > 1 && d.Cin * p.nb_n >= 1024;
-  if (flat) {
-    p.TY = fg.TY; p.ntiles = fg.ntiles; p.fragW = fg.fragW;
-    p.dTY = make_fastdiv(fg.TY); p.dFragW = make_fastdiv(fg.fragW);
-    p.MS = fg.MS; p.Hp1 = d.H + 1; p.Wp1 = d.W + 1;
-    p.dHp1 = make_fastdiv(d.H + 1); p.dWp1 = make_fastdiv(d.W + 1);
-  }
-  // balanced persistent grid: every block walks the same number of items (one block per CU)
-  // cfg.MT = CU share divisor: the grid is sized for (CUs of the device) / MT.  A block needs a whole CU (LDS), all blocks of a launch run
-  // their K loops (MFMA-bound, HBM nearly idle) and their store phases (HBM-write-bound, MFMA idle) in lockstep; two launches
-  // of different lanes on half of the CUs each run out of phase and overlap one's stores with the other's MFMAs.
-  int mt = std::max(1, cfg.MT);
+  int mt = std::max(1, cfg.MT);      // CU share divisor (w4p_grid_blocks)
 #if W4P_EXP
   static const int mt_env = [] { const char* e = getenv("POCO_W4P_MT"); return e ? atoi(e) : 0; }();      // probe builds only
   if (mt_env > 0) mt = mt_env;
 #endif
-  const long cus = std::max(8, poco_num_cus() / mt);
-  const long items = (long)p.nblocks_m * p.nb_n;
-  const long rounds = (items + cus - 1) / cus;
-  long g4 = (items + rounds - 1) / rounds;
-  if (g4 > 8) g4 = std::min(cus, (g4 + 7) / 8 * 8);            // multiple of 8 for the XCD-aware walk
+  const unsigned g4 = w4p_grid_blocks(p, mt);
   const size_t lds = (size_t)L.totalF4 * sizeof(float4);
   const int mode = !flat ? 0 : fg.MS > 1 ? 2 : 1;
   void (*fn)(const W4PParams) =
@@ -863,7 +838,7 @@ int conv_wino4p_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
       configured[cfg.NT + 4 * mode] = true;
     }
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)g4, 1), dim3(768), lds, stream, p);
+  hipLaunchKernelGGL(fn, dim3(g4, 1), dim3(768), lds, stream, p);
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }

@@ -261,3 +261,41 @@ bool flat_geo(const ConvDesc& d, const ConvCfg& cfg, w4::Geo* g, FlatGeo* f) {
   if ((long)d.B * d.H * d.W * std::max(std::max(d.in_cs, d.out_cs), d.res_cs) >= (1L << 31)) return false;
   return true;
 }
+
+// ---- host: what the launchers of ALG 8 and ALG 13 share ----------------------------------------------------------------------
+// Launch parameters common to both kernels: pointers, strides, geometry, fast divisors and the flat / mosaic block (`fg` is read
+// for flat items, cfg.NI == 0, only).  Left to the caller: xoff, the walk order (ninner / minner) and its divisors.
+inline void w4p_fill_params(const ConvDesc& d, const ConvCfg& cfg, const w4::Geo& g, const FlatGeo& fg, const float* ufrag, int uoff,
+                            int voff, W4PParams& p) {
+  p.in = d.in + l16_chan_off(d.in_co, d.W);
+  p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr;
+  p.out = d.out + l16_chan_off(d.out_co, d.W);
+  p.ufrag = reinterpret_cast<const float4*>(ufrag); p.bias = d.bias;
+  p.B = d.B; p.H = d.H; p.W = d.W; p.nC4 = d.Cin / 4; p.nT16 = d.Cout / 16;
+  p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
+  p.R = g.R; p.NI = g.NI; p.S = g.S; p.nbands = g.nbands; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.rawF4 = g.rawF4;
+  p.tiles_per_slab = g.tps;
+  p.act = d.act; p.res_after_act = d.res_after_act;
+  p.uoff = uoff; p.voff = voff;
+  p.dPW = make_fastdiv(g.PW); p.dSlab = make_fastdiv(g.PR * g.PW); p.dBands = make_fastdiv(g.nbands);
+  p.dTX = make_fastdiv(g.TX); p.dTslab = make_fastdiv(g.tps);
+  const bool flat = cfg.NI == 0;
+  p.nblocks_m = flat ? g.S : (g.S + g.NI - 1) / g.NI; p.nb_n = (p.nT16 + cfg.NT - 1) / cfg.NT;
+  if (flat) {
+    p.TY = fg.TY; p.ntiles = fg.ntiles; p.fragW = fg.fragW;
+    p.dTY = make_fastdiv(fg.TY); p.dFragW = make_fastdiv(fg.fragW);
+    p.MS = fg.MS; p.Hp1 = d.H + 1; p.Wp1 = d.W + 1;
+    p.dHp1 = make_fastdiv(d.H + 1); p.dWp1 = make_fastdiv(d.W + 1);
+  }
+}
+// Balanced persistent grid: every block walks the same number of items (one block per CU: the LDS).  mt = CU share divisor (cfg.MT): the grid is sized for (CUs of the device) / mt.  A block needs a whole CU, all blocks of a launch run
+// their K loops (MFMA-bound, HBM nearly idle) and their store phases (HBM-write-bound, MFMA idle) in lockstep; two launches
+// of different lanes on half of the CUs each run out of phase and overlap one's stores with the other's MFMAs.
+inline unsigned w4p_grid_blocks(const W4PParams& p, int mt) {
+  const long cus = std::max(8, poco_num_cus() / mt);
+  const long items = (long)p.nblocks_m * p.nb_n;
+  const long rounds = (items + cus - 1) / cus;
+  long g4 = (items + rounds - 1) / rounds;
+  if (g4 > 8) g4 = std::min(cus, (g4 + 7) / 8 * 8);            // multiple of 8 for the XCD-aware walk
+  return (unsigned)g4;
+}

@@ -817,7 +817,7 @@ int conv_wino4w_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
   W4WLayout L;
   FlatGeo fg{};
   const bool flat = cfg.NI == 0;
-  if (!w4w_geo(d, cfg, &g, &L, &fg) || !d.w.wino4w) {
+  if (!w4w_geo(d, cfg, &g, &L, &fg) || !d.w.of[CONV_W_WINO4W]) {
     poco_set_error("conv(winograd 4x4, whole-position waves): needs ks = 3, stride 1, NT 1..3, WM = 2, WN = 1, R % 4 == 0, "
                    "NI*(R/4)*ceil(W/4) <= 32 tiles (or R = 4 MS, NI = 0: flat items), a patch of <= 1024 slots, tensors below 2^30 elements and the ALG 13 weight fragments");
     return POCO_ERR_ARG;
@@ -825,19 +825,8 @@ int conv_wino4w_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
   if (d.act == 3 || d.act == 2) { poco_set_error("conv(winograd 4x4): activation must be none or ReLU"); return POCO_ERR_ARG; }
   W4WParams pp{};
   W4PParams& p = pp.g;
-  p.in = d.in + l16_chan_off(d.in_co, d.W);
-  p.res = d.res ? d.res + l16_chan_off(d.res_co, d.W) : nullptr;
-  p.out = d.out + l16_chan_off(d.out_co, d.W);
-  p.ufrag = reinterpret_cast<const float4*>(d.w.wino4w); p.bias = d.bias;
-  p.B = d.B; p.H = d.H; p.W = d.W; p.nC4 = d.Cin / 4; p.nT16 = d.Cout / 16;
-  p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16; p.res_rs = d.res_cs * d.W; p.out_rs = d.out_cs * d.W; p.out_ss = d.W * 16;
-  p.R = g.R; p.NI = g.NI; p.S = g.S; p.nbands = g.nbands; p.TX = g.TX; p.PR = g.PR; p.PW = g.PW; p.npos = g.npos; p.rawF4 = g.rawF4;
-  p.tiles_per_slab = g.tps;
-  p.act = d.act; p.res_after_act = d.res_after_act;
-  p.uoff = L.uoff; p.voff = L.voff; p.xoff = 0;
-  p.dPW = make_fastdiv(g.PW); p.dSlab = make_fastdiv(g.PR * g.PW); p.dBands = make_fastdiv(g.nbands);
-  p.dTX = make_fastdiv(g.TX); p.dTslab = make_fastdiv(g.tps);
-  p.nblocks_m = flat ? g.S : (g.S + g.NI - 1) / g.NI; p.nb_n = (p.nT16 + cfg.NT - 1) / cfg.NT;
+  w4p_fill_params(d, cfg, g, fg, d.w.of[CONV_W_WINO4W], L.uoff, L.voff, p);
+  p.xoff = 0;
   pp.dNbn = make_fastdiv(p.nb_n);
   pp.dNbm = make_fastdiv(p.nblocks_m);
   // Walk order by what it costs in L2 fills (8 XCDs, each with its own 4 MB L2): n-group-innermost = activations once + 8 x the U stream,
@@ -847,19 +836,7 @@ int conv_wino4w_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
     const double ubytes = 36.0 * d.Cin * d.Cout * 4.0, abytes = (double)d.B * d.H * d.W * d.Cin * 4.0;
     pp.minner = (p.nb_n > 1 && ubytes > abytes) ? 1 : 0;
   }
-  if (flat) {
-    p.TY = fg.TY; p.ntiles = fg.ntiles; p.fragW = fg.fragW;
-    p.dTY = make_fastdiv(fg.TY); p.dFragW = make_fastdiv(fg.fragW);
-    p.MS = fg.MS; p.Hp1 = d.H + 1; p.Wp1 = d.W + 1;
-    p.dHp1 = make_fastdiv(d.H + 1); p.dWp1 = make_fastdiv(d.W + 1);
-  }
-  // balanced persistent grid: every block walks the same number of items (one block per CU: the LDS); cfg.MT = CU-share divisor
-  const int mt = std::max(1, cfg.MT);
-  const long cus = std::max(8, poco_num_cus() / mt);
-  const long items = (long)p.nblocks_m * p.nb_n;
-  const long rounds = (items + cus - 1) / cus;
-  long g4 = (items + rounds - 1) / rounds;
-  if (g4 > 8) g4 = std::min(cus, (g4 + 7) / 8 * 8);            // multiple of 8 for the XCD-aware walk
+  const unsigned g4 = w4p_grid_blocks(p, std::max(1, cfg.MT));      // cfg.MT = CU-share divisor
   const size_t lds = (size_t)L.totalF4 * sizeof(float4);
   const int mode = !flat ? 0 : fg.MS > 1 ? 2 : 1;
   void (*fn)(const W4WParams) =
@@ -874,7 +851,7 @@ int conv_wino4w_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream
       configured[cfg.NT + 4 * mode] = true;
     }
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)g4, 1), dim3(64 * (cfg.NT == 3 ? w4w_block_waves<3>() : cfg.NT == 2 ? w4w_block_waves<2>() : w4w_block_waves<1>())), lds, stream, pp);
+  hipLaunchKernelGGL(fn, dim3(g4, 1), dim3(64 * (cfg.NT == 3 ? w4w_block_waves<3>() : cfg.NT == 2 ? w4w_block_waves<2>() : w4w_block_waves<1>())), lds, stream, pp);
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }

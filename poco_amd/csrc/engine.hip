@@ -256,20 +256,22 @@ static void op_accesses(const Engine& e, const Op& op, std::vector<OpAccess>* rd
   for (const Op& su : op.sub) op_accesses(e, su, rd, wr);
 }
 
-// Which Winograd forms a conv op may run: the ONE statement of the rule.  Builder::conv packs exactly the weight layouts of the forms
-// it names, poco_set_conv_cfg refuses every other one (whatever else its validation says).
-struct ConvAlgs { bool wino, wino4, wino4p, wino4w, wino4g; };   // ALG 3 / 4, 7, 8, 13, 11
+// Which weight layouts a conv op may carry next to the plain one, i.e. which Winograd forms it may run: the ONE statement of the rule.
+// Builder::conv packs exactly these, poco_set_conv_cfg refuses every ALG whose row (conv_alg) reads another one (whatever else its
+// validation says).
+struct ConvAlgs { bool has[CONV_W_COUNT]; };
 static ConvAlgs conv_algs(const EngineOpts& o, int H, int W, int ks, int stride, int actfn) {
   ConvAlgs a{};
+  a.has[CONV_W_PLAIN] = true;
   if (ks != 3 || stride != 1 || actfn > 1) return a;      // 3x3 stride-1 convs with no activation or a plain ReLU
   const int lo = std::min(H, W), hi = std::max(H, W);
-  a.wino = true;                                           // F(2x2,3x3): any plane
+  a.has[CONV_W_WINO] = true;                               // F(2x2,3x3): any plane
   // F(4x4,3x3) in LDS: 56x56 / 28x28 planes, 14x14 (16 tiles per image, 31 % padding), 7x7 with ALG 13 only (option w4_min_plane <= 14)
-  a.wino4w = lo >= o.w4_min_plane;
-  a.wino4p = a.wino4w && lo >= 14;
-  a.wino4 = a.wino4w && lo >= 28;
+  a.has[CONV_W_WINO4W] = lo >= o.w4_min_plane;
+  a.has[CONV_W_WINO4P] = a.has[CONV_W_WINO4W] && lo >= 14;
+  a.has[CONV_W_WINO4] = a.has[CONV_W_WINO4W] && lo >= 28;
   // F(4x4,3x3) as 36 position GEMMs with V / M staged in memory (scratch sized for max_batch; poco_forward refuses larger batches)
-  a.wino4g = hi <= o.wg_max_plane && H * W > 1;
+  a.has[CONV_W_WINO4G] = hi <= o.wg_max_plane && H * W > 1;
   return a;
 }
 
@@ -513,28 +515,16 @@ struct Builder {
       op.wdev = upload(packed);
       op.bdev = upload(sh);
       // one more layout per Winograd form the op may run (every packer: OIHW weights x scale -> its fragment order)
-      auto layout = [&](bool on, size_t floats, void (*pack)(const float*, const float*, int, int, int, float*)) -> const float* {
-        if (!on) return nullptr;
-        std::vector<float> buf(floats);
-        pack(wp, scale.data(), Cout, Cin, Cout16, buf.data());
-        return upload(buf);
-      };
-#if POCO_EXPERIMENTS
-      op.w.split_f16 = layout(e.opts.split_f16 && ks == 1 && !s.linear && Cin % 32 == 0 && ain.H * ain.W >= 16 && !s.kperm && !(s.merged && s.merged->stacked),
-                              gemm1x1h_packed_floats(Cin, Cout16), gemm1x1h_pack_weights);
-#endif
-      const ConvAlgs alg = conv_algs(e.opts, ain.H, ain.W, ks, s.stride, s.act);
-      if (alg.wino) {
-        std::vector<float> wt, pu(conv_packed_weight_floats(Cin, Cout16, 4));
-        conv_wino_transform_weights(wp, Cout, Cin, &wt);
-        conv_pack_weights(wt.data(), scale.data(), Cout, Cin, 4, Cout16, pu.data());
-        op.w.wino = upload(pu);
+      ConvAlgs alg = conv_algs(e.opts, ain.H, ain.W, ks, s.stride, s.act);
+      alg.has[CONV_W_SPLIT_F16] = e.opts.split_f16 && ks == 1 && !s.linear && Cin % 32 == 0 && ain.H * ain.W >= 16 && !s.kperm && !(s.merged && s.merged->stacked);
+      for (int l = CONV_W_PLAIN + 1; l < CONV_W_COUNT; ++l) {
+        const ConvWLayoutOps& L = conv_w_layout(l);
+        if (!alg.has[l] || !L.pack) continue;
+        std::vector<float> buf(L.floats(Cin, Cout16));
+        L.pack(wp, scale.data(), Cout, Cin, Cout16, buf.data());
+        op.w.of[l] = upload(buf);
       }
-      op.w.wino4 = layout(alg.wino4, conv_wino4_packed_floats(Cin, Cout16), conv_wino4_pack_weights);
-      op.w.wino4p = layout(alg.wino4p, conv_wino4p_packed_floats(Cin, Cout16), conv_wino4p_pack_weights);      // (+ slack for the streamed requests)
-      op.w.wino4w = layout(alg.wino4w, conv_wino4w_packed_floats(Cin, Cout16), conv_wino4w_pack_weights);
-      op.w.wino4g = layout(alg.wino4g, conv_wino4g_packed_floats(Cin, Cout16), conv_wino4g_pack_weights);
-      if (alg.wino4g) e.wino4g_scratch_need = std::max(e.wino4g_scratch_need, conv_wino4g_scratch_floats(e.max_batch, ain.H, ain.W, Cin, Cout16));
+      if (alg.has[CONV_W_WINO4G]) e.wino4g_scratch_need = std::max(e.wino4g_scratch_need, conv_wino4g_scratch_floats(e.max_batch, ain.H, ain.W, Cin, Cout16));
     }
     const int out_act = op.out.act;
     push(std::move(op));
@@ -1508,7 +1498,7 @@ int run_op(Engine& e, Op& op, int B, const IO& io, hipStream_t s) {
       d.sk_scratch = e.sk_scratch[op.lane & 3]; d.sk_scratch_floats = d.sk_scratch ? gemm1x1sk_scratch_floats() : 0; d.sk_err_host = e.mlp_err_host; d.sk_max_spins = (unsigned)e.opts.debug_wait_spins;
       auto it = op.cfg.find(B);
       if (it == op.cfg.end()) it = op.cfg.emplace(B, conv_default_cfg(d)).first;
-      if (op.w.split_f16 && (op.in.co & 31) == 0) {          // split-fp16 experiment: every plain 1x1 conv runs on ALG 12
+      if (op.w.of[CONV_W_SPLIT_F16] && (op.in.co & 31) == 0) {          // split-fp16 experiment: every plain 1x1 conv runs on ALG 12
         const int nT16 = op.Cout / 16;
         const long Pout = (long)B * ((ai.H - 1) / op.stride + 1) * ((ai.W - 1) / op.stride + 1);
         const bool tiled = Pout >= 2048 && nT16 >= 4;      // 128 x 128 block tiles (LDS-staged, converted once per block)
@@ -1526,7 +1516,7 @@ int run_op(Engine& e, Op& op, int B, const IO& io, hipStream_t s) {
           Op& nx = e.ops[k + 1];
           auto nit = nx.cfg.find(B);
           if (nx.type == OP_CONV && nx.phase == op.phase && nx.lane == op.lane && nx.in.act == op.out.act && nx.in.co == 0 &&
-              op.out.co == 0 && nit != nx.cfg.end() && nit->second.ALG == 11 && nx.w.wino4g && ao.C == op.Cout &&
+              op.out.co == 0 && nit != nx.cfg.end() && nit->second.ALG == 11 && nx.w.of[CONV_W_WINO4G] && ao.C == op.Cout &&
               conv_wino4g_can_chain(ai.H, ai.W, op.Cout, nx.Cin) &&
               std::max(op.Cin, op.Cout) == std::max(nx.Cin, nx.Cout)) {      // both convs split the lane's scratch into V | M the same way
             d.wg_emit_next = 1;
@@ -1803,7 +1793,7 @@ extern "C" int poco_finalize(poco_handle_t h) {
   // lane: ensure_sk_scratch; configurations set before finalize get theirs here)
   for (const Op& op : e->ops)
     for (const auto& kv : op.cfg)
-      if (kv.second.ALG == 14)
+      if (conv_alg(kv.second.ALG)->scratch == CONV_SCRATCH_SK)
         if (int rc = ensure_sk_scratch(e, op.lane)) return rc;
   POCO_HIP_CHECK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
   for (Op& op : e->ops)
@@ -2048,14 +2038,14 @@ extern "C" int poco_set_conv_cfg(poco_handle_t h, int op_index, int B, const int
   // (ALG 3 / 4 BEFORE finalize: held against the activation only, as it always was - conv_lds_bytes does not look at the kernel size
   // for them, so such an entry is accepted here for a conv that is not 3x3 stride-1 and refused by its launch.  Kept: closing it
   // changes which table entries an engine accepts)
-  const bool wino_ok = e->finalized ? ok.wino : conv_algs(e->opts, d.H, d.W, 3, 1, d.act).wino;
-  const bool no_weights = ((c.ALG == 3 || c.ALG == 4) && !wino_ok) || (c.ALG == 7 && !ok.wino4) || (c.ALG == 8 && !ok.wino4p) ||
-                          (c.ALG == 13 && !ok.wino4w) || (c.ALG == 11 && !ok.wino4g);
+  const ConvAlg* row = conv_alg(c.ALG);      // (null: lds == 0)
+  const bool f2_early = row && row->layout == CONV_W_WINO && !e->finalized;
+  const bool no_weights = row && !(f2_early ? conv_algs(e->opts, d.H, d.W, 3, 1, d.act) : ok).has[row->layout];
   if (B < 1 || lds == 0 || lds > 160 * 1024 || no_weights) {
     poco_set_error("poco_set_conv_cfg: configuration does not fit op '" + op.name + "' at this batch size");
     return POCO_ERR_ARG;
   }
-  if (c.ALG == 14 && e->finalized)
+  if (row->scratch == CONV_SCRATCH_SK && e->finalized)
     if (int rc = ensure_sk_scratch(e, op.lane)) return rc;
   e->ops[op_index].cfg[B] = c;
   return POCO_OK;

@@ -347,7 +347,7 @@ bool gemm1x1h_cfg_valid(const ConvDesc& d, const ConvCfg& cfg) {
 }
 
 int gemm1x1h_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
-  if (!gemm1x1h_cfg_valid(d, cfg) || !d.w.split_f16) {
+  if (!gemm1x1h_cfg_valid(d, cfg) || !d.w.of[CONV_W_SPLIT_F16]) {
     poco_set_error("gemm1x1h (split-fp16 experiment): ALG 12 needs ks = 1, Cin % 32 == 0, (MT,NT) in {2,4}x{2,4}, WM*WN <= 8 and its hi/lo weight fragments");
     return POCO_ERR_ARG;
   }
@@ -362,7 +362,7 @@ int gemm1x1h_launch(const ConvDesc& d, const ConvCfg& cfg, hipStream_t stream) {
   p.in = d.in + l16_chan_off(d.in_co, d.W);
   p.res = d.res ? d.res + l16_chan_off(d.res_co, p.Wo) : nullptr;
   p.out = d.out + l16_chan_off(d.out_co, p.Wo);
-  p.wfrag = reinterpret_cast<const float4*>(d.w.split_f16); p.bias = d.bias;
+  p.wfrag = reinterpret_cast<const float4*>(d.w.of[CONV_W_SPLIT_F16]); p.bias = d.bias;
   p.P = d.B * p.Ho * p.Wo; p.nC32 = d.Cin / 32; p.nT16 = d.Cout / 16; p.WM = cfg.WM; p.WN = cfg.WN;
   p.in_rs = d.in_cs * d.W; p.in_ss = d.W * 16;
   p.res_rs = d.res_cs * p.Wo; p.out_rs = d.out_cs * p.Wo; p.out_ss = p.Wo * 16;

@@ -34,9 +34,9 @@ struct ConvView {
   int act, relu_from, res_after_act;
 };
 
-// Host-side validation of a view, before any GPU work.  `alg`: the ALG of the caller's configuration (-1 = heuristic).
+// Host-side validation of a view, before any GPU work.  `alg`: the row of the caller's configuration (null = heuristic / unknown ALG).
 static int conv_view_check(const char* who, const void* d_in, const void* h_w, const void* d_out, const void* d_res, int B, int H,
-                           int W, int Cin, int Cout, int ks, int stride, const ConvView& v, int alg) {
+                           int W, int Cin, int Cout, int ks, int stride, const ConvView& v, const ConvAlg* alg) {
   auto bad = [&](const std::string& m) { poco_set_error(std::string(who) + ": " + m); return POCO_ERR_ARG; };
   if (!d_in || !h_w || !d_out) return bad("null pointer");
   if (B < 1 || H < 1 || W < 1 || Cin < 16 || Cout < 16) return bad("B, H, W must be >= 1 and Cin, Cout >= 16");
@@ -47,7 +47,7 @@ static int conv_view_check(const char* who, const void* d_in, const void* h_w, c
   if (v.res_after_act != 0 && v.res_after_act != 1) return bad("res_after_act must be 0 or 1");
   // what conv_launch admits: multiples of 4 (ALG 11 / 12: of 16).  On a plane the L16 layout itself needs whole 16-channel slices
   // (l16_chan_off of any other offset is no channel slice); only vectors (H = W = 1: plain [B][C] rows) can use the multiples of 4.
-  const int gran = (H == 1 && W == 1 && alg != 11 && alg != 12) ? 4 : 16;
+  const int gran = (H == 1 && W == 1) ? (alg ? alg->gran : 4) : 16;
   const int all = v.in_cs | v.in_co | v.out_cs | v.out_co | (d_res ? (v.res_cs | v.res_co) : 0);
   if (v.in_co < 0 || v.out_co < 0 || (d_res && v.res_co < 0) || (all & (gran - 1)))
     return bad("channel strides / offsets must be non-negative multiples of " + std::to_string(gran) +
@@ -62,62 +62,37 @@ static int conv_common(const float* d_in, int B, int H, int W, int Cin, const fl
                        const float* h_scale, const float* h_shift, int Cout, int ks, int stride,
                        const float* d_res, const ConvView& v, float* d_out, const int* cfg7, int iters,
                        float* ms_out, hipStream_t stream, const char* who = "conv2d") {
-  if (int rc = conv_view_check(who, d_in, h_w, d_out, d_res, B, H, W, Cin, Cout, ks, stride, v, (cfg7 && cfg7[0] > 0) ? cfg7[6] : -1)) return rc;
+  if (int rc = conv_view_check(who, d_in, h_w, d_out, d_res, B, H, W, Cin, Cout, ks, stride, v, (cfg7 && cfg7[0] > 0) ? conv_alg(cfg7[6]) : nullptr)) return rc;
   const int Cout16 = Cout;
   std::vector<float> packed(conv_packed_weight_floats(Cin, Cout16, ks));
   conv_pack_weights(h_w, h_scale, Cout, Cin, ks, Cout16, packed.data());
   std::vector<float> shift(Cout16, 0.f);
   if (h_shift)
     for (int i = 0; i < Cout; ++i) shift[i] = h_shift[i];
-  DevBuf dw, db, dwu, dwu4, dwu4p, dwu4w, dwu4g, dscr, dsk;
+  DevBuf dw, db, dwu, dwl, dscr, dsk;
   POCO_HIP_CHECK(dw.upload(packed));
   POCO_HIP_CHECK(db.upload(shift));
   ConvDesc d{};
-  DevBuf dwh;
-#if POCO_EXPERIMENTS
-  if (ks == 1 && cfg7 && cfg7[6] == 12 && Cin % 32 == 0) {       // split-fp16 experiment: hi / lo halves of the weights
-    std::vector<float> ph(gemm1x1h_packed_floats(Cin, Cout16));
-    gemm1x1h_pack_weights(h_w, h_scale, Cout, Cin, Cout16, ph.data());
-    POCO_HIP_CHECK(dwh.upload(ph));
-    d.w.split_f16 = dwh.p;
+  auto layout = [&](int l, DevBuf* buf) -> hipError_t {
+    std::vector<float> p(conv_w_layout(l).floats(Cin, Cout16));
+    conv_w_layout(l).pack(h_w, h_scale, Cout, Cin, Cout16, p.data());
+    const hipError_t e = buf->upload(p);
+    d.w.of[l] = buf->p;
+    return e;
+  };
+  // the layout and the scratch of the row of the configuration's ALG, where the conv has the shape that layout is packed for ...
+  const ConvAlg* row = cfg7 ? conv_alg(cfg7[6]) : nullptr;
+  const bool wino_shape = ks == 3 && stride == 1;
+  const bool row_fits = row && (row->wino ? wino_shape : row->layout == CONV_W_PLAIN || (ks == 1 && Cin % 32 == 0));
+  if (wino_shape) POCO_HIP_CHECK(layout(CONV_W_WINO, &dwu));      // ... and F(2x2) always: the heuristic may pick ALG 3
+  if (row_fits && row->layout > CONV_W_WINO && conv_w_layout(row->layout).pack) POCO_HIP_CHECK(layout(row->layout, &dwl));
+  if (row_fits && row->scratch == CONV_SCRATCH_WG) {      // V / M staging
+    d.scratch_floats = conv_wino4g_scratch_floats(B, H, W, Cin, Cout16);
+    POCO_HIP_CHECK(hipMalloc(&dscr.p, d.scratch_floats * sizeof(float)));
+    POCO_HIP_CHECK(hipMemsetAsync(dscr.p, 0xFF, d.scratch_floats * sizeof(float), stream));   // NaN: the engine never initialises this staging either
+    d.scratch = dscr.p;
   }
-#endif
-  if (ks == 3 && stride == 1) {
-    std::vector<float> wt, pu(conv_packed_weight_floats(Cin, Cout16, 4));
-    conv_wino_transform_weights(h_w, Cout, Cin, &wt);
-    conv_pack_weights(wt.data(), h_scale, Cout, Cin, 4, Cout16, pu.data());
-    POCO_HIP_CHECK(dwu.upload(pu));
-    d.w.wino = dwu.p;
-    if (cfg7 && cfg7[6] == 7) {                   // F(4x4,3x3): 36-position fragments
-      std::vector<float> pu4(conv_wino4_packed_floats(Cin, Cout16));
-      conv_wino4_pack_weights(h_w, h_scale, Cout, Cin, Cout16, pu4.data());
-      POCO_HIP_CHECK(dwu4.upload(pu4));
-      d.w.wino4 = dwu4.p;
-    }
-    if (cfg7 && cfg7[6] == 8) {                   // the same fragments in the LDS order of the specialised-wave kernel
-      std::vector<float> pu4(conv_wino4p_packed_floats(Cin, Cout16));
-      conv_wino4p_pack_weights(h_w, h_scale, Cout, Cin, Cout16, pu4.data());
-      POCO_HIP_CHECK(dwu4p.upload(pu4));
-      d.w.wino4p = dwu4p.p;
-    }
-    if (cfg7 && cfg7[6] == 13) {                  // ... and in the quad order of the whole-position kernel
-      std::vector<float> pu4(conv_wino4w_packed_floats(Cin, Cout16));
-      conv_wino4w_pack_weights(h_w, h_scale, Cout, Cin, Cout16, pu4.data());
-      POCO_HIP_CHECK(dwu4w.upload(pu4));
-      d.w.wino4w = dwu4w.p;
-    }
-    if (cfg7 && cfg7[6] == 11) {                  // F(4x4,3x3) as 36 position GEMMs: per-position fragments + V / M staging
-      std::vector<float> pg(conv_wino4g_packed_floats(Cin, Cout16));
-      conv_wino4g_pack_weights(h_w, h_scale, Cout, Cin, Cout16, pg.data());
-      POCO_HIP_CHECK(dwu4g.upload(pg));
-      d.w.wino4g = dwu4g.p;
-      d.scratch_floats = conv_wino4g_scratch_floats(B, H, W, Cin, Cout16);
-      POCO_HIP_CHECK(hipMalloc(&dscr.p, d.scratch_floats * sizeof(float)));
-      POCO_HIP_CHECK(hipMemsetAsync(dscr.p, 0xFF, d.scratch_floats * sizeof(float), stream));   // NaN: the engine never initialises this staging either
-      d.scratch = dscr.p;
-    }
-  }
-  if (cfg7 && cfg7[6] == 14) {                    // stream-K 1x1 GEMM: flags (zero) + partial accumulators, the pinned error word
+  if (row_fits && row->scratch == CONV_SCRATCH_SK) {      // flags (zero) + partial accumulators, the pinned error word
     static unsigned* sk_err = nullptr;
     if (!sk_err) { POCO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sk_err), 64, hipHostMallocMapped)); *sk_err = 0; }
     d.sk_scratch_floats = gemm1x1sk_scratch_floats();
@@ -219,15 +194,14 @@ extern "C" int poco_tune_conv(int B, int H, int W, int Cin, int Cout, int ks, in
   for (auto& v : hw) v = rnd() * ws;
   for (auto& v : hb) v = rnd() * 0.1f;
   DevBuf din, dw, db, dout, dwu, dwu4, dwu4g, dscr;
-  bool any11 = false;
-  for (int i = 0; i < ncfg; ++i) any11 = any11 || cfgs7[CONV_CFG_INTS * i + 6] == 11;
+  bool lay[CONV_W_COUNT] = {}, scr[CONV_SCRATCH_KINDS] = {};      // what the rows of the configurations read / need
+  for (int i = 0; i < ncfg; ++i)
+    if (const ConvAlg* a = conv_alg(cfgs7[CONV_CFG_INTS * i + 6])) lay[a->layout] = scr[a->scratch] = true;
   if (ks == 3 && stride == 1) {
     std::vector<float> hu((size_t)16 * Cin * Cout);
     for (auto& v : hu) v = rnd() * ws;
     POCO_HIP_CHECK(dwu.upload(hu));
-    bool any7 = false;
-    for (int i = 0; i < ncfg; ++i) any7 = any7 || cfgs7[CONV_CFG_INTS * i + 6] == 7 || cfgs7[CONV_CFG_INTS * i + 6] == 8 || cfgs7[CONV_CFG_INTS * i + 6] == 13;
-    if (any7) {
+    if (lay[CONV_W_WINO4] || lay[CONV_W_WINO4P] || lay[CONV_W_WINO4W]) {
       std::vector<float> hu4((size_t)36 * Cin * Cout + 2 * 9 * 256);          // (+ the slack ALG 13 reads behind the last n-tile)
       for (auto& v : hu4) v = rnd() * ws;
       POCO_HIP_CHECK(dwu4.upload(hu4));
@@ -239,20 +213,18 @@ extern "C" int poco_tune_conv(int B, int H, int W, int Cin, int Cout, int ks, in
   POCO_HIP_CHECK(hipMalloc(&dout.p, nout * sizeof(float)));
   ConvDesc d{};
   d.in = din.p; d.in_cs = Cin; d.out = dout.p; d.out_cs = Cout; d.wfrag = dw.p; d.bias = db.p;
-  d.w.wino = dwu.p; d.w.wino4 = dwu4.p; d.w.wino4p = dwu4.p; d.w.wino4w = dwu4.p;     // timing only: random fragments serve all orders
-  if (any11 && ks == 3 && stride == 1 && H <= 16 && W <= 16) {
+  d.w.of[CONV_W_WINO] = dwu.p; d.w.of[CONV_W_WINO4] = d.w.of[CONV_W_WINO4P] = d.w.of[CONV_W_WINO4W] = dwu4.p;     // timing only: random fragments serve all orders
+  if (lay[CONV_W_WINO4G] && ks == 3 && stride == 1 && H <= 16 && W <= 16) {
     std::vector<float> hg(conv_wino4g_packed_floats(Cin, Cout));
     for (auto& v : hg) v = rnd() * ws;
     POCO_HIP_CHECK(dwu4g.upload(hg));
-    d.w.wino4g = dwu4g.p;
+    d.w.of[CONV_W_WINO4G] = dwu4g.p;
     d.scratch_floats = conv_wino4g_scratch_floats(B, H, W, Cin, Cout);
     POCO_HIP_CHECK(hipMalloc(&dscr.p, d.scratch_floats * sizeof(float)));
     d.scratch = dscr.p;
   }
   DevBuf dsk;
-  bool any14 = false;
-  for (int i = 0; i < ncfg; ++i) any14 = any14 || cfgs7[CONV_CFG_INTS * i + 6] == 14;
-  if (any14) {                                            // stream-K 1x1 GEMM: flags (zero) + partials, the pinned error word
+  if (scr[CONV_SCRATCH_SK]) {                                           // stream-K 1x1 GEMM: flags (zero) + partials, the pinned error word
     static unsigned* sk_err = nullptr;
     if (!sk_err) { POCO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sk_err), 64, hipHostMallocMapped)); *sk_err = 0; }
     d.sk_scratch_floats = gemm1x1sk_scratch_floats();
@@ -261,16 +233,14 @@ extern "C" int poco_tune_conv(int B, int H, int W, int Cin, int Cout, int ks, in
     d.sk_scratch = dsk.p;
     d.sk_err_host = sk_err;
   }
-  DevBuf dwh;
-  bool any12 = false;
-  for (int i = 0; i < ncfg; ++i) any12 = any12 || cfgs7[CONV_CFG_INTS * i + 6] == 12;
 #if POCO_EXPERIMENTS
-  if (any12 && ks == 1 && Cin % 32 == 0) {               // split-fp16 experiment: timing only, hi / lo halves of random weights
+  DevBuf dwh;
+  if (lay[CONV_W_SPLIT_F16] && ks == 1 && Cin % 32 == 0) {               // split-fp16 experiment: timing only, hi / lo halves of random weights
     std::vector<float> hw2((size_t)Cout * Cin), ph(gemm1x1h_packed_floats(Cin, Cout));
     for (auto& v : hw2) v = rnd() * ws;
     gemm1x1h_pack_weights(hw2.data(), nullptr, Cout, Cin, Cout, ph.data());
     POCO_HIP_CHECK(dwh.upload(ph));
-    d.w.split_f16 = dwh.p;
+    d.w.of[CONV_W_SPLIT_F16] = dwh.p;
   }
 #endif
   d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout; d.ks = ks; d.stride = stride; d.act = 1;

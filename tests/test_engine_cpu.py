@@ -350,3 +350,32 @@ def test_apply_table_prefers_the_larger_neighbour_and_keeps_split_k_convs_small(
     before3 = active(3)
     tune.apply_table(m, 3, table)                                     # ... but downwards it does (if the library accepts it for the op)
     assert active(3) in (splitk, before3)
+
+
+def test_set_conv_cfg_refuses_an_alg_without_a_table_row():
+    """An ALG the conv table (conv_mfma.hip: conv_alg) has no row for is refused by poco_set_conv_cfg, not priced as an
+    LDS-staged conv: the six tile ints an ALG 1 entry is accepted with come back POCO_ERR_ARG with ALG -1, 15 and 99.
+    What the table does know stays as it was: ALG 7 is refused on a 7x7 plane and accepted on a 56x56 3x3 stride-1 conv."""
+    from tools.dump_program import ALG7_CFG
+    m = POCO(backbone="hrnet_w48_cls-cliff", num_flow_layers=1, max_batch=128)      # declarations only
+    convs = [(i, m.conv_desc(i)) for i in range(len(m.ops())) if m.conv_desc(i) is not None]
+    set_cfg, get_cfg = m._L.poco_set_conv_cfg, m._L.poco_get_conv_cfg
+    arr = lambda c: (C.c_int * 7)(*c)
+    B = 16
+    picked = None
+    for i, _ in convs:                       # the heuristic's tile of an op, as an ALG 1 entry
+        c = (C.c_int * 7)()
+        assert get_cfg(m._h, i, B, c) == 0
+        if c[6] == 0 and set_cfg(m._h, i, B, arr(tuple(c)[:6] + (1,))) == 0:
+            picked = (i, tuple(c)[:6])
+            break
+    assert picked is not None
+    i, six = picked
+    for alg in (-1, 15, 99):
+        assert set_cfg(m._h, i, B, arr(six + (alg,))) == 1, alg          # POCO_ERR_ARG
+    assert set_cfg(m._h, i, B, arr(six + (1,))) == 0
+    plane7 = [i for i, d in convs if d[:2] == (7, 7) and d[4:6] == (3, 1)]
+    plane56 = [i for i, d in convs if d[:2] == (56, 56) and d[4:6] == (3, 1)]
+    assert plane7 and plane56
+    assert set_cfg(m._h, plane7[0], B, arr(ALG7_CFG)) == 1
+    assert set_cfg(m._h, plane56[0], B, arr(ALG7_CFG)) == 0
