@@ -8,7 +8,8 @@ Same flags as the reference where they concern the regressor (--cfg --ckpt --mod
 tracker are third-party and out of scope: person boxes come from
 --detections (json {image name: [[cx,cy,w,h],...]}, the format multi_person_tracker produces) or
 default to one centred box; results are written as .npz.  --render (opt-in; the reference renders by default) draws the
-uncertainty-coloured meshes on the GPU (poco_amd/render.py) into the PNGs the reference writes.
+uncertainty-coloured meshes on the GPU (poco_amd/render.py) into the PNGs the reference writes; --image_format jpg encodes them on
+the GPU instead (poco_amd/jpeg.py) and --save_video adds the result video as a Motion-JPEG .avi (the reference's ffmpeg step).
 --mode video expects --vid_file to be a folder of extracted frames (the reference shells out to
 ffmpeg first, demo.py:71; ffmpeg/cv2 are not part of this image).
 """
@@ -35,6 +36,13 @@ def parse_args(argv=None):
                    help="draw the uncertainty-coloured meshes over the input (GPU): folder mode <out>/poco_results/<image>.png, "
                         "video mode <out>/tmp_images_output/%%06d.png + uncertainty.log; needs `faces` in the --smpl file")
     p.add_argument("--sideview", action="store_true", help="with --render: add the Ry(270) view to the right of each picture")
+    p.add_argument("--image_format", default="png", choices=["png", "jpg"],
+                   help="with --render: format of the per-frame pictures; jpg is encoded on the GPU (baseline JPEG, 4:2:0) and only "
+                        "its bytes are copied to the host")
+    p.add_argument("--jpeg_quality", type=int, default=90, help="quality 1..100 of --image_format jpg and --save_video")
+    p.add_argument("--save_video", action="store_true",
+                   help="video mode with --render: also write <out>/<frame folder>_poco_result.avi (Motion-JPEG, --fps)")
+    p.add_argument("--fps", type=float, default=30.0, help="frame rate of --save_video")
     p.add_argument("--no_uncert_color", action="store_true", help="with --render: plain grey meshes instead of the uncertainty colour")
     p.add_argument("--no_kinematic_uncert", action="store_false",
                    help="Do not use SMPL Kinematic for uncert (same store_false semantics as the reference)")
@@ -94,6 +102,10 @@ def main(args):
         sys.exit("webcam mode needs a capture device + renderer: out of scope")
     if render_enabled(args):
         _check_render_assets(args)
+    if not 1 <= getattr(args, "jpeg_quality", 90) <= 100:
+        sys.exit(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
+    if getattr(args, "save_video", False) and not (args.mode == "video" and render_enabled(args)):
+        sys.exit("--save_video writes the rendered frames of video mode: it needs --mode video and --render")
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")

@@ -376,6 +376,37 @@ int poco_renderer_render(poco_renderer_t r, unsigned char* d_frame, int H, int W
                          const float* d_params, const float* h_rot3x3, int* d_frag_count, void* stream);
 void poco_renderer_destroy(poco_renderer_t r);
 
+/* ---- JPEG encoder: the demo's rendered frames as baseline JPEG, encoded where they are ------------------------------------------
+ * Replaces the host-side picture encoding behind pocolib/core/tester.py:338-345 (cv2.imwrite per frame) and, with
+ * poco_amd/jpeg.py's Motion-JPEG .avi writer on top, the ffmpeg call of demo.py:148-157 / demo_utils.py:237-245 (images_to_video,
+ * -pix_fmt yuv420p); csrc/jpeg_enc.hip.  Takes a uint8 [H,W,3] RGB device frame, leaves the bytes of a JFIF file on the device.
+ *   Format: baseline sequential (SOF0), 8 bit, YCbCr 4:2:0 (luma sampling 2x2), JFIF 1.01 with density 1:1.  Stream: SOI, APP0,
+ *     DQT x2, SOF0, DHT x4, DRI, SOS, the restart intervals, EOI; the header is 629 bytes.
+ *   Arithmetic: integers only, so the bytes are a function of (frame, quality) alone and equal those of the numpy restatement
+ *     tests/jpeg_np.py.  RGB -> YCbCr in libjpeg's 16-bit fixed point (jccolor.c, SCALEBITS 16); chroma = the 2x2 box sum with
+ *     libjpeg's alternating bias 1, 2, 1, 2 ... along a row, >> 2 (jcsample.c h2v2_downsample); a frame whose sides are no
+ *     multiples of 16 is padded by edge replication to whole 16x16 MCUs, SOF0 carries the true H and W; forward DCT = libjpeg's
+ *     "islow" integer DCT (jfdctint.c: 13-bit constants, PASS1_BITS 2) on samples minus 128; quantisation by the Annex K tables
+ *     scaled by jpeg_quality_scaling (quality 1..100) and clamped to 1..255, rounding to nearest with ties away from zero
+ *     (jcdctmgr.c forward_DCT).
+ *   Entropy coding: the four Annex K Huffman tables (not optimised), zigzag order, EOB and ZRL.  One restart interval per MCU row
+ *     (DRI = MCUs per row): each starts with DC predictors 0, ends padded with 1-bits to a byte boundary, has 0xFF -> 0xFF 0x00
+ *     stuffing and is followed by RSTm (m counting modulo 8), the last one by EOI.  The intervals are what is coded in parallel.
+ *   Size bound: a block codes into at most 64 x (16 + 11) bits = 216 bytes, at most twice that after stuffing, so
+ *     worst case(H, W) = 629 + ceil(H/16) x (ceil(W/16) x 6 x 432 + 2) bytes.  The scratch planned at create and the caller's
+ *     out_cap are held to it: overflow cannot happen and is not a status code. */
+typedef struct poco_jpeg_encoder* poco_jpeg_encoder_t;
+/* Tables, coefficient scratch (768 bytes per MCU) and worst-case interval slots (2592 bytes per MCU) for frames up to max_h x max_w
+ * (1 .. 16384 each, else POCO_ERR_ARG without touching the GPU).  Needs the GPU after validation. */
+int poco_jpeg_encoder_create(int max_h, int max_w, poco_jpeg_encoder_t* out);
+/* d_rgb uint8 [H,W,3] (any alignment) -> d_out[0 .. *d_len): three launches on `stream` - transform, entropy coding, compaction -
+ * with no allocation, no synchronisation and no global atomics; nothing outside d_out[0 .. *d_len) and the word d_len is written.
+ * POCO_ERR_ARG before any GPU work: a null handle or pointer, H or W < 1 or above the created maximum, quality outside 1..100,
+ * out_cap below worst case(H, W).  One encoder is used from one stream at a time (its scratch is reused in stream order). */
+int poco_jpeg_encode(poco_jpeg_encoder_t enc, const unsigned char* d_rgb, int H, int W, int quality, unsigned char* d_out,
+                     size_t out_cap, unsigned int* d_len, void* stream);
+void poco_jpeg_encoder_destroy(poco_jpeg_encoder_t enc);
+
 /* ---- evaluator: MPJPE, PA-MPJPE, V2V and the uncertainty / pose-error correlation of eval.py ---------------------------------
  * Replaces the host side of pocolib/core/trainer.py:298-336 (validation_step) and :365-391 (validation_epoch_end):
  * get_jnts_from_mesh, mpjpe_error, pampjpe_error (one np.linalg.svd per crop, in Python), vert_error, calculate_distance_pose,

@@ -101,6 +101,21 @@ class POCOTester:
                                     uncert_color=not getattr(self.args, "no_uncert_color", False),
                                     sideview=bool(getattr(self.args, "sideview", False)), side_bg=side_bg)
 
+    # ---- --image_format jpg / --save_video ------------------------------------------------------------------------------
+    @property
+    def image_format(self) -> str:
+        return getattr(self.args, "image_format", "png") or "png"
+
+    def encode_jpeg(self, pic: torch.Tensor) -> bytes:
+        """The .jpg bytes of a device picture, encoded on the device (poco_amd/jpeg.py): only the bytes cross to the host.  The
+        encoder is created for the first picture's size and re-created when a larger one arrives (folder mode)."""
+        from .jpeg import JpegEncoder
+        H, W = int(pic.shape[0]), int(pic.shape[1])
+        enc = getattr(self, "_jpeg", None)
+        if enc is None or H > enc.max_h or W > enc.max_w:
+            self._jpeg = enc = JpegEncoder(self.device, max(H, enc.max_h if enc else 0), max(W, enc.max_w if enc else 0))
+        return enc.encode(pic.contiguous(), int(getattr(self.args, "jpeg_quality", 90)))
+
     def _save_meshes(self, folder: str, verts: np.ndarray, names):
         from .postproc import write_obj
         for v, n in zip(verts, names):
@@ -373,8 +388,12 @@ class POCOTester:
                 if r is not None:
                     writes.append(wr_pool.submit(write, n, r))
                     if render_on:                                 # tester.py:248-345: detection order, white side canvas
-                        pic = self.render_frame(fr, r["verts"], r["orig_cam"], r["var"], side_bg=255).cpu().numpy()
-                        writes.append(wr_pool.submit(_write_png, os.path.join(img_dir, os.path.splitext(n)[0] + ".png"), pic))
+                        pic = self.render_frame(fr, r["verts"], r["orig_cam"], r["var"], side_bg=255)
+                        stem = os.path.join(img_dir, os.path.splitext(n)[0])
+                        if self.image_format == "jpg":
+                            writes.append(wr_pool.submit(_write_bytes, stem + ".jpg", self.encode_jpeg(pic)))
+                        else:
+                            writes.append(wr_pool.submit(_write_png, stem + ".png", pic.cpu().numpy()))
                 while len(writes) > ahead:
                     writes.popleft().result()
             for w in writes:
@@ -491,14 +510,23 @@ def _write_png(path: str, img: np.ndarray) -> None:
     Image.fromarray(img).save(path)
 
 
+def _write_bytes(path: str, data: bytes) -> None:
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def _render_video(self, results: dict, frame_folder: str, names, load, output_path: str) -> None:
     """render_results of tester.py:482-580: every frame of the folder with the people the tracks place in it, in ascending
     orig_cam[1] (demo_utils.py:307-313, ties in track order), black side canvas, <output>/tmp_images_output/%06d.png, and the
-    lines of <output>/uncertainty.log (tester.py:547-550)."""
+    lines of <output>/uncertainty.log (tester.py:547-550).  --image_format jpg writes %06d.jpg, encoded on the device;
+    --save_video adds <output>/<frame folder>_poco_result.avi (Motion-JPEG of the same pictures at --fps: the reference's
+    images_to_video, demo.py:148-157)."""
     from concurrent.futures import ThreadPoolExecutor
     from .render import video_order
     out_dir = os.path.join(output_path, "tmp_images_output")
     os.makedirs(out_dir, exist_ok=True)
+    jpg = self.image_format == "jpg"
+    video = None
     per_frame = [[] for _ in names]
     for pid, r in results.items():
         for k, f in enumerate(r["frame_ids"]):
@@ -523,11 +551,24 @@ def _render_video(self, results: dict, frame_folder: str, names, load, output_pa
                     log_lines.append(f"img_f:{os.path.join(frame_folder, name)} person:{who} var:{g:.3f}")
             else:
                 pic = torch.cat([fr, torch.zeros_like(fr)], 1) if sideview else fr
-            writes.append(pool.submit(_write_png, os.path.join(out_dir, f"{fi:06d}.png"), pic.cpu().numpy()))
+            data = self.encode_jpeg(pic) if jpg or getattr(self.args, "save_video", False) else None
+            if getattr(self.args, "save_video", False):
+                if video is None:
+                    from .jpeg import MjpegWriter
+                    avi = os.path.basename(os.path.normpath(frame_folder)) + "_poco_result.avi"
+                    video = MjpegWriter(os.path.join(output_path, avi), int(pic.shape[1]), int(pic.shape[0]),
+                                        float(getattr(self.args, "fps", 30.0)))
+                video.add(data)
+            if jpg:
+                writes.append(pool.submit(_write_bytes, os.path.join(out_dir, f"{fi:06d}.jpg"), data))
+            else:
+                writes.append(pool.submit(_write_png, os.path.join(out_dir, f"{fi:06d}.png"), pic.cpu().numpy()))
             while len(writes) > 16:
                 writes.pop(0).result()
         for w in writes:
             w.result()
+    if video is not None:
+        video.close()
     with open(os.path.join(output_path, "uncertainty.log"), "a") as f:
         for ln in log_lines:
             print(ln, file=f)

@@ -1,9 +1,12 @@
 """Time the demo renderer (poco_renderer_render: memset + vertex, raster and shade launches) with HIP events at 1920 x 1080 for
 1, 4 and 16 SMPL-sized meshes (6890 vertices, 13776 faces, procedurally generated: a deformed torus grid), one JSON line per case.
 
-    python tools/bench_render.py [--iters 50] [--folder 32]
+    python tools/bench_render.py [--iters 50] [--folder 32] [--encode]
 --folder N: also the folder-mode wall time per image of demo.py on N synthetic 1080p images (one person each, resnet50-cliff
-synthetic checkpoint) without and with --render (PNG encoding on the host included)."""
+synthetic checkpoint) without and with --render (PNG encoding on the host included).
+--encode: instead of the renderer, the JPEG encoder (poco_jpeg_encode: transform, entropy, compaction) at 1920 x 1080 and at
+3840 x 1080 (--sideview) on a rendered frame and on a noise frame, device events around each call, median of --iters; with
+--folder N the folder-mode wall time per image without --render and with --render as png and as jpg, without and with --sideview."""
 import argparse
 import json
 import sys
@@ -82,7 +85,42 @@ def bench(iters):
                           "covered_px": covered, "ms": round(ms, 4), "iters": iters}), flush=True)
 
 
-def folder(n):
+def encode(iters):
+    """One encode call (three launches, no host sync inside the timed window) per frame kind and size; also the bytes it makes."""
+    from poco_amd import jpeg
+    dev = torch.device("cuda:0")
+    H, W = 1080, 1920
+    verts, faces = smpl_sized_mesh()
+    R = render.Renderer(faces, V_SMPL, dev)
+    vs, cams = people(4, H, W, verts)
+    cols = np.array([render.vertex_color(np.full(24, 0.3 + 0.04 * p, np.float32), "hrnet_w48_cls-cliff") for p in range(4)])
+    g = torch.linspace(0, 255, W, device=dev)[None, :, None] * torch.tensor([1.0, 0.6, 0.3], device=dev)
+    smooth = (g + torch.linspace(0, 60, H, device=dev)[:, None, None]).clamp(0, 255).to(torch.uint8).contiguous()
+    rendered = render.render_people(R, smooth.clone(), torch.from_numpy(vs).to(dev), cams, None, "hrnet_w48_cls-cliff",
+                                    uncert_color=False, sideview=True, side_bg=255).contiguous()
+    R.render(smooth, torch.from_numpy(vs).to(dev), cams, cols, np.zeros(4, np.float32))
+    noise = torch.randint(0, 256, (H, 2 * W, 3), dtype=torch.uint8, device=dev, generator=torch.Generator(dev).manual_seed(0))
+    enc = jpeg.JpegEncoder(dev, H, 2 * W)
+    out = torch.empty(jpeg.worst_case_bytes(H, 2 * W), dtype=torch.uint8, device=dev)
+    n = torch.empty(1, dtype=torch.int32, device=dev)
+    for kind, w, frame in (("rendered", W, smooth), ("rendered", 2 * W, rendered), ("noise", W, noise[:, :W].contiguous()),
+                           ("noise", 2 * W, noise)):
+        for q in (90,):
+            for _ in range(5):
+                enc.encode_into(frame, out, q, n)
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+            for e0, e1 in ev:
+                e0.record()
+                enc.encode_into(frame, out, q, n)
+                e1.record()
+            torch.cuda.synchronize()
+            ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+            print(json.dumps({"bench": "jpeg_encode", "frame": kind, "H": H, "W": w, "quality": q, "bytes": int(n.item()),
+                              "ms_median": round(ms[len(ms) // 2], 4), "ms_min": round(ms[0], 4), "ms_max": round(ms[-1], 4),
+                              "iters": iters}), flush=True)
+
+
+def folder(n, flag_sets=([], ["--render"], ["--render", "--sideview"])):
     import demo
     from PIL import Image
     from poco_amd import synth
@@ -99,7 +137,7 @@ def folder(n):
     for i in range(n):
         Image.fromarray(r.integers(0, 256, (1080, 1920, 3), dtype=np.uint8)).save(imgs / f"im{i:05d}.png")
     from poco_amd.tester import POCOTester
-    for extra in ([], ["--render"], ["--render", "--sideview"]):
+    for extra in flag_sets:
         a = demo.parse_args(["--cfg", "configs/demo_poco_cliff_resnet50.yaml", "--ckpt", str(tmp / "ckpt.pt"), "--mode", "folder",
                              "--image_folder", str(imgs), "--output_folder", str(tmp / "out"), "--batch_size", "16",
                              "--smpl", str(tmp / "smpl.npz"), *extra])
@@ -115,7 +153,14 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--folder", type=int, default=0)
+    ap.add_argument("--encode", action="store_true")
     args = ap.parse_args()
-    bench(args.iters)
-    if args.folder:
-        folder(args.folder)
+    if args.encode:
+        encode(args.iters)
+        if args.folder:
+            jpg = ["--image_format", "jpg"]
+            folder(args.folder, ([], ["--render"], ["--render", *jpg], ["--render", "--sideview"], ["--render", "--sideview", *jpg]))
+    else:
+        bench(args.iters)
+        if args.folder:
+            folder(args.folder)
