@@ -11,7 +11,9 @@ default to one centred box; results are written as .npz.  --render (opt-in; the 
 uncertainty-coloured meshes on the GPU (poco_amd/render.py) into the PNGs the reference writes; --image_format jpg encodes them on
 the GPU instead (poco_amd/jpeg.py) and --save_video adds the result video as a Motion-JPEG .avi (the reference's ffmpeg step).
 --mode video expects --vid_file to be a folder of extracted frames (the reference shells out to
-ffmpeg first, demo.py:71; ffmpeg/cv2 are not part of this image).
+ffmpeg first, demo.py:71; ffmpeg/cv2 are not part of this image) or a Motion-JPEG .avi, which is read frame by frame
+(poco_amd/jpeg.py MjpegReader).  --decode gpu decodes baseline .jpg input on the GPU (poco_amd/jpeg.py JpegDecoder): the file's
+bytes cross PCIe instead of its pixels; other files go through PIL as with the default --decode host.
 """
 import argparse
 import json
@@ -25,7 +27,10 @@ def parse_args(argv=None):
     p.add_argument("--ckpt", type=str, required=True, help="checkpoint path (.pt/.ckpt/.pth or run dir)")
     p.add_argument("--inf_model", type=str, default="best")
     p.add_argument("--mode", default="folder", choices=["video", "folder", "directory", "webcam"])
-    p.add_argument("--vid_file", type=str, help="folder of extracted video frames")
+    p.add_argument("--vid_file", type=str, help="folder of extracted video frames, or a Motion-JPEG .avi file")
+    p.add_argument("--decode", default="host", choices=["host", "gpu"],
+                   help="where input images are decoded: host = PIL on a thread pool; gpu = baseline .jpg files and Motion-JPEG "
+                        "frames on the GPU, same pixels (anything else still goes through PIL)")
     p.add_argument("--image_folder", type=str, help="input image folder")
     p.add_argument("--output_folder", type=str, default="out", help="output folder to write results")
     p.add_argument("--batch_size", type=int, default=64, help="batch size of POCO")
@@ -122,10 +127,18 @@ def main(args):
             dist.init_process_group("gloo")
     from poco_amd.tester import POCOTester, load_detections
     folder = args.image_folder if args.mode in ("folder", "directory") else args.vid_file
-    if not folder or not os.path.isdir(folder):
+    stem = os.path.basename(os.path.normpath(folder)) if folder else ""
+    if args.mode == "video" and folder and os.path.isfile(folder):
+        from poco_amd.jpeg import MjpegReader
+        try:                                                              # a video file: only Motion-JPEG AVI is read
+            MjpegReader(folder).close()
+        except ValueError as e:
+            sys.exit(f"--vid_file: {e}")
+        stem = os.path.splitext(stem)[0]
+    elif not folder or not os.path.isdir(folder):
         sys.exit(f"input folder not found: {folder}")
     tester = POCOTester(args)
-    out_dir = os.path.join(args.output_folder, os.path.basename(os.path.normpath(folder)) + "_")
+    out_dir = os.path.join(args.output_folder, stem + "_")
     if args.mode == "video":
         stats = tester.run_on_video_folder(folder, args.tracking, out_dir)
     else:

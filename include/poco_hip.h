@@ -407,6 +407,54 @@ int poco_jpeg_encode(poco_jpeg_encoder_t enc, const unsigned char* d_rgb, int H,
                      size_t out_cap, unsigned int* d_len, void* stream);
 void poco_jpeg_encoder_destroy(poco_jpeg_encoder_t enc);
 
+/* ---- JPEG decoder: baseline JPEG input frames decoded on the device --------------------------------------------------------------
+ * Replaces the host-side decode behind pocolib/core/tester.py:171 (cv2.imread + cvtColor per image of the folder) and :507
+ * (cv2.imread per frame of the result video), and the frames that demo.py:69-90 / demo_utils.py:183-199 (video_to_images) extract
+ * from a video; csrc/jpeg_dec.hip.  Takes the entropy-coded bytes of up to max_batch parsed files (poco_amd/jpeg.py parse_jpeg
+ * walks the markers on the host), leaves one uint8 [H,W,3] RGB picture per file on the device: a few hundred KB cross PCIe
+ * instead of 6 MB per 1080p frame.
+ *   Streams: baseline sequential (SOF0), 8 bit, one interleaved scan; three components YCbCr with luma sampling 1x1, 2x1 or 2x2
+ *     and chroma 1x1, or one component (replicated to R = G = B); any 8-bit DQT, any DHT, any DRI or none.
+ *   Arithmetic: integers only; the pixels equal libjpeg's with jpeg_decompress defaults (what PIL gives) and those of the numpy
+ *     restatement tests/jpegdec_np.py.  Dequantisation, the "islow" inverse DCT (jidctint.c: 13-bit constants, PASS1_BITS 2),
+ *     + 128 and a clamp to 0..255; "fancy" chroma upsampling (jdsample.c: h2v1 weights 3/4 1/4 with roundings + 1 / + 2, h2v2
+ *     weights 9 3 3 1 / 16 with roundings + 8 / + 7, over the component's own width ceil(W/2) and height ceil(H/2) with the
+ *     first / last column and row repeated; plain replication when that width is 2 or less); YCbCr -> RGB in jdcolor.c's 16-bit
+ *     fixed point.  Where the inverse DCT leaves 0..255 by more than libjpeg's range-limit table holds the result is clamped.
+ *   Entropy decoding: every restart interval is cut into subsequences of 128 bytes; a lane decodes its subsequence from a guessed
+ *     state (bit position, block within the MCU, zigzag index) and, round after round, from its predecessor's exit state until
+ *     no exit state changes; counts, a prefix sum and a write pass store the coefficients; DC differences become values in a
+ *     segmented scan per component.  The Huffman tables (a 9-bit lookahead table + maxcode / valptr) are built on the host.
+ *   Safety: every read of the byte stream is clamped to its restart interval, every store is guarded by its own index; a code
+ *     that is in no table, a zigzag index past 63 or an interval that ends before its blocks do sets that image's status word. */
+typedef struct poco_jpeg_decoder* poco_jpeg_decoder_t;
+/* One parsed file (all pointers on the host except d_rgb).  Tables are given per component as the file selects them. */
+typedef struct poco_jpeg_image {
+  const unsigned char* data;      /* the scan's entropy-coded bytes, RSTm markers included, EOI excluded */
+  size_t nbytes;
+  const unsigned int* segs;       /* [nseg][3]: offset into data, length, first MCU of every restart interval */
+  int nseg;
+  int H, W, ncomp;                /* ncomp 1 or 3 */
+  int hsamp, vsamp;               /* luma sampling: 1x1, 2x1 or 2x2 (1x1 for one component) */
+  unsigned short qt[3][64];       /* quantisation table per component, natural (row-major) order */
+  unsigned char dc_bits[3][16], dc_vals[3][16], ac_bits[3][16], ac_vals[3][256];
+  unsigned char* d_rgb;           /* device: receives H * W * 3 bytes, any alignment */
+} poco_jpeg_image;
+/* Device scratch (coefficients, planes, per-subsequence states) and one pinned staging buffer for up to max_batch images of up to
+ * max_h x max_w (1 .. 16384 each) whose bytes and tables add up to at most max_bytes per call; POCO_ERR_ARG without touching the
+ * GPU for sizes outside that, max_batch outside 1 .. 4096 or max_bytes outside 1 .. 2^30.  Needs the GPU after validation. */
+int poco_jpeg_decoder_create(int max_h, int max_w, int max_batch, size_t max_bytes, poco_jpeg_decoder_t* out);
+/* Decode imgs[0 .. n) in one call: one host-to-device copy of bytes, tables and interval tables from the pinned staging buffer,
+ * two memsets and the launches (synchronisation rounds, counts, write, DC scan, inverse DCT, upsampling + colour) on `stream`; no
+ * allocation, no global atomics.  d_status int32 [n] on the device receives 0 for a decoded image and non-zero for one whose
+ * stream was damaged (its pixels are then unspecified; the other images are decoded); nothing outside the n pictures and
+ * d_status is written.  The only host wait is for the previous call's copy out of the staging buffer.  POCO_ERR_ARG before any
+ * GPU work: null handle or pointer, n outside 1 .. max_batch, a size outside the created maximum, sampling or component counts
+ * other than those above, a Huffman table that is no prefix code or names more symbols than its array holds (16 for DC, 256 for
+ * AC), an interval outside the data, or more bytes / intervals (2048 per image of max_batch) than the decoder was created for.  One decoder is used from one stream at a time. */
+int poco_jpeg_decode(poco_jpeg_decoder_t dec, const poco_jpeg_image* imgs, int n, int* d_status, void* stream);
+void poco_jpeg_decoder_destroy(poco_jpeg_decoder_t dec);
+
 /* ---- evaluator: MPJPE, PA-MPJPE, V2V and the uncertainty / pose-error correlation of eval.py ---------------------------------
  * Replaces the host side of pocolib/core/trainer.py:298-336 (validation_step) and :365-391 (validation_epoch_end):
  * get_jnts_from_mesh, mpjpe_error, pampjpe_error (one np.linalg.svd per crop, in Python), vert_error, calculate_distance_pose,

@@ -6,12 +6,22 @@ csrc/jpeg_enc.hip), and a Motion-JPEG .avi writer on top of it: the result video
     data = enc.encode(frame_u8_cuda, quality=90)          # bytes of a .jpg file: a few hundred KB cross PCIe instead of 6 MB
     with MjpegWriter("out.avi", 1920, 1080, fps=30) as w:
         w.add(data)
+
+The way back is here too: parse_jpeg walks a file's markers on the host, JpegDecoder hands the entropy-coded bytes of a whole
+batch to the device decoder (poco_jpeg_decode, csrc/jpeg_dec.hip) and MjpegReader reads a Motion-JPEG .avi frame by frame.
+
+    dec = JpegDecoder(device, 1080, 1920, max_batch=16, max_bytes=32 << 20)
+    frames = dec.decode([open(p, "rb").read() for p in paths])       # uint8 [H,W,3] device tensors, PIL's pixels
+    for data in MjpegReader("movie.avi"): ...
 """
 from __future__ import annotations
 
 import ctypes as C
 import struct
+from dataclasses import dataclass
+from typing import List, Optional
 
+import numpy as np
 import torch
 
 from ._lib import PocoHipError, check, lib
@@ -150,6 +160,405 @@ class MjpegWriter:
         self._f.write(self._headers(self._pos - self._movi - 4))
         self._f.close()
         self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# ---- decoding: the marker walk, the device decoder's binding, the .avi reader ----------------------------------------------------
+SUBSEQ_BYTES = 128                     # the device's subsequence size (JD_SUBSEQ in csrc/jpeg_dec.hip)
+SEGS_PER_IMAGE = 2048                  # restart intervals a decoder plans per image of its batch (JD_SEGS_PER_IMAGE there)
+
+# ITU-T T.81 Annex K: the tables of a frame that carries no DHT (Motion-JPEG frames inside AVI commonly omit them)
+_K_DC_BITS = ([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0], [0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0])
+_K_AC_BITS = ([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D], [0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77])
+_K_AC_VALS = (bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a43444546"
+    "4748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8"
+    "b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"), bytes.fromhex(
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445"
+    "464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6"
+    "b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"))
+ANNEX_K_TABLES = {(0, t): (bytes(_K_DC_BITS[t]), bytes(range(12))) for t in (0, 1)}
+ANNEX_K_TABLES.update({(1, t): (bytes(_K_AC_BITS[t]), _K_AC_VALS[t]) for t in (0, 1)})
+
+_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+                    28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61,
+                    54, 47, 55, 62, 63])
+
+
+@dataclass
+class JpegInfo:
+    """What parse_jpeg found.  Tables are per component, as the frame and scan headers select them."""
+    height: int
+    width: int
+    ncomp: int                         # 1 (grayscale) or 3 (YCbCr)
+    hsamp: int                         # luma sampling, chroma is 1 x 1: (1,1) 4:4:4, (2,1) 4:2:2, (2,2) 4:2:0
+    vsamp: int
+    qt: np.ndarray                     # uint16 [ncomp, 64], natural (row-major) order
+    dc: list                           # per component (bits: 16 bytes, huffval: bytes)
+    ac: list
+    restart_interval: int              # MCUs per restart interval, 0 = none
+    scan_offset: int                   # the entropy-coded data: data[scan_offset : scan_offset + scan_length]
+    scan_length: int
+    segments: np.ndarray               # uint32 [nseg, 3]: offset from scan_offset, length, first MCU of every restart interval
+    data: bytes
+
+    @property
+    def mcus(self):
+        """(MCU rows, MCU columns)"""
+        return (-(-self.height // (8 * self.vsamp)), -(-self.width // (8 * self.hsamp)))
+
+
+def _parse(data: bytes) -> Optional[JpegInfo]:
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        return None
+    qts, huff = {}, {}
+    frame, dri, adobe = None, 0, None
+    i = 2
+    while True:
+        if i + 4 > n or data[i] != 0xFF:
+            return None
+        m = data[i + 1]
+        if m == 0xFF:                  # fill byte
+            i += 1
+            continue
+        ln = (data[i + 2] << 8) | data[i + 3]
+        if m in (0xD8, 0xD9, 0x01) or 0xD0 <= m <= 0xD7 or ln < 2 or i + 2 + ln > n:
+            return None
+        p = data[i + 4:i + 2 + ln]
+        i += 2 + ln
+        if m == 0xC0:
+            if frame is not None or len(p) < 6 or p[0] != 8:
+                return None
+            H, W, nc = (p[1] << 8) | p[2], (p[3] << 8) | p[4], p[5]
+            if len(p) != 6 + 3 * nc or nc not in (1, 3) or not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+                return None
+            frame = (H, W, [(p[6 + 3 * c], p[7 + 3 * c] >> 4, p[7 + 3 * c] & 15, p[8 + 3 * c]) for c in range(nc)])
+        elif 0xC1 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return None                # extended, progressive, lossless, arithmetic: not decoded here
+        elif m == 0xCC:
+            return None
+        elif m == 0xC4:
+            j = 0
+            while j < len(p):
+                if j + 17 > len(p):
+                    return None
+                tc, th = p[j] >> 4, p[j] & 15
+                cnt = sum(p[j + 1:j + 17])
+                if tc > 1 or th > 3 or cnt > 256 or j + 17 + cnt > len(p):
+                    return None
+                huff[(tc, th)] = (bytes(p[j + 1:j + 17]), bytes(p[j + 17:j + 17 + cnt]))
+                j += 17 + cnt
+        elif m == 0xDB:
+            j = 0
+            while j < len(p):
+                if p[j] >> 4 != 0 or (p[j] & 15) > 3 or j + 65 > len(p):       # 16-bit entries: not baseline
+                    return None
+                q = np.zeros(64, np.uint16)
+                q[_ZIGZAG] = np.frombuffer(p[j + 1:j + 65], np.uint8)
+                qts[p[j] & 15] = q
+                j += 65
+        elif m == 0xDD:
+            if len(p) != 2:
+                return None
+            dri = (p[0] << 8) | p[1]
+        elif m == 0xEE and len(p) >= 12 and p[:5] == b"Adobe":
+            adobe = p[11]
+        elif m == 0xDA:
+            break
+        # other APPn (JFIF, Exif ...) and COM: skipped
+    if frame is None:
+        return None
+    H, W, comps = frame
+    nc = len(comps)
+    if len(p) != 4 + 2 * nc or p[0] != nc or p[1 + 2 * nc] != 0 or p[2 + 2 * nc] != 63 or p[3 + 2 * nc] != 0:
+        return None                    # not one interleaved scan of all components
+    if nc == 3:
+        if [c[0] for c in comps] == [82, 71, 66] or adobe == 0 or adobe == 2:      # RGB / YCCK files
+            return None
+        if (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            return None
+    elif (comps[0][1], comps[0][2]) != (1, 1):
+        return None
+    hs, vs = comps[0][1], comps[0][2]
+    dc, ac, qt = [], [], np.zeros((nc, 64), np.uint16)
+    for c in range(nc):
+        if p[1 + 2 * c] != comps[c][0] or comps[c][3] not in qts:
+            return None
+        td, ta = p[2 + 2 * c] >> 4, p[2 + 2 * c] & 15
+        qt[c] = qts[comps[c][3]]
+        for tc, th, dst in ((0, td, dc), (1, ta, ac)):
+            t = huff.get((tc, th)) if huff else ANNEX_K_TABLES.get((tc, th))
+            if t is None or not _prefix_code(t[0]) or (tc == 0 and (len(t[1]) > 16 or any(v > 15 for v in t[1]))):
+                return None
+            dst.append(t)
+    # the entropy-coded data ends at the first marker that is neither stuffing nor RSTm; anything but EOI there is another scan
+    a = np.frombuffer(data, np.uint8, offset=i)
+    ff = np.flatnonzero(a[:-1] == 0xFF) if a.size > 1 else np.zeros(0, np.int64)
+    nxt = a[ff + 1]
+    is_rst = (nxt >= 0xD0) & (nxt <= 0xD7)
+    other = ff[(nxt != 0) & ~is_rst & (nxt != 0xFF)]
+    end = a.size                       # a truncated file: the device reports it in the image's status word
+    if other.size:
+        if a[other[0] + 1] != 0xD9:
+            return None
+        end = int(other[0])
+    rst = ff[is_rst & (ff < end)]
+    mcuy, mcux = -(-H // (8 * vs)), -(-W // (8 * hs))
+    nmcu = mcuy * mcux
+    if dri == 0 or rst.size == 0:
+        segs = np.array([[0, end, 0]], np.uint32)
+    else:
+        if rst.size > (nmcu - 1) // dri or not np.array_equal(a[rst + 1] - 0xD0, np.arange(rst.size) & 7):
+            return None
+        start = np.concatenate([[0], rst + 2])
+        stop = np.concatenate([rst, [end]])
+        segs = np.stack([start, stop - start, np.arange(start.size) * dri], 1).astype(np.uint32)
+    return JpegInfo(H, W, nc, hs, vs, qt, dc, ac, dri, i, end, segs, data)
+
+
+def _prefix_code(bits: bytes) -> bool:
+    """Kraft: the counts per length describe a prefix code that leaves the all-ones code word free."""
+    code = 0
+    for ln in range(16):
+        code += bits[ln]
+        if bits[ln] and code >= (2 << ln):
+            return False
+        code <<= 1
+    return any(bits)
+
+
+def parse_jpeg(data) -> Optional[JpegInfo]:
+    """The marker walk of one .jpg file: sizes, sampling, tables, the restart interval and the table of restart intervals of
+    its entropy-coded data - or None for a file the device decoder does not take (progressive, lossless, arithmetic coding, 12
+    bit, CMYK / YCCK / RGB, other sampling factors, more than one scan, a damaged header); the caller then decodes with PIL.  A
+    file cut short inside its scan is parsed: the decoder reports it in the image's status word."""
+    try:
+        return _parse(bytes(data))
+    except (IndexError, ValueError):
+        return None
+
+
+class _CImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("nbytes", C.c_size_t), ("segs", C.c_void_p), ("nseg", C.c_int), ("H", C.c_int),
+                ("W", C.c_int), ("ncomp", C.c_int), ("hsamp", C.c_int), ("vsamp", C.c_int), ("qt", C.c_uint16 * 64 * 3),
+                ("dc_bits", C.c_uint8 * 16 * 3), ("dc_vals", C.c_uint8 * 16 * 3), ("ac_bits", C.c_uint8 * 16 * 3),
+                ("ac_vals", C.c_uint8 * 256 * 3), ("d_rgb", C.c_void_p)]
+
+
+class JpegDecoder:
+    """Baseline JPEG files -> uint8 [H,W,3] RGB device tensors holding the pixels PIL gives, up to max_batch images of up to
+    max_h x max_w and max_bytes of entropy-coded data and tables per call, of mixed sizes and samplings.  Device scratch and
+    the pinned staging buffer are planned here; decode / decode_into allocate nothing on the C side."""
+
+    def __init__(self, device, max_h: int, max_w: int, max_batch: int = 1, max_bytes: int = 0):
+        max_h, max_w, max_batch = int(max_h), int(max_w), int(max_batch)
+        max_bytes = int(max_bytes) or max_batch * max(1 << 16, max_h * max_w)
+        if not (1 <= max_h <= MAX_SIDE and 1 <= max_w <= MAX_SIDE):
+            raise PocoHipError(f"JpegDecoder: max_h, max_w must be in 1..{MAX_SIDE}, got {max_h} x {max_w}")
+        if not 1 <= max_batch <= 4096:
+            raise PocoHipError(f"JpegDecoder: max_batch must be in 1..4096, got {max_batch}")
+        if not 1 <= max_bytes <= 1 << 30:
+            raise PocoHipError(f"JpegDecoder: max_bytes must be in 1..2^30, got {max_bytes}")
+        self.max_h, self.max_w, self.max_batch, self.max_bytes = max_h, max_w, max_batch, max_bytes
+        self._h = C.c_void_p()
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        L = lib()
+        L.poco_jpeg_decoder_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.poco_jpeg_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.poco_jpeg_decoder_destroy.argtypes = [C.c_void_p]
+        L.poco_jpeg_decoder_destroy.restype = None
+        with torch.cuda.device(self.device):
+            check(L.poco_jpeg_decoder_create(max_h, max_w, max_batch, max_bytes, C.byref(self._h)), "poco_jpeg_decoder_create")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().poco_jpeg_decoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def fits(self, info: JpegInfo) -> bool:
+        """The picture's size and its number of restart intervals are within what every image of a batch may have."""
+        return info.height <= self.max_h and info.width <= self.max_w and len(info.segments) <= SEGS_PER_IMAGE
+
+    def decode_into(self, images, outs, status: torch.Tensor = None) -> torch.Tensor:
+        """Enqueue the decode of `images` (bytes of .jpg files or JpegInfo, at most max_batch) into `outs` (contiguous uint8
+        [H,W,3] device tensors of the files' sizes) on the current stream: one host-to-device copy, no host synchronisation.
+        Returns `status`, an int32 [n] device tensor: 0 per decoded image, non-zero for a damaged stream."""
+        infos = []
+        for im in images:
+            info = im if isinstance(im, JpegInfo) else parse_jpeg(im)
+            if info is None:
+                raise PocoHipError("JpegDecoder: not a baseline JPEG file this decoder takes (parse_jpeg returned None)")
+            infos.append(info)
+        n = len(infos)
+        if not 1 <= n <= self.max_batch:
+            raise PocoHipError(f"JpegDecoder: {n} images in one call, the decoder was created for 1..{self.max_batch}")
+        if len(outs) != n:
+            raise PocoHipError(f"JpegDecoder: {n} images but {len(outs)} output tensors")
+        for info, o in zip(infos, outs):
+            if not (torch.is_tensor(o) and o.device == self.device and o.dtype == torch.uint8 and o.is_contiguous()
+                    and tuple(o.shape) == (info.height, info.width, 3)):
+                raise PocoHipError(f"JpegDecoder: an output must be a contiguous uint8 [{info.height},{info.width},3] tensor on "
+                                   f"{self.device}")
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=self.device)
+        elif not (torch.is_tensor(status) and status.device == self.device and status.dtype == torch.int32
+                  and status.is_contiguous() and status.numel() >= n):
+            raise PocoHipError("JpegDecoder: status must be a contiguous int32 tensor of at least n elements on the decoder's device")
+        arr = (_CImage * n)()
+        keep = []
+        for s, info, o in zip(arr, infos, outs):
+            buf = np.frombuffer(info.data, np.uint8)
+            segs = np.ascontiguousarray(info.segments, np.uint32)
+            qt = np.ascontiguousarray(info.qt, np.uint16)
+            keep += [buf, segs, qt]
+            s.data, s.nbytes = buf.ctypes.data + info.scan_offset, info.scan_length
+            s.segs, s.nseg = segs.ctypes.data, segs.shape[0]
+            s.H, s.W, s.ncomp, s.hsamp, s.vsamp = info.height, info.width, info.ncomp, info.hsamp, info.vsamp
+            C.memmove(s.qt, qt.ctypes.data, info.ncomp * 128)
+            for c in range(info.ncomp):
+                C.memmove(s.dc_bits[c], info.dc[c][0], 16)
+                C.memmove(s.dc_vals[c], info.dc[c][1], len(info.dc[c][1]))
+                C.memmove(s.ac_bits[c], info.ac[c][0], 16)
+                C.memmove(s.ac_vals[c], info.ac[c][1], len(info.ac[c][1]))
+            s.d_rgb = o.data_ptr()
+        check(lib().poco_jpeg_decode(self._h, C.cast(arr, C.c_void_p), n, status.data_ptr(),
+                                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "poco_jpeg_decode")
+        return status
+
+    def decode(self, images, return_status: bool = False):
+        """The pictures of `images` as new device tensors.  return_status: also the list of status words (this reads them back,
+        the call's only host synchronisation)."""
+        infos = [im if isinstance(im, JpegInfo) else parse_jpeg(im) for im in images]
+        if any(i is None for i in infos):
+            raise PocoHipError("JpegDecoder: not a baseline JPEG file this decoder takes (parse_jpeg returned None)")
+        outs = [torch.empty(i.height, i.width, 3, dtype=torch.uint8, device=self.device) for i in infos]
+        status = self.decode_into(infos, outs)
+        return (outs, status.cpu().tolist()) if return_status else outs
+
+
+class MjpegReader:
+    """A plain RIFF AVI file with one Motion-JPEG video stream, frame by frame: the inverse of MjpegWriter.  width, height and
+    fps come from avih / strh, the frame table from idx1 when the file has one and from a walk of movi otherwise.  len(),
+    reader[i] (the bytes of frame i's JPEG file) and iteration; each access reads from the file, nothing is held."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self._f = open(path, "rb")
+        try:
+            self._read_headers()
+        except Exception:
+            self._f.close()
+            raise
+
+    def _read_headers(self):
+        f = self._f
+        size = f.seek(0, 2)
+        f.seek(0)
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
+            raise ValueError(f"MjpegReader: {self.path} is not a RIFF AVI file; only Motion-JPEG AVI is read - extract the frames "
+                             "to a folder and pass the folder")
+        riff_end = min(size, 8 + struct.unpack("<I", head[4:8])[0])
+        self.width = self.height = 0
+        self.fps = 0.0
+        handler, stream_type, movi, idx = None, None, None, None
+        stack = [(12, riff_end)]
+        while stack:
+            p, hi = stack.pop()
+            while p + 8 <= hi:
+                f.seek(p)
+                cid, n = struct.unpack("<4sI", f.read(8))
+                if cid == b"LIST":
+                    kind = f.read(4)
+                    if kind == b"movi":
+                        movi = (p + 8, min(p + 8 + n, size))
+                    elif kind in (b"hdrl", b"strl"):
+                        stack.append((p + 12, min(p + 8 + n, hi)))
+                    elif kind == b"odml":
+                        raise ValueError(f"MjpegReader: {self.path} is an OpenDML (AVI 2.0) file, which is not read")
+                elif cid == b"avih":
+                    h = f.read(min(n, 56))
+                    if len(h) < 56:
+                        raise ValueError(f"MjpegReader: {self.path} is damaged: its avih chunk holds {len(h)} bytes, not 56")
+                    a = struct.unpack("<14I", h)
+                    self.width, self.height = a[8], a[9]
+                    if a[0]:
+                        self.fps = 1e6 / a[0]
+                elif cid == b"strh" and handler is None:
+                    h = f.read(min(n, 56))
+                    if len(h) < 28:
+                        raise ValueError(f"MjpegReader: {self.path} is damaged: its strh chunk holds {len(h)} bytes, not 56")
+                    stream_type, handler = h[:4], h[4:8]
+                    scale, rate = struct.unpack("<II", h[20:28])
+                    if scale and rate:
+                        self.fps = rate / scale
+                elif cid == b"indx":
+                    raise ValueError(f"MjpegReader: {self.path} is an OpenDML (AVI 2.0) file, which is not read")
+                elif cid == b"idx1":
+                    idx = (p + 8, n)
+                p += 8 + n + (n & 1)
+        if riff_end + 12 <= size:
+            f.seek(riff_end)
+            if f.read(4) == b"RIFF" and f.read(8)[4:] == b"AVIX":
+                raise ValueError(f"MjpegReader: {self.path} is an OpenDML (AVI 2.0) file, which is not read")
+        if stream_type != b"vids" or handler not in (b"MJPG", b"mjpg"):
+            raise ValueError(f"MjpegReader: the stream of {self.path} has handler {handler!r}, not MJPG: only Motion-JPEG AVI is "
+                             "read - extract the frames to a folder and pass the folder")
+        if movi is None:
+            raise ValueError(f"MjpegReader: {self.path} has no movi list")
+        self._frames = []              # (file offset of the payload, size)
+        if idx is not None:
+            f.seek(idx[0])
+            raw = f.read(idx[1])
+            ent = np.frombuffer(raw[:len(raw) - len(raw) % 16], "<u4").reshape(-1, 4)
+            vid = ent[(ent[:, 0] == 0x63643030) | (ent[:, 0] == 0x62643030)]          # '00dc' | '00db'
+            if vid.size:
+                # offsets count from the movi fourcc, in some writers from the start of the file: the first entry tells which
+                f.seek(movi[0] + int(vid[0, 2]))
+                base = movi[0] if f.read(4) in (b"00dc", b"00db") else 0
+                self._frames = [(base + int(o) + 8, int(s)) for o, s in zip(vid[:, 2], vid[:, 3]) if s > 0]
+        if not self._frames:
+            p = movi[0] + 4
+            while p + 8 <= movi[1]:
+                f.seek(p)
+                cid, n = struct.unpack("<4sI", f.read(8))
+                if cid == b"LIST":     # 'rec ' groups
+                    p += 12
+                    continue
+                if cid in (b"00dc", b"00db") and n > 0:
+                    self._frames.append((p + 8, n))
+                p += 8 + n + (n & 1)
+        if any(o + s > size for o, s in self._frames):
+            raise ValueError(f"MjpegReader: {self.path} is cut short: a frame lies past the end of the file")
+
+    def __len__(self) -> int:
+        return len(self._frames)
+
+    def __getitem__(self, i: int) -> bytes:
+        off, n = self._frames[range(len(self._frames))[i]]
+        self._f.seek(off)
+        return self._f.read(n)
+
+    def __iter__(self):
+        for i in range(len(self._frames)):
+            yield self[i]
+
+    def close(self) -> None:
+        if self._f is not None:
+            self._f.close()
+            self._f = None
 
     def __enter__(self):
         return self

@@ -116,6 +116,56 @@ class POCOTester:
             self._jpeg = enc = JpegEncoder(self.device, max(H, enc.max_h if enc else 0), max(W, enc.max_w if enc else 0))
         return enc.encode(pic.contiguous(), int(getattr(self.args, "jpeg_quality", 90)))
 
+    # ---- --decode gpu ----------------------------------------------------------------------------------------------------
+    @property
+    def decode_on_gpu(self) -> bool:
+        return getattr(self.args, "decode", "host") == "gpu"
+
+    def to_device(self, frame) -> torch.Tensor:
+        """A frame as a uint8 [H,W,3] device tensor: decoded there already (--decode gpu) or uploaded."""
+        return frame if torch.is_tensor(frame) else torch.from_numpy(np.ascontiguousarray(frame)).to(self.device)
+
+    def decode_frames(self, named) -> list:
+        """named: [(name, the bytes of an image file)] -> the frames in order, all baseline JPEGs of the list decoded in ONE
+        device call (uint8 [H,W,3] device tensors, PIL's pixels).  A file parse_jpeg declines (.png, progressive ...) and an
+        image whose status word comes back non-zero go through PIL (host arrays); the latter is named in one warning, and so
+        is a file with more restart intervals than a decoder plans per image.  Any error of the decode call is raised.  The
+        decoder is created for the first batch's sizes and re-created when a larger one arrives."""
+        import io
+        import warnings
+        from PIL import Image
+        from .jpeg import SEGS_PER_IMAGE, JpegDecoder, parse_jpeg
+        out = [None] * len(named)
+        infos = [parse_jpeg(b) if b[:2] == b"\xff\xd8" else None for _, b in named]
+        many = [i for i, f in enumerate(infos) if f is not None and len(f.segments) > SEGS_PER_IMAGE]
+        if many:                       # checked here, so that every error of the decode call below is a real one and is raised
+            warnings.warn(f"--decode gpu: {', '.join(named[i][0] for i in many)}: more than {SEGS_PER_IMAGE} restart intervals, "
+                          "which the device decoder does not plan for; decoding with PIL")
+            for i in many:
+                infos[i] = None
+        idx = [i for i, f in enumerate(infos) if f is not None]
+        for lo in range(0, len(idx), max(1, self.model.max_batch)):
+            part = idx[lo:lo + max(1, self.model.max_batch)]
+            H, W = max(infos[i].height for i in part), max(infos[i].width for i in part)
+            nbytes = sum(infos[i].scan_length + 16 for i in part)
+            dec = getattr(self, "_jdec", None)
+            if dec is None or H > dec.max_h or W > dec.max_w or len(part) > dec.max_batch or nbytes > dec.max_bytes:
+                old = (dec.max_h, dec.max_w, dec.max_bytes) if dec else (0, 0, 0)
+                if dec is not None:
+                    dec.close()
+                self._jdec = dec = JpegDecoder(self.device, max(H, old[0]), max(W, old[1]), max(1, self.model.max_batch),
+                                               max(2 * nbytes, old[2], 1 << 20))
+            tensors, status = dec.decode([infos[i] for i in part], return_status=True)
+            for i, t, st in zip(part, tensors, status):
+                if st == 0:
+                    out[i] = t
+                else:
+                    warnings.warn(f"--decode gpu: {named[i][0]} is damaged (status {st}); decoding it with PIL")
+        for i, (_, b) in enumerate(named):
+            if out[i] is None:
+                out[i] = np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))
+        return out
+
     def _save_meshes(self, folder: str, verts: np.ndarray, names):
         from .postproc import write_obj
         for v, n in zip(verts, names):
@@ -198,7 +248,7 @@ class POCOTester:
             e = {"dets": raw, "W": frame.shape[1], "H": frame.shape[0], "parts": [], "todo": len(raw), "frame": None}
             queue.append(e)
             if len(raw):
-                fr = torch.from_numpy(np.ascontiguousarray(frame)).to(self.device)
+                fr = self.to_device(frame)
                 if keep_frames:
                     e["frame"] = fr
                 lo = 0
@@ -260,7 +310,8 @@ class POCOTester:
             j = i
             while j < len(items) and items[j][0] == f:
                 j += 1
-            fr = torch.from_numpy(np.ascontiguousarray(get(f))).to(self.device, non_blocking=True)
+            fr = get(f)
+            fr = fr if torch.is_tensor(fr) else torch.from_numpy(np.ascontiguousarray(fr)).to(self.device, non_blocking=True)
             group = items[i:j]
             while group:                     # a frame with more people than fit goes out in pieces
                 room = bs - len(pend_meta)
@@ -325,7 +376,12 @@ class POCOTester:
         ahead = max(4, self.model.max_batch)
         ahead_bytes = 256 << 20
 
+        on_gpu = self.decode_on_gpu
+
         def decode(n):
+            if on_gpu:                                   # the file's bytes: decoded per batch on the device (decode_frames)
+                with open(os.path.join(image_folder, n), "rb") as f:
+                    return f.read()
             return np.asarray(Image.open(os.path.join(image_folder, n)).convert("RGB"))
 
         def dets_of(pos, n, img):
@@ -371,10 +427,18 @@ class POCOTester:
                             q.append((nxt[0], nxt[1], dec_pool.submit(decode, nxt[1])))
 
                 fill()
-                while q:
-                    pos, n, fut = q.popleft()
-                    img = fut.result()
-                    ahead = max(4, min(ahead, ahead_bytes // max(1, img.nbytes)))       # big images: fewer of them decoded ahead
+                ready = deque()                      # --decode gpu: (pos, name, frame) of the batch decoded last
+                while q or ready:
+                    if on_gpu and not ready:
+                        group = [q.popleft() for _ in range(min(len(q), max(1, self.model.max_batch)))]
+                        frames = self.decode_frames([(n, fut.result()) for _, n, fut in group])
+                        ready.extend((pos, n, fr) for (pos, n, _), fr in zip(group, frames))
+                    if on_gpu:
+                        pos, n, img = ready.popleft()
+                    else:
+                        pos, n, fut = q.popleft()
+                        img = fut.result()
+                    ahead = max(4, min(ahead, ahead_bytes // max(1, img.shape[0] * img.shape[1] * 3)))   # big images: fewer of them decoded ahead
                     fill()
                     d = dets_of(pos, n, img)
                     counts.append(len(d))
@@ -406,13 +470,33 @@ class POCOTester:
 
 
 def _run_on_video_folder(self, frame_folder: str, tracking_path: Optional[str], output_path: str, bbox_scale=1.0):
-    """demo.py --mode video on a folder of extracted frames (demo.py:60-160): per-track results written as
-    <output>/poco_results.npz (the reference joblib-dumps the same dict, demo.py:147-150)."""
+    """demo.py --mode video on a folder of extracted frames or a Motion-JPEG .avi (demo.py:60-160): per-track results written
+    as <output>/poco_results.npz (the reference joblib-dumps the same dict, demo.py:147-150)."""
+    if os.path.isfile(frame_folder):
+        from .jpeg import MjpegReader
+        with MjpegReader(frame_folder) as reader:
+            return _run_on_frames(self, frame_folder, tracking_path, output_path, bbox_scale, reader)
+    return _run_on_frames(self, frame_folder, tracking_path, output_path, bbox_scale, None)
+
+
+def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output_path: str, bbox_scale, reader):
+    import io
     from PIL import Image
-    names = sorted(x for x in os.listdir(frame_folder) if x.lower().endswith(IMG_EXT))
+    if reader is not None:                             # a Motion-JPEG .avi: frames named as the reference's ffmpeg extraction names them
+        names = [f"{i + 1:06d}.jpg" for i in range(len(reader))]
+        read = lambda i: reader[i]                                                                 # noqa: E731
+    else:
+        names = sorted(x for x in os.listdir(frame_folder) if x.lower().endswith(IMG_EXT))
+
+        def read(i):
+            with open(os.path.join(frame_folder, names[i]), "rb") as f:
+                return f.read()
     if not names:
         raise FileNotFoundError(f"no frames in {frame_folder}")
-    first = np.asarray(Image.open(os.path.join(frame_folder, names[0])).convert("RGB"))
+    if reader is not None:
+        first = np.asarray(Image.open(io.BytesIO(read(0))).convert("RGB"))
+    else:
+        first = np.asarray(Image.open(os.path.join(frame_folder, names[0])).convert("RGB"))
     H, W = first.shape[:2]
     if tracking_path:
         tracking = load_tracking(tracking_path)
@@ -423,7 +507,12 @@ def _run_on_video_folder(self, frame_folder: str, tracking_path: Optional[str], 
     skip = max(int(getattr(self.args, "skip_frame", 1)), 1)
     if skip > 1:
         tracking = {k: {"bbox": v["bbox"][::skip], "frames": v["frames"][::skip]} for k, v in tracking.items()}
-    load = lambda i: np.asarray(Image.open(os.path.join(frame_folder, names[i])).convert("RGB"))   # noqa: E731
+    if self.decode_on_gpu:
+        load = lambda i: self.decode_frames([(names[i], read(i))])[0]                              # noqa: E731
+    elif reader is not None:
+        load = lambda i: np.asarray(Image.open(io.BytesIO(read(i))).convert("RGB"))                # noqa: E731
+    else:
+        load = lambda i: np.asarray(Image.open(os.path.join(frame_folder, names[i])).convert("RGB"))   # noqa: E731
     import torch.distributed as tdist
     world = tdist.get_world_size() if tdist.is_available() and tdist.is_initialized() else 1
     rank = tdist.get_rank() if world > 1 else 0
@@ -537,7 +626,7 @@ def _render_video(self, results: dict, frame_folder: str, names, load, output_pa
     with ThreadPoolExecutor(max(1, min(8, (os.cpu_count() or 2) // 2))) as pool:
         writes = []
         for fi, name in enumerate(names):
-            fr = torch.from_numpy(np.ascontiguousarray(load(fi))).to(self.device)
+            fr = self.to_device(load(fi))
             people = per_frame[fi]
             if people:
                 cams = np.stack([results[pid]["orig_cam"][k] for pid, k in people])
@@ -555,7 +644,8 @@ def _render_video(self, results: dict, frame_folder: str, names, load, output_pa
             if getattr(self.args, "save_video", False):
                 if video is None:
                     from .jpeg import MjpegWriter
-                    avi = os.path.basename(os.path.normpath(frame_folder)) + "_poco_result.avi"
+                    avi = os.path.basename(os.path.normpath(frame_folder))
+                    avi = (os.path.splitext(avi)[0] if os.path.isfile(frame_folder) else avi) + "_poco_result.avi"
                     video = MjpegWriter(os.path.join(output_path, avi), int(pic.shape[1]), int(pic.shape[0]),
                                         float(getattr(self.args, "fps", 30.0)))
                 video.add(data)
