@@ -9,7 +9,7 @@ tracker are third-party and out of scope: person boxes come from
 --detections (json {image name: [[cx,cy,w,h],...]}, the format multi_person_tracker produces) or
 default to one centred box; results are written as .npz.  --render (opt-in; the reference renders by default) draws the
 uncertainty-coloured meshes on the GPU (poco_amd/render.py) into the PNGs the reference writes; --image_format jpg encodes them on
-the GPU instead (poco_amd/jpeg.py) and --save_video adds the result video as a Motion-JPEG .avi (the reference's ffmpeg step).
+the GPU instead (poco_amd/jpeg.py), --encode gpu compresses the PNGs on the GPU (poco_amd/png.py) and --save_video adds the result video as a Motion-JPEG .avi (the reference's ffmpeg step).
 --mode video expects --vid_file to be a folder of extracted frames (the reference shells out to
 ffmpeg first, demo.py:71; ffmpeg/cv2 are not part of this image) or a Motion-JPEG .avi, which is read frame by frame
 (poco_amd/jpeg.py MjpegReader).  --decode gpu decodes baseline .jpg input on the GPU (poco_amd/jpeg.py JpegDecoder): the file's
@@ -44,6 +44,11 @@ def parse_args(argv=None):
     p.add_argument("--image_format", default="png", choices=["png", "jpg"],
                    help="with --render: format of the per-frame pictures; jpg is encoded on the GPU (baseline JPEG, 4:2:0) and only "
                         "its bytes are copied to the host")
+    p.add_argument("--encode", default="host", choices=["host", "gpu"],
+                   help="with --render --image_format png: where the pictures are compressed: host = PIL on a thread pool; gpu = "
+                        "filtered and deflated on the GPU (poco_amd/png.py: lossless, the same pixels, other bytes), only the "
+                        "file's bytes are copied to the host.  --image_format jpg is always encoded on the GPU and does not look "
+                        "at this flag; without --render there is nothing to encode")
     p.add_argument("--jpeg_quality", type=int, default=90, help="quality 1..100 of --image_format jpg and --save_video")
     p.add_argument("--save_video", action="store_true",
                    help="video mode with --render: also write <out>/<frame folder>_poco_result.avi (Motion-JPEG, --fps)")

@@ -455,6 +455,45 @@ int poco_jpeg_decoder_create(int max_h, int max_w, int max_batch, size_t max_byt
 int poco_jpeg_decode(poco_jpeg_decoder_t dec, const poco_jpeg_image* imgs, int n, int* d_status, void* stream);
 void poco_jpeg_decoder_destroy(poco_jpeg_decoder_t dec);
 
+/* ---- PNG encoder: the demo's rendered frames as PNG, filtered and deflated where they are --------------------------------------
+ * Replaces the host-side cv2.imwrite(... '%06d.png') of pocolib/core/tester.py:350 and :572; csrc/png_enc.hip.  Takes a uint8
+ * [H,W,3] RGB device frame, leaves the bytes of a .png file on the device: lossless, and byte for byte a function of the frame
+ * (tests/png_np.py restates every byte in numpy).
+ *   Container: the 8-byte signature, IHDR (W, H, bit depth 8, colour type 2, compression 0, filter 0, interlace 0), one IDAT
+ *     chunk per segment, IEND; nothing else.  The first IDAT also carries the zlib header 78 01, the last the big-endian Adler-32
+ *     of the filtered stream; every chunk carries the CRC-32 of its type and data.
+ *   Row filters: every row gets the one of the five PNG filter types (bpp 3) with the smallest sum of |signed byte| (v < 128 ?
+ *     v : 256 - v: libpng's heuristic), ties to the lowest type; the row above the first is zeros.  Filtered stream: H x (1 + 3W).
+ *   Segments: the stream is cut every 32 768 bytes regardless of rows; each segment is coded on its own - no match reaches out
+ *     of it, it has its own Huffman tables - as one deflate block with BFINAL 0, followed by an empty stored block (000, pad to
+ *     the byte, 00 00 FF FF; BFINAL 1 after the last segment), so every segment starts on a byte boundary.  A segment of n bytes
+ *     whose dynamic block would be longer than 5 + n bytes is one stored block instead.
+ *   LZ77: position p has the candidates p - 3, p - (1 + 3W) where that is inside the segment, and the largest q < p - p % 1024
+ *     with hash(q) = hash(p), hash(x) = (le32(s[x .. x+4)) * 2654435761 mod 2^32) >> 19 for x + 4 <= n (a table of positions
+ *     filled chunk by chunk of 1024 positions, a chunk seeing the chunks before it).  A candidate's length is the number of equal
+ *     bytes, at most min(258, n - p); the longest wins, ties to the smallest distance; below 3 there is no match.  The parse is
+ *     greedy from the segment's start.  Every token is a function of the segment's bytes alone.
+ *   Huffman: 286 literal/length and 30 distance symbols, at most 15 bits.  Symbols with a non-zero count (end-of-block counts
+ *     once; a distance histogram with fewer than two non-zero counts has symbols 0 and 1 raised to 1) are sorted by (count,
+ *     symbol) and merged with two queues, the leaf first on equal weight.  Depths above 15 count as 15 and, while the Kraft sum
+ *     exceeds 1, count[15] -= 1, the longest shorter length l in use gives count[l] -= 1, count[l+1] += 2.  Lengths are handed
+ *     out by rank (the rarest symbols the longest), codes are canonical.  Block header: HLIT 286, HDIST 30, HCLEN 19; the
+ *     code-length code is fixed and complete (lengths 0..12 in 4 bits, 13..18 in 5); all 316 lengths are sent literally.
+ *   Size bound: a segment of n bytes takes at most n + 10 bytes, its chunk 12 more, so
+ *     worst case(H, W) = 51 + S + 22 x ceil(S / 32768) bytes, S = H x (1 + 3W).  The scratch planned at create and the caller's
+ *     out_cap are held to it: overflow cannot happen and is not a status code. */
+typedef struct poco_png_encoder* poco_png_encoder_t;
+/* The filtered stream, worst-case segment slots, lengths and Adler sums for frames up to max_h x max_w (1 .. 16384 each, else
+ * POCO_ERR_ARG without touching the GPU).  Needs the GPU after validation. */
+int poco_png_encoder_create(int max_h, int max_w, poco_png_encoder_t* out);
+/* d_rgb uint8 [H,W,3] (any alignment) -> d_out[0 .. *d_len): three launches on `stream` - row filters, segment coding (the
+ * segment staged in LDS), compaction with Adler combine and CRCs - with no allocation, no synchronisation and no global atomics;
+ * nothing outside d_out[0 .. *d_len) and the word d_len is written.  POCO_ERR_ARG before any GPU work: a null handle or pointer,
+ * H or W < 1 or above the created maximum, out_cap below worst case(H, W).  One encoder is used from one stream at a time. */
+int poco_png_encode(poco_png_encoder_t enc, const unsigned char* d_rgb, int H, int W, unsigned char* d_out, size_t out_cap,
+                    unsigned int* d_len, void* stream);
+void poco_png_encoder_destroy(poco_png_encoder_t enc);
+
 /* ---- evaluator: MPJPE, PA-MPJPE, V2V and the uncertainty / pose-error correlation of eval.py ---------------------------------
  * Replaces the host side of pocolib/core/trainer.py:298-336 (validation_step) and :365-391 (validation_epoch_end):
  * get_jnts_from_mesh, mpjpe_error, pampjpe_error (one np.linalg.svd per crop, in Python), vert_error, calculate_distance_pose,

@@ -116,6 +116,24 @@ class POCOTester:
             self._jpeg = enc = JpegEncoder(self.device, max(H, enc.max_h if enc else 0), max(W, enc.max_w if enc else 0))
         return enc.encode(pic.contiguous(), int(getattr(self.args, "jpeg_quality", 90)))
 
+    # ---- --encode gpu --------------------------------------------------------------------------------------------------------
+    @property
+    def encode_on_gpu(self) -> bool:
+        return getattr(self.args, "encode", "host") == "gpu"
+
+    def encode_png(self, pic: torch.Tensor) -> bytes:
+        """The .png bytes of a device picture, filtered and deflated on the device (poco_amd/png.py): only the bytes cross to the
+        host.  The encoder is created for the first picture's size and re-created when a larger one arrives."""
+        from .png import PngEncoder
+        H, W = int(pic.shape[0]), int(pic.shape[1])
+        enc = getattr(self, "_png", None)
+        if enc is None or H > enc.max_h or W > enc.max_w:
+            old = (enc.max_h, enc.max_w) if enc else (0, 0)
+            if enc is not None:
+                enc.close()
+            self._png = enc = PngEncoder(self.device, max(H, old[0]), max(W, old[1]))
+        return enc.encode(pic.contiguous())
+
     # ---- --decode gpu ----------------------------------------------------------------------------------------------------
     @property
     def decode_on_gpu(self) -> bool:
@@ -456,6 +474,8 @@ class POCOTester:
                         stem = os.path.join(img_dir, os.path.splitext(n)[0])
                         if self.image_format == "jpg":
                             writes.append(wr_pool.submit(_write_bytes, stem + ".jpg", self.encode_jpeg(pic)))
+                        elif self.encode_on_gpu:
+                            writes.append(wr_pool.submit(_write_bytes, stem + ".png", self.encode_png(pic)))
                         else:
                             writes.append(wr_pool.submit(_write_png, stem + ".png", pic.cpu().numpy()))
                 while len(writes) > ahead:
@@ -607,7 +627,8 @@ def _write_bytes(path: str, data: bytes) -> None:
 def _render_video(self, results: dict, frame_folder: str, names, load, output_path: str) -> None:
     """render_results of tester.py:482-580: every frame of the folder with the people the tracks place in it, in ascending
     orig_cam[1] (demo_utils.py:307-313, ties in track order), black side canvas, <output>/tmp_images_output/%06d.png, and the
-    lines of <output>/uncertainty.log (tester.py:547-550).  --image_format jpg writes %06d.jpg, encoded on the device;
+    lines of <output>/uncertainty.log (tester.py:547-550).  --image_format jpg writes %06d.jpg, encoded on the device; --encode gpu
+    compresses the .png files on the device;
     --save_video adds <output>/<frame folder>_poco_result.avi (Motion-JPEG of the same pictures at --fps: the reference's
     images_to_video, demo.py:148-157)."""
     from concurrent.futures import ThreadPoolExecutor
@@ -651,6 +672,8 @@ def _render_video(self, results: dict, frame_folder: str, names, load, output_pa
                 video.add(data)
             if jpg:
                 writes.append(pool.submit(_write_bytes, os.path.join(out_dir, f"{fi:06d}.jpg"), data))
+            elif self.encode_on_gpu:
+                writes.append(pool.submit(_write_bytes, os.path.join(out_dir, f"{fi:06d}.png"), self.encode_png(pic)))
             else:
                 writes.append(pool.submit(_write_png, os.path.join(out_dir, f"{fi:06d}.png"), pic.cpu().numpy()))
             while len(writes) > 16:

@@ -6,7 +6,9 @@
 synthetic checkpoint) without and with --render (PNG encoding on the host included).
 --encode: instead of the renderer, the JPEG encoder (poco_jpeg_encode: transform, entropy, compaction) at 1920 x 1080 and at
 3840 x 1080 (--sideview) on a rendered frame and on a noise frame, device events around each call, median of --iters; with
---folder N the folder-mode wall time per image without --render and with --render as png and as jpg, without and with --sideview."""
+--folder N the folder-mode wall time per image without --render and with --render as png and as jpg, without and with --sideview.
+The PNG encoder (poco_png_encode) follows on the same frames, beside the host path it replaces (D2H copy + PIL to memory on one
+thread) and PIL's size, and with --folder N the wall time per image of --render --encode host and --encode gpu, 5 repeats each."""
 import argparse
 import json
 import sys
@@ -118,9 +120,38 @@ def encode(iters):
             print(json.dumps({"bench": "jpeg_encode", "frame": kind, "H": H, "W": w, "quality": q, "bytes": int(n.item()),
                               "ms_median": round(ms[len(ms) // 2], 4), "ms_min": round(ms[0], 4), "ms_max": round(ms[-1], 4),
                               "iters": iters}), flush=True)
+    # the PNG encoder on the same frames: the encode call (device events), the host path it replaces (D2H copy + PIL's encoder to
+    # memory, one thread, median of 5) and the two sizes
+    import io
+    import time
+    from PIL import Image
+    from poco_amd import png
+    penc = png.PngEncoder(dev, H, 2 * W)
+    pout = torch.empty(png.worst_case_bytes(H, 2 * W), dtype=torch.uint8, device=dev)
+    for kind, w, frame in (("rendered", W, smooth), ("rendered", 2 * W, rendered), ("noise", W, noise[:, :W].contiguous()),
+                           ("noise", 2 * W, noise)):
+        for _ in range(5):
+            penc.encode_into(frame, pout, n)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for e0, e1 in ev:
+            e0.record()
+            penc.encode_into(frame, pout, n)
+            e1.record()
+        torch.cuda.synchronize()
+        ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+        host = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            buf = io.BytesIO()
+            Image.fromarray(frame.cpu().numpy()).save(buf, "PNG")
+            host.append(1000 * (time.perf_counter() - t0))
+        print(json.dumps({"bench": "png_encode", "frame": kind, "H": H, "W": w, "bytes": int(n.item()), "pil_bytes": buf.tell(),
+                          "ms_median": round(ms[len(ms) // 2], 4), "ms_min": round(ms[0], 4), "ms_max": round(ms[-1], 4),
+                          "host_d2h_pil_ms_median": round(sorted(host)[2], 2), "iters": iters}), flush=True)
 
 
-def folder(n, flag_sets=([], ["--render"], ["--render", "--sideview"])):
+def folder(n, flag_sets=([], ["--render"], ["--render", "--sideview"]), repeats=1):
     import demo
     from PIL import Image
     from poco_amd import synth
@@ -143,9 +174,12 @@ def folder(n, flag_sets=([], ["--render"], ["--render", "--sideview"])):
                              "--smpl", str(tmp / "smpl.npz"), *extra])
         t = POCOTester(a)
         t.run_on_image_folder(str(imgs), None, str(tmp / "out"))          # warm-up (allocator, file cache)
-        st = t.run_on_image_folder(str(imgs), None, str(tmp / "out"))
-        print(json.dumps({"bench": "folder_render", "images": n, "H": 1080, "W": 1920, "flags": " ".join(extra) or "(none)",
-                          "ms_per_image": round(1000 * st["seconds"] / n, 2)}), flush=True)
+        runs = [1000 * t.run_on_image_folder(str(imgs), None, str(tmp / "out"))["seconds"] / n for _ in range(repeats)]
+        rec = {"bench": "folder_render", "images": n, "H": 1080, "W": 1920, "flags": " ".join(extra) or "(none)",
+               "ms_per_image": round(sorted(runs)[len(runs) // 2], 2)}
+        if repeats > 1:
+            rec.update(repeats=repeats, ms_per_image_min=round(min(runs), 2), ms_per_image_max=round(max(runs), 2))
+        print(json.dumps(rec), flush=True)
         del t
 
 
@@ -160,6 +194,8 @@ if __name__ == "__main__":
         if args.folder:
             jpg = ["--image_format", "jpg"]
             folder(args.folder, ([], ["--render"], ["--render", *jpg], ["--render", "--sideview"], ["--render", "--sideview", *jpg]))
+            # the PNG path on the host against the PNG path on the device: 5 repeats each, the spread is reported
+            folder(args.folder, (["--render", "--encode", "host"], ["--render", "--encode", "gpu"]), repeats=5)
     else:
         bench(args.iters)
         if args.folder:
