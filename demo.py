@@ -13,7 +13,9 @@ the GPU instead (poco_amd/jpeg.py), --encode gpu compresses the PNGs on the GPU 
 --mode video expects --vid_file to be a folder of extracted frames (the reference shells out to
 ffmpeg first, demo.py:71; ffmpeg/cv2 are not part of this image) or a Motion-JPEG .avi, which is read frame by frame
 (poco_amd/jpeg.py MjpegReader).  --decode gpu decodes baseline .jpg input on the GPU (poco_amd/jpeg.py JpegDecoder): the file's
-bytes cross PCIe instead of its pixels; other files go through PIL as with the default --decode host.
+bytes cross PCIe instead of its pixels; other files go through PIL as with the default --decode host.  --decode_png gpu does the
+same for .png input - what the reference's ffmpeg extraction and this demo's own --render write - with the device inflate and
+unfilter of poco_amd/png.py PngDecoder; the two flags are independent.
 """
 import argparse
 import json
@@ -31,6 +33,9 @@ def parse_args(argv=None):
     p.add_argument("--decode", default="host", choices=["host", "gpu"],
                    help="where input images are decoded: host = PIL on a thread pool; gpu = baseline .jpg files and Motion-JPEG "
                         "frames on the GPU, same pixels (anything else still goes through PIL)")
+    p.add_argument("--decode_png", default="host", choices=["host", "gpu"],
+                   help="where .png input is decoded: host = PIL; gpu = 8-bit non-interlaced .png files are inflated and unfiltered "
+                        "on the GPU, same pixels (anything else still goes through PIL); independent of --decode")
     p.add_argument("--image_folder", type=str, help="input image folder")
     p.add_argument("--output_folder", type=str, default="out", help="output folder to write results")
     p.add_argument("--batch_size", type=int, default=64, help="batch size of POCO")

@@ -494,6 +494,56 @@ int poco_png_encode(poco_png_encoder_t enc, const unsigned char* d_rgb, int H, i
                     unsigned int* d_len, void* stream);
 void poco_png_encoder_destroy(poco_png_encoder_t enc);
 
+/* ---- PNG decoder: PNG input frames inflated and unfiltered on the device -----------------------------------------------------------
+ * Replaces the host-side decode behind pocolib/core/tester.py:171 (cv2.imread + cvtColor per image of the folder) and :507
+ * (cv2.imread per frame of the result video) for .png files - what the reference's ffmpeg extraction writes (%06d.png,
+ * demo_utils.py:193); csrc/png_dec.hip, DESIGN.md 15.  Takes the IDAT payloads of up to max_batch parsed files (poco_amd/png.py
+ * parse_png walks the chunks and checks their CRCs on the host), leaves one uint8 [H,W,3] RGB picture per file on the device: the
+ * pixels of PIL's Image.open(f).convert("RGB"), restated in numpy by tests/pngdec_np.py.
+ *   Files: bit depth 8; colour type 0 (grey), 2 (RGB), 3 (palette), 4 (grey + alpha), 6 (RGBA); no interlace; sides 1 .. 16384.
+ *     Alpha is dropped, grey is replicated, a palette index reads the 256 x 3 table the caller pads with zeros.
+ *   Inflate: one workgroup per image.  One lane walks the symbols (the serial part) from an input ring in LDS, stores literals
+ *     into a 64 KiB output ring in LDS and queues matches as tokens; a second wave copies the matches of the batch before, in
+ *     order, each by 64 lanes (dist < len by the modulo), reading LDS only; two more waves flush finished bytes to the image's
+ *     filtered-stream scratch in whole dwords and refill the input ring.  The Huffman tables of a block are built in LDS by the
+ *     workgroup.  Stored, fixed and dynamic blocks, any window size.  The Adler-32 is NOT verified (the IDAT CRCs checked by
+ *     parse_png cover the same bytes).
+ *   Unfilter: one launch per band of 64 rows, one wave per image; lane r undoes row y0 + r one pixel behind lane r - 1 and takes
+ *     the pixel above from that lane.  The row above the first and the bpp bytes left of the first pixel are zeros; Average is
+ *     (left + up) >> 1 on the 9-bit sum; Paeth breaks ties in the order left, up, up-left.
+ *   Status: 0 only for a stream zlib's inflate accepts that yields exactly H x (1 + bpp x W) bytes with filter bytes 0 .. 4.
+ *     Non-zero: block type 3, LEN != ~NLEN, HLIT > 286, HDIST > 30, a repeat with nothing to repeat or past HLIT + HDIST, no
+ *     end-of-block code, an over-subscribed or incomplete code set (a single code of one bit excepted), literal/length symbols
+ *     286 / 287, distance symbols 30 / 31, a distance beyond the bytes produced, input exhausted, another output size, a filter
+ *     byte above 4.  The pixels of such an image are unspecified; the other images of the call are decoded.
+ *   Safety: every stream read is clamped to the stream, every LDS index masked, every store compared with the image's scratch
+ *     or its 3HW output bytes; every loop is bounded by a constant or a count validated on the host. */
+typedef struct poco_png_decoder* poco_png_decoder_t;
+/* One parsed file (all pointers on the host except d_rgb). */
+typedef struct poco_png_image {
+  const unsigned char* data;      /* the file's bytes */
+  size_t nbytes;
+  const unsigned int* idat;       /* [nidat][2]: offset into data and length of every IDAT payload, in file order */
+  int nidat;
+  int H, W, colour_type;          /* colour_type 0, 2, 3, 4 or 6 */
+  unsigned char palette[768];     /* PLTE, padded with zeros (colour type 3) */
+  unsigned char* d_rgb;           /* device: receives H * W * 3 bytes, any alignment */
+} poco_png_image;
+/* Device scratch (the filtered streams at 1 + 4 W bytes per row, two carry rows per image) and one pinned staging buffer for up to
+ * max_batch images of up to max_h x max_w (1 .. 16384 each) whose deflate streams add up to at most max_bytes per call;
+ * POCO_ERR_ARG without touching the GPU for sizes outside that, max_batch outside 1 .. 4096 or max_bytes outside 1 .. 2^30. */
+int poco_png_decoder_create(int max_h, int max_w, int max_batch, size_t max_bytes, poco_png_decoder_t* out);
+/* Decode imgs[0 .. n) in one call: the IDAT payloads of each image are copied end to end into the staging buffer, without chunk
+ * framing, zlib header or Adler-32, each stream padded by 16 bytes, with the palettes and one descriptor per image; one
+ * host-to-device copy, one memset and 1 + ceil(max H / 64) launches on `stream`; no allocation, no global atomics.  d_status int32
+ * [n] on the device receives 0 or the non-zero status above; nothing outside the n pictures and d_status is written.  The only
+ * host wait is for the previous call's copy out of the staging buffer.  POCO_ERR_ARG before any GPU work: null handle or
+ * pointer, n outside 1 .. max_batch, a size outside the created maximum, a colour type outside {0, 2, 3, 4, 6}, an IDAT payload
+ * outside the file or fewer than 6 payload bytes, or more stream bytes than max_bytes.  One decoder is used from one stream at a
+ * time. */
+int poco_png_decode(poco_png_decoder_t dec, const poco_png_image* imgs, int n, int* d_status, void* stream);
+void poco_png_decoder_destroy(poco_png_decoder_t dec);
+
 /* ---- evaluator: MPJPE, PA-MPJPE, V2V and the uncertainty / pose-error correlation of eval.py ---------------------------------
  * Replaces the host side of pocolib/core/trainer.py:298-336 (validation_step) and :365-391 (validation_epoch_end):
  * get_jnts_from_mesh, mpjpe_error, pampjpe_error (one np.linalg.svd per crop, in Python), vert_error, calculate_distance_pose,

@@ -134,51 +134,69 @@ class POCOTester:
             self._png = enc = PngEncoder(self.device, max(H, old[0]), max(W, old[1]))
         return enc.encode(pic.contiguous())
 
-    # ---- --decode gpu ----------------------------------------------------------------------------------------------------
+    # ---- --decode gpu / --decode_png gpu -----------------------------------------------------------------------------------
     @property
     def decode_on_gpu(self) -> bool:
         return getattr(self.args, "decode", "host") == "gpu"
 
+    @property
+    def decode_png_on_gpu(self) -> bool:
+        return getattr(self.args, "decode_png", "host") == "gpu"
+
     def to_device(self, frame) -> torch.Tensor:
-        """A frame as a uint8 [H,W,3] device tensor: decoded there already (--decode gpu) or uploaded."""
+        """A frame as a uint8 [H,W,3] device tensor: decoded there already (--decode gpu, --decode_png gpu) or uploaded."""
         return frame if torch.is_tensor(frame) else torch.from_numpy(np.ascontiguousarray(frame)).to(self.device)
 
-    def decode_frames(self, named) -> list:
-        """named: [(name, the bytes of an image file)] -> the frames in order, all baseline JPEGs of the list decoded in ONE
-        device call (uint8 [H,W,3] device tensors, PIL's pixels).  A file parse_jpeg declines (.png, progressive ...) and an
-        image whose status word comes back non-zero go through PIL (host arrays); the latter is named in one warning, and so
-        is a file with more restart intervals than a decoder plans per image.  Any error of the decode call is raised.  The
-        decoder is created for the first batch's sizes and re-created when a larger one arrives."""
-        import io
+    def _device_decode(self, named, out, infos, attr, cls, flag, nbytes_of):
+        """One device call per batch of at most max_batch parsed files of one format: out[i] becomes a device tensor where the
+        status word is 0; a damaged file is named in one warning and left to PIL.  The decoder (self.<attr>) is created for the
+        first batch's sizes and re-created when a larger one arrives."""
         import warnings
-        from PIL import Image
-        from .jpeg import SEGS_PER_IMAGE, JpegDecoder, parse_jpeg
-        out = [None] * len(named)
-        infos = [parse_jpeg(b) if b[:2] == b"\xff\xd8" else None for _, b in named]
-        many = [i for i, f in enumerate(infos) if f is not None and len(f.segments) > SEGS_PER_IMAGE]
-        if many:                       # checked here, so that every error of the decode call below is a real one and is raised
-            warnings.warn(f"--decode gpu: {', '.join(named[i][0] for i in many)}: more than {SEGS_PER_IMAGE} restart intervals, "
-                          "which the device decoder does not plan for; decoding with PIL")
-            for i in many:
-                infos[i] = None
         idx = [i for i, f in enumerate(infos) if f is not None]
         for lo in range(0, len(idx), max(1, self.model.max_batch)):
             part = idx[lo:lo + max(1, self.model.max_batch)]
             H, W = max(infos[i].height for i in part), max(infos[i].width for i in part)
-            nbytes = sum(infos[i].scan_length + 16 for i in part)
-            dec = getattr(self, "_jdec", None)
+            nbytes = sum(nbytes_of(infos[i]) + 32 for i in part)
+            dec = getattr(self, attr, None)
             if dec is None or H > dec.max_h or W > dec.max_w or len(part) > dec.max_batch or nbytes > dec.max_bytes:
                 old = (dec.max_h, dec.max_w, dec.max_bytes) if dec else (0, 0, 0)
                 if dec is not None:
                     dec.close()
-                self._jdec = dec = JpegDecoder(self.device, max(H, old[0]), max(W, old[1]), max(1, self.model.max_batch),
-                                               max(2 * nbytes, old[2], 1 << 20))
+                dec = cls(self.device, max(H, old[0]), max(W, old[1]), max(1, self.model.max_batch), max(2 * nbytes, old[2], 1 << 20))
+                setattr(self, attr, dec)
             tensors, status = dec.decode([infos[i] for i in part], return_status=True)
             for i, t, st in zip(part, tensors, status):
                 if st == 0:
                     out[i] = t
                 else:
-                    warnings.warn(f"--decode gpu: {named[i][0]} is damaged (status {st}); decoding it with PIL")
+                    warnings.warn(f"{flag}: {named[i][0]} is damaged (status {st}); decoding it with PIL")
+
+    def decode_frames(self, named) -> list:
+        """named: [(name, the bytes of an image file)] -> the frames in order, routed by signature: with --decode gpu all baseline
+        JPEGs of the list are decoded in ONE device call, with --decode_png gpu all PNGs parse_png accepts in another (uint8
+        [H,W,3] device tensors, PIL's pixels).  A file the parser declines (progressive JPEG, 16-bit or interlaced PNG ...), a
+        format whose flag is not set and an image whose status word comes back non-zero go through PIL (host arrays); the
+        latter is named in one warning, and so is a JPEG with more restart intervals than a decoder plans per image.  Any error
+        of a decode call is raised.  The decoders are created for the first batch's sizes and re-created when a larger one
+        arrives."""
+        import io
+        import warnings
+        from PIL import Image
+        out = [None] * len(named)
+        if self.decode_on_gpu:
+            from .jpeg import SEGS_PER_IMAGE, JpegDecoder, parse_jpeg
+            infos = [parse_jpeg(b) if b[:2] == b"\xff\xd8" else None for _, b in named]
+            many = [i for i, f in enumerate(infos) if f is not None and len(f.segments) > SEGS_PER_IMAGE]
+            if many:                   # checked here, so that every error of the decode call below is a real one and is raised
+                warnings.warn(f"--decode gpu: {', '.join(named[i][0] for i in many)}: more than {SEGS_PER_IMAGE} restart intervals, "
+                              "which the device decoder does not plan for; decoding with PIL")
+                for i in many:
+                    infos[i] = None
+            self._device_decode(named, out, infos, "_jdec", JpegDecoder, "--decode gpu", lambda f: f.scan_length)
+        if self.decode_png_on_gpu:
+            from .png import SIGNATURE, PngDecoder, parse_png
+            infos = [parse_png(b) if b[:8] == SIGNATURE else None for _, b in named]
+            self._device_decode(named, out, infos, "_pdec", PngDecoder, "--decode_png gpu", lambda f: f.stream_length)
         for i, (_, b) in enumerate(named):
             if out[i] is None:
                 out[i] = np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))
@@ -394,10 +412,10 @@ class POCOTester:
         ahead = max(4, self.model.max_batch)
         ahead_bytes = 256 << 20
 
-        on_gpu = self.decode_on_gpu
+        on_gpu = self.decode_on_gpu or self.decode_png_on_gpu
 
         def decode(n):
-            if on_gpu:                                   # the file's bytes: decoded per batch on the device (decode_frames)
+            if on_gpu:                                   # the file's bytes: routed and decoded per batch (decode_frames)
                 with open(os.path.join(image_folder, n), "rb") as f:
                     return f.read()
             return np.asarray(Image.open(os.path.join(image_folder, n)).convert("RGB"))
@@ -445,7 +463,7 @@ class POCOTester:
                             q.append((nxt[0], nxt[1], dec_pool.submit(decode, nxt[1])))
 
                 fill()
-                ready = deque()                      # --decode gpu: (pos, name, frame) of the batch decoded last
+                ready = deque()                      # --decode gpu / --decode_png gpu: (pos, name, frame) of the batch decoded last
                 while q or ready:
                     if on_gpu and not ready:
                         group = [q.popleft() for _ in range(min(len(q), max(1, self.model.max_batch)))]
@@ -499,6 +517,31 @@ def _run_on_video_folder(self, frame_folder: str, tracking_path: Optional[str], 
     return _run_on_frames(self, frame_folder, tracking_path, output_path, bbox_scale, None)
 
 
+class _GroupLoader:
+    """load(i) of video mode when frames are decoded on the device.  One workgroup per image (PNG) or a handful of small launches
+    (JPEG) leave a frame-by-frame call with most of the device idle, and the frames a pass will read are known before it starts
+    (plan): on a miss, frame i is decoded together with the next wanted frames in ONE decode_frames call - at most batch_size
+    frames and at most 256 MiB of decoded pixels.  A group is dropped when the next one is made."""
+
+    def __init__(self, tester, names, read, H: int, W: int):
+        self.tester, self.names, self.read = tester, names, read
+        self.limit = max(1, min(max(1, tester.model.max_batch), (256 << 20) // max(1, H * W * 3)))
+        self.wanted, self.group = [], {}
+
+    def plan(self, frames) -> None:
+        self.wanted, self.group = [int(f) for f in frames if 0 <= int(f) < len(self.names)], {}
+
+    def __call__(self, i: int):
+        i = int(i)
+        if i not in self.group:
+            import bisect
+            k = bisect.bisect_left(self.wanted, i)
+            ids = [i] + [f for f in self.wanted[k:k + self.limit] if f != i][:self.limit - 1]
+            frames = self.tester.decode_frames([(self.names[f], self.read(f)) for f in ids])
+            self.group = dict(zip(ids, frames))
+        return self.group[i]
+
+
 def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output_path: str, bbox_scale, reader):
     import io
     from PIL import Image
@@ -527,8 +570,8 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
     skip = max(int(getattr(self.args, "skip_frame", 1)), 1)
     if skip > 1:
         tracking = {k: {"bbox": v["bbox"][::skip], "frames": v["frames"][::skip]} for k, v in tracking.items()}
-    if self.decode_on_gpu:
-        load = lambda i: self.decode_frames([(names[i], read(i))])[0]                              # noqa: E731
+    if self.decode_on_gpu or self.decode_png_on_gpu:
+        load = _GroupLoader(self, names, read, H, W)
     elif reader is not None:
         load = lambda i: np.asarray(Image.open(io.BytesIO(read(i))).convert("RGB"))                # noqa: E731
     else:
@@ -544,9 +587,13 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
         # - the writer - re-derives the meshes of the tracks regressed elsewhere
         from . import dist as pdist
         mine = pdist.shard_tracks(tracking, rank, world)
+        if isinstance(load, _GroupLoader):
+            load.plan(sorted({int(f) for v in mine.values() for f in v["frames"]}))
         raw = self.run_on_video(mine, load, W, H, bbox_scale, raw=True) if mine else {}
         results = self._merge_rank_results(raw, tracking, W, H)
     else:
+        if isinstance(load, _GroupLoader):
+            load.plan(sorted({int(f) for v in tracking.values() for f in v["frames"]}))
         results = self.run_on_video(tracking, load, W, H, bbox_scale)
     torch.cuda.synchronize()
     dt = time.time() - t0
@@ -562,6 +609,8 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
                 sub = f"{int(pid):04d}" if str(pid).lstrip("-").isdigit() else str(pid)
                 self._save_meshes(os.path.join(output_path, "meshes", sub), r["verts"], [f"{int(f):06d}" for f in r["frame_ids"]])
         if self.render_on:                                             # demo.py:147-150 -> tester.py:482-580, rank 0 only
+            if isinstance(load, _GroupLoader):
+                load.plan(list(range(len(names))))
             self._render_video(results, frame_folder, names, load, output_path)
     finally:
         if world > 1:               # the other ranks wait here: release them also when the write fails

@@ -5,7 +5,12 @@ on a thread pool of the tester's size plus the pinned upload.  One JSON line per
 
     python tools/bench_decode.py [--iters 50] [--folder 16]
 Every case runs in a child process of its own under a time limit, so a case that hangs ends alone.
---folder N: also the folder-mode wall time per image of demo.py on N synthetic 1080p .jpg images with --decode host and --decode gpu."""
+--folder N: also the folder-mode wall time per image of demo.py on N synthetic 1080p .jpg images with --decode host and --decode gpu.
+
+    python tools/bench_decode.py --png [--folder 16]
+The PNG decoder (poco_png_decode: one copy, inflate, unfilter) instead, 5 repeats per case, against PIL decode on 16 threads plus
+the upload; the files are a photo-like frame saved by PIL at its default level and the same frame from this project's PngEncoder.
+Writes profiles/decode_png.txt; --folder N times folder mode with and without --decode_png gpu."""
 import argparse
 import io
 import json
@@ -89,7 +94,58 @@ def case(kind, restart, n, iters):
             "host_pil_upload_ms_median": round(hs[len(hs) // 2], 3), "host_threads": POOL, "iters": iters}
 
 
-def folder(n):
+PNG_REPEATS, PNG_POOL = 5, 16
+
+
+def png_case(source, n):
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from poco_amd import png
+    dev = torch.device("cuda:0")
+    frame = picture("photo")
+    if source == "pil":
+        buf = io.BytesIO()
+        Image.fromarray(frame).save(buf, "PNG")
+        data = buf.getvalue()
+    else:
+        data = png.PngEncoder(dev, H, W).encode(torch.from_numpy(frame).to(dev))
+    info = png.parse_png(data)
+    dec = png.PngDecoder(dev, H, W, max_batch=n, max_bytes=min(1 << 30, n * (len(data) + 4096)))
+    outs = [torch.empty(H, W, 3, dtype=torch.uint8, device=dev) for _ in range(n)]
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    dec.decode_into([info] * n, outs, status)
+    torch.cuda.synchronize()
+    assert status.cpu().tolist() == [0] * n
+    assert np.array_equal(outs[-1].cpu().numpy(), frame), "device pixels differ from the frame"
+    ms = []
+    for _ in range(PNG_REPEATS):           # wall time of the call as the demo makes it: bytes in, pixels on the device
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dec.decode_into([info] * n, outs, status)
+        torch.cuda.synchronize()
+        ms.append(1000 * (time.perf_counter() - t0))
+    pinned = [torch.empty(H, W, 3, dtype=torch.uint8).pin_memory() for _ in range(n)]
+
+    def host(i):
+        pinned[i].numpy()[...] = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+
+    hs = []
+    with ThreadPoolExecutor(PNG_POOL) as pool:
+        list(pool.map(host, range(n)))
+        for _ in range(PNG_REPEATS):
+            t0 = time.perf_counter()
+            list(pool.map(host, range(n)))
+            for i in range(n):
+                outs[i].copy_(pinned[i], non_blocking=True)
+            torch.cuda.synchronize()
+            hs.append(1000 * (time.perf_counter() - t0))
+    return {"bench": "png_decode", "source": source, "images": n, "H": H, "W": W, "bytes": len(data),
+            "gpu_ms": [round(v, 3) for v in ms], "host_pil_upload_ms": [round(v, 3) for v in hs], "host_threads": PNG_POOL,
+            "gpu_worst_below_host_best": max(ms) < min(hs)}
+
+
+def folder(n, png=False):
     import torch
     import demo
     from poco_amd import synth
@@ -101,18 +157,25 @@ def folder(n):
     np.savez(tmp / "smpl.npz", **synth.synth_smpl(7))
     imgs = tmp / "imgs"
     imgs.mkdir()
-    data = stream("photo", False)
+    if png:
+        from PIL import Image
+        buf = io.BytesIO()
+        Image.fromarray(picture("photo")).save(buf, "PNG")
+        data = buf.getvalue()
+    else:
+        data = stream("photo", False)
     for i in range(n):
-        (imgs / f"im{i:05d}.jpg").write_bytes(data)
+        (imgs / (f"im{i:05d}.png" if png else f"im{i:05d}.jpg")).write_bytes(data)
     out = []
     for mode in ("host", "gpu"):
         a = demo.parse_args(["--cfg", "configs/demo_poco_cliff_resnet50.yaml", "--ckpt", str(tmp / "ckpt.pt"), "--mode", "folder",
                              "--image_folder", str(imgs), "--output_folder", str(tmp / "out"), "--batch_size", "16",
-                             "--smpl", str(tmp / "smpl.npz"), "--decode", mode])
+                             "--smpl", str(tmp / "smpl.npz"), "--decode_png" if png else "--decode", mode])
         t = POCOTester(a)
         t.run_on_image_folder(str(imgs), None, str(tmp / "out"))          # warm-up (allocator, file cache)
         st = t.run_on_image_folder(str(imgs), None, str(tmp / "out"))
-        out.append({"bench": "folder_decode", "images": n, "H": H, "W": W, "decode": mode, "ms_per_image": round(1000 * st["seconds"] / n, 2)})
+        out.append({"bench": "folder_decode_png" if png else "folder_decode", "images": n, "H": H, "W": W, "decode": mode,
+                    "ms_per_image": round(1000 * st["seconds"] / n, 2)})
         del t
     return out
 
@@ -121,26 +184,34 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--folder", type=int, default=0)
+    ap.add_argument("--png", action="store_true", help="the PNG decoder's cases instead of the JPEG decoder's")
     ap.add_argument("--case", default=None, help="(internal) kind,restart,n | folder,N: run one case in this process")
     ap.add_argument("--limit", type=int, default=240, help="seconds per case")
     args = ap.parse_args()
     if args.case:
         parts = args.case.split(",")
-        res = folder(int(parts[1])) if parts[0] == "folder" else [case(parts[0], parts[1] == "1", int(parts[2]), args.iters)]
+        if parts[0] == "png":
+            res = [png_case(parts[1], int(parts[2]))]
+        elif parts[0] in ("folder", "pngfolder"):
+            res = folder(int(parts[1]), png=parts[0] == "pngfolder")
+        else:
+            res = [case(parts[0], parts[1] == "1", int(parts[2]), args.iters)]
         for r in res:
             print(json.dumps(r), flush=True)
         sys.exit(0)
     cases = [f"{k},{r},{n}" for k in ("photo", "noise") for r in (0, 1) for n in (1, 16, 64)]
+    if args.png:
+        cases = [f"png,{src},{n}" for src in ("pil", "own") for n in (1, 16, 64)]
     if args.folder:
-        cases.append(f"folder,{args.folder}")
-    prof = ROOT / "profiles" / "decode.txt"
+        cases.append(f"{'pngfolder' if args.png else 'folder'},{args.folder}")
+    prof = ROOT / "profiles" / ("decode_png.txt" if args.png else "decode.txt")
     prof.parent.mkdir(exist_ok=True)
     with open(prof, "a") as log:
         for c in cases:
             cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--iters", str(args.iters)]
             p = subprocess.run(cmd, capture_output=True, text=True)
             if p.returncode != 0:          # a fault, an abort or the time limit: nothing more is started on the GPU
-                msg = json.dumps({"bench": "jpeg_decode", "case": c, "failed": p.returncode, "stderr": p.stderr[-400:]})
+                msg = json.dumps({"bench": "png_decode" if args.png else "jpeg_decode", "case": c, "failed": p.returncode, "stderr": p.stderr[-400:]})
                 print(msg, flush=True)
                 print(msg, file=log, flush=True)
                 sys.exit(1)
