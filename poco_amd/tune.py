@@ -257,10 +257,26 @@ def tune_model(model, B: int, verbose=True, skip=(), only_ks=0) -> Dict[str, dic
     return out
 
 
+def transfer_candidates(entries, B: int, ks: int):
+    """(tuned batch, cfg) of one shape's table entries in the order apply_table tries them for batch size B:
+    nearest tuned batch in log space, ties to the LARGER neighbour (its tiles were chosen with more blocks in flight, the safer
+    direction).  The split-K direct conv (ALG 5 with ks = 3) re-streams all 9 Cin Cout weights per 64-pixel block: its
+    entries were tuned at 1 / 4 crops and only transfer to batch sizes up to the tuned one."""
+    for b, cfg in sorted(entries, key=lambda bc: (abs(math.log(bc[0] / B)), -bc[0])):
+        if not cfg or cfg[0] <= 0:
+            continue
+        if cfg[6] == 5 and ks == 3 and B > b:
+            continue
+        yield b, cfg
+
+
 def apply_table(model, B: int, table=None) -> int:
     """Set the measured configuration of every conv op for batch size B.  Without an entry for exactly B the
     entry of the nearest tuned batch size is used if it is valid for B (tiles are per image / row band, so
-    they transfer; the library validates and the built-in heuristic stays in place otherwise)."""
+    they transfer; the library validates and the built-in heuristic stays in place otherwise).
+    That tiles transfer is held by tests/test_conv_transfer_gpu.py: every (shape at B, cfg) this function leaves behind at the
+    first and last batch size of each transfer range against an fp64 conv, and whole forwards at 23 / 46 / 91 crops against the
+    same crops run in tuned-size batches."""
     from ._lib import PocoHipError
     table = load_table() if table is None else table
     by_shape: Dict[str, List[Tuple[int, List[int]]]] = {}
@@ -273,14 +289,7 @@ def apply_table(model, B: int, table=None) -> int:
         if d is None:
             continue
         rest = shape_key(B, *d[:6]).split("x", 1)[1]
-        # nearest tuned batch in log space, ties to the LARGER neighbour (its tiles were chosen with more blocks in flight, the safer
-        # direction).  The split-K direct conv (ALG 5 with ks = 3) re-streams all 9 Cin Cout weights per 64-pixel block: its
-        # entries were tuned at 1 / 4 crops and only transfer to batch sizes up to the tuned one
-        for b, cfg in sorted(by_shape.get(rest, []), key=lambda bc: (abs(math.log(bc[0] / B)), -bc[0])):
-            if not cfg or cfg[0] <= 0:
-                continue
-            if cfg[6] == 5 and d[4] == 3 and B > b:
-                continue
+        for b, cfg in transfer_candidates(by_shape.get(rest, []), B, d[4]):
             try:
                 model.set_conv_cfg(i, B, cfg)
                 n += 1

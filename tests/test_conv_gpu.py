@@ -674,7 +674,7 @@ def test_tuned_table_entries(batch, cuda):
         err = float((out.double() - ref).abs().max())
         tol = ALG_TOL.get(cfg[6], 2e-5) * max(1.0, float(ref.abs().max()))
         by_alg[cfg[6]] = max(by_alg.get(cfg[6], 0.0), err / max(1.0, float(ref.abs().max())))
-        if err > tol:
+        if not err <= tol:      # (NaN - an element the kernel left unwritten - fails too)
             worst[key] = (cfg, err, tol)
         del x, res, out, ref
     print(f"B={batch}: {len(entries)} tuned entries, {len(refused)} refused by the library; worst relative deviation per ALG:",
