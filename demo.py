@@ -4,7 +4,8 @@
                    --mode folder --image_folder <dir> --output_folder out --smpl data/smpl/SMPL_NEUTRAL.npz
 
 Same flags as the reference where they concern the regressor (--cfg --ckpt --mode --image_folder
---vid_file --output_folder --batch_size --no_render --no_kinematic_uncert --inf_model --sideview --no_uncert_color).  Detector /
+--vid_file --output_folder --batch_size --no_render --no_kinematic_uncert --inf_model --sideview --no_uncert_color --wireframe
+--draw_keypoints --render_crop).  Detector /
 tracker are third-party and out of scope: person boxes come from
 --detections (json {image name: [[cx,cy,w,h],...]}, the format multi_person_tracker produces) or
 default to one centred box; results are written as .npz.  --render (opt-in; the reference renders by default) draws the
@@ -46,6 +47,14 @@ def parse_args(argv=None):
                    help="draw the uncertainty-coloured meshes over the input (GPU): folder mode <out>/poco_results/<image>.png, "
                         "video mode <out>/tmp_images_output/%%06d.png + uncertainty.log; needs `faces` in the --smpl file")
     p.add_argument("--sideview", action="store_true", help="with --render: add the Ry(270) view to the right of each picture")
+    p.add_argument("--wireframe", action="store_true",
+                   help="with --render: draw the meshes (the --sideview canvas too) as wireframes: the edges of the front-facing "
+                        "triangles as one-pixel depth-tested lines")
+    p.add_argument("--draw_keypoints", action="store_true",
+                   help="with --render: stamp the 2-D joints on the main view after each person's mesh: folder mode SMPL joints "
+                        "white and OpenPose joints black, video mode all 49 in green")
+    p.add_argument("--render_crop", action="store_true",
+                   help="with --render, folder mode: draw only the first detection of each image, over its own 224 x 224 crop")
     p.add_argument("--image_format", default="png", choices=["png", "jpg"],
                    help="with --render: format of the per-frame pictures; jpg is encoded on the GPU (baseline JPEG, 4:2:0) and only "
                         "its bytes are copied to the host")

@@ -376,6 +376,59 @@ int poco_renderer_render(poco_renderer_t r, unsigned char* d_frame, int H, int W
                          const float* d_params, const float* h_rot3x3, int* d_frag_count, void* stream);
 void poco_renderer_destroy(poco_renderer_t r);
 
+/* Wireframe (RenderFlags.ALL_WIREFRAME, pocolib/utils/vibe_renderer.py:133-136, asked for by demo.py:290-303 --wireframe through
+ * pocolib/core/tester.py:266-271,485-490): GL polygon mode LINE with the depth test and back-face culling on.  Geometry, clipping,
+ * painter's order between people, shading formulas and composite are those of poco_renderer_render; csrc/render.hip.
+ *   Edges: the three edges of every FRONT-FACING triangle, ((q1 - q0) x (q2 - q0)).z > 0 in the transformed space q (GL
+ *     counter-clockwise, camera looking down -z); a zero-area triangle draws nothing.  An edge between a front- and a back-facing
+ *     triangle is drawn, an edge between two back-facing ones is not.
+ *   Line rule (one pixel wide, one sample per pixel): an edge is walked from its lower vertex index (A) to its higher one (B), so
+ *     both triangles sharing it make bit-identical fragments.  Endpoints in continuous (col, row) float32; the major axis a is the
+ *     one with the larger |delta| (a tie: columns), b the other.  Major pixel i is covered when min(a_A, a_B) <= i + 0.5 <
+ *     max(a_A, a_B); t = (i + 0.5 - a_A) / (a_B - a_A); minor pixel floor(b_A + t (b_B - b_A)); q_z and the vertex normal are
+ *     x_A + t (x_B - x_A).  a_A == a_B draws nothing.  Fragments with |q_z| > 1 or outside the frame are dropped.
+ *   Visibility: only line fragments write depth (back edges show through the gaps, as in GL).  Inside one person the nearest
+ *     fragment wins, ties go to the lower (triangle << 2 | edge), edge e = the edge opposite vertex e of the triangle.
+ *   Shading: the interpolated normal is renormalised and goes through the shader above with the person's colour and material.
+ *   Pixels no line covers keep their bytes exactly.
+ * Limit: the id (triangle << 2 | edge) takes the key's 22 low bits, so a wireframe call needs F < 2^20 = 1048576 faces
+ * (POCO_ERR_ARG beyond; SMPL has 13776).  Fidelity to GL's own line rasterisation (diamond-exit rule) is unpinned. */
+#define POCO_RENDER_WIREFRAME 1u   /* bit 0: draw the meshes as wireframes */
+#define POCO_RENDER_IDS 2u         /* bit 1: NOT FOR USERS - a test hook like d_frag_count itself, kept only so that the tests can
+                                    * compare the winner of each pixel; it may change without an ABI bump.  d_frag_count receives,
+                                    * instead of the fragment count, the id that won each pixel - the triangle, or
+                                    * (triangle << 2 | edge) of a wireframe call - and -1 where none did */
+#define POCO_RENDER_MAX_WIRE_FACES ((1 << 20) - 1)
+/* poco_renderer_render with a flags word: flags = 0 is that call exactly (the same launches, the same bytes); any bit other than
+ * the two above is POCO_ERR_ARG, and so is POCO_RENDER_IDS without d_frag_count.  A wireframe call enqueues a memset and three
+ * launches like the filled one (POCO_RENDER_IDS adds one). */
+int poco_renderer_render_ex(poco_renderer_t r, unsigned char* d_frame, int H, int W, const float* d_verts, int P,
+                            const float* d_params, const float* h_rot3x3, int* d_frag_count, unsigned flags, void* stream);
+
+/* Keypoint discs: cv2.circle(img, (int(pt[0]), int(pt[1])), 4, colour, -1) of pocolib/core/tester.py:324-328 (folder mode: SMPL
+ * joints white, OpenPose joints black) and :552-554 (video mode: green), demo.py:290-303 --draw_keypoints; csrc/render.hip.
+ * d_frame uint8 [H,W,3] (in place); d_points fp32 [N,2] (col, row), each truncated toward zero as int() does; d_rgb uint8 [N,3];
+ * radius r in 0 .. POCO_DISC_MAX_RADIUS.  Point k paints the pixels (cx + dx, cy + dy), |dy| <= r, |dx| <= half_width[r][|dy|],
+ * clipped to the frame: 2r + 1 rows.  Points are painted in index order: where stamps overlap the higher index wins (a per-pixel
+ * scan from the last point down; no atomics, deterministic).  A point that is not finite or >= 2^30 in magnitude paints nothing.
+ * half_width = the midpoint circle (x = 0, y = r, d = 1 - r; a visited (x, y) gives row y the half-width x and row x the
+ * half-width y, the larger one stays), row r[|dy|] of the one table below, which tests/render_overlay_np.py reads from this file.
+ * Equality with cv2.circle's own filled circle is unpinned (tools/validate_assets.py --keypoints compares where cv2 exists).
+ * Limits: H, W <= 16384, 0 <= N <= 65536 (N = 0 is a no-op).  One launch on `stream`, no allocation, no synchronisation. */
+#define POCO_DISC_MAX_RADIUS 8
+#define POCO_DISC_HALF_WIDTHS { \
+  {0, 0, 0, 0, 0, 0, 0, 0, 0}, \
+  {1, 0, 0, 0, 0, 0, 0, 0, 0}, \
+  {2, 2, 1, 0, 0, 0, 0, 0, 0}, \
+  {3, 3, 2, 1, 0, 0, 0, 0, 0}, \
+  {4, 4, 3, 3, 1, 0, 0, 0, 0}, \
+  {5, 5, 5, 4, 3, 2, 0, 0, 0}, \
+  {6, 6, 6, 5, 4, 3, 2, 0, 0}, \
+  {7, 7, 7, 6, 6, 5, 4, 2, 0}, \
+  {8, 8, 8, 7, 7, 6, 5, 4, 2} }
+int poco_renderer_draw_discs(unsigned char* d_frame, int H, int W, const float* d_points, const unsigned char* d_rgb, int N,
+                             int r, void* stream);
+
 /* ---- JPEG encoder: the demo's rendered frames as baseline JPEG, encoded where they are ------------------------------------------
  * Replaces the host-side picture encoding behind pocolib/core/tester.py:338-345 (cv2.imwrite per frame) and, with
  * poco_amd/jpeg.py's Motion-JPEG .avi writer on top, the ffmpeg call of demo.py:148-157 / demo_utils.py:237-245 (images_to_video,

@@ -207,3 +207,17 @@ struct RenderXform {
 void launch_render(const float* verts, int P, int V, const int* faces, int F, const int* csr_off, const int* csr_face,
                    const RenderXform& xf, const float* params, int H, int W, float4* pos, float4* nrm, unsigned long long* vis,
                    int* count, unsigned char* frame, hipStream_t s);
+// The wireframe call: same arguments (verts is read again for the back-face test); count: +1 per line fragment.  F < 2^20.
+void launch_render_wire(const float* verts, int P, int V, const int* faces, int F, const int* csr_off, const int* csr_face,
+                        const RenderXform& xf, const float* params, int H, int W, float4* pos, float4* nrm, unsigned long long* vis,
+                        int* count, unsigned char* frame, hipStream_t s);
+// ids [n] <- the low 22 bits of each visibility key, -1 where the key is empty (POCO_RENDER_IDS).
+void launch_render_ids(const unsigned long long* vis, int n, int* ids, hipStream_t s);
+// Half-widths of a filled disc stamp per |dy| = 0 .. r (include/poco_hip.h POCO_DISC_HALF_WIDTHS).
+constexpr int RENDER_DISC_MAX_RADIUS = 8;
+struct DiscRows {
+  int hw[RENDER_DISC_MAX_RADIUS + 1];
+};
+// points fp32 [N,2] (col, row), rgb uint8 [N,3]: stamps painted over frame in index order.
+void launch_render_discs(unsigned char* frame, int H, int W, const float* points, const unsigned char* rgb, int N, int r,
+                         const DiscRows& rows, hipStream_t s);

@@ -583,17 +583,31 @@ extern "C" int poco_renderer_create(const int32_t* h_faces, int F, int V, poco_r
   return POCO_OK;
 }
 
-extern "C" int poco_renderer_render(poco_renderer_t r, unsigned char* d_frame, int H, int W, const float* d_verts, int P,
-                                    const float* d_params, const float* h_rot3x3, int* d_frag_count, void* stream) {
+// the one body of poco_renderer_render (flags = 0) and poco_renderer_render_ex
+static int renderer_render(const char* who, poco_renderer_t r, unsigned char* d_frame, int H, int W, const float* d_verts, int P,
+                           const float* d_params, const float* h_rot3x3, int* d_frag_count, unsigned flags, void* stream) {
+  if (flags & ~(POCO_RENDER_WIREFRAME | POCO_RENDER_IDS)) {
+    poco_set_error(std::string(who) + ": unknown flag bit (known: bit 0 = wireframe, bit 1 = winning ids)");
+    return POCO_ERR_ARG;
+  }
+  const bool wire = flags & POCO_RENDER_WIREFRAME, ids = flags & POCO_RENDER_IDS;
+  if (ids && !d_frag_count) {
+    poco_set_error(std::string(who) + ": flag bit 1 (winning ids) needs d_frag_count");
+    return POCO_ERR_ARG;
+  }
+  if (r && wire && r->F > POCO_RENDER_MAX_WIRE_FACES) {
+    poco_set_error(std::string(who) + ": a wireframe call needs F < 2^20 faces (the key's 22 low bits hold triangle << 2 | edge)");
+    return POCO_ERR_ARG;
+  }
   if (!r || !d_frame || H < 1 || W < 1 || H > RENDER_MAX_SIDE || W > RENDER_MAX_SIDE || P < 0 || P > RENDER_MAX_PEOPLE ||
       (P > 0 && (!d_verts || !d_params))) {
-    poco_set_error("poco_renderer_render: bad arguments (need a handle, a frame of 1..16384 x 1..16384, 0 <= P <= 1024 and, "
+    poco_set_error(std::string(who) + ": bad arguments (need a handle, a frame of 1..16384 x 1..16384, 0 <= P <= 1024 and, "
                    "for P > 0, vertices and parameters)");
     return POCO_ERR_ARG;
   }
   const hipStream_t s = (hipStream_t)stream;
   const size_t npix = (size_t)H * W;
-  if (d_frag_count) POCO_HIP_CHECK(hipMemsetAsync(d_frag_count, 0, npix * sizeof(int), s));
+  if (d_frag_count) POCO_HIP_CHECK(hipMemsetAsync(d_frag_count, ids ? 0xFF : 0, npix * sizeof(int), s));
   if (P == 0) return POCO_OK;
   const size_t nvert = (size_t)P * r->V;
   // growth frees the old buffer: hipFree waits for the device, so a render still in flight on another stream finishes first
@@ -619,8 +633,38 @@ extern "C" int poco_renderer_render(poco_renderer_t r, unsigned char* d_frame, i
       xf.m[3 * i + j] = j == 0 ? rij : -rij;
     }
   POCO_HIP_CHECK(hipMemsetAsync(r->vis, 0xFF, npix * sizeof(unsigned long long), s));
-  launch_render(d_verts, P, r->V, r->faces, r->F, r->csr_off, r->csr_face, xf, d_params, H, W, r->scratch, r->scratch + nvert,
-                r->vis, d_frag_count, d_frame, s);
+  (wire ? launch_render_wire : launch_render)(d_verts, P, r->V, r->faces, r->F, r->csr_off, r->csr_face, xf, d_params, H, W,
+                                              r->scratch, r->scratch + nvert, r->vis, ids ? nullptr : d_frag_count, d_frame, s);
+  if (ids) launch_render_ids(r->vis, (int)npix, d_frag_count, s);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_renderer_render(poco_renderer_t r, unsigned char* d_frame, int H, int W, const float* d_verts, int P,
+                                    const float* d_params, const float* h_rot3x3, int* d_frag_count, void* stream) {
+  return renderer_render("poco_renderer_render", r, d_frame, H, W, d_verts, P, d_params, h_rot3x3, d_frag_count, 0u, stream);
+}
+
+extern "C" int poco_renderer_render_ex(poco_renderer_t r, unsigned char* d_frame, int H, int W, const float* d_verts, int P,
+                                       const float* d_params, const float* h_rot3x3, int* d_frag_count, unsigned flags,
+                                       void* stream) {
+  return renderer_render("poco_renderer_render_ex", r, d_frame, H, W, d_verts, P, d_params, h_rot3x3, d_frag_count, flags, stream);
+}
+
+extern "C" int poco_renderer_draw_discs(unsigned char* d_frame, int H, int W, const float* d_points, const unsigned char* d_rgb,
+                                        int N, int r, void* stream) {
+  static const int table[POCO_DISC_MAX_RADIUS + 1][POCO_DISC_MAX_RADIUS + 1] = POCO_DISC_HALF_WIDTHS;
+  static_assert(POCO_DISC_MAX_RADIUS == RENDER_DISC_MAX_RADIUS, "the header's table and the kernel's argument must agree");
+  if (!d_frame || H < 1 || W < 1 || H > RENDER_MAX_SIDE || W > RENDER_MAX_SIDE || N < 0 || N > 65536 || r < 0 ||
+      r > POCO_DISC_MAX_RADIUS || (N > 0 && (!d_points || !d_rgb))) {
+    poco_set_error("poco_renderer_draw_discs: bad arguments (need a frame of 1..16384 x 1..16384, 0 <= N <= 65536, 0 <= r <= 8 and, "
+                   "for N > 0, points and colours)");
+    return POCO_ERR_ARG;
+  }
+  if (N == 0) return POCO_OK;
+  DiscRows rows;
+  for (int k = 0; k <= POCO_DISC_MAX_RADIUS; ++k) rows.hw[k] = table[r][k];
+  launch_render_discs(d_frame, H, W, d_points, d_rgb, N, r, rows, (hipStream_t)stream);
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }

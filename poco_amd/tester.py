@@ -59,6 +59,18 @@ DEVICE_ONLY_KEYS = ("uncert_feat", "body_feat2", "pred_pose6d", "pred_pose_6d", 
                     "pred_segm_mask", "backbone_feat")
 
 
+def crop_keypoints(joints2d, box, res: int = 224, bbox_scale: float = 1.0) -> np.ndarray:
+    """Original-image keypoints [K, >= 2] in the pixel coordinates of the crop of `box` = (cx, cy, w, h): where the crop's affine
+    map (gen_trans_from_patch_cv, vibe_image_utils.py:58-92) puts them, x_c = res / 2 + (x - cx) res / (w scale), y_c = res / 2 +
+    (y - cy) res / (h scale); computed in float64, returned as float32 [K,2]."""
+    j = np.asarray(joints2d, np.float64)[:, :2]
+    cx, cy, bw, bh = (float(v) for v in np.asarray(box, np.float64).reshape(4))
+    out = np.empty((j.shape[0], 2), np.float64)
+    out[:, 0] = res / 2.0 + (j[:, 0] - cx) * (res / (bw * bbox_scale))
+    out[:, 1] = res / 2.0 + (j[:, 1] - cy) * (res / (bh * bbox_scale))
+    return out.astype(np.float32)
+
+
 class POCOTester:
     def __init__(self, args):
         self.args = args
@@ -88,9 +100,11 @@ class POCOTester:
         """--render is opt-in; --no_render wins (demo.py render_enabled)."""
         return bool(getattr(self.args, "render", False)) and not getattr(self.args, "no_render", False)
 
-    def render_frame(self, frame: torch.Tensor, verts, orig_cam, var, side_bg: int) -> torch.Tensor:
+    def render_frame(self, frame: torch.Tensor, verts, orig_cam, var, side_bg: int, keypoints=None) -> torch.Tensor:
         """The picture of one frame: people (in painter's order) drawn over the device frame `frame` (in place), with
-        --sideview the Ry(270) view on a canvas of value side_bg to its right; --no_uncert_color = plain grey."""
+        --sideview the Ry(270) view on a canvas of value side_bg to its right; --no_uncert_color = plain grey; --wireframe =
+        both views as wireframes.  keypoints (--draw_keypoints): per person (points, rgb), stamped on the main view after that
+        person's mesh."""
         from . import render
         if self.faces is None:
             raise RuntimeError(f"--render: {self.args.smpl} has no `faces` array")
@@ -99,7 +113,39 @@ class POCOTester:
             self._renderer = render.Renderer(self.faces, V, self.device)
         return render.render_people(self._renderer, frame, verts, orig_cam, var, self.backbone,
                                     uncert_color=not getattr(self.args, "no_uncert_color", False),
-                                    sideview=bool(getattr(self.args, "sideview", False)), side_bg=side_bg)
+                                    sideview=bool(getattr(self.args, "sideview", False)), side_bg=side_bg,
+                                    wireframe=bool(getattr(self.args, "wireframe", False)), keypoints=keypoints)
+
+    @property
+    def draw_keypoints(self) -> bool:
+        return bool(getattr(self.args, "draw_keypoints", False))
+
+    def crop_canvas(self, frame_u8: torch.Tensor, box, bbox_scale: float = 1.0) -> torch.Tensor:
+        """--render_crop: the uint8 [res,res,3] crop of one detection, the bytes cv2.warpAffine cuts before ToTensor / Normalize
+        (`raw_img` of get_single_image_crop_demo, tester.py:184-190,257).  The crop kernel hands out the normalised floats
+        (x = (p / 255 - mean) / std); p is recovered exactly by inverting that and rounding.  This relies on the crop output
+        being float32 (the float error is then below 1e-3 of a level; a half-precision output would not round back) and on the
+        mean / std constants below being the kernel's."""
+        res = self.model_cfg.DATASET.IMG_RES
+        raw = np.asarray(box)
+        b = torch.from_numpy(np.ascontiguousarray(raw.reshape(1, 4), np.float64 if raw.dtype == np.float64 else np.float32)).to(self.device)
+        x = crop_normalize(frame_u8, b, bbox_scale, res)[0]
+        assert x.dtype == torch.float32
+        mean = torch.tensor([0.485, 0.456, 0.406], device=self.device).view(3, 1, 1)
+        std = torch.tensor([0.229, 0.224, 0.225], device=self.device).view(3, 1, 1)
+        return ((x * std + mean) * 255.0).round_().clamp_(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+
+    def render_crop_frame(self, frame_u8: torch.Tensor, r: dict, box, bbox_scale: float = 1.0) -> torch.Tensor:
+        """--render_crop (folder mode, tester.py:256-285): the FIRST detection of the image on its own 224 x 224 crop, camera
+        (s, s, tx, ty) of that crop's pred_cam; keypoints in crop pixel coordinates (crop_keypoints)."""
+        from . import render
+        s, tx, ty = (float(c) for c in r["pred_cam"][0][:3])
+        kp = None
+        if self.draw_keypoints:
+            j = crop_keypoints(r["smpl_joints2d"][0], box, self.model_cfg.DATASET.IMG_RES, bbox_scale)
+            kp = [render.folder_keypoints(j)]
+        return self.render_frame(self.crop_canvas(frame_u8, box, bbox_scale), r["verts"][:1], np.array([[s, s, tx, ty]], np.float32),
+                                 r["var"][:1], side_bg=255, keypoints=kp)
 
     # ---- --image_format jpg / --save_video ------------------------------------------------------------------------------
     @property
@@ -434,6 +480,8 @@ class POCOTester:
             return np.array([[W / 2.0, H / 2.0, s, s]], dtype=np.float32)
 
         render_on = self.render_on
+        render_crop = render_on and bool(getattr(self.args, "render_crop", False))
+        first_box = deque()                                          # --render_crop: each image's first detection, as it was cropped
         img_dir = os.path.join(output_path, "poco_results")          # reference demo.py:95
         if render_on:
             os.makedirs(img_dir, exist_ok=True)
@@ -478,6 +526,8 @@ class POCOTester:
                     fill()
                     d = dets_of(pos, n, img)
                     counts.append(len(d))
+                    if render_crop:
+                        first_box.append(d[0])
                     yield img, d
 
             writes = deque()
@@ -485,10 +535,18 @@ class POCOTester:
                 n_img += 1
                 if render_on:
                     r, fr = r
+                box0 = first_box.popleft() if render_crop else None
                 if r is not None:
                     writes.append(wr_pool.submit(write, n, r))
-                    if render_on:                                 # tester.py:248-345: detection order, white side canvas
-                        pic = self.render_frame(fr, r["verts"], r["orig_cam"], r["var"], side_bg=255)
+                    if render_crop:                               # tester.py:256-285: the first detection on its own crop
+                        pic = self.render_crop_frame(fr, r, box0, bbox_scale)
+                    elif render_on:                               # tester.py:248-345: detection order, white side canvas
+                        kp = None
+                        if self.draw_keypoints:
+                            from .render import folder_keypoints
+                            kp = [folder_keypoints(j) for j in r["smpl_joints2d"]]
+                        pic = self.render_frame(fr, r["verts"], r["orig_cam"], r["var"], side_bg=255, keypoints=kp)
+                    if render_on:
                         stem = os.path.join(img_dir, os.path.splitext(n)[0])
                         if self.image_format == "jpg":
                             writes.append(wr_pool.submit(_write_bytes, stem + ".jpg", self.encode_jpeg(pic)))
@@ -681,7 +739,7 @@ def _render_video(self, results: dict, frame_folder: str, names, load, output_pa
     --save_video adds <output>/<frame folder>_poco_result.avi (Motion-JPEG of the same pictures at --fps: the reference's
     images_to_video, demo.py:148-157)."""
     from concurrent.futures import ThreadPoolExecutor
-    from .render import video_order
+    from .render import video_keypoints, video_order
     out_dir = os.path.join(output_path, "tmp_images_output")
     os.makedirs(out_dir, exist_ok=True)
     jpg = self.image_format == "jpg"
@@ -703,7 +761,9 @@ def _render_video(self, results: dict, frame_folder: str, names, load, output_pa
                 people = [people[i] for i in video_order(cams)]
                 pic = self.render_frame(fr, np.stack([results[pid]["verts"][k] for pid, k in people]),
                                         np.stack([results[pid]["orig_cam"][k] for pid, k in people]),
-                                        np.stack([results[pid]["var"][k] for pid, k in people]), side_bg=0)
+                                        np.stack([results[pid]["var"][k] for pid, k in people]), side_bg=0,
+                                        keypoints=[video_keypoints(results[pid]["smpl_joints2d"][k]) for pid, k in people]
+                                        if self.draw_keypoints else None)
                 for pid, k in people:
                     g = float(np.clip(results[pid]["var_global"][k], 0, 0.99))
                     who = f"{int(pid):02d}" if str(pid).lstrip("-").isdigit() else str(pid)

@@ -1,7 +1,9 @@
 """Time the demo renderer (poco_renderer_render: memset + vertex, raster and shade launches) with HIP events at 1920 x 1080 for
 1, 4 and 16 SMPL-sized meshes (6890 vertices, 13776 faces, procedurally generated: a deformed torus grid), one JSON line per case.
 
-    python tools/bench_render.py [--iters 50] [--folder 32] [--encode]
+    python tools/bench_render.py [--iters 50] [--folder 32] [--encode] [--wireframe]
+--wireframe: next to each filled call, the wireframe call (poco_renderer_render_ex with POCO_RENDER_WIREFRAME) on the same meshes,
+and the keypoint stamp (poco_renderer_draw_discs) of 49 points per person.
 --folder N: also the folder-mode wall time per image of demo.py on N synthetic 1080p images (one person each, resnet50-cliff
 synthetic checkpoint) without and with --render (PNG encoding on the host included).
 --encode: instead of the renderer, the JPEG encoder (poco_jpeg_encode: transform, entropy, compaction) at 1920 x 1080 and at
@@ -60,7 +62,19 @@ def people(P, H, W, verts, seed=0):
     return np.stack(vs), np.array(cams, np.float32)
 
 
-def bench(iters):
+def _time(fn, iters):
+    for _ in range(5):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def bench(iters, wireframe=False):
     dev = torch.device("cuda:0")
     H, W = 1080, 1920
     verts, faces = smpl_sized_mesh()
@@ -85,6 +99,18 @@ def bench(iters):
         ms = e0.elapsed_time(e1) / iters
         print(json.dumps({"bench": "render", "H": H, "W": W, "people": P, "verts": V_SMPL, "faces": F_SMPL, "fragments": frags,
                           "covered_px": covered, "ms": round(ms, 4), "iters": iters}), flush=True)
+        if wireframe:
+            R.render(frame, dv, cams, cols, mats, frag_count=cnt, wireframe=True)
+            frags, covered = int(cnt.sum()), int((cnt > 0).sum())
+            ms = _time(lambda: R.render(frame, dv, cams, cols, mats, wireframe=True), iters)
+            print(json.dumps({"bench": "render_wireframe", "H": H, "W": W, "people": P, "verts": V_SMPL, "faces": F_SMPL,
+                              "fragments": frags, "covered_px": covered, "ms": round(ms, 4), "iters": iters}), flush=True)
+            r = np.random.default_rng(P)
+            pts = torch.from_numpy(r.uniform([0, 0], [W, H], (49 * P, 2)).astype(np.float32)).to(dev)
+            rgb = torch.full((49 * P, 3), 255, dtype=torch.uint8, device=dev)
+            ms = _time(lambda: render.draw_discs(frame, pts, rgb), iters)
+            print(json.dumps({"bench": "draw_discs", "H": H, "W": W, "points": 49 * P, "radius": render.DISC_RADIUS,
+                              "ms": round(ms, 4), "iters": iters}), flush=True)
 
 
 def encode(iters):
@@ -188,6 +214,7 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--folder", type=int, default=0)
     ap.add_argument("--encode", action="store_true")
+    ap.add_argument("--wireframe", action="store_true")
     args = ap.parse_args()
     if args.encode:
         encode(args.iters)
@@ -197,6 +224,6 @@ if __name__ == "__main__":
             # the PNG path on the host against the PNG path on the device: 5 repeats each, the spread is reported
             folder(args.folder, (["--render", "--encode", "host"], ["--render", "--encode", "gpu"]), repeats=5)
     else:
-        bench(args.iters)
+        bench(args.iters, args.wireframe)
         if args.folder:
             folder(args.folder)

@@ -19,6 +19,10 @@ Every stage whose inputs are missing is reported as SKIPPED (exit code 0); a sta
      cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT) on uint8 exactly as pocolib/utils/vibe_image_utils.py:58-107 calls them - against
      the fixed-point restatement oracle/crop_np.py (uint8, byte for byte; the transform matrix bit for bit) and, with a GPU, against
      poco_crop_normalize.  `--crop` runs only this stage.
+  5. Keypoint stamp (needs `cv2` importable; licence-free; opt-in): cv2.circle(img, (x, y), r, colour, -1) as
+     pocolib/core/tester.py:324-328,552-554 calls it against the half-width table of include/poco_hip.h
+     (POCO_DISC_HALF_WIDTHS, restated in tests/render_overlay_np.py) for every radius of the table, at the centre and clipped at the
+     borders.  Runs only with `--keypoints`.
 """
 from __future__ import annotations
 
@@ -236,6 +240,27 @@ def stage_crop(args):
     return (OK if ok else FAIL), msg
 
 
+def stage_keypoints(args):
+    try:
+        import cv2
+    except Exception as e:                                     # noqa: BLE001
+        return SKIP, f"cv2 is not importable ({type(e).__name__}); the stamp of --draw_keypoints stays unpinned"
+    from tests import render_overlay_np as ov
+    H, W = 40, 48
+    bad = []
+    for r in range(ov.disc_table().shape[0]):
+        for cx, cy in ((24, 20), (0, 0), (W - 1, H - 1), (2, H - 2), (-3, 7), (W + 2, 5)):
+            ref = np.zeros((H, W, 3), np.uint8)
+            cv2.circle(ref, (cx, cy), r, (255, 255, 255), -1)
+            got = ov.draw_discs_np(np.zeros((H, W, 3), np.uint8), [[cx, cy]], [[255, 255, 255]], r)
+            if not np.array_equal(ref, got):
+                bad.append((r, cx, cy, int((ref != got).any(-1).sum())))
+    r4 = [b for b in bad if b[0] == 4]
+    msg = f"cv2 {cv2.__version__}: {len(bad)} of {6 * ov.disc_table().shape[0]} stamps differ" + \
+          (f" (radius, cx, cy, pixels): {bad[:6]}" if bad else "") + f"; radius 4 (the demo's): {'differs' if r4 else 'equal'}"
+    return (FAIL if r4 else OK), msg
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--smpl-pkl", default="data/smpl/SMPL_NEUTRAL.pkl")
@@ -247,8 +272,13 @@ def main(argv=None):
     ap.add_argument("--inf_model", default="best")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--crop", action="store_true", help="only stage 4: the crop against the real cv2")
+    ap.add_argument("--keypoints", action="store_true", help="only stage 5: the keypoint stamp against the real cv2.circle")
     args = ap.parse_args(argv)
     results = []
+    if args.keypoints:
+        st, msg = stage_keypoints(args)
+        print(f"[{st:7s}] 5 keypoint stamp vs cv2: {msg}")
+        return 1 if st == FAIL else 0
     if args.crop:
         st, msg = stage_crop(args)
         print(f"[{st:7s}] 4 crop vs cv2: {msg}")
