@@ -16,7 +16,8 @@ ffmpeg first, demo.py:71; ffmpeg/cv2 are not part of this image) or a Motion-JPE
 (poco_amd/jpeg.py MjpegReader).  --decode gpu decodes baseline .jpg input on the GPU (poco_amd/jpeg.py JpegDecoder): the file's
 bytes cross PCIe instead of its pixels; other files go through PIL as with the default --decode host.  --decode_png gpu does the
 same for .png input - what the reference's ffmpeg extraction and this demo's own --render write - with the device inflate and
-unfilter of poco_amd/png.py PngDecoder; the two flags are independent.
+unfilter of poco_amd/png.py PngDecoder.  --decode_progressive gpu does it for progressive .jpg files (SOF2: what web servers
+and export pipelines write) with poco_amd/jpeg.py ProgressiveJpegDecoder; the three flags are independent.
 """
 import argparse
 import json
@@ -37,6 +38,10 @@ def parse_args(argv=None):
     p.add_argument("--decode_png", default="host", choices=["host", "gpu"],
                    help="where .png input is decoded: host = PIL; gpu = 8-bit non-interlaced .png files are inflated and unfiltered "
                         "on the GPU, same pixels (anything else still goes through PIL); independent of --decode")
+    p.add_argument("--decode_progressive", default="host", choices=["host", "gpu"],
+                   help="where progressive .jpg input is decoded: host = PIL; gpu = progressive Huffman files (8 bit, no restart "
+                        "interval) are decoded on the GPU, same pixels (anything else still goes through PIL); independent of "
+                        "--decode and --decode_png")
     p.add_argument("--image_folder", type=str, help="input image folder")
     p.add_argument("--output_folder", type=str, default="out", help="output folder to write results")
     p.add_argument("--batch_size", type=int, default=64, help="batch size of POCO")

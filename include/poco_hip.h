@@ -508,6 +508,64 @@ int poco_jpeg_decoder_create(int max_h, int max_w, int max_batch, size_t max_byt
 int poco_jpeg_decode(poco_jpeg_decoder_t dec, const poco_jpeg_image* imgs, int n, int* d_status, void* stream);
 void poco_jpeg_decoder_destroy(poco_jpeg_decoder_t dec);
 
+/* ---- progressive JPEG decoder: SOF2 input frames decoded on the device ------------------------------------------------------------
+ * Replaces the same host-side decode as the baseline decoder above (pocolib/core/tester.py:171 and :507, cv2.imread per image)
+ * for the files poco_jpeg_decode does not take: progressive DCT (SOF2), what web servers and export pipelines commonly write;
+ * csrc/jpeg_prog.hip, DESIGN.md 17.  Takes the bytes of up to max_batch parsed files and their scan tables (poco_amd/jpeg.py
+ * parse_progressive_jpeg walks the markers and validates the scan script on the host), leaves one uint8 [H,W,3] RGB picture per
+ * file on the device.
+ *   Streams: progressive Huffman (SOF2), 8 bit, no restart interval; components and sampling as for poco_jpeg_decode; up to 64
+ *     scans: DC first and refinement scans (of one component, or interleaved over all), AC first scans with end-of-band runs and
+ *     AC refinement scans with correction bits (one component each), any successive approximation; DHT between scans.
+ *   Arithmetic: integers only; the pixels equal libjpeg's (what PIL gives) and those of tests/jpegprog_np.py.  The coefficient
+ *     stage follows jdphuff.c and writes final values (DC prediction undone by the lane that walks the scan) into the zeroed int16
+ *     coefficient buffer in natural order; dequantisation, inverse DCT, upsampling and colour are poco_jpeg_decode's kernels.
+ *   Order: a scan runs after every earlier scan of its file that touches one of its (component, coefficient) pairs: the host
+ *     gives every scan the length of its longest such chain as its level and launches level after level, one wave per scan;
+ *     scans of one level - other components, other bands, other images - run concurrently.
+ *   Geometry: a scan of one component covers ceil(w_c / 8) x ceil(h_c / 8) blocks of that component's own size in raster order,
+ *     an interleaved scan covers whole MCUs; the coefficient buffer holds whole MCUs.
+ *   Safety: every read of the stream is clamped to its scan, every store is guarded by its own index, every loop is bounded by a
+ *     constant or a validated count; a window without a code, a run past Se, an end-of-band run past the last block or a scan whose
+ *     bytes end before its blocks do sets that image's status word and ends that scan. */
+typedef struct poco_jpeg_prog_decoder* poco_jpeg_prog_decoder_t;
+typedef struct poco_jpeg_prog_table {
+  unsigned char bits[16], vals[256];   /* one DHT table: codes per length 1 .. 16, symbols */
+} poco_jpeg_prog_table;
+typedef struct poco_jpeg_prog_scan {
+  unsigned int offset, length;    /* the scan's entropy-coded bytes in data, up to the next marker */
+  unsigned char ncomp, comp[3];   /* components of the scan (indices into the frame's): 1, or all of them for a DC scan */
+  unsigned char ss, se, ah, al;   /* spectral selection and successive approximation */
+  short tab[3];                   /* tables[]: per component the DC table of a first DC scan; [0] the AC table of an AC scan */
+  short pad;
+} poco_jpeg_prog_scan;
+/* One parsed file (all pointers on the host except d_rgb). */
+typedef struct poco_jpeg_prog_image {
+  const unsigned char* data;      /* the file's bytes from its first scan to the end of its last */
+  size_t nbytes;
+  const poco_jpeg_prog_scan* scans;     /* in file order */
+  int nscan;                      /* 1 .. 64 */
+  const poco_jpeg_prog_table* tables;
+  int ntable;                     /* 0 .. 256 */
+  int H, W, ncomp;                /* ncomp 1 or 3 */
+  int hsamp, vsamp;               /* luma sampling: 1x1, 2x1 or 2x2 (1x1 for one component) */
+  unsigned short qt[3][64];       /* quantisation table per component, natural (row-major) order */
+  unsigned char* d_rgb;           /* device: receives H * W * 3 bytes, any alignment */
+} poco_jpeg_prog_image;
+/* Device scratch (coefficients, planes) and one pinned staging buffer for up to max_batch images of up to max_h x max_w (1 .. 16384
+ * each) whose bytes add up to at most max_bytes per call; POCO_ERR_ARG without touching the GPU for sizes outside that, max_batch
+ * outside 1 .. 4096 or max_bytes outside 1 .. 2^30.  Needs the GPU after validation. */
+int poco_jpeg_prog_decoder_create(int max_h, int max_w, int max_batch, size_t max_bytes, poco_jpeg_prog_decoder_t* out);
+/* Decode imgs[0 .. n) in one call: one host-to-device copy of bytes, tables and scan tables from the pinned staging buffer, two
+ * memsets, one launch per level of the scan order, then inverse DCT and upsampling + colour on `stream`; no allocation, no global
+ * atomics.  d_status int32 [n] as for poco_jpeg_decode.  POCO_ERR_ARG before any GPU work: null handle or pointer, n outside
+ * 1 .. max_batch, a size outside the created maximum, sampling or component counts other than those above, a scan table that
+ * breaks the rules of parse_progressive_jpeg (band, components, successive approximation, a table index outside tables[], a scan
+ * outside the data), a Huffman table that is no prefix code, or more bytes than the decoder was created for.  One decoder is used
+ * from one stream at a time. */
+int poco_jpeg_prog_decode(poco_jpeg_prog_decoder_t dec, const poco_jpeg_prog_image* imgs, int n, int* d_status, void* stream);
+void poco_jpeg_prog_decoder_destroy(poco_jpeg_prog_decoder_t dec);
+
 /* ---- PNG encoder: the demo's rendered frames as PNG, filtered and deflated where they are --------------------------------------
  * Replaces the host-side cv2.imwrite(... '%06d.png') of pocolib/core/tester.py:350 and :572; csrc/png_enc.hip.  Takes a uint8
  * [H,W,3] RGB device frame, leaves the bytes of a .png file on the device: lossless, and byte for byte a function of the frame

@@ -19,6 +19,7 @@
 // count the host validated; every read of the stream is clamped to its interval, every store is guarded by its own index.  No
 // global atomics: every word has one writer, except the status words, to which every writer stores a non-zero value.
 #include "common.h"
+#include "jpeg_dec_internal.h"
 #include "../../include/poco_hip.h"
 
 #include <algorithm>
@@ -29,38 +30,10 @@
 
 namespace {
 
-constexpr int JD_MAX_SIDE = 16384;
+using namespace jdec;
+
 constexpr int JD_SUBSEQ = 128;           // bytes per subsequence (poco_amd/jpeg.py SUBSEQ_BYTES): the one place it is set
-constexpr int JD_LOOKAHEAD = 9;          // bits of the lookahead table
-constexpr int JD_THREADS = 256;          // subsequences per workgroup
-constexpr int JD_MAX_BATCH = 4096;
 constexpr int JD_SEGS_PER_IMAGE = 2048;  // restart intervals planned per image of the batch (a call may spread them unevenly)
-constexpr int JD_ERR_CODE = 1, JD_ERR_SHORT = 2;
-
-typedef unsigned long long u64;
-
-struct HuffTab {
-  unsigned short look[1 << JD_LOOKAHEAD];   // length << 8 | symbol of the code at the top of the window, 0 = none this short
-  int maxcode[18];                          // [l]: largest code of length l, -1 = none
-  int delta[17];                            // valptr[l] - mincode[l]
-  unsigned char vals[256];
-};
-static_assert(sizeof(HuffTab) % 4 == 0, "copied as dwords");
-
-struct DImg {
-  u64 coef_off;                 // first block of the image in the coefficient scratch
-  u64 plane_off[3];             // bytes into the plane scratch
-  unsigned char* out;
-  unsigned data_off, nbytes;    // the image's bytes in the blob
-  int H, W, ncomp, hs, vs, bpm, mcux, mcuy, nblocks;
-  int cw, ch, fancy;            // chroma planes' own size; the fancy filters apply (cw > 2)
-  int pw[3];                    // plane widths (whole blocks)
-  int nseg, seg_off, nsub, sub_off, nwg, wg_off;
-  unsigned char comp_of[8];     // component of each block of an MCU
-  unsigned short qt[3][64];
-  HuffTab tab[6];               // [component * 2 + (AC)]
-};
-static_assert(sizeof(DImg) % 8 == 0, "array of 8-byte aligned records");
 
 struct DSeg {
   unsigned off, len;            // in the image's bytes
@@ -503,6 +476,12 @@ __global__ __launch_bounds__(JD_THREADS) void jdec_colour(const DImg* __restrict
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+}  // namespace
+
+namespace jdec {
+
 bool build_table(const unsigned char* bits, const unsigned char* vals, bool dc, HuffTab* t) {
   std::memset(t, 0, sizeof(HuffTab));
   int code = 0, k = 0;
@@ -534,9 +513,13 @@ size_t max_blocks(int H, int W) {
   return std::max({3 * b8h * b8w, 4 * b8h * b16w, 6 * b16h * b16w});
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+void launch_idct_colour(const DImg* d_img, int n, const short* coef, unsigned char* planes, int max_idct, long long max_dwords,
+                        hipStream_t s) {
+  jdec_idct<<<dim3(max_idct, n), JD_THREADS, 0, s>>>(d_img, coef, planes);
+  jdec_colour<<<dim3((unsigned)((max_dwords + JD_THREADS - 1) / JD_THREADS), n), JD_THREADS, 0, s>>>(d_img, planes);
+}
 
-}  // namespace
+}  // namespace jdec
 
 struct poco_jpeg_decoder {
   int max_h = 0, max_w = 0, max_batch = 0;
@@ -718,8 +701,7 @@ extern "C" int poco_jpeg_decode(poco_jpeg_decoder_t dec, const poco_jpeg_image* 
   jdec_scan<<<n, JD_THREADS, 0, s>>>(d_img, d_seg, dec->count, dec->seg_of, dec->prefix, dec->base, d_status);
   jdec_write<<<dim3(max_wg, n), JD_THREADS, 0, s>>>(dec->d_blob, d_img, d_seg, dec->entry, dec->seg_of, dec->base, dec->coef, d_status);
   jdec_dc<<<dim3((unsigned)nsegs, 3), JD_THREADS, 0, s>>>(d_img, d_seg, dec->coef);
-  jdec_idct<<<dim3(max_idct, n), JD_THREADS, 0, s>>>(d_img, dec->coef, dec->planes);
-  jdec_colour<<<dim3((unsigned)((max_dwords + JD_THREADS - 1) / JD_THREADS), n), JD_THREADS, 0, s>>>(d_img, dec->planes);
+  launch_idct_colour(d_img, n, dec->coef, dec->planes, max_idct, max_dwords, s);
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }

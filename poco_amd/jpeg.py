@@ -13,6 +13,9 @@ batch to the device decoder (poco_jpeg_decode, csrc/jpeg_dec.hip) and MjpegReade
     dec = JpegDecoder(device, 1080, 1920, max_batch=16, max_bytes=32 << 20)
     frames = dec.decode([open(p, "rb").read() for p in paths])       # uint8 [H,W,3] device tensors, PIL's pixels
     for data in MjpegReader("movie.avi"): ...
+
+Progressive files (SOF2) have their own pair: parse_progressive_jpeg records every scan of the file, ProgressiveJpegDecoder
+(poco_jpeg_prog_decode, csrc/jpeg_prog.hip) decodes a batch of them with the same call shape.
 """
 from __future__ import annotations
 
@@ -344,6 +347,186 @@ def parse_jpeg(data) -> Optional[JpegInfo]:
         return None
 
 
+# ---- progressive files: the scan table --------------------------------------------------------------------------------------------
+MAX_SCANS = 64                         # scans a progressive file may have (JP_MAX_SCANS in csrc/jpeg_prog.hip)
+TABLES_PER_IMAGE = 16                  # distinct Huffman tables a decoder plans per image of its batch (JP_TABS_PER_IMAGE there)
+
+
+@dataclass
+class ProgressiveScan:
+    """One SOS of a progressive file and the tables in force there."""
+    comps: tuple                       # indices into the frame's components
+    ss: int
+    se: int
+    ah: int
+    al: int
+    dc: list                           # per component of the scan (bits, huffval) - of a first DC scan, else None
+    ac: Optional[tuple]                # (bits, huffval) of an AC scan (first or refinement), else None
+    offset: int                        # the entropy-coded bytes: data[offset : offset + length], up to the next marker
+    length: int
+
+
+@dataclass
+class ProgressiveJpegInfo:
+    """What parse_progressive_jpeg found."""
+    height: int
+    width: int
+    ncomp: int                         # 1 (grayscale) or 3 (YCbCr)
+    hsamp: int                         # luma sampling, chroma is 1 x 1
+    vsamp: int
+    qt: np.ndarray                     # uint16 [ncomp, 64], natural order: the table in force at the component's first scan
+    scans: list                        # ProgressiveScan, in file order
+    data: bytes
+
+    @property
+    def mcus(self):
+        """(MCU rows, MCU columns)"""
+        return (-(-self.height // (8 * self.vsamp)), -(-self.width // (8 * self.hsamp)))
+
+    @property
+    def stream_length(self) -> int:
+        """Bytes from the first scan's data to the end of the last: what a decode call copies to the device."""
+        return self.scans[-1].offset + self.scans[-1].length - self.scans[0].offset
+
+
+def _parse_progressive(data: bytes) -> Optional[ProgressiveJpegInfo]:
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        return None
+    a = np.frombuffer(data, np.uint8)
+    markers = np.flatnonzero((a[:-1] == 0xFF) & (a[1:] != 0))       # every FF that is no stuffed data byte
+    qts, huff = {}, {}
+    frame, adobe = None, None
+    scans, qt, coef_bits = [], None, None
+    i = 2
+    while True:
+        if i >= n and scans:           # cut short inside (or right after) a scan: the device reports it
+            break
+        if i + 2 > n or data[i] != 0xFF:
+            return None
+        m = data[i + 1]
+        if m == 0xFF:                  # fill byte
+            i += 1
+            continue
+        if m == 0xD9:
+            break
+        if i + 4 > n:
+            return None
+        ln = (data[i + 2] << 8) | data[i + 3]
+        if m in (0xD8, 0x01) or 0xD0 <= m <= 0xD7 or ln < 2 or i + 2 + ln > n:
+            return None
+        p = data[i + 4:i + 2 + ln]
+        i += 2 + ln
+        if m == 0xC2:
+            if frame is not None or len(p) < 6 or p[0] != 8:
+                return None
+            H, W, nc = (p[1] << 8) | p[2], (p[3] << 8) | p[4], p[5]
+            if len(p) != 6 + 3 * nc or nc not in (1, 3) or not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+                return None
+            comps = [(p[6 + 3 * c], p[7 + 3 * c] >> 4, p[7 + 3 * c] & 15, p[8 + 3 * c]) for c in range(nc)]
+            if len({c[0] for c in comps}) != nc:
+                return None
+            if nc == 3:
+                if (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+                    return None
+            elif (comps[0][1], comps[0][2]) != (1, 1):
+                return None
+            frame = (H, W, comps)
+            qt = np.zeros((nc, 64), np.uint16)
+            coef_bits = np.full((nc, 64), -1, np.int64)             # jdphuff.c: the Al each coefficient has been sent down to
+        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8):
+            return None                # baseline, extended, lossless, arithmetic (and DAC): not decoded here
+        elif m == 0xC4:
+            j = 0
+            while j < len(p):
+                if j + 17 > len(p):
+                    return None
+                tc, th = p[j] >> 4, p[j] & 15
+                cnt = sum(p[j + 1:j + 17])
+                if tc > 1 or th > 3 or cnt > 256 or j + 17 + cnt > len(p):
+                    return None
+                huff[(tc, th)] = (bytes(p[j + 1:j + 17]), bytes(p[j + 17:j + 17 + cnt]))
+                j += 17 + cnt
+        elif m == 0xDB:
+            j = 0
+            while j < len(p):
+                if p[j] >> 4 != 0 or (p[j] & 15) > 3 or j + 65 > len(p):
+                    return None
+                q = np.zeros(64, np.uint16)
+                q[_ZIGZAG] = np.frombuffer(p[j + 1:j + 65], np.uint8)
+                qts[p[j] & 15] = q
+                j += 65
+        elif m == 0xDD:
+            if len(p) != 2 or p[0] or p[1]:
+                return None            # restart intervals in a progressive file: left to PIL
+        elif m == 0xEE and len(p) >= 12 and p[:5] == b"Adobe":
+            adobe = p[11]
+        elif m == 0xDA:
+            if frame is None or len(scans) >= MAX_SCANS or len(p) < 1:
+                return None
+            H, W, comps = frame
+            nc = len(comps)
+            if nc == 3 and not scans and ([c[0] for c in comps] == [82, 71, 66] or adobe == 0 or adobe == 2):
+                return None            # RGB / YCCK files
+            ns = p[0]
+            if len(p) != 4 + 2 * ns or ns not in (1, nc):
+                return None
+            ss, se, ah, al = p[1 + 2 * ns], p[2 + 2 * ns], p[3 + 2 * ns] >> 4, p[3 + 2 * ns] & 15
+            ids = [c[0] for c in comps]
+            if any(p[1 + 2 * k] not in ids for k in range(ns)):
+                return None
+            cs = tuple(ids.index(p[1 + 2 * k]) for k in range(ns))
+            if ns > 1 and cs != tuple(range(nc)):
+                return None
+            # jdphuff.c start_pass_phuff_decoder, with its warnings taken as errors
+            if (ss == 0 and se != 0) or (ss > 0 and (se < ss or se > 63 or ns != 1)) or al > 13 or (ah != 0 and ah != al + 1):
+                return None
+            dc, ac = [None] * ns, None
+            for k, c in enumerate(cs):
+                if ss > 0 and coef_bits[c, 0] < 0:
+                    return None        # an AC scan before the component's DC scan
+                band = coef_bits[c, ss:se + 1]
+                if np.any(band != (ah if ah else -1)):
+                    return None        # a first scan of coefficients sent before, or a refinement that does not follow Al = Ah
+                if np.all(coef_bits[c] < 0):
+                    if comps[c][3] not in qts:
+                        return None
+                    qt[c] = qts[comps[c][3]]
+                band[:] = al
+                td, ta = p[2 + 2 * k] >> 4, p[2 + 2 * k] & 15
+                if ss == 0 and ah == 0:
+                    dc[k] = t = huff.get((0, td))
+                    if t is None or not _prefix_code(t[0]) or len(t[1]) > 16 or any(v > 15 for v in t[1]):
+                        return None
+                elif ss > 0:
+                    ac = t = huff.get((1, ta))
+                    if t is None or not _prefix_code(t[0]):
+                        return None
+            j = int(np.searchsorted(markers, i))
+            end = int(markers[j]) if j < markers.size else n
+            scans.append(ProgressiveScan(cs, ss, se, ah, al, dc, ac, i, end - i))
+            i = end
+        # other APPn (JFIF, Exif ...) and COM: skipped
+    if frame is None or not scans or np.any(coef_bits < 0):
+        return None                    # a coefficient no scan sends: libjpeg smooths such blocks, this decoder does not
+    H, W, comps = frame
+    return ProgressiveJpegInfo(H, W, len(comps), comps[0][1], comps[0][2], qt, scans, data)
+
+
+def parse_progressive_jpeg(data) -> Optional[ProgressiveJpegInfo]:
+    """The marker walk of one progressive .jpg file (SOF2, 8 bit, Huffman): sizes, sampling, quantisation tables and per scan its
+    components, band (Ss, Se), successive approximation (Ah, Al), the Huffman tables in force at its SOS and where its
+    entropy-coded bytes lie - or None for a file ProgressiveJpegDecoder does not take (baseline - that is parse_jpeg's -,
+    arithmetic coding, 12 bit, CMYK / YCCK / RGB, other sampling factors, a restart interval, more than 64 scans, a scan of two
+    of three components, a scan script that breaks jdphuff.c's rules or leaves a coefficient of a component without any scan,
+    a damaged header); the caller then decodes with PIL.  A file cut short inside a scan is parsed when the scans it still has
+    cover every coefficient: the decoder reports it in the image's status word."""
+    try:
+        return _parse_progressive(bytes(data))
+    except (IndexError, ValueError):
+        return None
+
+
 class _CImage(C.Structure):
     _fields_ = [("data", C.c_void_p), ("nbytes", C.c_size_t), ("segs", C.c_void_p), ("nseg", C.c_int), ("H", C.c_int),
                 ("W", C.c_int), ("ncomp", C.c_int), ("hsamp", C.c_int), ("vsamp", C.c_int), ("qt", C.c_uint16 * 64 * 3),
@@ -443,6 +626,146 @@ class JpegDecoder:
         infos = [im if isinstance(im, JpegInfo) else parse_jpeg(im) for im in images]
         if any(i is None for i in infos):
             raise PocoHipError("JpegDecoder: not a baseline JPEG file this decoder takes (parse_jpeg returned None)")
+        outs = [torch.empty(i.height, i.width, 3, dtype=torch.uint8, device=self.device) for i in infos]
+        status = self.decode_into(infos, outs)
+        return (outs, status.cpu().tolist()) if return_status else outs
+
+
+class _CProgTable(C.Structure):
+    _fields_ = [("bits", C.c_uint8 * 16), ("vals", C.c_uint8 * 256)]
+
+
+class _CProgScan(C.Structure):
+    _fields_ = [("offset", C.c_uint), ("length", C.c_uint), ("ncomp", C.c_uint8), ("comp", C.c_uint8 * 3), ("ss", C.c_uint8),
+                ("se", C.c_uint8), ("ah", C.c_uint8), ("al", C.c_uint8), ("tab", C.c_short * 3), ("pad", C.c_short)]
+
+
+class _CProgImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("nbytes", C.c_size_t), ("scans", C.c_void_p), ("nscan", C.c_int), ("tables", C.c_void_p),
+                ("ntable", C.c_int), ("H", C.c_int), ("W", C.c_int), ("ncomp", C.c_int), ("hsamp", C.c_int), ("vsamp", C.c_int),
+                ("qt", C.c_uint16 * 64 * 3), ("d_rgb", C.c_void_p)]
+
+
+def _scan_tables(info: ProgressiveJpegInfo):
+    """The distinct Huffman tables of a file's scans, as (is AC, bits, huffval), and per scan the indices of its tables."""
+    tables, index, per_scan = [], {}, []
+    for sc in info.scans:
+        used = [(1, *sc.ac)] if sc.ac is not None else [(0, *t) for t in sc.dc if t is not None]
+        ids = []
+        for t in used:
+            if t not in index:
+                index[t] = len(tables)
+                tables.append(t)
+            ids.append(index[t])
+        per_scan.append(ids)
+    return tables, per_scan
+
+
+class ProgressiveJpegDecoder:
+    """Progressive JPEG files -> uint8 [H,W,3] RGB device tensors holding the pixels PIL gives: JpegDecoder's call shape for the
+    files parse_progressive_jpeg accepts (a binding of poco_jpeg_prog_* in include/poco_hip.h, csrc/jpeg_prog.hip).  Up to
+    max_batch images of up to max_h x max_w and max_bytes of scan data per call, of mixed sizes, samplings and scan scripts."""
+
+    def __init__(self, device, max_h: int, max_w: int, max_batch: int = 1, max_bytes: int = 0):
+        max_h, max_w, max_batch = int(max_h), int(max_w), int(max_batch)
+        max_bytes = int(max_bytes) or max_batch * max(1 << 16, max_h * max_w)
+        if not (1 <= max_h <= MAX_SIDE and 1 <= max_w <= MAX_SIDE):
+            raise PocoHipError(f"ProgressiveJpegDecoder: max_h, max_w must be in 1..{MAX_SIDE}, got {max_h} x {max_w}")
+        if not 1 <= max_batch <= 4096:
+            raise PocoHipError(f"ProgressiveJpegDecoder: max_batch must be in 1..4096, got {max_batch}")
+        if not 1 <= max_bytes <= 1 << 30:
+            raise PocoHipError(f"ProgressiveJpegDecoder: max_bytes must be in 1..2^30, got {max_bytes}")
+        self.max_h, self.max_w, self.max_batch, self.max_bytes = max_h, max_w, max_batch, max_bytes
+        self._h = C.c_void_p()
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        L = lib()
+        L.poco_jpeg_prog_decoder_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.poco_jpeg_prog_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.poco_jpeg_prog_decoder_destroy.argtypes = [C.c_void_p]
+        L.poco_jpeg_prog_decoder_destroy.restype = None
+        with torch.cuda.device(self.device):
+            check(L.poco_jpeg_prog_decoder_create(max_h, max_w, max_batch, max_bytes, C.byref(self._h)),
+                  "poco_jpeg_prog_decoder_create")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().poco_jpeg_prog_decoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def fits(self, info: ProgressiveJpegInfo) -> bool:
+        """The picture's size and its number of distinct Huffman tables are within what every image of a batch may have."""
+        return info.height <= self.max_h and info.width <= self.max_w and len(_scan_tables(info)[0]) <= TABLES_PER_IMAGE
+
+    def decode_into(self, images, outs, status: torch.Tensor = None) -> torch.Tensor:
+        """Enqueue the decode of `images` (bytes of progressive .jpg files or ProgressiveJpegInfo, at most max_batch) into `outs`
+        (contiguous uint8 [H,W,3] device tensors of the files' sizes) on the current stream: one host-to-device copy, no host
+        synchronisation.  Returns `status`, an int32 [n] device tensor: 0 per decoded image, non-zero for a damaged stream."""
+        infos = []
+        for im in images:
+            info = im if isinstance(im, ProgressiveJpegInfo) else parse_progressive_jpeg(im)
+            if info is None:
+                raise PocoHipError("ProgressiveJpegDecoder: not a progressive JPEG file this decoder takes (parse_progressive_jpeg "
+                                   "returned None)")
+            infos.append(info)
+        n = len(infos)
+        if not 1 <= n <= self.max_batch:
+            raise PocoHipError(f"ProgressiveJpegDecoder: {n} images in one call, the decoder was created for 1..{self.max_batch}")
+        if len(outs) != n:
+            raise PocoHipError(f"ProgressiveJpegDecoder: {n} images but {len(outs)} output tensors")
+        for info, o in zip(infos, outs):
+            if not (torch.is_tensor(o) and o.device == self.device and o.dtype == torch.uint8 and o.is_contiguous()
+                    and tuple(o.shape) == (info.height, info.width, 3)):
+                raise PocoHipError(f"ProgressiveJpegDecoder: an output must be a contiguous uint8 [{info.height},{info.width},3] "
+                                   f"tensor on {self.device}")
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=self.device)
+        elif not (torch.is_tensor(status) and status.device == self.device and status.dtype == torch.int32
+                  and status.is_contiguous() and status.numel() >= n):
+            raise PocoHipError("ProgressiveJpegDecoder: status must be a contiguous int32 tensor of at least n elements on the "
+                               "decoder's device")
+        arr = (_CProgImage * n)()
+        keep = []
+        for s, info, o in zip(arr, infos, outs):
+            buf = np.frombuffer(info.data, np.uint8)
+            qt = np.ascontiguousarray(info.qt, np.uint16)
+            tables, per_scan = _scan_tables(info)
+            ctab = (_CProgTable * max(1, len(tables)))()
+            for ct, (_, bits, vals) in zip(ctab, tables):
+                C.memmove(ct.bits, bits, 16)
+                C.memmove(ct.vals, vals, len(vals))
+            base = info.scans[0].offset
+            cscan = (_CProgScan * len(info.scans))()
+            for cs, sc, tabs in zip(cscan, info.scans, per_scan):
+                cs.offset, cs.length, cs.ncomp = sc.offset - base, sc.length, len(sc.comps)
+                cs.ss, cs.se, cs.ah, cs.al = sc.ss, sc.se, sc.ah, sc.al
+                for k, c in enumerate(sc.comps):
+                    cs.comp[k] = c
+                for k, t in enumerate(tabs):
+                    cs.tab[k] = t
+            keep += [buf, qt, ctab, cscan]
+            s.data, s.nbytes = buf.ctypes.data + base, info.stream_length
+            s.scans, s.nscan = C.addressof(cscan), len(info.scans)
+            s.tables, s.ntable = C.addressof(ctab), len(tables)
+            s.H, s.W, s.ncomp, s.hsamp, s.vsamp = info.height, info.width, info.ncomp, info.hsamp, info.vsamp
+            C.memmove(s.qt, qt.ctypes.data, info.ncomp * 128)
+            s.d_rgb = o.data_ptr()
+        check(lib().poco_jpeg_prog_decode(self._h, C.cast(arr, C.c_void_p), n, status.data_ptr(),
+                                          C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "poco_jpeg_prog_decode")
+        return status
+
+    def decode(self, images, return_status: bool = False):
+        """The pictures of `images` as new device tensors.  return_status: also the list of status words (this reads them back,
+        the call's only host synchronisation)."""
+        infos = [im if isinstance(im, ProgressiveJpegInfo) else parse_progressive_jpeg(im) for im in images]
+        if any(i is None for i in infos):
+            raise PocoHipError("ProgressiveJpegDecoder: not a progressive JPEG file this decoder takes (parse_progressive_jpeg "
+                               "returned None)")
         outs = [torch.empty(i.height, i.width, 3, dtype=torch.uint8, device=self.device) for i in infos]
         status = self.decode_into(infos, outs)
         return (outs, status.cpu().tolist()) if return_status else outs

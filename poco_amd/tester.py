@@ -189,8 +189,17 @@ class POCOTester:
     def decode_png_on_gpu(self) -> bool:
         return getattr(self.args, "decode_png", "host") == "gpu"
 
+    @property
+    def decode_progressive_on_gpu(self) -> bool:
+        return getattr(self.args, "decode_progressive", "host") == "gpu"
+
+    @property
+    def decode_any_on_gpu(self) -> bool:
+        return self.decode_on_gpu or self.decode_png_on_gpu or self.decode_progressive_on_gpu
+
     def to_device(self, frame) -> torch.Tensor:
-        """A frame as a uint8 [H,W,3] device tensor: decoded there already (--decode gpu, --decode_png gpu) or uploaded."""
+        """A frame as a uint8 [H,W,3] device tensor: decoded there already (--decode gpu, --decode_png gpu, --decode_progressive
+        gpu) or uploaded."""
         return frame if torch.is_tensor(frame) else torch.from_numpy(np.ascontiguousarray(frame)).to(self.device)
 
     def _device_decode(self, named, out, infos, attr, cls, flag, nbytes_of):
@@ -220,7 +229,8 @@ class POCOTester:
     def decode_frames(self, named) -> list:
         """named: [(name, the bytes of an image file)] -> the frames in order, routed by signature: with --decode gpu all baseline
         JPEGs of the list are decoded in ONE device call, with --decode_png gpu all PNGs parse_png accepts in another (uint8
-        [H,W,3] device tensors, PIL's pixels).  A file the parser declines (progressive JPEG, 16-bit or interlaced PNG ...), a
+        [H,W,3] device tensors, PIL's pixels), with --decode_progressive gpu all progressive JPEGs parse_progressive_jpeg accepts
+        in a third.  A file the parser declines (progressive JPEG without its flag, 16-bit or interlaced PNG ...), a
         format whose flag is not set and an image whose status word comes back non-zero go through PIL (host arrays); the
         latter is named in one warning, and so is a JPEG with more restart intervals than a decoder plans per image.  Any error
         of a decode call is raised.  The decoders are created for the first batch's sizes and re-created when a larger one
@@ -243,6 +253,17 @@ class POCOTester:
             from .png import SIGNATURE, PngDecoder, parse_png
             infos = [parse_png(b) if b[:8] == SIGNATURE else None for _, b in named]
             self._device_decode(named, out, infos, "_pdec", PngDecoder, "--decode_png gpu", lambda f: f.stream_length)
+        if self.decode_progressive_on_gpu:
+            from .jpeg import TABLES_PER_IMAGE, ProgressiveJpegDecoder, _scan_tables, parse_progressive_jpeg
+            infos = [parse_progressive_jpeg(b) if b[:2] == b"\xff\xd8" else None for _, b in named]
+            many = [i for i, f in enumerate(infos) if f is not None and len(_scan_tables(f)[0]) > TABLES_PER_IMAGE]
+            if many:
+                warnings.warn(f"--decode_progressive gpu: {', '.join(named[i][0] for i in many)}: more than {TABLES_PER_IMAGE} Huffman "
+                              "tables, which the device decoder does not plan for; decoding with PIL")
+                for i in many:
+                    infos[i] = None
+            self._device_decode(named, out, infos, "_jpdec", ProgressiveJpegDecoder, "--decode_progressive gpu",
+                                lambda f: f.stream_length)
         for i, (_, b) in enumerate(named):
             if out[i] is None:
                 out[i] = np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))
@@ -458,7 +479,7 @@ class POCOTester:
         ahead = max(4, self.model.max_batch)
         ahead_bytes = 256 << 20
 
-        on_gpu = self.decode_on_gpu or self.decode_png_on_gpu
+        on_gpu = self.decode_any_on_gpu
 
         def decode(n):
             if on_gpu:                                   # the file's bytes: routed and decoded per batch (decode_frames)
@@ -628,7 +649,7 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
     skip = max(int(getattr(self.args, "skip_frame", 1)), 1)
     if skip > 1:
         tracking = {k: {"bbox": v["bbox"][::skip], "frames": v["frames"][::skip]} for k, v in tracking.items()}
-    if self.decode_on_gpu or self.decode_png_on_gpu:
+    if self.decode_any_on_gpu:
         load = _GroupLoader(self, names, read, H, W)
     elif reader is not None:
         load = lambda i: np.asarray(Image.open(io.BytesIO(read(i))).convert("RGB"))                # noqa: E731

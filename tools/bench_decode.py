@@ -10,7 +10,12 @@ Every case runs in a child process of its own under a time limit, so a case that
     python tools/bench_decode.py --png [--folder 16]
 The PNG decoder (poco_png_decode: one copy, inflate, unfilter) instead, 5 repeats per case, against PIL decode on 16 threads plus
 the upload; the files are a photo-like frame saved by PIL at its default level and the same frame from this project's PngEncoder.
-Writes profiles/decode_png.txt; --folder N times folder mode with and without --decode_png gpu."""
+Writes profiles/decode_png.txt; --folder N times folder mode with and without --decode_png gpu.
+
+    python tools/bench_decode.py --progressive [--folder 16]
+The progressive JPEG decoder (poco_jpeg_prog_decode: one copy, one launch per level of the scan order, inverse DCT, colour) on the
+photo-like frame saved by PIL as a progressive 4:2:0 file of quality 90 (10 scans), measured as the PNG decoder is.  Writes
+profiles/decode_progressive.txt; --folder N times folder mode per setting of --decode_progressive."""
 import argparse
 import io
 import json
@@ -145,7 +150,57 @@ def png_case(source, n):
             "gpu_worst_below_host_best": max(ms) < min(hs)}
 
 
-def folder(n, png=False):
+def prog_case(n):
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from poco_amd import jpeg
+    dev = torch.device("cuda:0")
+    data = prog_stream()
+    info = jpeg.parse_progressive_jpeg(data)
+    dec = jpeg.ProgressiveJpegDecoder(dev, H, W, max_batch=n, max_bytes=n * (len(data) + 4096))
+    outs = [torch.empty(H, W, 3, dtype=torch.uint8, device=dev) for _ in range(n)]
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    dec.decode_into([info] * n, outs, status)
+    torch.cuda.synchronize()
+    assert status.cpu().tolist() == [0] * n
+    ref = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+    assert np.array_equal(outs[-1].cpu().numpy(), ref), "device pixels differ from PIL's"
+    ms = []
+    for _ in range(PNG_REPEATS):           # wall time of the call as the demo makes it: bytes in, pixels on the device
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dec.decode_into([info] * n, outs, status)
+        torch.cuda.synchronize()
+        ms.append(1000 * (time.perf_counter() - t0))
+    pinned = [torch.empty(H, W, 3, dtype=torch.uint8).pin_memory() for _ in range(n)]
+
+    def host(i):
+        pinned[i].numpy()[...] = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+
+    hs = []
+    with ThreadPoolExecutor(PNG_POOL) as pool:
+        list(pool.map(host, range(n)))
+        for _ in range(PNG_REPEATS):
+            t0 = time.perf_counter()
+            list(pool.map(host, range(n)))
+            for i in range(n):
+                outs[i].copy_(pinned[i], non_blocking=True)
+            torch.cuda.synchronize()
+            hs.append(1000 * (time.perf_counter() - t0))
+    return {"bench": "jpeg_progressive_decode", "images": n, "H": H, "W": W, "bytes": len(data), "scans": len(info.scans),
+            "gpu_ms": [round(v, 3) for v in ms], "host_pil_upload_ms": [round(v, 3) for v in hs], "host_threads": PNG_POOL,
+            "gpu_worst_below_host_best": max(ms) < min(hs)}
+
+
+def prog_stream():
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(picture("photo")).save(buf, "JPEG", quality=90, subsampling="4:2:0", progressive=True)
+    return buf.getvalue()
+
+
+def folder(n, png=False, progressive=False):
     import torch
     import demo
     from poco_amd import synth
@@ -162,6 +217,8 @@ def folder(n, png=False):
         buf = io.BytesIO()
         Image.fromarray(picture("photo")).save(buf, "PNG")
         data = buf.getvalue()
+    elif progressive:
+        data = prog_stream()
     else:
         data = stream("photo", False)
     for i in range(n):
@@ -170,11 +227,11 @@ def folder(n, png=False):
     for mode in ("host", "gpu"):
         a = demo.parse_args(["--cfg", "configs/demo_poco_cliff_resnet50.yaml", "--ckpt", str(tmp / "ckpt.pt"), "--mode", "folder",
                              "--image_folder", str(imgs), "--output_folder", str(tmp / "out"), "--batch_size", "16",
-                             "--smpl", str(tmp / "smpl.npz"), "--decode_png" if png else "--decode", mode])
+                             "--smpl", str(tmp / "smpl.npz"), "--decode_png" if png else "--decode_progressive" if progressive else "--decode", mode])
         t = POCOTester(a)
         t.run_on_image_folder(str(imgs), None, str(tmp / "out"))          # warm-up (allocator, file cache)
         st = t.run_on_image_folder(str(imgs), None, str(tmp / "out"))
-        out.append({"bench": "folder_decode_png" if png else "folder_decode", "images": n, "H": H, "W": W, "decode": mode,
+        out.append({"bench": "folder_decode_png" if png else "folder_decode_progressive" if progressive else "folder_decode", "images": n, "H": H, "W": W, "decode": mode,
                     "ms_per_image": round(1000 * st["seconds"] / n, 2)})
         del t
     return out
@@ -185,6 +242,7 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--folder", type=int, default=0)
     ap.add_argument("--png", action="store_true", help="the PNG decoder's cases instead of the JPEG decoder's")
+    ap.add_argument("--progressive", action="store_true", help="the progressive JPEG decoder's cases instead")
     ap.add_argument("--case", default=None, help="(internal) kind,restart,n | folder,N: run one case in this process")
     ap.add_argument("--limit", type=int, default=240, help="seconds per case")
     args = ap.parse_args()
@@ -192,8 +250,10 @@ if __name__ == "__main__":
         parts = args.case.split(",")
         if parts[0] == "png":
             res = [png_case(parts[1], int(parts[2]))]
-        elif parts[0] in ("folder", "pngfolder"):
-            res = folder(int(parts[1]), png=parts[0] == "pngfolder")
+        elif parts[0] == "prog":
+            res = [prog_case(int(parts[1]))]
+        elif parts[0] in ("folder", "pngfolder", "progfolder"):
+            res = folder(int(parts[1]), png=parts[0] == "pngfolder", progressive=parts[0] == "progfolder")
         else:
             res = [case(parts[0], parts[1] == "1", int(parts[2]), args.iters)]
         for r in res:
@@ -202,16 +262,18 @@ if __name__ == "__main__":
     cases = [f"{k},{r},{n}" for k in ("photo", "noise") for r in (0, 1) for n in (1, 16, 64)]
     if args.png:
         cases = [f"png,{src},{n}" for src in ("pil", "own") for n in (1, 16, 64)]
+    if args.progressive:
+        cases = [f"prog,{n}" for n in (1, 16, 64)]
     if args.folder:
-        cases.append(f"{'pngfolder' if args.png else 'folder'},{args.folder}")
-    prof = ROOT / "profiles" / ("decode_png.txt" if args.png else "decode.txt")
+        cases.append(f"{'pngfolder' if args.png else 'progfolder' if args.progressive else 'folder'},{args.folder}")
+    prof = ROOT / "profiles" / ("decode_png.txt" if args.png else "decode_progressive.txt" if args.progressive else "decode.txt")
     prof.parent.mkdir(exist_ok=True)
     with open(prof, "a") as log:
         for c in cases:
             cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--iters", str(args.iters)]
             p = subprocess.run(cmd, capture_output=True, text=True)
             if p.returncode != 0:          # a fault, an abort or the time limit: nothing more is started on the GPU
-                msg = json.dumps({"bench": "png_decode" if args.png else "jpeg_decode", "case": c, "failed": p.returncode, "stderr": p.stderr[-400:]})
+                msg = json.dumps({"bench": "png_decode" if args.png else "jpeg_progressive_decode" if args.progressive else "jpeg_decode", "case": c, "failed": p.returncode, "stderr": p.stderr[-400:]})
                 print(msg, flush=True)
                 print(msg, file=log, flush=True)
                 sys.exit(1)
