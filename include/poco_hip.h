@@ -516,7 +516,12 @@ void poco_jpeg_decoder_destroy(poco_jpeg_decoder_t dec);
  * file on the device.
  *   Streams: progressive Huffman (SOF2), 8 bit, no restart interval; components and sampling as for poco_jpeg_decode; up to 64
  *     scans: DC first and refinement scans (of one component, or interleaved over all), AC first scans with end-of-band runs and
- *     AC refinement scans with correction bits (one component each), any successive approximation; DHT between scans.
+ *     AC refinement scans with correction bits (one component each), any successive approximation with Al <= 13; DHT between
+ *     scans, at most 16 distinct Huffman tables per file.  Every coefficient of every component must end at Al = 0: libjpeg
+ *     smooths the blocks of a picture whose script stops above that (jdcoefct.c), this decoder does not, so such a script is
+ *     refused (POCO_ERR_ARG) and the pixels of every file that is taken are libjpeg's.  The one exception is a file cut short
+ *     (no EOI; its last scan carries POCO_JPEG_PROG_SCAN_CUT): it is taken whatever Al it ends at, and if that is above 0 its
+ *     status word is non-zero (2) whatever its last scan decodes to.
  *   Arithmetic: integers only; the pixels equal libjpeg's (what PIL gives) and those of tests/jpegprog_np.py.  The coefficient
  *     stage follows jdphuff.c and writes final values (DC prediction undone by the lane that walks the scan) into the zeroed int16
  *     coefficient buffer in natural order; dequantisation, inverse DCT, upsampling and colour are poco_jpeg_decode's kernels.
@@ -537,8 +542,9 @@ typedef struct poco_jpeg_prog_scan {
   unsigned char ncomp, comp[3];   /* components of the scan (indices into the frame's): 1, or all of them for a DC scan */
   unsigned char ss, se, ah, al;   /* spectral selection and successive approximation */
   short tab[3];                   /* tables[]: per component the DC table of a first DC scan; [0] the AC table of an AC scan */
-  short pad;
+  short flags;                    /* POCO_JPEG_PROG_SCAN_CUT on the last scan of a file that ends without EOI, else 0 */
 } poco_jpeg_prog_scan;
+#define POCO_JPEG_PROG_SCAN_CUT 1
 /* One parsed file (all pointers on the host except d_rgb). */
 typedef struct poco_jpeg_prog_image {
   const unsigned char* data;      /* the file's bytes from its first scan to the end of its last */
@@ -561,8 +567,9 @@ int poco_jpeg_prog_decoder_create(int max_h, int max_w, int max_batch, size_t ma
  * atomics.  d_status int32 [n] as for poco_jpeg_decode.  POCO_ERR_ARG before any GPU work: null handle or pointer, n outside
  * 1 .. max_batch, a size outside the created maximum, sampling or component counts other than those above, a scan table that
  * breaks the rules of parse_progressive_jpeg (band, components, successive approximation, a table index outside tables[], a scan
- * outside the data), a Huffman table that is no prefix code, or more bytes than the decoder was created for.  One decoder is used
- * from one stream at a time. */
+ * outside the data, a coefficient no scan sends, a script that ends above Al = 0 in a file not marked as cut short), a Huffman table
+ * that is no prefix code, more than 16 distinct Huffman tables in one file, or more bytes than the decoder was created for.  One
+ * decoder is used from one stream at a time. */
 int poco_jpeg_prog_decode(poco_jpeg_prog_decoder_t dec, const poco_jpeg_prog_image* imgs, int n, int* d_status, void* stream);
 void poco_jpeg_prog_decoder_destroy(poco_jpeg_prog_decoder_t dec);
 

@@ -364,6 +364,7 @@ extern "C" int poco_jpeg_prog_decode(poco_jpeg_prog_decoder_t dec, const poco_jp
   std::vector<PScan> scans;                 // in call order; sorted by level below
   std::vector<int> level;
   std::vector<HuffTab> tabs;
+  std::vector<int> cut_short;               // images cut short above Al = 0: their status word starts non-zero
   for (int i = 0; i < n; ++i) {
     const poco_jpeg_prog_image& im = imgs[i];
     const std::string who = "poco_jpeg_prog_decode: image " + std::to_string(i) + ": ";
@@ -458,6 +459,18 @@ extern "C" int poco_jpeg_prog_decode(poco_jpeg_prog_decoder_t dec, const poco_jp
     for (int c = 0; c < im.ncomp; ++c)
       for (int z = 0; z < 64; ++z)
         if (bits[c][z] < 0) { poco_set_error(who + "a coefficient no scan sends"); return POCO_ERR_ARG; }
+    // libjpeg smooths the blocks of a picture whose low AC coefficients have not reached Al = 0 (jdcoefct.c); this decoder does not, so
+    // such a script is not taken.  A file CUT SHORT inside such a script is taken, and is damaged whatever its last scan decodes to.
+    bool above = false;
+    for (int c = 0; c < im.ncomp; ++c)
+      for (int z = 0; z < 64; ++z) above = above || bits[c][z] > 0;
+    if (above) {
+      if (!(im.scans[im.nscan - 1].flags & POCO_JPEG_PROG_SCAN_CUT)) {
+        poco_set_error(who + "the scan script ends with a coefficient above Al = 0 (libjpeg smooths such pictures; decode them with it)");
+        return POCO_ERR_ARG;
+      }
+      cut_short.push_back(i);
+    }
     if (tabs.size() - tabs0 > (size_t)JP_TABS_PER_IMAGE) {
       poco_set_error(who + "more than " + std::to_string(JP_TABS_PER_IMAGE) + " Huffman tables");
       return POCO_ERR_ARG;
@@ -499,6 +512,7 @@ extern "C" int poco_jpeg_prog_decode(poco_jpeg_prog_decoder_t dec, const poco_jp
   POCO_HIP_CHECK(hipEventRecord(dec->copied, s));
   dec->in_flight = true;
   POCO_HIP_CHECK(hipMemsetAsync(d_status, 0, (size_t)n * sizeof(int), s));
+  for (int i : cut_short) POCO_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(d_status + i), JD_ERR_SHORT, 1, s));
   POCO_HIP_CHECK(hipMemsetAsync(dec->coef, 0, nblocks * 64 * sizeof(short), s));
   const DImg* d_img = reinterpret_cast<const DImg*>(dec->d_blob);
   const PScan* d_scan = reinterpret_cast<const PScan*>(dec->d_blob + img_bytes);

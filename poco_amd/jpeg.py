@@ -377,6 +377,7 @@ class ProgressiveJpegInfo:
     qt: np.ndarray                     # uint16 [ncomp, 64], natural order: the table in force at the component's first scan
     scans: list                        # ProgressiveScan, in file order
     data: bytes
+    cut: bool = False                  # the file ends inside (or right after) its last scan, without EOI
 
     @property
     def mcus(self):
@@ -398,9 +399,11 @@ def _parse_progressive(data: bytes) -> Optional[ProgressiveJpegInfo]:
     qts, huff = {}, {}
     frame, adobe = None, None
     scans, qt, coef_bits = [], None, None
+    cut = False
     i = 2
     while True:
         if i >= n and scans:           # cut short inside (or right after) a scan: the device reports it
+            cut = True
             break
         if i + 2 > n or data[i] != 0xFF:
             return None
@@ -509,8 +512,10 @@ def _parse_progressive(data: bytes) -> Optional[ProgressiveJpegInfo]:
         # other APPn (JFIF, Exif ...) and COM: skipped
     if frame is None or not scans or np.any(coef_bits < 0):
         return None                    # a coefficient no scan sends: libjpeg smooths such blocks, this decoder does not
+    if np.any(coef_bits > 0) and not cut:
+        return None                    # a script that ends above Al = 0: libjpeg smooths such pictures too (jdcoefct.c smoothing_ok)
     H, W, comps = frame
-    return ProgressiveJpegInfo(H, W, len(comps), comps[0][1], comps[0][2], qt, scans, data)
+    return ProgressiveJpegInfo(H, W, len(comps), comps[0][1], comps[0][2], qt, scans, data, cut)
 
 
 def parse_progressive_jpeg(data) -> Optional[ProgressiveJpegInfo]:
@@ -518,9 +523,14 @@ def parse_progressive_jpeg(data) -> Optional[ProgressiveJpegInfo]:
     components, band (Ss, Se), successive approximation (Ah, Al), the Huffman tables in force at its SOS and where its
     entropy-coded bytes lie - or None for a file ProgressiveJpegDecoder does not take (baseline - that is parse_jpeg's -,
     arithmetic coding, 12 bit, CMYK / YCCK / RGB, other sampling factors, a restart interval, more than 64 scans, a scan of two
-    of three components, a scan script that breaks jdphuff.c's rules or leaves a coefficient of a component without any scan,
-    a damaged header); the caller then decodes with PIL.  A file cut short inside a scan is parsed when the scans it still has
-    cover every coefficient: the decoder reports it in the image's status word."""
+    of three components, a scan script that breaks jdphuff.c's rules, leaves a coefficient of a component without any scan or
+    ends with any coefficient of any component above Al = 0 - libjpeg smooths the blocks of such pictures, this decoder does
+    not, so only PIL gives PIL's pixels for them -, a damaged header); the caller then decodes with PIL.  A file cut short
+    inside a scan (no EOI behind its last scan; `cut` is set) keeps being parsed when the scans it still has cover every
+    coefficient, whatever Al they end at: it yields no pixels, the decoder reports it in the image's status word - non-zero
+    whenever the script it still has ends above Al = 0, also when the cut falls exactly between two scans.  A file may hold more
+    distinct Huffman tables than a decoder plans per image (TABLES_PER_IMAGE): it is parsed, ProgressiveJpegDecoder.fits says
+    no and decode refuses it."""
     try:
         return _parse_progressive(bytes(data))
     except (IndexError, ValueError):
@@ -637,7 +647,10 @@ class _CProgTable(C.Structure):
 
 class _CProgScan(C.Structure):
     _fields_ = [("offset", C.c_uint), ("length", C.c_uint), ("ncomp", C.c_uint8), ("comp", C.c_uint8 * 3), ("ss", C.c_uint8),
-                ("se", C.c_uint8), ("ah", C.c_uint8), ("al", C.c_uint8), ("tab", C.c_short * 3), ("pad", C.c_short)]
+                ("se", C.c_uint8), ("ah", C.c_uint8), ("al", C.c_uint8), ("tab", C.c_short * 3), ("flags", C.c_short)]
+
+
+PROG_SCAN_CUT = 1                      # POCO_JPEG_PROG_SCAN_CUT
 
 
 class _CProgImage(C.Structure):
@@ -748,6 +761,7 @@ class ProgressiveJpegDecoder:
                     cs.comp[k] = c
                 for k, t in enumerate(tabs):
                     cs.tab[k] = t
+            cscan[len(info.scans) - 1].flags = PROG_SCAN_CUT if info.cut else 0
             keep += [buf, qt, ctab, cscan]
             s.data, s.nbytes = buf.ctypes.data + base, info.stream_length
             s.scans, s.nscan = C.addressof(cscan), len(info.scans)

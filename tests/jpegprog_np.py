@@ -5,6 +5,9 @@ the pixels are PIL's, byte for byte, and the device must produce these BYTES.
 
     decode(data) -> uint8 [H,W,3]                 raises JpegError on a damaged stream
     decode_status(data) -> (pixels | None, status) status as the device's word: 0, ERR_CODE or ERR_SHORT of the first damaged scan
+    both take a dict `stats` that receives counters of what the file made the decoder do (longest end-of-band runs, runs of
+    exactly 32767, correction bits - also those of blocks wholly inside an end-of-band run of a refinement scan -, symbols and
+    how many of them had codes past the lookahead table, the levels of the scan order, DC scans of one component)
 
 The bit reader is the device's: bits MSB first from the scan's bytes with the 0x00 behind every 0xFF skipped; a scan that asks
 for more bits than it has is ERR_SHORT.  Damage ends the scan: a window that holds no code, a run that passes Se, an end-of-band
@@ -29,7 +32,8 @@ class JpegError(J.JpegError):
 class Bits:
     """The scan's bits, MSB first."""
 
-    def __init__(self, data: bytes, lo: int, hi: int):
+    def __init__(self, data: bytes, lo: int, hi: int, stats=None):
+        self.stats = stats
         raw = data[lo:hi].replace(b"\xff\x00", b"\xff")
         self.real = 8 * len(raw)
         self.total = self.real + 64                        # zeros behind the end, so that a 16-bit window can always be read
@@ -60,6 +64,9 @@ class Bits:
         if ln == 0:
             raise JpegError("no Huffman code at bit %d" % self.pos)
         self.skip(ln)
+        if self.stats is not None:
+            self.stats["symbols"] += 1
+            self.stats["long_codes"] += ln > J.LOOKAHEAD   # the device's slow path: no entry in the lookahead table
         return sym
 
     def value(self, s: int) -> int:
@@ -129,6 +136,7 @@ def ac_first(bits, scan, blocks, coef, tab, stats):
                 if run > n - 1 - i:
                     raise JpegError("an end-of-band run passes the last block")
                 stats["eobrun"] = max(stats["eobrun"], run + 1)
+                stats["eobrun_cap"] += run + 1 == 0x7FFF
                 i += run
                 break
             k += 1
@@ -147,6 +155,7 @@ def ac_refine(bits, scan, blocks, coef, tab, stats):
     eobrun = 0
     for i, (_, blk) in enumerate(blocks):
         k = scan.ss
+        inside = eobrun > 0                                # the whole block lies inside an end-of-band run
         if eobrun == 0:
             while k <= scan.se:
                 sym = bits.symbol(tab)
@@ -160,6 +169,7 @@ def ac_refine(bits, scan, blocks, coef, tab, stats):
                     eobrun = (1 << r) + bits.get(r)
                     if eobrun - 1 > len(blocks) - 1 - i:
                         raise JpegError("an end-of-band run passes the last block")
+                    stats["refine_eobrun"] = max(stats["refine_eobrun"], eobrun)
                     break
                 else:
                     stats["refine_zrl"] += 1
@@ -182,6 +192,7 @@ def ac_refine(bits, scan, blocks, coef, tab, stats):
                 if coef[blk, ZZ[k]] != 0:
                     _correct(bits, coef, blk, k, p1)
                     stats["corrections"] += 1
+                    stats["eob_corrections"] += inside
                 k += 1
             eobrun -= 1
 
@@ -192,11 +203,20 @@ def coefficients(info, stats=None):
     g = Geometry(info)
     coef = np.zeros((g.nblocks, 64), np.int32)
     stats = stats if stats is not None else {}
-    for key in ("eobrun", "refine_zrl", "corrections"):
+    for key in ("eobrun", "eobrun_cap", "refine_eobrun", "refine_zrl", "corrections", "eob_corrections", "symbols", "long_codes",
+                "levels", "dc_alone", "dc_refine_ragged_luma"):
         stats.setdefault(key, 0)
+    depth = np.zeros((info.ncomp, 64), np.int64)           # scans that have touched each (component, coefficient) so far
     for scan in info.scans:
-        bits = Bits(info.data, scan.offset, scan.offset + scan.length)
+        bits = Bits(info.data, scan.offset, scan.offset + scan.length, stats)
         blocks = g.scan_blocks(scan.comps)
+        band = depth[list(scan.comps), scan.ss:scan.se + 1]
+        depth[list(scan.comps), scan.ss:scan.se + 1] = band.max() + 1      # the device's level of this scan, plus one
+        stats["levels"] = max(stats["levels"], int(depth.max()))
+        if scan.ss == 0 and len(scan.comps) == 1 and info.ncomp > 1:
+            stats["dc_alone"] += 1
+            # luma's own raster is narrower than the MCU raster: the walk differs from the interleaved one
+            stats["dc_refine_ragged_luma"] += scan.ah > 0 and scan.comps[0] == 0 and g.bw[0] % g.hs != 0
         try:
             if scan.ss == 0 and scan.ah == 0:
                 dc_first(bits, scan, blocks, coef, [J.HuffTable(*t) for t in scan.dc])
@@ -235,6 +255,13 @@ def decode_status(data: bytes, stats=None):
     if info is None:
         raise JpegError("not a progressive JPEG this decoder takes")
     coef, status = coefficients(info, stats)
+    if status == 0 and info.cut:
+        # a file cut short whose script ends above Al = 0 is damaged even when the cut falls exactly between two scans
+        final = np.zeros((info.ncomp, 64), np.int64)
+        for sc in info.scans:
+            final[list(sc.comps), sc.ss:sc.se + 1] = sc.al
+        if final.any():
+            status = ERR_SHORT
     return (pixels(info, coef) if status == 0 else None), status
 
 

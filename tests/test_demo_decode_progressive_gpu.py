@@ -1,6 +1,7 @@
 """GPU: demo.py --decode_progressive gpu end to end on a synthetic checkpoint: a folder of baseline .jpg, progressive .jpg and .png
 files gives the same .npz contents and rendered .png bytes as the default host decode; the progressive files are decoded on the
-device with the flag and by PIL without it."""
+device with the flag and by PIL without it.  A file with a scan script PIL never writes (DC scans of one component) goes to the
+device too; one whose script ends above Al = 0 - libjpeg smooths its blocks - is PIL's under every setting."""
 import warnings
 
 from poco_amd import jpeg
@@ -45,3 +46,27 @@ def test_folder_decode_progressive_gpu_equals_host(tmp_path, cuda, monkeypatch):
         assert seen == {n: n == "im3.jpg" for n in files}               # the progressive files are PIL's again
     for out in ("prog", "only", "base"):
         _same_outputs(tmp_path, "host", out, files)
+
+
+def test_folder_with_unusual_scan_scripts_equals_host(tmp_path, cuda, monkeypatch):
+    import demo
+    from tests.jpegprog_enc_np import rescan
+    ckpt, smpl = _assets(tmp_path)
+    imgs = tmp_path / "imgs"
+    imgs.mkdir()
+    src = K.encode(photo_like(200, 300, 46), "420", quality=85)
+    files = {"im0.jpg": rescan(src, K.scripts(3)["dc-split"]),
+             "im1.jpg": K.cut_after(K.encode(photo_like(240, 320, 47), "420", quality=90), 5)}
+    for n, d in files.items():
+        (imgs / n).write_bytes(d)
+    prog = {n: jpeg.parse_progressive_jpeg(d) is not None for n, d in files.items()}
+    assert prog == {"im0.jpg": True, "im1.jpg": False}
+    assert (K.reference(files["im0.jpg"]) == K.reference(src)).all()
+    common = _folder_args(tmp_path, ckpt, smpl, imgs, {"im0.jpg": [[200, 100, 120, 160]], "im1.jpg": [[160, 120, 150, 150]]})
+    demo.main(demo.parse_args(common + ["--output_folder", str(tmp_path / "host")]))
+    seen = _record_decodes(monkeypatch)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        demo.main(demo.parse_args(common + ["--output_folder", str(tmp_path / "prog"), "--decode_progressive", "gpu"]))
+    assert seen == prog                                                 # the declined file came back from PIL
+    _same_outputs(tmp_path, "host", "prog", files)

@@ -1,6 +1,9 @@
 """CPU: the progressive JPEG parser (poco_amd.jpeg.parse_progressive_jpeg) and the numpy restatement of the progressive coefficient
 stage (tests/jpegprog_np.py), which must give PIL's pixels byte for byte - the contract csrc/jpeg_prog.hip is tested against on
-the GPU (tests/test_jpegprog_gpu.py)."""
+the GPU (tests/test_jpegprog_gpu.py).  The scan scripts PIL never writes come from the transcoder tests/jpegprog_enc_np.py, which is
+held to libjpeg alone (PIL's pixels of a rescanned file equal PIL's pixels of its source) before the parser and the restatement
+are held to its files; what each case is there to reach is asserted on the restatement's counters."""
+import functools
 import io
 
 import numpy as np
@@ -10,9 +13,10 @@ from PIL import Image
 from tests import jpegprog_cases as K
 from tests import jpegprog_np as P
 from poco_amd import _lib
-from poco_amd.jpeg import MAX_SCANS, parse_jpeg, parse_progressive_jpeg
+from poco_amd.jpeg import MAX_SCANS, TABLES_PER_IMAGE, _scan_tables, parse_jpeg, parse_progressive_jpeg
 
 CASES = K.cases()
+SCRIPTS = K.script_cases()
 
 
 def test_pil_writes_progressive_files_with_all_four_scan_kinds():
@@ -82,7 +86,7 @@ def test_parser_validates_the_scan_script():
 def test_truncated_file_is_parsed_and_the_restatement_reports_it():
     cut = K.truncated()
     info = parse_progressive_jpeg(cut)
-    assert info is not None and len(info.scans) == 5
+    assert info is not None and len(info.scans) == 5 and info.cut
     px, status = P.decode_status(cut)
     assert px is None and status == P.ERR_SHORT
 
@@ -112,3 +116,125 @@ def test_c_abi_entries_are_declared_and_exported():
     for s in ("poco_jpeg_prog_decoder_create", "poco_jpeg_prog_decode", "poco_jpeg_prog_decoder_destroy"):
         assert s in syms and hasattr(L, s), s
     assert "#define POCO_ABI_VERSION 4" in _lib.HEADER.read_text()     # additions only
+
+
+# ---- scan scripts PIL never writes ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _decoded(name):
+    """(pixels, status, stats) of the restatement, once per case."""
+    stats = {}
+    px, status = P.decode_status(SCRIPTS[name].data, stats)
+    return px, status, stats
+
+
+def _names(**want):
+    return sorted(n for n, c in SCRIPTS.items() if all(getattr(c, k) == v for k, v in want.items()))
+
+
+def test_script_cases_hold_every_kind_and_source():
+    kinds = {c.kind for c in SCRIPTS.values()}
+    assert kinds == {"spectral", "dc-split", "deep", "bands-64", "bands-65", "resplit-join", "resplit-split", "component-major",
+                     "eob-cap", "eob-corrections", "tables-flat", "tables-deep", "tables-one-id", "tables-many", "ends-above-zero"}
+    for kind in ("spectral", "deep", "resplit-join", "resplit-split", "eob-corrections"):
+        assert {n[len(kind) + 1:] for n in _names(kind=kind)} == set(K.SMALL_SOURCES), kind
+    assert {n[len("dc-split") + 1:] for n in _names(kind="dc-split")} == {f"{s}-q95-{z}" for s in ("420", "422") for z in ("33x47", "17x13")}
+    assert len(_names(kind="ends-above-zero")) == 3 + len(K.SMALL_SOURCES)
+    assert [n for n, c in SCRIPTS.items() if c.big] == ["eob-cap"]
+    for c in SCRIPTS.values():
+        assert c.decodable <= (c.parses and c.complete)
+
+
+@pytest.mark.parametrize("name", _names(complete=True))
+def test_transcoder_keeps_the_pixels_libjpeg_gives(name):
+    """The coefficients are the source's, so libjpeg decodes both files to the same picture: the transcoder's self-check, which
+    involves no code of this repository's decoder."""
+    c = SCRIPTS[name]
+    assert np.array_equal(K.reference(c.data), K.reference(c.source))
+
+
+@pytest.mark.parametrize("name", _names(parses=True))
+def test_parser_reads_the_script_back(name):
+    c = SCRIPTS[name]
+    info = parse_progressive_jpeg(c.data)
+    assert info is not None and not info.cut
+    assert [(s.comps, s.ss, s.se, s.ah, s.al) for s in info.scans] == [tuple(s) for s in c.script]
+    assert parse_jpeg(c.data) is None
+    for s in info.scans:
+        assert (s.ac is not None) == (s.ss > 0) and all((t is not None) == (s.ss == 0 and s.ah == 0) for t in s.dc)
+
+
+@pytest.mark.parametrize("name", _names(parses=True))
+def test_restatement_equals_pil_on_script_cases(name):
+    px, status, _ = _decoded(name)
+    assert status == 0
+    assert np.array_equal(px, K.reference(SCRIPTS[name].data))
+
+
+def test_script_cases_reach_what_they_are_there_for():
+    """On the restatement's counters alone."""
+    for n in _names(kind="spectral"):
+        assert _decoded(n)[2]["levels"] == 1 and _decoded(n)[2]["corrections"] == 0
+    for n in _names(kind="dc-split"):
+        st = _decoded(n)[2]
+        info = parse_progressive_jpeg(SCRIPTS[n].data)
+        assert -(-info.width // 8) % info.hsamp != 0                    # luma's own raster is narrower than the MCUs'
+        assert st["dc_alone"] == 9 and st["dc_refine_ragged_luma"] == 2 and st["levels"] == 3
+    for n in _names(kind="deep"):
+        st = _decoded(n)[2]
+        assert st["levels"] == 5 and st["corrections"] > 0 and st["refine_zrl"] > 0
+        assert len(_scan_tables(parse_progressive_jpeg(SCRIPTS[n].data))[0]) <= TABLES_PER_IMAGE
+    st = _decoded("eob-cap")[2]
+    assert st["eobrun"] == 0x7FFF and st["eobrun_cap"] == 1 and st["refine_eobrun"] == 0x7FFF
+    for n in _names(kind="eob-corrections"):
+        assert _decoded(n)[2]["eob_corrections"] > 0, n
+    for n in _names(kind="tables-deep"):
+        st = _decoded(n)[2]
+        assert st["symbols"] > 1000 and 2 * st["long_codes"] > st["symbols"]
+    for n in _names(kind="tables-flat") + _names(kind="bands-64"):
+        st = _decoded(n)[2]
+        assert st["symbols"] > 1000 and st["long_codes"] == 0
+        info = parse_progressive_jpeg(SCRIPTS[n].data)
+        lengths = {ln + 1 for _, bits, _ in _scan_tables(info)[0] for ln in range(16) if bits[ln]}
+        assert lengths == {8, 9}                                       # the last code the lookahead table holds, and the one before
+    for n in _names(kind="tables-one-id"):
+        data = SCRIPTS[n].data
+        dht = [i for i in range(len(data) - 4) if data[i:i + 2] == b"\xff\xc4" and data[i + 4] & 15 == 0]
+        assert len(dht) >= len(SCRIPTS[n].script) - 2                  # a table in id 0 before every scan that has symbols
+    for n in _names(kind="resplit-join") + _names(kind="resplit-split") + _names(kind="component-major"):
+        assert _decoded(n)[2]["levels"] == 2 and _decoded(n)[2]["corrections"] > 0
+
+
+def test_64_scans_parse_and_65_do_not():
+    (n64,), (n65,) = _names(kind="bands-64"), _names(kind="bands-65")
+    info = parse_progressive_jpeg(SCRIPTS[n64].data)
+    assert len(info.scans) == MAX_SCANS == 64 and all(s.ss == s.se for s in info.scans)
+    assert len(_scan_tables(info)[0]) == 2                              # one DC and one AC table, written 64 times
+    assert len(SCRIPTS[n65].script) == 65 and parse_progressive_jpeg(SCRIPTS[n65].data) is None
+    assert np.array_equal(K.reference(SCRIPTS[n65].data), K.reference(SCRIPTS[n65].source))      # (a file libjpeg takes)
+
+
+def test_more_tables_than_a_decoder_plans_do_not_fit():
+    from poco_amd.jpeg import ProgressiveJpegDecoder
+    (name,) = _names(kind="tables-many")
+    info = parse_progressive_jpeg(SCRIPTS[name].data)
+    assert info is not None and len(_scan_tables(info)[0]) > TABLES_PER_IMAGE == 16
+    dec = ProgressiveJpegDecoder.__new__(ProgressiveJpegDecoder)      # fits() reads the planned sizes only: no device is needed
+    dec.max_h = dec.max_w = 256
+    assert not dec.fits(info)
+    assert dec.fits(parse_progressive_jpeg(SCRIPTS[_names(kind="bands-64")[0]].data))
+
+
+@pytest.mark.parametrize("name", _names(kind="ends-above-zero"))
+def test_script_that_ends_above_zero_is_declined(name):
+    """libjpeg smooths the blocks of such pictures (jdcoefct.c): without that the restatement - and the device - would give
+    other pixels than PIL with status 0 (73875 of 90000 bytes, up to 12 levels, for 420-q75-200x150 cut after five scans).
+    The parser declines them, so every caller decodes them with PIL."""
+    c = SCRIPTS[name]
+    K.reference(c.data)                                                 # a file PIL takes
+    assert parse_progressive_jpeg(c.data) is None and parse_jpeg(c.data) is None
+    with pytest.raises(P.JpegError):
+        P.decode_status(c.data)
+    # the same bytes without their EOI are a file cut short: parsed, and damaged whatever the last scan decodes to
+    info = parse_progressive_jpeg(c.data[:-2])
+    assert info is not None and info.cut
+    assert P.decode_status(c.data[:-2]) == (None, P.ERR_SHORT)

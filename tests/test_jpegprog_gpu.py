@@ -1,6 +1,9 @@
 """GPU: the progressive JPEG decoder (poco_amd.jpeg.ProgressiveJpegDecoder over poco_jpeg_prog_decode, csrc/jpeg_prog.hip) gives
 PIL's pixels byte for byte over the matrix of tests/jpegprog_cases.py - alone, in one mixed batch and call after call - and
-reports a file cut short in its fifth scan in that image's status word only."""
+reports a file cut short in its fifth scan in that image's status word only.  The scan scripts, table shapes and table id layouts
+PIL never writes (K.script_cases(), held to libjpeg and to the restatement in tests/test_jpegprog_cpu.py) are decoded alone and in
+one call with the matrix; files with more tables than a decoder plans and scripts that end above Al = 0 are refused before any
+GPU work."""
 import numpy as np
 import pytest
 import torch
@@ -12,6 +15,9 @@ from tests import jpegprog_np as P
 pytestmark = pytest.mark.gpu
 
 CASES = K.cases()
+SCRIPTS = K.script_cases()
+DECODABLE = sorted(n for n, c in SCRIPTS.items() if c.decodable)
+SMALL = [n for n in DECODABLE if not SCRIPTS[n].big]
 
 
 @pytest.fixture(scope="module")
@@ -98,3 +104,77 @@ def test_argument_errors(dec, cuda):
     assert not small.fits(jpeg.parse_progressive_jpeg(CASES["420-q75-33x47"]))
     with pytest.raises(PocoHipError, match="1..1"):
         small.decode([CASES["420-q75-8x8"]] * 2)
+
+
+# ---- scan scripts PIL never writes ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sdec(cuda):
+    return jpeg.ProgressiveJpegDecoder(cuda, 256, 256, max_batch=len(CASES) + len(SMALL), max_bytes=4 << 20)
+
+
+@pytest.fixture(scope="module")
+def srefs():
+    return {n: K.reference(SCRIPTS[n].data) for n in SMALL}
+
+
+@pytest.mark.parametrize("name", DECODABLE)
+def test_every_script_case_alone(sdec, cuda, name):
+    c = SCRIPTS[name]
+    info = jpeg.parse_progressive_jpeg(c.data)
+    d = jpeg.ProgressiveJpegDecoder(cuda, K.EOB_CAP_SIDE, K.EOB_CAP_SIDE, max_bytes=1 << 16) if c.big else sdec
+    assert d.fits(info)
+    (out,), st = d.decode([info], return_status=True)
+    assert st == [0]
+    ref = K.reference(c.data)
+    assert _diff(out, ref) is None, _diff(out, ref)
+
+
+def test_one_call_mixes_script_cases_with_the_matrix(sdec, refs, srefs):
+    """Scripts of one to five levels, 64-scan files and libjpeg's own script share the level launches of one call: forward and
+    reverse order, twice each."""
+    files = [(n, CASES[n], refs[n]) for n in sorted(CASES)] + [(n, SCRIPTS[n].data, srefs[n]) for n in SMALL]
+    infos = [jpeg.parse_progressive_jpeg(d) for _, d, _ in files]
+    assert {len(i.scans) for i in infos} >= {2, 4, 6, 10, 12, 15, 16, 19, 64}
+    runs = []
+    for order in (infos, infos[::-1], infos, infos[::-1]):
+        outs, st = sdec.decode(order, return_status=True)
+        assert st == [0] * len(files)
+        runs.append(outs if order is infos else outs[::-1])
+    for k, (n, _, ref) in enumerate(files):
+        assert _diff(runs[0][k], ref) is None, (n, _diff(runs[0][k], ref))
+        assert all(torch.equal(runs[0][k], r[k]) for r in runs[1:]), n
+
+
+def test_more_tables_than_planned_are_refused_before_gpu_work(sdec, srefs):
+    from poco_amd._lib import PocoHipError
+    (many,) = [n for n, c in SCRIPTS.items() if c.kind == "tables-many"]
+    info = jpeg.parse_progressive_jpeg(SCRIPTS[many].data)
+    assert info is not None and not sdec.fits(info)
+    names = ["dc-split-420-q95-33x47", "deep-444-q95-17x13"]
+    with pytest.raises(PocoHipError, match="more than 16 Huffman tables"):
+        sdec.decode([SCRIPTS[names[0]].data, info, SCRIPTS[names[1]].data])
+    outs, st = sdec.decode([SCRIPTS[n].data for n in names], return_status=True)
+    assert st == [0, 0]
+    for n, o in zip(names, outs):
+        assert _diff(o, srefs[n]) is None, n
+
+
+@pytest.mark.parametrize("name", sorted(n for n, c in SCRIPTS.items() if c.kind == "ends-above-zero"))
+def test_script_that_ends_above_zero_is_refused(sdec, srefs, name):
+    """By the parser, and by poco_jpeg_prog_decode itself for a caller that brings its own scan table; the same bytes without
+    EOI are a file cut short: taken, and reported in its status word only."""
+    import dataclasses
+    from poco_amd._lib import PocoHipError
+    data = SCRIPTS[name].data
+    d = sdec
+    with pytest.raises(PocoHipError, match="parse_progressive_jpeg"):
+        d.decode([data])
+    cut = jpeg.parse_progressive_jpeg(data[:-2])
+    assert cut is not None and cut.cut
+    with pytest.raises(PocoHipError, match="above Al = 0"):
+        d.decode([dataclasses.replace(cut, cut=False)])
+    assert P.decode_status(data[:-2])[1] == P.ERR_SHORT
+    good = "dc-split-422-q95-17x13"
+    outs, st = d.decode([SCRIPTS[good].data, cut, SCRIPTS[good].data], return_status=True)
+    assert st == [0, P.ERR_SHORT, 0]
+    assert _diff(outs[0], srefs[good]) is None and _diff(outs[2], srefs[good]) is None
