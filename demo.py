@@ -18,6 +18,12 @@ bytes cross PCIe instead of its pixels; other files go through PIL as with the d
 same for .png input - what the reference's ffmpeg extraction and this demo's own --render write - with the device inflate and
 unfilter of poco_amd/png.py PngDecoder.  --decode_progressive gpu does it for progressive .jpg files (SOF2: what web servers
 and export pipelines write) with poco_amd/jpeg.py ProgressiveJpegDecoder; the three flags are independent.
+--tracking reads both kinds of tracker output of the reference: box tracks ({'bbox', 'frames'}) and 2-D pose tracks ({'joints2d'
+[T,K,3], 'frames'}: the reference's --tracking_method pose), whose boxes are derived from the keypoints on the host
+(poco_amd/tracks.py); the file's content decides.  --tracking_method pose insists that every track has keypoints,
+--kp_vis_thresh is the confidence a keypoint needs to count (0.3 as in the reference), --smooth_bbox median- and Gaussian-filters
+the derived box parameters (off, as in the reference's Inference).  A keypoint track's result carries its keypoints as `joints2d`,
+and --draw_keypoints stamps those above the threshold black over the green model joints.
 """
 import argparse
 import json
@@ -57,7 +63,8 @@ def parse_args(argv=None):
                         "triangles as one-pixel depth-tested lines")
     p.add_argument("--draw_keypoints", action="store_true",
                    help="with --render: stamp the 2-D joints on the main view after each person's mesh: folder mode SMPL joints "
-                        "white and OpenPose joints black, video mode all 49 in green")
+                        "white and OpenPose joints black, video mode all 49 in green and a keypoint track's input keypoints above "
+                        "--kp_vis_thresh black")
     p.add_argument("--render_crop", action="store_true",
                    help="with --render, folder mode: draw only the first detection of each image, over its own 224 x 224 crop")
     p.add_argument("--image_format", default="png", choices=["png", "jpg"],
@@ -80,7 +87,16 @@ def parse_args(argv=None):
     p.add_argument("--beta", type=float, default=1.5)
     p.add_argument("--tracking", type=str, default=None,
                    help="video mode: json or the reference's tracking_results_<method>.pkl {person_id: {'bbox': [[cx,cy,w,h],...], "
-                        "'frames': [idx,...]}} (multi_person_tracker output); default = one centred track over all frames")
+                        "'frames': [idx,...]}} (multi_person_tracker output) or {person_id: {'joints2d': [T,K,3] (x,y,confidence), "
+                        "'frames': [idx,...]}} (a 2-D pose tracker's output: boxes are derived from the keypoints); default = one "
+                        "centred track over all frames")
+    p.add_argument("--tracking_method", default="bbox", choices=["bbox", "pose"],
+                   help="video mode: as the reference's flag.  The --tracking file's content decides how each track is read; "
+                        "pose = a track without joints2d is an error")
+    p.add_argument("--kp_vis_thresh", type=float, default=0.3,
+                   help="keypoint tracks: the confidence above which a keypoint counts for the box (and is drawn by --draw_keypoints)")
+    p.add_argument("--smooth_bbox", action="store_true",
+                   help="keypoint tracks: median (11) + Gaussian (sigma 8) filter of the derived box parameters (cx, cy, scale)")
     p.add_argument("--skip_frame", type=int, default=1)
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
@@ -149,7 +165,7 @@ def main(args):
             dist.init_process_group("nccl", device_id=dev)
         else:
             dist.init_process_group("gloo")
-    from poco_amd.tester import POCOTester, load_detections
+    from poco_amd.tester import POCOTester, load_detections, load_tracking, tracking_options
     folder = args.image_folder if args.mode in ("folder", "directory") else args.vid_file
     stem = os.path.basename(os.path.normpath(folder)) if folder else ""
     if args.mode == "video" and folder and os.path.isfile(folder):
@@ -161,10 +177,16 @@ def main(args):
         stem = os.path.splitext(stem)[0]
     elif not folder or not os.path.isdir(folder):
         sys.exit(f"input folder not found: {folder}")
+    tracking = args.tracking
+    if args.mode == "video" and tracking:                                 # read before the engine is built: a bad file ends here
+        try:
+            tracking = load_tracking(tracking, **tracking_options(args))
+        except ValueError as e:
+            sys.exit(str(e))
     tester = POCOTester(args)
     out_dir = os.path.join(args.output_folder, stem + "_")
     if args.mode == "video":
-        stats = tester.run_on_video_folder(folder, args.tracking, out_dir)
+        stats = tester.run_on_video_folder(folder, tracking, out_dir)
     else:
         stats = tester.run_on_image_folder(folder, load_detections(args.detections), out_dir)
     if "fps" in stats:                                                    # rank 0 (the reference logs 'poco FPS', demo.py:136-145)

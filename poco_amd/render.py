@@ -235,6 +235,14 @@ def video_keypoints(joints2d):
     return j, np.tile(np.array([[0, 255, 0]], np.uint8), (49, 1))
 
 
+def input_keypoints(joints2d, vis_thresh: float = 0.3):
+    """(points [n,2], rgb [n,3]) of the keypoints a track came in with (video mode, --tracking_method pose): those of the
+    [K,3] (x, y, confidence) rows whose confidence exceeds vis_thresh, in folder mode's OpenPose colour, black."""
+    j = np.asarray(joints2d, np.float32).reshape(-1, 3)
+    j = j[j[:, 2] > np.float32(vis_thresh)]
+    return np.ascontiguousarray(j[:, :2]), np.zeros((j.shape[0], 3), np.uint8)
+
+
 def person_style(var, backbone: str, uncert_color: bool = True):
     """(colour, material) of one person: the uncertainty colour (vertex_color) or the plain grey of --no_uncert_color."""
     if uncert_color and var is not None:

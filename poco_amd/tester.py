@@ -377,8 +377,9 @@ class POCOTester:
         """Per-track results like pocolib/core/tester.py:362-479.
 
         tracking_results: {person_id: {'bbox': [T,4] (cx,cy,w,h), 'frames': [T] frame indices}} - what
-        multi_person_tracker hands to the reference (tester.py:113-151).  frames: sequence or callable
-        frame index -> uint8 [H,W,3] RGB.
+        multi_person_tracker hands to the reference (tester.py:113-151); a track may carry 'joints2d' [T,K,3], the pose
+        tracker's keypoints its boxes were derived from (load_tracking), which are handed back in its result.  frames:
+        sequence or callable frame index -> uint8 [H,W,3] RGB.
 
         The reference walks person by person and re-reads every frame for every person
         (dataset/inference.py:72-135).  Here the stream is frame-major: a frame is decoded and uploaded once,
@@ -437,7 +438,8 @@ class POCOTester:
         """Per-track post-processing of tester.py:416-479 on the raw per-frame network outputs `st` (keys: pred_cam,
         smpl_vertices, pred_pose, pred_shape, smpl_joints3d, smpl_joints2d, var_pose): optional one-euro smoothing
         (meshes / 3-D joints re-derived from the filtered pose; the 2-D joints stay those of the raw prediction, as in
-        the reference), uncertainty post-processing, camera / keypoint conversion to the original image."""
+        the reference), uncertainty post-processing, camera / keypoint conversion to the original image.  `joints2d` is the
+        track's own input keypoints (original-image pixels, what the reference's run_on_video stores) or None."""
         bboxes = np.asarray(tr["bbox"], np.float32).reshape(-1, 4)
         pose, betas = st["pred_pose"], st["pred_shape"]
         verts, j3d = st["smpl_vertices"], st["smpl_joints3d"]
@@ -450,7 +452,7 @@ class POCOTester:
         return {
             "pred_cam": st["pred_cam"],
             "orig_cam": postproc.convert_crop_cam_to_orig_img(st["pred_cam"], bboxes, orig_width, orig_height),
-            "verts": verts, "pose": pose, "betas": betas, "joints2d": None,
+            "verts": verts, "pose": pose, "betas": betas, "joints2d": tr.get("joints2d"),
             "smpl_joints3d": j3d,
             "smpl_joints2d": postproc.convert_crop_coords_to_orig_img(bboxes, st["smpl_joints2d"],
                                                                       self.model_cfg.DATASET.IMG_RES),
@@ -588,7 +590,8 @@ class POCOTester:
 
 def _run_on_video_folder(self, frame_folder: str, tracking_path: Optional[str], output_path: str, bbox_scale=1.0):
     """demo.py --mode video on a folder of extracted frames or a Motion-JPEG .avi (demo.py:60-160): per-track results written
-    as <output>/poco_results.npz (the reference joblib-dumps the same dict, demo.py:147-150)."""
+    as <output>/poco_results.npz (the reference joblib-dumps the same dict, demo.py:147-150).  tracking_path: a tracking file
+    (load_tracking), what load_tracking returned for one, or None = one centred track over all frames."""
     if os.path.isfile(frame_folder):
         from .jpeg import MjpegReader
         with MjpegReader(frame_folder) as reader:
@@ -640,15 +643,17 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
     else:
         first = np.asarray(Image.open(os.path.join(frame_folder, names[0])).convert("RGB"))
     H, W = first.shape[:2]
-    if tracking_path:
-        tracking = load_tracking(tracking_path)
+    if isinstance(tracking_path, dict):                # already loaded (demo.py checks the file before the engine is built)
+        tracking = tracking_path
+    elif tracking_path:
+        tracking = load_tracking(tracking_path, **tracking_options(self.args))
     else:
         s = float(min(H, W))
         tracking = {"0": {"bbox": np.tile([[W / 2.0, H / 2.0, s, s]], (len(names), 1)).astype(np.float32),
                           "frames": np.arange(len(names))}}
     skip = max(int(getattr(self.args, "skip_frame", 1)), 1)
     if skip > 1:
-        tracking = {k: {"bbox": v["bbox"][::skip], "frames": v["frames"][::skip]} for k, v in tracking.items()}
+        tracking = {k: {n: a[::skip] for n, a in v.items()} for k, v in tracking.items()}      # bbox, frames (, joints2d)
     if self.decode_any_on_gpu:
         load = _GroupLoader(self, names, read, H, W)
     elif reader is not None:
@@ -755,12 +760,13 @@ def _write_bytes(path: str, data: bytes) -> None:
 def _render_video(self, results: dict, frame_folder: str, names, load, output_path: str) -> None:
     """render_results of tester.py:482-580: every frame of the folder with the people the tracks place in it, in ascending
     orig_cam[1] (demo_utils.py:307-313, ties in track order), black side canvas, <output>/tmp_images_output/%06d.png, and the
-    lines of <output>/uncertainty.log (tester.py:547-550).  --image_format jpg writes %06d.jpg, encoded on the device; --encode gpu
+    lines of <output>/uncertainty.log (tester.py:547-550).  --draw_keypoints stamps each person's 49 model joints green and, for a
+    track that came with keypoints, its input keypoints above --kp_vis_thresh black on top.  --image_format jpg writes %06d.jpg, encoded on the device; --encode gpu
     compresses the .png files on the device;
     --save_video adds <output>/<frame folder>_poco_result.avi (Motion-JPEG of the same pictures at --fps: the reference's
     images_to_video, demo.py:148-157)."""
     from concurrent.futures import ThreadPoolExecutor
-    from .render import video_keypoints, video_order
+    from .render import input_keypoints, video_keypoints, video_order
     out_dir = os.path.join(output_path, "tmp_images_output")
     os.makedirs(out_dir, exist_ok=True)
     jpg = self.image_format == "jpg"
@@ -771,6 +777,16 @@ def _render_video(self, results: dict, frame_folder: str, names, load, output_pa
             if 0 <= int(f) < len(names):
                 per_frame[int(f)].append((pid, k))
     sideview = bool(getattr(self.args, "sideview", False))
+    vis_thresh = float(getattr(self.args, "kp_vis_thresh", 0.3))
+
+    def keypoints_of(pid, k):
+        """--draw_keypoints: the 49 model joints green; for a keypoint track the confident input keypoints black on top."""
+        kp = video_keypoints(results[pid]["smpl_joints2d"][k])
+        if results[pid].get("joints2d") is None:
+            return kp
+        inp = input_keypoints(results[pid]["joints2d"][k], vis_thresh)
+        return np.concatenate([kp[0], inp[0]], 0), np.concatenate([kp[1], inp[1]], 0)
+
     log_lines = []
     with ThreadPoolExecutor(max(1, min(8, (os.cpu_count() or 2) // 2))) as pool:
         writes = []
@@ -783,8 +799,7 @@ def _render_video(self, results: dict, frame_folder: str, names, load, output_pa
                 pic = self.render_frame(fr, np.stack([results[pid]["verts"][k] for pid, k in people]),
                                         np.stack([results[pid]["orig_cam"][k] for pid, k in people]),
                                         np.stack([results[pid]["var"][k] for pid, k in people]), side_bg=0,
-                                        keypoints=[video_keypoints(results[pid]["smpl_joints2d"][k]) for pid, k in people]
-                                        if self.draw_keypoints else None)
+                                        keypoints=[keypoints_of(pid, k) for pid, k in people] if self.draw_keypoints else None)
                 for pid, k in people:
                     g = float(np.clip(results[pid]["var_global"][k], 0, 0.99))
                     who = f"{int(pid):02d}" if str(pid).lstrip("-").isdigit() else str(pid)
@@ -842,16 +857,47 @@ def load_detections(path: Optional[str]):
     return _load_any(path) if path else None
 
 
-def load_tracking(path: Optional[str]) -> Optional[dict]:
+def tracking_options(args) -> dict:
+    """load_tracking's keyword arguments from the demo's flags (--tracking_method, --kp_vis_thresh, --smooth_bbox)."""
+    return {"method": getattr(args, "tracking_method", "bbox") or "bbox", "vis_thresh": float(getattr(args, "kp_vis_thresh", 0.3)),
+            "smooth_bbox": bool(getattr(args, "smooth_bbox", False))}
+
+
+def load_tracking(path: Optional[str], vis_thresh: float = 0.3, smooth_bbox: bool = False, method: str = "bbox") -> Optional[dict]:
     """{person_id: {'bbox': [T,4] (cx,cy,w,h), 'frames': [T]}} from json or the reference's
     `tracking_results_<method>.pkl` (demo.py:125-131); tracks shorter than MIN_NUM_FRAMES = 25 frames are dropped as in
-    tester.py:133-136."""
+    tester.py:133-136.
+
+    The file's content decides how a track is read.  A track with `bbox` is read as it is; a `joints2d` array of the same length
+    next to it is kept.  A track with `joints2d` [T,K,3] and no `bbox` - a pose tracker's output, the reference's
+    --tracking_method pose - goes through tracks.boxes_from_keypoints (vis_thresh; smooth_bbox = median + Gaussian filter of the
+    box parameters): its `bbox`, `frames` and `joints2d` are the derived, trimmed ones, the 25-frame rule applies to the trimmed
+    length, and a track without a usable frame is dropped with one line on stderr.  method = 'pose' (--tracking_method pose):
+    a track without `joints2d` is a ValueError that names it."""
     if not path:
         return None
     raw = _load_any(path)
+    is_json = path.lower().endswith(".json")
     out = {}
     for k, v in raw.items():
+        if method == "pose" and v.get("joints2d") is None:
+            raise ValueError(f"--tracking_method pose: track {k!r} of {path} has no joints2d")
         frames = np.asarray(v["frames"], np.int64).reshape(-1)
-        if path.lower().endswith(".json") or frames.shape[0] >= 25:
+        if v.get("bbox") is None and v.get("joints2d") is not None:
+            from .tracks import boxes_from_keypoints
+            tr = boxes_from_keypoints(v["joints2d"], frames, vis_thresh, smooth=smooth_bbox)
+            if not len(tr["frames"]):
+                import sys
+                print(f"load_tracking: track {k!r} of {path} has no frame with a keypoint above {vis_thresh}: dropped", file=sys.stderr)
+            elif is_json or len(tr["frames"]) >= 25:
+                out[str(k)] = tr
+        elif is_json or frames.shape[0] >= 25:
             out[str(k)] = {"bbox": np.asarray(v["bbox"], np.float32).reshape(-1, 4), "frames": frames}
+            if v.get("joints2d") is not None and len(v["joints2d"]) == frames.shape[0]:
+                try:
+                    j = np.asarray(v["joints2d"], np.float64 if is_json else None)
+                except (TypeError, ValueError):          # ragged, or None entries: not an array of keypoints
+                    j = None
+                if j is not None and j.ndim == 3 and j.dtype.kind == "f":
+                    out[str(k)]["joints2d"] = j
     return out
