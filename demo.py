@@ -24,6 +24,9 @@ and export pipelines write) with poco_amd/jpeg.py ProgressiveJpegDecoder; the th
 --kp_vis_thresh is the confidence a keypoint needs to count (0.3 as in the reference), --smooth_bbox median- and Gaussian-filters
 the derived box parameters (off, as in the reference's Inference).  A keypoint track's result carries its keypoints as `joints2d`,
 and --draw_keypoints stamps those above the threshold black over the green model joints.
+--occlusion_map (folder mode) adds PARE's occlusion analysis per detection (poco_amd/occlusion.py): a --occ_patch square of grey
+level --occ_fill slides over the crop in steps of --occ_stride, the engine regresses every occluded copy, and
+<out>/occlusion/<image>_<det>.png shows --occ_metric per position as a heat map over the crop, <image>_<det>.npz the records.
 """
 import argparse
 import json
@@ -98,6 +101,19 @@ def parse_args(argv=None):
     p.add_argument("--smooth_bbox", action="store_true",
                    help="keypoint tracks: median (11) + Gaussian (sigma 8) filter of the derived box parameters (cx, cy, scale)")
     p.add_argument("--skip_frame", type=int, default=1)
+    p.add_argument("--occlusion_map", action="store_true",
+                   help="folder mode: per detection, slide a grey square over the crop, regress every occluded copy on the GPU and "
+                        "write <out>/occlusion/<image>_<det>.png (the heat map over the crop, through --image_format / --encode) "
+                        "and .npz (records [nh,nw,77], positions, patch, stride, the unoccluded var_pose and pred_cam)")
+    p.add_argument("--occ_patch", type=int, default=40, help="--occlusion_map: side of the square, 1..224 pixels of the crop")
+    p.add_argument("--occ_stride", type=int, default=10, help="--occlusion_map: step of the square, >= 1")
+    p.add_argument("--occ_fill", type=float, default=None,
+                   help="--occlusion_map: grey level 0..255 of the square (default: the dataset mean colour, 0 after normalisation)")
+    p.add_argument("--occ_metric", type=str, default="v2v",
+                   help="--occlusion_map: what the heat map shows: v2v = mean vertex displacement, var = mean change of the "
+                        "per-joint uncertainty, joints = mean displacement of the 49 joints, var:<0..23> = one joint's uncertainty")
+    p.add_argument("--occ_scale", type=str, default="auto",
+                   help="--occlusion_map: the value drawn as the hottest colour: auto = the map's maximum, or a positive float")
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
@@ -127,6 +143,30 @@ def _check_render_assets(args) -> None:
                      "keeps its triangles)")
 
 
+def _check_occlusion(args) -> None:
+    """--occlusion_map: refuse video mode and out-of-range options before the engine is built."""
+    if not getattr(args, "occlusion_map", False):
+        return
+    if args.mode not in ("folder", "directory"):
+        sys.exit("--occlusion_map sweeps the crops of folder mode: it needs --mode folder")
+    if not 1 <= args.occ_patch <= 224:
+        sys.exit(f"--occ_patch must be in 1..224, got {args.occ_patch}")
+    if args.occ_stride < 1:
+        sys.exit(f"--occ_stride must be >= 1, got {args.occ_stride}")
+    if args.occ_fill is not None and not 0 <= args.occ_fill <= 255:
+        sys.exit(f"--occ_fill must be in 0..255, got {args.occ_fill}")
+    m = args.occ_metric
+    if not (m in ("v2v", "var", "joints") or (m.startswith("var:") and m[4:].isdigit() and 0 <= int(m[4:]) <= 23)):
+        sys.exit(f"--occ_metric must be v2v, var, joints or var:<0..23>, got {m}")
+    if args.occ_scale != "auto":
+        try:
+            v = float(args.occ_scale)
+        except ValueError:
+            v = float("nan")
+        if not 0 < v < float("inf"):
+            sys.exit(f"--occ_scale must be auto or a positive number, got {args.occ_scale}")
+
+
 def _spawn_ranks(args) -> int:
     """`demo.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU."""
     import socket
@@ -151,6 +191,7 @@ def main(args):
         sys.exit(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
     if getattr(args, "save_video", False) and not (args.mode == "video" and render_enabled(args)):
         sys.exit("--save_video writes the rendered frames of video mode: it needs --mode video and --render")
+    _check_occlusion(args)
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")

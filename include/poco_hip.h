@@ -429,6 +429,41 @@ int poco_renderer_render_ex(poco_renderer_t r, unsigned char* d_frame, int H, in
 int poco_renderer_draw_discs(unsigned char* d_frame, int H, int W, const float* d_points, const unsigned char* d_rgb, int N,
                              int r, void* stream);
 
+/* ---- occlusion sensitivity sweep: demo.py --occlusion_map (csrc/occlusion.hip, poco_amd/occlusion.py) ------------
+ * The occlusion analysis of PARE (a grey square slides over the crop, the regressor runs on every occluded copy, the change of
+ * the output is drawn per position) around the engine's forwards.  All three calls are one launch on `stream`: no allocation, no
+ * synchronisation, arguments validated before the launch.  numpy restatement: tests/occlusion_np.py.
+ *
+ * poco_op_occlude_batch: d_out fp32 [m,3,res,res] = m copies of d_src fp32 [3,res,res]; copy i holds h_fill3[c] (host, three
+ *   normalised values) at rows y0 .. y0 + patch - 1, columns x0 .. x0 + patch - 1, (y0, x0) = d_pos[i] (int32 [m,2] on the device:
+ *   it only selects, so a value outside the crop paints less or nothing and never moves an address).  Copy and select only: the
+ *   output's bits are the source's or the fill's.  16-byte loads and stores throughout (a patch edge inside a quad is a per-element
+ *   select), hence res % 4 == 0 and d_src, d_out 16-byte aligned.  Limits: 4 <= res <= 4096, 1 <= patch <= res, 0 <= m <= 65536. */
+int poco_op_occlude_batch(const float* d_src, int res, const int* d_pos, int m, int patch, const float* h_fill3, float* d_out,
+                          void* stream);
+/* poco_op_occlusion_records: row i of the engine's outputs for the occluded copies (d_verts [m,V,3] = smpl_vertices, d_var [m,24]
+ *   = var_pose, d_j3d [m,49,3] = smpl_joints3d) against ONE baseline row (d_base_*), POCO_OCCLUSION_RECORD_FLOATS per row:
+ *     [0] mean over the V vertices of |v_occ - v_base| (Euclidean)   [1] the maximum of that
+ *     [2] mean of var_occ over its 24 entries                        [3] mean of var_occ - var_base
+ *     [4:28] var_occ[j] - var_base[j]                                [28:77] |j3d_occ[k] - j3d_base[k]| of the 49 joints
+ *   One workgroup per row; fixed reduction order (lane-strided partial sums, a wave shuffle tree, four LDS partials added in wave
+ *   order), no atomics: two calls give the same bits.  V even and d_verts, d_base_verts 8-byte aligned (two vertices are read as
+ *   three 8-byte loads; SMPL has 6890).  Limits: 2 <= V <= 2^20, 0 <= m <= 65536. */
+#define POCO_OCCLUSION_RECORD_FLOATS 77
+int poco_op_occlusion_records(const float* d_verts, const float* d_var, const float* d_j3d, int m, int V,
+                              const float* d_base_verts, const float* d_base_var, const float* d_base_j3d, float* d_records,
+                              void* stream);
+/* poco_op_heat_overlay: d_field fp32 [n] (one value per position: a record column), d_pos int32 [n,2] and patch as above, d_crop
+ *   uint8 [res,res,3] (the --render_crop canvas), d_lut uint8 [256,3] (the jet table), d_out uint8 [res,res,3] (may be d_crop).
+ *   Per pixel: value = (the float32 sum, in position order, of the field over the patches that cover the pixel) / their count;
+ *   t = value / scale clamped to [0, 1] (NaN -> 0); index = (int)(255 t + 0.5); out = (128 lut[index] + 128 crop + 128) >> 8 per
+ *   byte.  Every operation is rounded on its own (no contraction), so the bytes equal the float32 restatement.  scale > 0 (finite),
+ *   or 0 = "auto": the field's maximum, found on the device (NaN entries skipped); a field whose maximum is not a positive finite
+ *   number leaves the crop unchanged, and so does a pixel no patch covers.  Limits: 1 <= res <= 4096, 1 <= patch <= res,
+ *   1 <= n <= 65536. */
+int poco_op_heat_overlay(const float* d_field, const int* d_pos, int n, int patch, int res, float scale,
+                         const unsigned char* d_lut, const unsigned char* d_crop, unsigned char* d_out, void* stream);
+
 /* ---- JPEG encoder: the demo's rendered frames as baseline JPEG, encoded where they are ------------------------------------------
  * Replaces the host-side picture encoding behind pocolib/core/tester.py:338-345 (cv2.imwrite per frame) and, with
  * poco_amd/jpeg.py's Motion-JPEG .avi writer on top, the ffmpeg call of demo.py:148-157 / demo_utils.py:237-245 (images_to_video,

@@ -221,3 +221,16 @@ struct DiscRows {
 // points fp32 [N,2] (col, row), rgb uint8 [N,3]: stamps painted over frame in index order.
 void launch_render_discs(unsigned char* frame, int H, int W, const float* points, const unsigned char* rgb, int N, int r,
                          const DiscRows& rows, hipStream_t s);
+
+// ---- occlusion sensitivity sweep (occlusion.hip) -----------------------------------------------------------
+// out [m,3,res,res] = src [3,res,res] with fill3[c] inside the patch x patch square at pos[i] = (y0, x0); res % 4 == 0, src and out
+// 16-byte aligned.
+void launch_occlude_batch(const float* src, const int* pos, int m, int res, int patch, const float* fill3, float* out,
+                          hipStream_t s);
+// rec [m,77] of rows verts [m,V,3] / var [m,24] / j3d [m,49,3] against one baseline row; V even, verts and base_verts 8-byte aligned.
+void launch_occlusion_records(const float* verts, const float* var, const float* j3d, int m, int V, const float* base_verts,
+                              const float* base_var, const float* base_j3d, float* rec, hipStream_t s);
+// out uint8 [res,res,3] = crop blended with lut[index of the per-pixel mean of field over the covering patches]; scale 0 = the
+// field's maximum.
+void launch_heat_overlay(const float* field, const int* pos, int n, int patch, int res, float scale, const unsigned char* lut,
+                         const unsigned char* crop, unsigned char* out, hipStream_t s);

@@ -670,3 +670,48 @@ extern "C" int poco_renderer_draw_discs(unsigned char* d_frame, int H, int W, co
 }
 
 extern "C" void poco_renderer_destroy(poco_renderer_t r) { delete r; }
+
+// ---- occlusion sensitivity sweep (occlusion.hip) ----------------------------------------------------------------------------
+static_assert(POCO_OCCLUSION_RECORD_FLOATS == 77, "occlusion.hip writes 77 floats per record");
+static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+extern "C" int poco_op_occlude_batch(const float* d_src, int res, const int* d_pos, int m, int patch, const float* h_fill3,
+                                     float* d_out, void* stream) {
+  if (!d_src || !d_out || !h_fill3 || res < 4 || res > 4096 || (res & 3) || patch < 1 || patch > res || m < 0 || m > 65536 ||
+      (m > 0 && !d_pos) || !aligned_to(d_src, 16) || !aligned_to(d_out, 16)) {
+    poco_set_error("poco_op_occlude_batch: bad arguments (need res a multiple of 4 in 4..4096, 1 <= patch <= res, 0 <= m <= 65536, "
+                   "16-byte aligned source and output)");
+    return POCO_ERR_ARG;
+  }
+  if (m == 0) return POCO_OK;
+  launch_occlude_batch(d_src, d_pos, m, res, patch, h_fill3, d_out, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_op_occlusion_records(const float* d_verts, const float* d_var, const float* d_j3d, int m, int V,
+                                         const float* d_base_verts, const float* d_base_var, const float* d_base_j3d,
+                                         float* d_records, void* stream) {
+  if (!d_verts || !d_var || !d_j3d || !d_base_verts || !d_base_var || !d_base_j3d || !d_records || m < 0 || m > 65536 || V < 2 ||
+      V > (1 << 20) || (V & 1) || !aligned_to(d_verts, 8) || !aligned_to(d_base_verts, 8)) {
+    poco_set_error("poco_op_occlusion_records: bad arguments (need 0 <= m <= 65536, V even in 2..2^20, 8-byte aligned vertices)");
+    return POCO_ERR_ARG;
+  }
+  if (m == 0) return POCO_OK;
+  launch_occlusion_records(d_verts, d_var, d_j3d, m, V, d_base_verts, d_base_var, d_base_j3d, d_records, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_op_heat_overlay(const float* d_field, const int* d_pos, int n, int patch, int res, float scale,
+                                    const unsigned char* d_lut, const unsigned char* d_crop, unsigned char* d_out, void* stream) {
+  if (!d_field || !d_pos || !d_lut || !d_crop || !d_out || n < 1 || n > 65536 || res < 1 || res > 4096 || patch < 1 || patch > res ||
+      !(scale >= 0.f) || std::isinf(scale)) {
+    poco_set_error("poco_op_heat_overlay: bad arguments (need 1 <= n <= 65536, 1 <= res <= 4096, 1 <= patch <= res and a finite "
+                   "scale > 0, or 0 for the field's maximum)");
+    return POCO_ERR_ARG;
+  }
+  launch_heat_overlay(d_field, d_pos, n, patch, res, scale, d_lut, d_crop, d_out, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

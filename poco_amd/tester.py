@@ -147,6 +147,33 @@ class POCOTester:
         return self.render_frame(self.crop_canvas(frame_u8, box, bbox_scale), r["verts"][:1], np.array([[s, s, tx, ty]], np.float32),
                                  r["var"][:1], side_bg=255, keypoints=kp)
 
+    # ---- --occlusion_map ---------------------------------------------------------------------------------------------------
+    @property
+    def occlusion_on(self) -> bool:
+        return bool(getattr(self.args, "occlusion_map", False))
+
+    def occlusion_maps(self, frame_u8: torch.Tensor, dets: np.ndarray, bbox_scale: float = 1.0):
+        """--occlusion_map: per detection of one frame, (picture, arrays) - the heat map of --occ_metric over the detection's own
+        crop (a device uint8 [res,res,3]) and what <image>_<det>.npz holds.  One OcclusionSweep per detection (poco_amd/
+        occlusion.py): full batches of occluded copies through the engine, the records and the picture made on the device; only the
+        [n,77] records, the positions and the baseline's var_pose / pred_cam are copied to the host."""
+        from . import occlusion
+        a = self.args
+        if getattr(self, "_occ", None) is None:
+            fill = (0.0, 0.0, 0.0) if getattr(a, "occ_fill", None) is None else occlusion.fill_from_grey(a.occ_fill)
+            self._occ = occlusion.OcclusionSweep(self.model, getattr(a, "occ_patch", 40), getattr(a, "occ_stride", 10), fill)
+        scale = getattr(a, "occ_scale", "auto")
+        scale = scale if scale == "auto" else float(scale)
+        raw = np.asarray(dets)
+        for i in range(len(raw)):
+            res = self._occ.run(self.make_batch(frame_u8, raw[i:i + 1], bbox_scale))
+            field = occlusion.field_of(res.records, getattr(a, "occ_metric", "v2v"))
+            pic = occlusion.heat_overlay(field, res.positions, res.patch, self.crop_canvas(frame_u8, raw[i], bbox_scale), scale)
+            nh, nw = res.grid
+            yield pic, {"records": res.records.cpu().numpy().reshape(nh, nw, occlusion.REC), "positions": res.positions.cpu().numpy(),
+                        "patch": np.int32(res.patch), "stride": np.int32(res.stride),
+                        "var_pose": res.baseline["var_pose"][0].cpu().numpy(), "pred_cam": res.baseline["pred_cam"][0].cpu().numpy()}
+
     # ---- --image_format jpg / --save_video ------------------------------------------------------------------------------
     @property
     def image_format(self) -> str:
@@ -505,6 +532,11 @@ class POCOTester:
         render_on = self.render_on
         render_crop = render_on and bool(getattr(self.args, "render_crop", False))
         first_box = deque()                                          # --render_crop: each image's first detection, as it was cropped
+        occ_on = self.occlusion_on
+        occ_boxes = deque()                                          # --occlusion_map: each image's detections, as they were cropped
+        occ_dir = os.path.join(output_path, "occlusion")
+        if occ_on:
+            os.makedirs(occ_dir, exist_ok=True)
         img_dir = os.path.join(output_path, "poco_results")          # reference demo.py:95
         if render_on:
             os.makedirs(img_dir, exist_ok=True)
@@ -551,14 +583,30 @@ class POCOTester:
                     counts.append(len(d))
                     if render_crop:
                         first_box.append(d[0])
+                    if occ_on:
+                        occ_boxes.append(d)
                     yield img, d
 
             writes = deque()
-            for (pos, n), r in zip(picked, self.iter_frame_results(items(), bbox_scale, keep_frames=render_on)):
+
+            def picture(stem, pic):
+                if self.image_format == "jpg":
+                    return wr_pool.submit(_write_bytes, stem + ".jpg", self.encode_jpeg(pic))
+                if self.encode_on_gpu:
+                    return wr_pool.submit(_write_bytes, stem + ".png", self.encode_png(pic))
+                return wr_pool.submit(_write_png, stem + ".png", pic.cpu().numpy())
+
+            for (pos, n), r in zip(picked, self.iter_frame_results(items(), bbox_scale, keep_frames=render_on or occ_on)):
                 n_img += 1
-                if render_on:
+                if render_on or occ_on:
                     r, fr = r
                 box0 = first_box.popleft() if render_crop else None
+                boxes = occ_boxes.popleft() if occ_on else None
+                if occ_on and r is not None:
+                    for k, (pic, arrays) in enumerate(self.occlusion_maps(fr, boxes, bbox_scale)):
+                        stem = os.path.join(occ_dir, f"{os.path.splitext(n)[0]}_{k}")
+                        writes.append(picture(stem, pic))
+                        writes.append(wr_pool.submit(_write_npz, stem + ".npz", arrays))
                 if r is not None:
                     writes.append(wr_pool.submit(write, n, r))
                     if render_crop:                               # tester.py:256-285: the first detection on its own crop
@@ -570,13 +618,7 @@ class POCOTester:
                             kp = [folder_keypoints(j) for j in r["smpl_joints2d"]]
                         pic = self.render_frame(fr, r["verts"], r["orig_cam"], r["var"], side_bg=255, keypoints=kp)
                     if render_on:
-                        stem = os.path.join(img_dir, os.path.splitext(n)[0])
-                        if self.image_format == "jpg":
-                            writes.append(wr_pool.submit(_write_bytes, stem + ".jpg", self.encode_jpeg(pic)))
-                        elif self.encode_on_gpu:
-                            writes.append(wr_pool.submit(_write_bytes, stem + ".png", self.encode_png(pic)))
-                        else:
-                            writes.append(wr_pool.submit(_write_png, stem + ".png", pic.cpu().numpy()))
+                        writes.append(picture(os.path.join(img_dir, os.path.splitext(n)[0]), pic))
                 while len(writes) > ahead:
                     writes.popleft().result()
             for w in writes:
@@ -750,6 +792,10 @@ def _merge_rank_results(self, local_raw: dict, tracking: dict, W: int, H: int) -
 def _write_png(path: str, img: np.ndarray) -> None:
     from PIL import Image
     Image.fromarray(img).save(path)
+
+
+def _write_npz(path: str, arrays: dict) -> None:
+    np.savez_compressed(path, **arrays)
 
 
 def _write_bytes(path: str, data: bytes) -> None:
