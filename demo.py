@@ -27,6 +27,12 @@ and --draw_keypoints stamps those above the threshold black over the green model
 --occlusion_map (folder mode) adds PARE's occlusion analysis per detection (poco_amd/occlusion.py): a --occ_patch square of grey
 level --occ_fill slides over the crop in steps of --occ_stride, the engine regresses every occluded copy, and
 <out>/occlusion/<image>_<det>.png shows --occ_metric per position as a heat map over the crop, <image>_<det>.npz the records.
+--save_dataset FILE.npz closes POCO's self-training loop: the predictions become a pseudo-ground-truth dataset in the format the
+reference's BaseDataset (and eval.py --dataset) reads - pose as the reference's rotation_matrix_to_angle_axis of the predicted
+rotations, var without the kinematic accumulation (the reader applies it), keypoints, center and scale - made on the GPU behind
+each forward (poco_amd/pseudo.py, csrc/pseudo_gt.hip); --uncert_threshold T keeps only the crops get_confident_frames would keep.
+The printed JSON line gains dataset_offered, dataset_kept and dataset_threshold.  Video mode exports the raw predictions, not the
+--smooth-filtered ones.  Not with --gpus N > 1.
 """
 import argparse
 import json
@@ -114,6 +120,16 @@ def parse_args(argv=None):
                         "per-joint uncertainty, joints = mean displacement of the 49 joints, var:<0..23> = one joint's uncertainty")
     p.add_argument("--occ_scale", type=str, default="auto",
                    help="--occlusion_map: the value drawn as the hottest colour: auto = the map's maximum, or a positive float")
+    p.add_argument("--save_dataset", type=str, default=None, metavar="FILE.npz",
+                   help="also write the predictions as a pseudo-ground-truth dataset in the reference's format (imgname, center, "
+                        "scale, pose [N,72] axis-angle, shape, var, has_smpl, part, openpose, S, person_id; every array has N rows), "
+                        "made on the GPU from the regressor's RAW outputs: in video mode --smooth does not touch it (smoothing is "
+                        "presentation, labels are what the model said).  eval.py --dataset reads it; the reference's BaseDataset "
+                        "filters it by its own UNCERT_THRESHOLD.  Folder mode: imgname = file name, person_id = detection index; "
+                        "video mode: imgname = frame file name (<video stem>/<frame index> for an .avi), person_id = track id")
+    p.add_argument("--uncert_threshold", type=float, default=None,
+                   help="with --save_dataset: keep only the confident crops, selected as the reference's get_confident_frames "
+                        "selects (kinematic accumulation, then var[:, 0] < T); default: every crop")
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
@@ -167,6 +183,19 @@ def _check_occlusion(args) -> None:
             sys.exit(f"--occ_scale must be auto or a positive number, got {args.occ_scale}")
 
 
+def _check_dataset(args) -> None:
+    """--save_dataset / --uncert_threshold: refuse combinations that cannot work before the engine is built."""
+    path = getattr(args, "save_dataset", None)
+    thr = getattr(args, "uncert_threshold", None)
+    if thr is not None and not path:
+        sys.exit("--uncert_threshold selects the crops of --save_dataset: it needs --save_dataset FILE.npz")
+    if thr is not None and not thr == thr:
+        sys.exit("--uncert_threshold must be a number")
+    if path and args.gpus > 1:
+        sys.exit("--save_dataset with --gpus N > 1 is not supported: each rank keeps its records on its own device, and gathering "
+                 "them across the ranks in source order is a later change; run with --gpus 1")
+
+
 def _spawn_ranks(args) -> int:
     """`demo.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU."""
     import socket
@@ -192,6 +221,7 @@ def main(args):
     if getattr(args, "save_video", False) and not (args.mode == "video" and render_enabled(args)):
         sys.exit("--save_video writes the rendered frames of video mode: it needs --mode video and --render")
     _check_occlusion(args)
+    _check_dataset(args)
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")

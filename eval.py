@@ -7,7 +7,9 @@ Prints MPJPE, PA-MPJPE, V2V, the uncertainty / pose-error correlation and N, and
 arrays; the reference joblib-dumps a dict).  The metrics are computed on the GPU (poco_amd/evaluate.py, csrc/eval_metrics.hip):
 per crop nothing is copied to the host between the forward and the final reduction.  --likelihood adds the Var-MPJPE and Variance
 lines of the reference and the held-out flow NLL - the likelihood of the ground-truth pose under the model's own RealNVP, the
-quantity the uncertainty was trained on (csrc/eval_likelihood.hip, DESIGN.md "Likelihood").  Not computed: gendered SMPL models,
+quantity the uncertainty was trained on (csrc/eval_likelihood.hip, DESIGN.md "Likelihood").  --uncert_threshold T evaluates only
+the confident rows of a dataset that demo.py --save_dataset wrote (its `var` array, selected as the reference's BaseDataset selects).
+Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
 import argparse
@@ -36,6 +38,10 @@ def parse_args(argv=None):
     p.add_argument("--likelihood", action="store_true",
                    help="also print Var-MPJPE, Variance and the held-out flow NLL (needs `pose` in the dataset and "
                         "flow_head.cond_layer in the checkpoint)")
+    p.add_argument("--uncert_threshold", type=float, default=None,
+                   help="a dataset inferred from POCO (demo.py --save_dataset) carries `var`: evaluate only its confident rows, "
+                        "selected as the reference's BaseDataset selects them (kinematic accumulation, then column 0 < T); "
+                        "default: every row")
     return p.parse_args(argv)
 
 
@@ -65,8 +71,21 @@ def check_likelihood_inputs(args) -> None:
         sys.exit(f"{args.ckpt}: --likelihood needs {missing} (the checkpoint has no flow context layer)")
 
 
+def check_uncert_threshold(args) -> None:
+    """--uncert_threshold: refuse a dataset without `var` and a threshold that keeps no row before any GPU work."""
+    import numpy as np
+    from poco_amd.evaluate import select_confident
+    with np.load(args.dataset, allow_pickle=False) as z:
+        try:
+            select_confident(z, args.uncert_threshold, args.dataset)
+        except ValueError as e:
+            sys.exit(str(e))
+
+
 def main(args):
     check_dataset_file(args.dataset)
+    if getattr(args, "uncert_threshold", None) is not None:
+        check_uncert_threshold(args)
     if args.likelihood:
         check_likelihood_inputs(args)
     if not os.path.isfile(args.j_regressor):
@@ -75,9 +94,12 @@ def main(args):
     from poco_amd import evaluate
     from poco_amd.tester import POCOTester
     try:
-        ds = evaluate.EvalDataset(args.dataset, args.img_dir, args.dataset_name)
+        ds = evaluate.EvalDataset(args.dataset, args.img_dir, args.dataset_name,
+                                  uncert_threshold=getattr(args, "uncert_threshold", None))
     except ValueError as e:
         sys.exit(str(e))
+    if getattr(args, "uncert_threshold", None) is not None:
+        print(f"Confident rows (uncertainty < {args.uncert_threshold}): {len(ds)} of {ds.total}")
     J = np.load(args.j_regressor).astype(np.float32)
     tester = POCOTester(args)                       # builds the engine from --cfg / --ckpt / --smpl exactly as demo.py does
     res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),

@@ -319,6 +319,13 @@ int poco_op_rot6d(const float* d_in, float* d_rotmat, int B, void* stream);
  * function gives poco_evaluator_step its pose distance; this entry turns a ground-truth axis-angle pose [B,72] (N = 24 B) into
  * the rotation matrices poco_smpl_lbs takes.  Enqueued on `stream`. */
 int poco_op_rodrigues(const float* d_axis_angle, float* d_rotmat, int N, void* stream);
+/* rotation_matrix_to_angle_axis == pocolib/utils/geometry.py:264-429: d_rotmat [N,3,3] -> d_aa [N,3].  The reference's route, not a
+ * textbook logarithm and not batch_rot2aa: rotation_matrix_to_quaternion on the transposed matrix with its four masked candidates
+ * (the comparisons R22 < eps, R00 > R11 and R00 < -R11 on the float32 inputs, eps = float32(1e-6)), quaternion_to_angle_axis with
+ * its atan2 pair and k = 2 at sin^2 = 0, then aa[isnan] = 0 - so a matrix holding a NaN gives (0, 0, 0) and the zero matrix
+ * (0, pi, 0).  Evaluated in fp64, stored as fp32.  The same device function gives poco_pseudo_step its `pose`.  Enqueued on
+ * `stream`. */
+int poco_op_rotmat_to_aa(const float* d_rotmat, float* d_aa, int N, void* stream);
 
 /* GPU-side crop + normalise: replaces the per-detection CPU loop cv2.getAffineTransform -> cv2.warpAffine(INTER_LINEAR,
  * BORDER_CONSTANT) -> ToTensor -> Normalize + per-crop H2D copy of pocolib/core/tester.py:182-203 and
@@ -755,6 +762,51 @@ int poco_evaluator_uncert_summary(poco_evaluator_t e, double* h_summary2, void* 
 /* Rewind: the next step writes record 0. */
 int poco_evaluator_reset(poco_evaluator_t e);
 void poco_evaluator_destroy(poco_evaluator_t e);
+
+/* ---- pseudo-labeler: confident predictions as records of the reference's dataset .npz ---------------------------------------
+ * The writer of the file pocolib/dataset/base_dataset.py:54-147 reads ("If the dataset is inferred from POCO, select confident
+ * frames", :59-70); the released reference declares its accumulators (pocolib/core/tester.py:163) and never fills them;
+ * csrc/pseudo_gt.hip.  Created once, stepped per batch behind the forward, finished per run.
+ *   Record of a kept crop = POCO_PSEUDO_RECORD_FLOATS fp32 words:
+ *     [0]        source_id, the caller's int32 passed through as bits
+ *     [1..3)     center = (cx, cy) of the box                     [3] scale = max(w, h) / 200 (tester.py:194-196)
+ *     [4..76)    pose [72] = rotation_matrix_to_angle_axis of the 24 predicted matrices (poco_op_rotmat_to_aa's device function)
+ *     [76..86)   shape [10] = pred_shape
+ *     [86..110)  var [24] = var_pose averaged over its trailing elements in the order numpy's float32 mean adds them (what
+ *                postproc.prepare_uncert gives), NOT accumulated along the kinematic tree: the reader does that on load
+ *     [110..185) openpose [25,3] = joints2d[:25], confidence 1     [185..257) part [24,3] = joints2d[25:], confidence 1
+ *                (tester.py:232-233); with joints_in_crop the points first go through convert_crop_coords_to_orig_img
+ *                (pocolib/utils/demo_utils.py:268-281: box side = w), in its float32 operations
+ *     [257..353) S [24,4] = joints3d[25:], confidence 1            [353..384) 0
+ *   Selection = get_confident_frames (pocolib/utils/train_utils.py:31-45): var accumulated along the kinematic tree
+ *     (poco_utils.py:21-25), kept if column 0 < threshold; a NaN compares false and the crop is dropped.
+ *   Kept crops are appended in source order - within a step and from step to step - by a prefix sum, not by atomics; the running
+ *   count lives on the device.  Record memory that no kept crop has reached holds POCO_PSEUDO_UNWRITTEN in every word.
+ * One labeler is used from one stream at a time. */
+#define POCO_PSEUDO_RECORD_FLOATS 384
+#define POCO_PSEUDO_MAX_TRAILING 128
+#define POCO_PSEUDO_UNWRITTEN 0xFFFFFFFFu
+typedef struct poco_pseudo* poco_pseudo_t;
+/* capacity = crops that may be OFFERED (1 .. 2^24; the kept count is not known on the host); threshold: NaN or <= 0 = keep every
+ * crop; joints_in_crop = 1 for the PARE variants (smpl_joints2d in crop coordinates), 0 for the CLIFF variants (image coordinates);
+ * crop_res = DATASET.IMG_RES (1 .. 16384).  Host only: everything is validated here; the first step allocates the records
+ * (1536 bytes each) and a destination word per crop. */
+int poco_pseudo_create(int64_t capacity, float threshold, int joints_in_crop, int crop_res, poco_pseudo_t* out);
+/* Offer B crops: d_pred_pose [B,24,3,3], d_pred_shape [B,10], d_var_pose [B,24,var_t] (the engine's [B,24]: var_t = 1; at most
+ * POCO_PSEUDO_MAX_TRAILING), d_joints2d [B,49,2], d_joints3d [B,49,3], d_boxes [B,4] = cx, cy, w, h, d_source_id int32 [B].
+ * Argument errors - a null handle or pointer, B < 1, var_t outside 1..128, offered + B > capacity - return POCO_ERR_ARG before any
+ * GPU work and leave the records and counts as they were.  Enqueued on `stream` (two launches whatever B is), safe right behind
+ * poco_forward on the same stream: no synchronisation, nothing read back and, after the first step, no allocation. */
+int poco_pseudo_step(poco_pseudo_t p, int B, const float* d_pred_pose, const float* d_pred_shape, const float* d_var_pose, int var_t,
+                     const float* d_joints2d, const float* d_joints3d, const float* d_boxes, const int32_t* d_source_id,
+                     void* stream);
+/* *n_offered, *n_kept and, if h_records is not NULL, the record memory of every offered crop (host fp32 [records_cap,
+ * POCO_PSEUDO_RECORD_FLOATS], records_cap >= *n_offered): the first *n_kept records are the kept crops, the rest is unwritten.
+ * Two copies on `stream`, then one synchronisation.  Before the first step: both counts 0 and no GPU work. */
+int poco_pseudo_finish(poco_pseudo_t p, float* h_records, int64_t records_cap, int64_t* n_kept, int64_t* n_offered, void* stream);
+/* Rewind, enqueued on `stream`: both counts 0, the records unwritten again. */
+int poco_pseudo_reset(poco_pseudo_t p, void* stream);
+void poco_pseudo_destroy(poco_pseudo_t p);
 
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /

@@ -215,18 +215,47 @@ def check_dataset_keys(files) -> str:
     raise ValueError("dataset file has neither `pose` + `shape` (SMPL ground truth) nor `S` (joint ground truth)")
 
 
+class _Rows(dict):
+    """The arrays of a dataset file restricted to some rows, read like the NpzFile they came from."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def select_confident(z, threshold: float, path: str = "dataset") -> _Rows:
+    """base_dataset.py:59-70: every array of the file indexed with the rows get_confident_frames keeps.  A file without `var` and a
+    threshold that keeps nothing are refused."""
+    from .postproc import confident_frames
+    if "var" not in z.files:
+        raise ValueError(f"{path}: --uncert_threshold needs `var` (the file was not inferred from POCO: demo.py --save_dataset writes it)")
+    idx = confident_frames(z["var"], threshold)
+    n = len(z["imgname"])
+    if len(idx) == 0:
+        raise ValueError(f"{path}: --uncert_threshold {threshold} keeps none of the {n} rows")
+    out = _Rows({k: np.asarray(z[k])[idx] for k in z.files})
+    out.total = n
+    return out
+
+
 class EvalDataset:
     """The reference's dataset .npz (base_dataset.py:54-147): imgname, center [N,2], scale [N] (bbox size / 200), and pose [N,72]
     + shape [N,10] or S [N,24,3|4]; optional gender, person_id, orig_shape [N,2] (h, w) and img [N,3,224,224] = already normalised
-    crops.  Without `img` the images are read from img_dir and cropped on the GPU with the demo's crop (poco_amd/tester.py)."""
+    crops.  Without `img` the images are read from img_dir and cropped on the GPU with the demo's crop (poco_amd/tester.py).
+    uncert_threshold (eval.py --uncert_threshold): a file inferred from POCO carries `var` [N,24]; only its confident rows are
+    kept, as base_dataset.py:59-70 keeps them (postproc.confident_frames); `total` is the file's row count."""
 
-    def __init__(self, path: str, img_dir: Optional[str] = None, dataset_name: str = "3dpw", bbox_scale: float = 1.0):
+    def __init__(self, path: str, img_dir: Optional[str] = None, dataset_name: str = "3dpw", bbox_scale: float = 1.0,
+                 uncert_threshold: Optional[float] = None):
         if dataset_name not in DATASET_NAMES:
             raise ValueError(f"dataset_name must be one of {DATASET_NAMES}")
         z = np.load(path, allow_pickle=False)
         self.gt_form = check_dataset_keys(z.files)
+        if uncert_threshold is not None:
+            z = select_confident(z, uncert_threshold, path)
         self.name, self.img_dir, self.bbox_scale = dataset_name, img_dir, float(bbox_scale)
         self.imgname = [str(x) for x in z["imgname"]]
+        self.total = int(getattr(z, "total", len(self.imgname)))
         self.center = np.asarray(z["center"], np.float32).reshape(-1, 2)
         self.scale = np.asarray(z["scale"], np.float32).reshape(-1)
         n = len(self.imgname)

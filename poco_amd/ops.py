@@ -232,6 +232,16 @@ def rodrigues(aa: torch.Tensor) -> torch.Tensor:
     return out.view(*aa.shape[:-1], aa.shape[-1] // 3, 3, 3)
 
 
+def rotmat_to_aa(rotmat: torch.Tensor) -> torch.Tensor:
+    """rotation_matrix_to_angle_axis (geometry.py:264-429, the reference's quaternion route): rotation matrices [..., 3, 3] ->
+    axis-angle [..., 3]; a matrix holding a NaN gives zeros."""
+    assert rotmat.is_cuda and rotmat.dtype == torch.float32 and rotmat.shape[-2:] == (3, 3) and rotmat.numel() > 0
+    r = rotmat.contiguous().view(-1, 3, 3)
+    out = torch.empty((r.shape[0], 3), device=rotmat.device)
+    check(lib().poco_op_rotmat_to_aa(fptr(r), fptr(out), r.shape[0], current_stream()), "poco_op_rotmat_to_aa")
+    return out.view(*rotmat.shape[:-2], 3)
+
+
 # ---- backbone side kernels and fused launches on their own (include/poco_hip.h; tests/test_engine_kernels_gpu.py) -----------
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)

@@ -16,6 +16,14 @@ def kinematic_uncert(var: np.ndarray) -> np.ndarray:
     return var
 
 
+def confident_frames(var, threshold: float) -> np.ndarray:
+    """get_confident_frames (train_utils.py:31-45): the rows of a dataset file's `var` [N,24] that base_dataset.py:59-70 keeps -
+    accumulate along the kinematic tree, then column 0 < threshold.  A NaN compares false: the row is dropped."""
+    v = kinematic_uncert(np.asarray(var, np.float32).reshape(-1, 24))
+    with np.errstate(invalid="ignore"):
+        return np.nonzero(v[:, 0] < np.float32(threshold))[0]
+
+
 def prepare_uncert(var, kinematic: bool = True) -> np.ndarray:
     """POCOUtils.prepare_uncert for LOSS_VER norm_flow_* and SIGMA_DIM 1 (poco_utils.py:62-94)."""
     var = np.asarray(var.detach().cpu().numpy() if hasattr(var, "detach") else var, dtype=np.float32)

@@ -72,6 +72,8 @@ def crop_keypoints(joints2d, box, res: int = 224, bbox_scale: float = 1.0) -> np
 
 
 class POCOTester:
+    _pseudo = None                      # --save_dataset: the device-side labeler of the current run (pseudo_begin), else None
+
     def __init__(self, args):
         self.args = args
         self.model_cfg = update_hparams(args.cfg)
@@ -93,6 +95,39 @@ class POCOTester:
                 if "faces" in z.files:
                     self.faces = np.asarray(z["faces"], np.int64)
         self._renderer = None
+        self._pseudo_src = []                   # --save_dataset: the label of every crop offered to the labeler
+
+    # ---- --save_dataset ---------------------------------------------------------------------------------------------
+    def pseudo_begin(self, capacity: int) -> None:
+        """--save_dataset: a PseudoLabeler (poco_amd/pseudo.py) for the `capacity` crops this run will regress; every forward
+        of iter_frame_results / run_on_video then offers its device outputs to it."""
+        if not getattr(self.args, "save_dataset", None):
+            return
+        from .pseudo import PseudoLabeler
+        self._pseudo = PseudoLabeler(max(int(capacity), 1), getattr(self.args, "uncert_threshold", None), self.backbone,
+                                     self.model_cfg.DATASET.IMG_RES, self.device)
+        self._pseudo_src = []
+
+    def _pseudo_offer(self, out, boxes: np.ndarray, labels) -> None:
+        """One batch behind its forward, on the same stream: nothing is read back.  labels: one per crop, kept on the host and
+        found again through the crop's source_id = its position among the offered crops."""
+        base = len(self._pseudo_src)
+        self._pseudo_src.extend(labels)
+        self._pseudo.step(out, np.ascontiguousarray(boxes, np.float32).reshape(-1, 4), np.arange(base, base + len(labels), dtype=np.int32))
+
+    def pseudo_finish(self, imgname_of, person_of) -> dict:
+        """Write --save_dataset from the kept records; imgname_of / person_of map a label to the file's imgname / person_id.
+        Returns the counters of the printed JSON line."""
+        pl, self._pseudo = self._pseudo, None
+        if pl is None:
+            return {}
+        from .pseudo import write_dataset
+        arrays = pl.finish(imgname=[imgname_of(x) for x in self._pseudo_src], person_id=[person_of(x) for x in self._pseudo_src])
+        pl.close()
+        write_dataset(self.args.save_dataset, arrays)
+        thr = getattr(self.args, "uncert_threshold", None)
+        return {"dataset_offered": arrays["offered"], "dataset_kept": arrays["kept"],
+                "dataset_threshold": None if thr is None else float(thr)}
 
     # ---- --render ---------------------------------------------------------------------------------------------------
     @property
@@ -352,6 +387,9 @@ class POCOTester:
                 return
             batch = batches[0] if len(batches) == 1 else {k: torch.cat([b[k] for b in batches], 0) for k in batches[0]}
             out = self.model(batch, want_segm=False)
+            if self._pseudo is not None:       # --save_dataset: from the device outputs, before they are copied for the result files
+                self._pseudo_offer(out, np.concatenate([e["dets"][lo:lo + k] for e, lo, k in pieces]),
+                                   [(e["index"], lo + i) for e, lo, k in pieces for i in range(k)])
             # one D2H per tensor postprocess() reads (not uncert_feat / body_feat2 / pose6d / cam_t: MBs per batch that nothing
             # downstream uses), sliced per frame below
             out = {n: v.cpu() for n, v in out.items() if torch.is_tensor(v) and n not in DEVICE_ONLY_KEYS}
@@ -372,10 +410,10 @@ class POCOTester:
                 res = None if not e["parts"] else {k: np.concatenate([p[k] for p in e["parts"]], 0) for k in e["parts"][0]}
                 yield (res, e["frame"]) if keep_frames else res
 
-        for frame, dets in items:
+        for index, (frame, dets) in enumerate(items):
             raw = np.asarray(dets)
             raw = raw.reshape(-1, 4) if raw.size else np.zeros((0, 4), np.float32)
-            e = {"dets": raw, "W": frame.shape[1], "H": frame.shape[0], "parts": [], "todo": len(raw), "frame": None}
+            e = {"dets": raw, "W": frame.shape[1], "H": frame.shape[0], "parts": [], "todo": len(raw), "frame": None, "index": index}
             queue.append(e)
             if len(raw):
                 fr = self.to_device(frame)
@@ -420,13 +458,15 @@ class POCOTester:
         items = sorted((int(f), pid, k) for pid, tr in tracking_results.items() for k, f in enumerate(tr["frames"]))
         keys = ("pred_cam", "smpl_vertices", "pred_pose", "pred_shape", "smpl_joints3d", "smpl_joints2d", "var_pose")
         store = {pid: {k: [None] * len(tr["frames"]) for k in keys} for pid, tr in tracking_results.items()}
-        pend_batches, pend_meta = [], []
+        pend_batches, pend_meta, pend_dets = [], [], []
 
         def flush():
             if not pend_meta:
                 return
             batch = {k: torch.cat([b[k] for b in pend_batches], 0) for k in pend_batches[0]}
             out = self.model(batch, want_segm=False)
+            if self._pseudo is not None:       # --save_dataset: the regressor's raw outputs (smoothing comes later, per track)
+                self._pseudo_offer(out, np.concatenate(pend_dets), list(pend_meta))
             host = {k: out[k].cpu().numpy() for k in keys}
             self.model.check_status()          # after the synchronising copies, before the rows are stored
             for row, (pid, slot) in enumerate(pend_meta):
@@ -434,6 +474,7 @@ class POCOTester:
                     store[pid][k][slot] = host[k][row]
             pend_batches.clear()
             pend_meta.clear()
+            pend_dets.clear()
 
         i = 0
         while i < len(items):
@@ -450,6 +491,7 @@ class POCOTester:
                 dets = np.stack([np.asarray(tracking_results[pid]["bbox"][slot]) for _, pid, slot in part])   # keeps the tracks' dtype
                 pend_batches.append(self.make_batch(fr, dets, bbox_scale))
                 pend_meta.extend((pid, slot) for _, pid, slot in part)
+                pend_dets.append(dets.astype(np.float32).reshape(-1, 4))
                 if len(pend_meta) == bs:
                     flush()
             i = j
@@ -547,6 +589,12 @@ class POCOTester:
                 self._save_meshes(os.path.join(output_path, "meshes", os.path.splitext(n)[0]), r["verts"],
                                   [f"{i:06d}" for i in range(len(r["verts"]))])
 
+        def listed(pos, n):                                             # the detections dets_of will find, without the image
+            d = detections.get(n) if isinstance(detections, dict) else (
+                detections[pos] if detections is not None and pos < len(detections) else None)
+            return len(d) if d is not None and len(d) > 0 else 1
+
+        self.pseudo_begin(sum(listed(pos, n) for pos, n in picked))       # --save_dataset: every crop is offered once
         t0 = time.time()
         n_img = 0
         with ThreadPoolExecutor(nthreads) as dec_pool, ThreadPoolExecutor(nthreads) as wr_pool:
@@ -623,11 +671,12 @@ class POCOTester:
                     writes.popleft().result()
             for w in writes:
                 w.result()                                      # re-raises a failed write
+        dataset = self.pseudo_finish(lambda x: picked[x[0]][1], lambda x: x[1])   # imgname = the file name, person_id = detection index
         torch.cuda.synchronize()
         dt = time.time() - t0
         n_crops = int(sum(counts))
         return {"images": n_img, "crops": n_crops, "seconds": dt, "fps": n_img / max(dt, 1e-9),
-                "crops_per_s": n_crops / max(dt, 1e-9)}
+                "crops_per_s": n_crops / max(dt, 1e-9), **dataset}
 
 
 def _run_on_video_folder(self, frame_folder: str, tracking_path: Optional[str], output_path: str, bbox_scale=1.0):
@@ -707,6 +756,7 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
     rank = tdist.get_rank() if world > 1 else 0
     t0 = time.time()
     mine = tracking
+    dataset = {}
     if world > 1:
         # whole tracks are the unit of sharding (temporal smoothing stays local: the owning rank smooths and
         # finishes its tracks); the only exchange is one all-gather of the packed per-frame SMPL records, from which rank 0
@@ -720,7 +770,16 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
     else:
         if isinstance(load, _GroupLoader):
             load.plan(sorted({int(f) for v in tracking.values() for f in v["frames"]}))
+        self.pseudo_begin(sum(len(v["frames"]) for v in tracking.values()))
         results = self.run_on_video(tracking, load, W, H, bbox_scale)
+        order = {pid: i for i, pid in enumerate(tracking)}
+        vstem = os.path.splitext(os.path.basename(os.path.normpath(frame_folder)))[0]
+
+        def frame_name(x):              # the frame's file name; a video file has none: <stem>/<frame index>
+            f = int(tracking[x[0]]["frames"][x[1]])
+            return f"{vstem}/{f:06d}" if reader is not None else (names[f] if 0 <= f < len(names) else f"{f:06d}")
+
+        dataset = self.pseudo_finish(frame_name, lambda x: int(x[0]) if str(x[0]).lstrip("-").isdigit() else order[x[0]])
     torch.cuda.synchronize()
     dt = time.time() - t0
     if rank != 0:
@@ -744,7 +803,7 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
     n_crops = sum(len(v["frames"]) for v in tracking.values())
     n_frames = len({int(f) for v in tracking.values() for f in v["frames"]})
     return {"images": n_frames, "crops": n_crops, "tracks": len(tracking), "seconds": dt, "ranks": world,
-            "fps": n_frames / max(dt, 1e-9), "crops_per_s": n_crops / max(dt, 1e-9)}
+            "fps": n_frames / max(dt, 1e-9), "crops_per_s": n_crops / max(dt, 1e-9), **dataset}
 
 
 def _merge_rank_results(self, local_raw: dict, tracking: dict, W: int, H: int) -> dict:
