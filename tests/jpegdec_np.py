@@ -3,7 +3,7 @@ decoder in integer arithmetic whose pixels are libjpeg's with jpeg_decompress de
 produce these BYTES.
 
     decode(data) -> uint8 [H,W,3]         raises JpegError on a damaged stream
-    decode_stats(data) -> (pixels, stats) stats: what the fixture set is asserted to contain
+    decode_stats(data) -> (pixels, stats) stats: what the fixture sets are asserted to contain (new_stats lists the counters)
     sync_rounds(data) -> int              a model of the device's self-synchronising subsequences: the rounds a stream needs
 
 The marker walk is poco_amd.jpeg.parse_jpeg (host code, tested here against PIL through the pixels).  Entropy decoding follows
@@ -63,34 +63,41 @@ class HuffTable:
 
 
 def _window(d, end, bp, bo):
-    """32 bits from position (bp, bo) and the byte index after each of the 5 data bytes read."""
-    w, q, steps = 0, bp, []
+    """32 bits from position (bp, bo), the byte index after each of the 5 data bytes read, and the index of each of them."""
+    w, q, steps, pos = 0, bp, [], []
     for _ in range(5):
         b = d[q] if q < end else 0
         w = (w << 8) | b
+        pos.append(q)
         q += 2 if b == 0xFF else 1
         steps.append(q)
-    return ((w << bo) >> 8) & 0xFFFFFFFF, steps
+    return ((w << bo) >> 8) & 0xFFFFFFFF, steps, pos
 
 
-def decode_span(d, end, state, stop, tabs, comp_of, strict, sink=None, blk=0, max_blk=1 << 30, stats=None):
+def decode_span(d, end, state, stop, tabs, comp_of, strict, sink=None, blk=0, max_blk=1 << 30, stats=None, lo=0, later=False):
     """Decode symbols from `state` = (bp, bo, block within the MCU, zigzag index) while bp < stop (symbols that START before
     `stop`) and blk < max_blk.  Returns (exit state, blocks finished).  sink(blk, zigzag index, value) receives coefficients
     (DC as differences).  strict: a damaged stream raises; otherwise it is decoded by the device's fixed rule (a window that
-    holds no code counts as a 16-bit code of symbol 0, a zigzag index past 63 ends the block)."""
+    holds no code counts as a 16-bit code of symbol 0, a zigzag index past 63 ends the block).  stats: the counters of
+    decode_stats; `lo` is then the start of the restart interval, from which subsequence boundaries are counted, and `later`
+    says that it is not the file's first one."""
     bp, bo, b, z = state
     nblk = 0
     bpm = len(comp_of)
+    zrls = 0                                                   # ZRLs in a row just before this symbol
     while bp < stop and blk < max_blk:
-        w, steps = _window(d, end, bp, bo)
+        w, steps, pos = _window(d, end, bp, bo)
         dc, ac = tabs[comp_of[b]]
         ln, sym = (dc if z == 0 else ac).lookup(w >> 16)
         if ln == 0:
             if strict:
                 raise JpegError("no Huffman code at byte %d" % bp)
             ln, sym = 16, 0
-        elif stats is not None and ln > LOOKAHEAD:
-            stats["long_codes"] += 1
+        elif stats is not None:
+            stats["long_codes"] += ln > LOOKAHEAD
+            stats["max_code_len"] = max(stats["max_code_len"], ln)
+            stats["dc_code_lens" if z == 0 else "ac_code_lens"].add(ln)
+            stats["sym_fa"] += z != 0 and sym == 0xFA
         s = sym & 15
         r = sym >> 4 if z else 0
         val = None
@@ -127,15 +134,69 @@ def decode_span(d, end, state, stop, tabs, comp_of, strict, sink=None, blk=0, ma
         if val is not None and sink is not None and (val or k == 0):
             sink(blk, k, val)
         n = bo + ln + s
+        if stats is not None:
+            if val is not None and k == 0:
+                stats["max_dc_category"] = max(stats["max_dc_category"], s)
+                if s == 11:
+                    stats["dc11_signs"].add(1 if val > 0 else -1)
+            if val is not None and k == 63:
+                stats["full_blocks"] += 1
+                stats["zrl3_then_63"] += zrls == 3
+            zrls = zrls + 1 if (z > 1 and val is None and sym == 0xF0) else 0
+            # the symbol's first bit lies in byte bp, its last one in byte pos[(n - 1) >> 3]
+            if ln + s >= 20 and (bp - lo) // SUBSEQ_BYTES != (pos[(n - 1) >> 3] - lo) // SUBSEQ_BYTES:
+                _count(stats, "long_symbol_straddles", later)
         if n >= 8:
             bp = steps[(n >> 3) - 1]
         bo = n & 7
         if z >= 64:
+            if stats is not None and bo == 0 and bp > lo and bp < end and (bp - lo) % SUBSEQ_BYTES == 0:
+                _count(stats, "aligned_block_ends", later)
             z = 0
             b = (b + 1) % bpm
             blk += 1
             nblk += 1
     return (bp, bo, b, z), nblk
+
+
+def _count(stats, key, later):
+    stats[key] += 1
+    if later:
+        stats["later_intervals"][key] += 1
+
+
+def boundary_ff(info, stats):
+    """Stuffed FF 00 pairs at the subsequence boundaries of every restart interval: across one, and just before one."""
+    d = info.data
+    for si, (off, ln, _) in enumerate(info.segments.tolist()):
+        lo = info.scan_offset + off
+        for bnd in range(lo + SUBSEQ_BYTES, lo + ln, SUBSEQ_BYTES):
+            if d[bnd - 1] == 0xFF and d[bnd] == 0:
+                _count(stats, "ff_straddles", si > 0)
+            if d[bnd - 2] == 0xFF and d[bnd - 1] == 0:
+                _count(stats, "ff_before_boundary", si > 0)
+
+
+BOUNDARY_COUNTERS = ("ff_straddles", "ff_before_boundary", "long_symbol_straddles", "aligned_block_ends")
+
+
+def new_stats() -> dict:
+    """The counters of decode_stats.  A subsequence boundary is a multiple of SUBSEQ_BYTES from its restart interval's start
+    that lies inside the interval, as jdec_sync computes it.
+    ff_straddles           an 0xFF is the last byte before a boundary, its stuffed 0x00 the first one after it
+    ff_before_boundary     the stuffed 0x00 is the last byte before a boundary
+    long_symbol_straddles  a symbol of 20 bits or more (code + value bits) starts before a boundary and ends after it
+    aligned_block_ends     a block ends with bit offset 0 exactly on a boundary
+    later_intervals        the four above again, counted in restart intervals other than the file's first
+    full_blocks            blocks whose last symbol writes coefficient 63: no EOB
+    zrl3_then_63           blocks in which three ZRLs are followed by a non-zero coefficient 63
+    sym_fa                 AC symbols 0xFA (run 15, size 10)
+    max_code_len, dc_code_lens, ac_code_lens   the code lengths the stream uses
+    max_dc_category, dc11_signs                DC differences (the signs of those of category 11)"""
+    st = {k: 0 for k in ("zrl", "eob", "long_codes", "max_category", "max_code_len", "max_dc_category", "sym_fa", "full_blocks",
+                         "zrl3_then_63") + BOUNDARY_COUNTERS}
+    st.update(dc_code_lens=set(), ac_code_lens=set(), dc11_signs=set(), later_intervals={k: 0 for k in BOUNDARY_COUNTERS})
+    return st
 
 
 def _geometry(info):
@@ -167,7 +228,7 @@ def coefficients(info, stats=None):
             raise JpegError("restart intervals do not match the picture")
         lo, hi = info.scan_offset + off, info.scan_offset + off + ln
         b0, b1 = mcu0 * bpm, (mcu0 + n_mcu) * bpm
-        _, got = decode_span(d, hi, (lo, 0, 0, 0), hi, tabs, comp_of, True, sink, b0, b1, stats)
+        _, got = decode_span(d, hi, (lo, 0, 0, 0), hi, tabs, comp_of, True, sink, b0, b1, stats, lo, si > 0)
         if got != b1 - b0:
             raise JpegError("restart interval %d ends after %d of %d blocks" % (si, got, b1 - b0))
         # DC differences -> values, per component, from 0 at the start of the interval
@@ -272,9 +333,10 @@ def decode_stats(data: bytes):
     info = parse_jpeg(data)
     if info is None:
         raise JpegError("not a baseline JPEG this decoder takes")
-    stats = {"zrl": 0, "eob": 0, "long_codes": 0, "max_category": 0,
-             "stuffed": data[info.scan_offset:info.scan_offset + info.scan_length].count(b"\xff\x00"),
-             "segments": len(info.segments), "max_segment_bytes": int(info.segments[:, 1].max())}
+    stats = new_stats()
+    stats.update(stuffed=data[info.scan_offset:info.scan_offset + info.scan_length].count(b"\xff\x00"),
+                 segments=len(info.segments), max_segment_bytes=int(info.segments[:, 1].max()))
+    boundary_ff(info, stats)
     pl = planes(info, coefficients(info, stats))
     H, W = info.height, info.width
     if info.ncomp == 1:
@@ -312,7 +374,15 @@ def sync_rounds(data: bytes, subseq: int = SUBSEQ_BYTES) -> int:
         start = [lo + j * subseq for j in range(nsub)]
         stop = [min(lo + (j + 1) * subseq, hi) for j in range(nsub)]
         entry = [(s + (1 if j and d[s - 1] == 0xFF and d[s] == 0 else 0), 0, 0, 0) for j, s in enumerate(start)]
-        exits = [decode_span(d, hi, entry[j], stop[j], tabs, comp_of, False)[0] for j in range(nsub)]
+        memo = {}                                              # (lane, entry state) -> exit state: chains meet again and again
+
+        def span(j):
+            key = (j, entry[j])
+            if key not in memo:
+                memo[key] = decode_span(d, hi, entry[j], stop[j], tabs, comp_of, False)[0]
+            return memo[key]
+
+        exits = [span(j) for j in range(nsub)]
         rounds = 1
         for _ in range(nsub):
             changed = False
@@ -320,7 +390,7 @@ def sync_rounds(data: bytes, subseq: int = SUBSEQ_BYTES) -> int:
             for j in range(1, nsub):
                 if entry[j] != exits[j - 1]:
                     entry[j] = exits[j - 1]
-                    new[j] = decode_span(d, hi, entry[j], stop[j], tabs, comp_of, False)[0]
+                    new[j] = span(j)
                     changed |= new[j] != exits[j]
             exits = new
             if not changed:

@@ -1,5 +1,6 @@
 """The baseline JPEG decoder's contract without a GPU: the numpy restatement (tests/jpegdec_np.py) against PIL BYTE for byte on a
-fixture set whose coverage is asserted, parse_jpeg's refusals, damaged streams, and MjpegReader against MjpegWriter."""
+fixture set whose coverage is asserted, the same on the streams libjpeg's writer never makes (tests/jpegdec_cases.py),
+parse_jpeg's refusals, damaged streams, and MjpegReader against MjpegWriter."""
 import ctypes as C
 import functools
 import io
@@ -10,7 +11,8 @@ import pytest
 from PIL import Image
 
 from poco_amd import jpeg
-from tests import jpeg_np, jpegdec_np
+from tests import jpeg_np, jpegdec_cases, jpegdec_np
+from tests.jpegbase_enc_np import recode
 from tests.test_jpeg_cpu import photo_like
 
 SIZES = [(1, 1), (8, 8), (17, 33), (96, 128), (120, 168), (24, 700)]         # H x W
@@ -107,6 +109,115 @@ def test_fixture_set_covers_the_hard_cases():
     rounds = {n: jpegdec_np.sync_rounds(fs[n]) for n in ("64x96_noise_q100", "120x168_noise_q30")}
     assert max(rounds.values()) >= 2, rounds                                   # the synchronisation loop is exercised
     assert all(jpegdec_np.sync_rounds(d) == 1 for n, d in fs.items() if n.startswith("1x1_"))      # one subsequence: nothing to guess
+
+
+@functools.lru_cache(maxsize=None)
+def hand_restated(name):
+    """(pixels, stats) of the restatement for a hand case, computed once and shared with tests/test_jpegdec_gpu.py."""
+    px, st = jpegdec_np.decode_stats(jpegdec_cases.hand_cases()[name])
+    px.setflags(write=False)
+    return px, st
+
+
+@pytest.mark.parametrize("name", list(jpegdec_cases.hand_cases()))
+def test_hand_case_equals_pil(name):
+    data = jpegdec_cases.hand_cases()[name]
+    assert jpeg.parse_jpeg(data) is not None
+    ref = pil_pixels(data)
+    got = hand_restated(name)[0]
+    assert got.shape == ref.shape and got.dtype == np.uint8
+    assert np.array_equal(got, ref), (name, np.argwhere(got != ref)[:4].tolist())
+
+
+def test_transcoder_keeps_the_pixels():
+    """Without `edit` a recoded file is the source's picture, whatever the tables, ids, restart interval and DHT layout."""
+    for k, s in enumerate(("420", "422", "444", "grey")):
+        src = jpegdec_cases.source(s, 13, 17)
+        ref = pil_pixels(src)
+        for j, (t, ids) in enumerate((t, i) for t in jpegdec_cases.TABLES for i in jpegdec_cases.IDS):
+            out = recode(src, t, ids, (0, 1, 2, 5)[(j + k) % 4], dht=("each", "joined")[j & 1])
+            assert np.array_equal(pil_pixels(out), ref), (s, t, ids)
+    assert recode(src, "flat", dht="each").count(b"\xff\xc4") == 2 and recode(src, "flat", dht="joined").count(b"\xff\xc4") == 1
+    with pytest.raises(AssertionError, match="DC difference"):
+        recode(src, edit=[(0, 0, 1500), (1, 0, -1500)])
+    with pytest.raises(AssertionError, match="AC coefficient"):
+        recode(src, edit=[(0, 5, 1024)])
+
+
+def test_hand_cases_cover_what_libjpeg_never_writes():
+    """Each property on the case named for it.  Of these the old fixture set has no symbol 0xFA, no three ZRLs in front of
+    coefficient 63, no positive DC difference of category 11, no DC code longer than 10 bits, one table id layout only, and
+    at most 59 rounds of synchronisation; its boundary properties are there, but by luck."""
+    hc = jpegdec_cases.hand_cases()
+    st = {n: hand_restated(n)[1] for n in hc}
+    infos = {n: jpeg.parse_jpeg(d) for n, d in hc.items()}
+    assert len(set(hc.values())) == len(hc)
+    assert all(i.height <= 150 and i.width <= 200 for i in infos.values())
+    # tables: every deep stream uses 16-bit codes, and under every id layout one uses every length 10 .. 16 for DC and for AC
+    deep = [n for n in hc if "deep" in n]
+    assert len(deep) >= 12 and all(st[n]["max_code_len"] == 16 for n in deep)
+    every = set(range(10, 17))
+    for ids in jpegdec_cases.IDS:
+        assert st[f"tables-deep-{ids}-420-33x47"]["dc_code_lens"] == every == st[f"tables-deep-{ids}-420-33x47"]["ac_code_lens"]
+    assert all(st[n]["max_code_len"] == 9 and st[n]["long_codes"] == 0 for n in hc if "flat" in n)
+    # table ids: whichever id carries it, luma gets the table made from luma's symbols (shared and swapped parse alike, from
+    # different scan headers); per_component gives three different tables of each class
+    def layout(i):
+        return tuple(i.dc.index(t) for t in i.dc), tuple(i.ac.index(t) for t in i.ac)
+    for s in ("420", "444"):
+        for t in jpegdec_cases.TABLES:
+            i3 = {ids: infos[f"tables-{t}-{ids}-{s}-33x47"] for ids in jpegdec_cases.IDS}
+            assert i3["shared"].dc == i3["swapped"].dc and i3["shared"].ac == i3["swapped"].ac
+            if t != "flat":                                # (flat tables are the same table under every id)
+                assert layout(i3["shared"]) == ((0, 1, 1), (0, 1, 1)) and layout(i3["per_component"]) == ((0, 1, 2), (0, 1, 2))
+                assert i3["shared"].dc[1] != i3["per_component"].dc[1] and i3["shared"].ac[1] != i3["per_component"].ac[1]
+    ids_seen = set()
+    for n, d in hc.items():
+        k = d.index(b"\xff\xda")
+        ids_seen.add(tuple(d[k + 6 + 2 * c] for c in range(d[k + 4])))
+    assert {(0x00, 0x11, 0x11), (0x11, 0x00, 0x00), (0x00, 0x11, 0x33), (0x00,), (0x11,)} <= ids_seen
+    # restart intervals
+    assert infos["dri1-420-33x47"].restart_interval == 1 and len(infos["dri1-420-33x47"].segments) == 9 > 8
+    assert len(infos["dri1-noise"].segments) == 192 and len(infos["dri1-444-200x120"].segments) == 375 >= 256
+    assert len(infos["dri1-deep-per_component-444-200x120"].segments) >= 256 and st["dri1-deep-per_component-444-200x120"]["max_code_len"] == 16
+    assert max(infos["dri1-444-200x120"].segments[:, 1]) < jpeg.SUBSEQ_BYTES                   # far shorter than a subsequence
+    assert infos["dri7-noise"].restart_interval == 7 and len(infos["dri7-noise"].segments) == 28 > 8              # RSTm wraps
+    assert infos["dri-whole-420-33x47"].restart_interval == 9 and len(infos["dri-whole-420-33x47"].segments) == 1
+    assert b"\xff\xdd" in hc["dri-whole-420-33x47"] and b"\xff\xd0" not in hc["dri-whole-420-33x47"]
+    # subsequence boundaries
+    for prop, name in jpegdec_cases.BOUNDARY.items():
+        assert st[name][prop] > 0, (prop, name)
+        if prop in jpegdec_cases.LATER_INTERVAL:
+            assert st[name]["later_intervals"][prop] > 0 and min(infos[name].segments[:, 1]) > jpeg.SUBSEQ_BYTES, (prop, name)
+    assert "deep" in jpegdec_cases.BOUNDARY["long_symbol_straddles"]
+    # extremes
+    for n in ("extreme-dc11-checkerboard", "extreme-dc11-checkerboard-deep"):
+        assert st[n]["max_dc_category"] == 11 and st[n]["dc11_signs"] == {1, -1}, n
+    for n in ("extreme-edited-blocks", "extreme-edited-blocks-deep"):
+        assert st[n]["sym_fa"] >= 4 and st[n]["zrl3_then_63"] >= 2 and st[n]["full_blocks"] > 2 and st[n]["max_category"] == 10, n
+    # ... none of which the old set has
+    old = [restated(n)[1] for n in fixture_set()]
+    assert sum(s["sym_fa"] + s["zrl3_then_63"] for s in old) == 0 and all(1 not in s["dc11_signs"] for s in old)
+    assert max(max(s["dc_code_lens"]) for s in old) <= 10
+
+
+def test_slow_synchronisation_case():
+    """The flat-table noise stream needs more rounds than anything in the old fixture set, and no fewer than when it was written."""
+    rounds = jpegdec_np.sync_rounds(jpegdec_cases.hand_cases()["slow-sync"])
+    print("sync_rounds of slow-sync:", rounds)
+    assert rounds >= jpegdec_cases.SLOW_SYNC_ROUNDS
+    old = max(jpegdec_np.sync_rounds(d) for d in fixture_set().values())
+    print("the old fixture set's maximum:", old)
+    assert rounds > old
+
+
+def test_unowned_code_is_reported():
+    """Sixteen 1-bits where a symbol starts: the restatement names that byte."""
+    bad, bp = jpegdec_cases.unowned_code(jpegdec_cases.hand_cases()["tables-deep-per_component-444-33x47"])
+    info = jpeg.parse_jpeg(bad)
+    assert info is not None and bp - info.scan_offset >= 2 * jpeg.SUBSEQ_BYTES
+    with pytest.raises(jpegdec_np.JpegError, match=f"no Huffman code at byte {bp}$"):
+        jpegdec_np.decode(bad)
 
 
 def test_parse_jpeg_fields():

@@ -1,6 +1,7 @@
 """GPU: the JPEG decoder (csrc/jpeg_dec.hip) against its numpy restatement (tests/jpegdec_np.py, pinned on PIL in
 tests/test_jpegdec_cpu.py) BYTE for byte: the fixture set image by image and in one mixed call, a restart interval longer than one
-workgroup's lanes, guard bands, reuse, the encoder's round trip, damaged streams and argument errors."""
+workgroup's lanes, guard bands, reuse, the encoder's round trip, damaged streams and argument errors - and the streams libjpeg's
+writer never makes (tests/jpegdec_cases.py): alone, batched with the fixture set, around the slowest synchronisation, damaged."""
 import ctypes as C
 
 import numpy as np
@@ -10,7 +11,8 @@ import torch
 from poco_amd import jpeg
 from poco_amd._lib import lib
 from tests import jpeg_np, jpegdec_np
-from tests.test_jpegdec_cpu import fixture_set, pil_jpeg, restated
+from tests.jpegdec_cases import BOUNDARY, hand_cases, unowned_code
+from tests.test_jpegdec_cpu import fixture_set, hand_restated, pil_jpeg, restated
 from tests.test_jpeg_cpu import photo_like
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +23,7 @@ MAX_H, MAX_W = 120, 2048
 
 @pytest.fixture(scope="module")
 def dec(cuda):
-    return jpeg.JpegDecoder(cuda, MAX_H, MAX_W, max_batch=len(fixture_set()), max_bytes=2 << 20)
+    return jpeg.JpegDecoder(cuda, MAX_H, MAX_W, max_batch=len(fixture_set()) + len(hand_cases()), max_bytes=4 << 20)
 
 
 def _diff(got: torch.Tensor, ref: np.ndarray):
@@ -141,6 +143,54 @@ def test_damaged_streams_in_a_batch(dec, cuda):
         assert np.array_equal(host[spans[k][0]:spans[k][1]].reshape(restated(n)[0].shape), restated(n)[0]), n
     outs, st = dec.decode([fs[n] for n in good], return_status=True)
     assert st == [0, 0, 0] and all(_diff(o, restated(n)[0]) is None for n, o in zip(good, outs))
+
+
+def test_every_hand_case_alone(dec):
+    for name, data in hand_cases().items():
+        (out,), st = dec.decode([data], return_status=True)
+        assert st == [0], name
+        assert _diff(out, hand_restated(name)[0]) is None, (name, _diff(out, hand_restated(name)[0]))
+
+
+def test_one_call_mixes_hand_cases_and_fixtures(dec):
+    """Optimal, flat and deep tables under every id layout, restart intervals of one MCU and none, next to what PIL writes."""
+    refs = [(n, hand_restated(n)[0], d) for n, d in hand_cases().items()] + [(n, restated(n)[0], d) for n, d in fixture_set().items()]
+    refs = refs[0::2] + refs[1::2]                                         # neighbours in the batch are of different kinds
+    outs, st = dec.decode([d for _, _, d in refs], return_status=True)
+    assert st == [0] * len(refs)
+    for (n, ref, _), o in zip(refs, outs):
+        assert _diff(o, ref) is None, (n, _diff(o, ref))
+
+
+def test_boundary_cases_around_the_slowest_synchronisation(dec):
+    """The boundary cases first and last in the batch, the stream whose every lane waits for its predecessor between them;
+    then smaller batches on the same scratch: no entry or exit state of the many-round image may leak into the next call."""
+    hc = hand_cases()
+    b = list(BOUNDARY.values())
+    small = [n for n in hc if n.endswith("17x13")]
+    assert len(b) == 4 and len(small) >= 6
+    for names in (b[:2] + ["slow-sync"] + b[2:], small, ["slow-sync"], small[:3], b[2:3], ["slow-sync", b[0]], small[-1:]):
+        outs, st = dec.decode([hc[n] for n in names], return_status=True)
+        assert st == [0] * len(names), names
+        for n, o in zip(names, outs):
+            assert _diff(o, hand_restated(n)[0]) is None, (n, _diff(o, hand_restated(n)[0]))
+
+
+def test_code_that_no_table_owns(dec):
+    """A deep-table stream with sixteen 1-bits where a symbol starts, two subsequences into the scan: the window holds no code.
+    Non-zero status for that image, as the restatement reports it; its neighbours are what they are alone."""
+    hc = hand_cases()
+    good = ["tables-deep-shared-420-33x47", "tables-deep-per_component-444-33x47", "tables-flat-swapped-444-17x13"]
+    bad, bp = unowned_code(hc[good[1]])
+    with pytest.raises(jpegdec_np.JpegError, match=f"no Huffman code at byte {bp}$"):
+        jpegdec_np.decode(bad)
+    solo = [dec.decode([hc[n]])[0] for n in good]
+    outs, st = dec.decode([hc[good[0]], bad, hc[good[1]], hc[good[2]]], return_status=True)
+    assert [s != 0 for s in st] == [False, True, False, False], st
+    for n, o, alone in zip(good, [outs[0], outs[2], outs[3]], solo):
+        assert torch.equal(o, alone) and _diff(o, hand_restated(n)[0]) is None, n
+    outs, st = dec.decode([hc[good[1]]], return_status=True)               # and a clean decode afterwards
+    assert st == [0] and _diff(outs[0], hand_restated(good[1])[0]) is None
 
 
 def test_argument_errors_leave_the_decoder_usable(cuda):
