@@ -33,6 +33,10 @@ rotations, var without the kinematic accumulation (the reader applies it), keypo
 each forward (poco_amd/pseudo.py, csrc/pseudo_gt.hip); --uncert_threshold T keeps only the crops get_confident_frames would keep.
 The printed JSON line gains dataset_offered, dataset_kept and dataset_threshold.  Video mode exports the raw predictions, not the
 --smooth-filtered ones.  Not with --gpus N > 1.
+--save_segm (folder mode, PARE variants) writes <out>/segm/<image>_<det>.png per detection: the 224 x 224 crop blended 50/50 with the
+coloured argmax of the upsampled pred_segm_mask and, beside it, the same crop blended with the 24 body parts of the predicted mesh
+rasterised at pred_cam_t (poco_amd/segm.py, csrc/part_labels.hip, csrc/segm_metrics.hip); --part_mapping FILE replaces the default
+vertex -> part table (each vertex's largest skinning weight).
 """
 import argparse
 import json
@@ -130,6 +134,13 @@ def parse_args(argv=None):
     p.add_argument("--uncert_threshold", type=float, default=None,
                    help="with --save_dataset: keep only the confident crops, selected as the reference's get_confident_frames "
                         "selects (kinematic accumulation, then var[:, 0] < T); default: every crop")
+    p.add_argument("--save_segm", action="store_true",
+                   help="folder mode, PARE variants: per detection write <out>/segm/<image>_<det>.png, two 224 x 224 panels made on the "
+                        "GPU: the crop under the coloured argmax of pred_segm_mask, and under the body parts of the predicted mesh "
+                        "(needs `faces` in the --smpl file; --encode gpu compresses the pictures on the GPU too)")
+    p.add_argument("--part_mapping", type=str, default=None,
+                   help="with --save_segm: the vertex -> part table as .npy / .npz / the reference's smpl_partSegmentation_mapping.pkl "
+                        "(default: each vertex's largest skinning weight)")
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
@@ -196,6 +207,21 @@ def _check_dataset(args) -> None:
                  "them across the ranks in source order is a later change; run with --gpus 1")
 
 
+def _check_segm(args) -> None:
+    """--save_segm: refuse video mode, a head without a segmentation mask, a body model without triangles and an unreadable
+    --part_mapping before the engine is built."""
+    if not getattr(args, "save_segm", False):
+        return
+    from poco_amd import segm
+    from poco_amd.config import update_hparams
+    try:
+        segm.check_demo_inputs(args, update_hparams(args.cfg).POCO.BACKBONE)
+        if getattr(args, "part_mapping", None):
+            segm.load_part_mapping(args.part_mapping)
+    except ValueError as e:
+        sys.exit(str(e))
+
+
 def _spawn_ranks(args) -> int:
     """`demo.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU."""
     import socket
@@ -222,6 +248,7 @@ def main(args):
         sys.exit("--save_video writes the rendered frames of video mode: it needs --mode video and --render")
     _check_occlusion(args)
     _check_dataset(args)
+    _check_segm(args)
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")
@@ -259,7 +286,11 @@ def main(args):
     if args.mode == "video":
         stats = tester.run_on_video_folder(folder, tracking, out_dir)
     else:
-        stats = tester.run_on_image_folder(folder, load_detections(args.detections), out_dir)
+        dets = load_detections(args.detections)
+        stats = tester.run_on_image_folder(folder, dets, out_dir)
+        if getattr(args, "save_segm", False):
+            from poco_amd import segm
+            stats["segm_pictures"] = segm.write_segm_pictures(tester, folder, dets, out_dir)
     if "fps" in stats:                                                    # rank 0 (the reference logs 'poco FPS', demo.py:136-145)
         print(json.dumps({"poco_fps": round(stats["fps"], 2), **stats}))
     if args.gpus > 1:

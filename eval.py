@@ -9,6 +9,10 @@ per crop nothing is copied to the host between the forward and the final reducti
 lines of the reference and the held-out flow NLL - the likelihood of the ground-truth pose under the model's own RealNVP, the
 quantity the uncertainty was trained on (csrc/eval_likelihood.hip, DESIGN.md "Likelihood").  --uncert_threshold T evaluates only
 the confident rows of a dataset that demo.py --save_dataset wrote (its `var` array, selected as the reference's BaseDataset selects).
+--segm (PARE variants; the dataset needs `pose`, `shape` and `part`, as demo.py --save_dataset writes them) scores the part
+segmentation head: per batch the ground-truth mesh is rasterised on the GPU into the 24 body parts plus background with the
+reference's crop camera and pred_segm_mask is scored against it - cross-entropy, pixel accuracy, mean IoU (poco_amd/segm.py,
+csrc/part_labels.hip, csrc/segm_metrics.hip); --part_mapping FILE replaces the default vertex -> part table.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -42,6 +46,12 @@ def parse_args(argv=None):
                    help="a dataset inferred from POCO (demo.py --save_dataset) carries `var`: evaluate only its confident rows, "
                         "selected as the reference's BaseDataset selects them (kinematic accumulation, then column 0 < T); "
                         "default: every row")
+    p.add_argument("--segm", action="store_true",
+                   help="PARE variants: also print Segm CE, Segm pixel acc and Segm mIoU of pred_segm_mask against the body-part map "
+                        "of the ground-truth mesh (needs `pose`, `shape` and `part` in the dataset and `faces` in the --smpl file)")
+    p.add_argument("--part_mapping", type=str, default=None,
+                   help="with --segm: the vertex -> part table as .npy / .npz / the reference's smpl_partSegmentation_mapping.pkl "
+                        "(default: each vertex's largest skinning weight)")
     return p.parse_args(argv)
 
 
@@ -82,8 +92,31 @@ def check_uncert_threshold(args) -> None:
             sys.exit(str(e))
 
 
+def check_segm_inputs(args) -> None:
+    """--segm: refuse a head without a segmentation mask, a dataset without pose / shape / part, a body model without triangles and
+    an unreadable --part_mapping before any GPU work."""
+    import numpy as np
+    from poco_amd import segm
+    from poco_amd.config import update_hparams
+    try:
+        with np.load(args.dataset, allow_pickle=False) as z:
+            segm.check_eval_inputs(update_hparams(args.cfg).POCO.BACKBONE, z.files)
+        if getattr(args, "part_mapping", None):
+            segm.load_part_mapping(args.part_mapping)
+    except ValueError as e:
+        sys.exit(f"{args.dataset}: {e}")
+    if not os.path.isfile(args.smpl):
+        sys.exit(f"--segm: body-model file not found: {args.smpl}")
+    with np.load(args.smpl) as z:
+        if "faces" not in z.files:
+            sys.exit(f"--segm: {args.smpl} has no `faces` array (convert the SMPL .pkl with tools/convert_smpl.py, which keeps its "
+                     "triangles)")
+
+
 def main(args):
     check_dataset_file(args.dataset)
+    if getattr(args, "segm", False):
+        check_segm_inputs(args)
     if getattr(args, "uncert_threshold", None) is not None:
         check_uncert_threshold(args)
     if args.likelihood:
@@ -102,11 +135,24 @@ def main(args):
         print(f"Confident rows (uncertainty < {args.uncert_threshold}): {len(ds)} of {ds.total}")
     J = np.load(args.j_regressor).astype(np.float32)
     tester = POCOTester(args)                       # builds the engine from --cfg / --ckpt / --smpl exactly as demo.py does
-    res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
-                            kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
-                            likelihood=args.likelihood)
+    if getattr(args, "segm", False):
+        from poco_amd import segm
+        try:
+            res = segm.run_eval(tester.model, ds, args.dataset, J, args.smpl, part_mapping=args.part_mapping,
+                                batch_size=max(int(args.batch_size), 1), kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT),
+                                save_results=args.save_results, likelihood=args.likelihood,
+                                uncert_threshold=getattr(args, "uncert_threshold", None), res=tester.model_cfg.DATASET.IMG_RES)
+        except ValueError as e:
+            sys.exit(str(e))
+    else:
+        res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
+                                kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
+                                likelihood=args.likelihood)
     for line in (evaluate.likelihood_lines(res) if args.likelihood else []) + evaluate.report_lines(res):
         print(line)
+    if getattr(args, "segm", False):
+        for line in segm.report_lines(res):
+            print(line)
     out = os.path.join(args.output_folder, f"evaluation_results_{args.dataset_name}.npz")
     evaluate.save_npz(out, res, args.dataset_name)
     return res

@@ -808,6 +808,53 @@ int poco_pseudo_finish(poco_pseudo_t p, float* h_records, int64_t records_cap, i
 int poco_pseudo_reset(poco_pseudo_t p, void* stream);
 void poco_pseudo_destroy(poco_pseudo_t p);
 
+/* ---- body-part segmentation: SMPL part labels in the crop, the crop camera, and the score of PARE's mask ------------------------
+ * What the reference trains pred_segm_mask against (pocolib/core/trainer.py:231-262) and scores it with
+ * (pocolib/losses/segmentation.py:CrossEntropy); csrc/part_labels.hip, csrc/segm_metrics.hip; DESIGN.md section 21;
+ * tests/segm_np.py restates all of it in numpy.
+ *
+ * poco_op_part_labels: d_labels uint8 [B,res,res] <- the body part seen at every pixel centre of B crops, 0 = background.
+ *   d_verts [B,V,3], d_cam_t [B,3], d_faces int32 [F,3], d_face_part uint8 [F] (part 0..23 of each face), d_keys = B * res * res
+ *   64-bit words of scratch (set and consumed by the call).
+ *   Camera (geometry.py:480-508 perspective_projection, identity rotation, y down): (X, Y, Z) = v + cam_t,
+ *     x = focal * X / Z + res / 2, y = focal * Y / Z + res / 2, all in float32 in this order; pixel (r, c) is sampled at (c + 0.5, r + 0.5).
+ *   Coverage: the watertight edge rule of the demo renderer (csrc/raster_common.h): a centre on a shared edge or vertex belongs to
+ *     exactly one of the triangles around it.  Both windings are filled.  A face with a non-finite vertex, with a vertex at Z < 0.1,
+ *     of zero area or with an index outside [0, V) covers nothing.
+ *   Visibility: z of a fragment = 1 / ((w0 / z0 + w1 / z1 + w2 / z2) / area) with the edge values w at the centre (1 / z is linear in
+ *     screen space); the nearest fragment wins, at equal depth the lower face index: atomicMin of (float bits of z << 32 | face).
+ *   Label = d_face_part[winner] + 1: what the reference's bucketize(...) + 1 followed by * mask reduces to.
+ *   Two launches (per (crop, face), then per pixel) behind one memset, all on `stream`; no allocation, no synchronisation. */
+int poco_op_part_labels(const float* d_verts, int B, int V, const float* d_cam_t, const int32_t* d_faces, int F,
+                        const unsigned char* d_face_part, float focal, int res, unsigned long long* d_keys, unsigned char* d_labels,
+                        void* stream);
+/* geometry.py:511-551 estimate_translation_np per crop: d_cam_t [B,3] <- the translation that brings d_joints3d [B,J,3] closest to
+ * d_joints2d [B,J,3] = (x, y, confidence) in crop pixels under the camera above, by the weighted 3x3 normal equations.  The weight
+ * sqrt(confidence) is taken in float32 as the reference takes it; products and sums are fp64, added in joint order; the system is
+ * solved by Cramer's rule in fp64.  A determinant that is zero (or not finite) gives (1, 1, 1), the reference's `except` branch.
+ * One wave per crop, one launch.  J <= POCO_EST_TRANSLATION_MAX_J. */
+#define POCO_EST_TRANSLATION_MAX_J 64
+int poco_op_estimate_translation(const float* d_joints3d, const float* d_joints2d, int B, int J, float focal, int res,
+                                 float* d_cam_t, void* stream);
+/* poco_op_segm_score: d_records [B, POCO_SEGM_RECORD_WORDS(C)] 64-bit words <- per crop
+ *     [0]          the sum over the H * W label pixels of -log_softmax(upsampled logits)[label], an fp64 value
+ *     [1]          pixels whose argmax equals the label (integer, as all that follow)
+ *     [2 + 3c ..)  class c: pixels with argmax == label == c, pixels with argmax == c, pixels with label == c
+ *   d_logits [B,C,h,w] (pred_segm_mask), d_labels uint8 [B,H,W] with every label < C (a label >= C is counted nowhere).
+ *   Upsample: bilinear, align_corners=True: source coordinate s = scale * i with scale = float(n_src - 1) / float(n_dst - 1) (0 when
+ *     n_dst = 1), i0 = int(s), i1 = min(i0 + 1, n_src - 1), l = s - i0, h = 1 - l, value = hy * (hx * v00 + lx * v01) + ly * (hx * v10 +
+ *     lx * v11), float32, not contracted.  Argmax: the lowest channel wins a tie.  Loss: (max + logf(sum expf(v - max))) - v[label].
+ *   The integer words are exact; word 0 is summed in fp64 in a fixed order: the same input gives the same bits on every run.
+ *   d_partials: B * poco_op_segm_score_partials(h, H) doubles of scratch.  C <= POCO_SEGM_MAX_C, C * w <= 3750 (four source rows of
+ *   every channel are staged in LDS).  No assumption on H / h.  A memset and two launches on `stream`. */
+#define POCO_SEGM_MAX_C 32
+#define POCO_SEGM_RECORD_WORDS(C) (2 + 3 * (C))
+int poco_op_segm_score_partials(int h, int H);
+int poco_op_segm_score(const float* d_logits, int B, int C, int h, int w, const unsigned char* d_labels, int H, int W,
+                       unsigned long long* d_records, double* d_partials, void* stream);
+/* d_out uint8 [B,H,W] <- the argmax poco_op_segm_score takes at every pixel (the same interpolation and tie rule). */
+int poco_op_segm_argmax(const float* d_logits, int B, int C, int h, int w, int H, int W, unsigned char* d_out, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

@@ -234,3 +234,24 @@ void launch_occlusion_records(const float* verts, const float* var, const float*
 // field's maximum.
 void launch_heat_overlay(const float* field, const int* pos, int n, int patch, int res, float scale, const unsigned char* lut,
                          const unsigned char* crop, unsigned char* out, hipStream_t s);
+
+// ---- body-part labels and their crop camera (part_labels.hip) -------------------------------------------------
+// labels uint8 [B,res,res] <- face_part[nearest face] + 1 at every covered pixel centre, 0 elsewhere; verts [B,V,3], cam_t [B,3],
+// faces [F,3], face_part uint8 [F]; keys [B*res*res] must hold all ones (no fragment) on entry.
+void launch_part_labels(const float* verts, int B, int V, const float* cam_t, const int* faces, int F, const unsigned char* face_part,
+                        float focal, int res, unsigned long long* keys, unsigned char* labels, hipStream_t s);
+// cam_t [B,3] <- the weighted least-squares translation of j3d [B,J,3] onto j2d [B,J,3] (x, y, confidence); J <= POCO_EST_MAX_JOINTS.
+constexpr int POCO_EST_MAX_JOINTS = 64;
+void launch_estimate_translation(const float* j3d, const float* j2d, int B, int J, float focal, int res, float* cam_t, hipStream_t s);
+
+// ---- segmentation scoring (segm_metrics.hip) ---------------------------------------------------------------------
+constexpr int POCO_SEGM_MAX_CLASSES = 32;
+// label rows one block owns / blocks per crop = ceil(H / rows); dynamic LDS bytes of a launch
+int segm_tile_rows(int h, int H);
+size_t segm_score_lds_bytes(int C, int w);
+// records [B, 2 + 3C] 64-bit words: word 0 <- the cross-entropy sum (fp64), words 1.. += the counts (they must be zero on entry);
+// partials: B * ceil(H / segm_tile_rows(h, H)) doubles of scratch.
+void launch_segm_score(const float* logits, const unsigned char* labels, int B, int C, int h, int w, int H, int W,
+                       unsigned long long* records, double* partials, hipStream_t s);
+// out uint8 [B,H,W] <- the argmax over the C channels of the upsampled logits (the scorer's interpolation and tie rule)
+void launch_segm_argmax(const float* logits, int B, int C, int h, int w, int H, int W, unsigned char* out, hipStream_t s);

@@ -715,3 +715,77 @@ extern "C" int poco_op_heat_overlay(const float* d_field, const int* d_pos, int 
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- body-part labels, their crop camera and the segmentation score (part_labels.hip, segm_metrics.hip) ---------------------
+static_assert(POCO_SEGM_MAX_C == POCO_SEGM_MAX_CLASSES, "the header's class limit and the kernel's count array must agree");
+static_assert(POCO_EST_TRANSLATION_MAX_J == POCO_EST_MAX_JOINTS, "the header's joint limit and the kernel's LDS array must agree");
+
+extern "C" int poco_op_part_labels(const float* d_verts, int B, int V, const float* d_cam_t, const int32_t* d_faces, int F,
+                                   const unsigned char* d_face_part, float focal, int res, unsigned long long* d_keys,
+                                   unsigned char* d_labels, void* stream) {
+  if (!d_verts || !d_cam_t || !d_faces || !d_face_part || !d_keys || !d_labels || B < 1 || B > 65535 || V < 1 || V > (1 << 24) ||
+      F < 1 || F > (1 << 24) || res < 1 || res > 4096 || !(focal > 0.f) || std::isinf(focal) || !aligned_to(d_keys, 8)) {
+    poco_set_error("poco_op_part_labels: bad arguments (need non-null pointers, 1 <= B <= 65535, 1 <= V, F <= 2^24, 1 <= res <= 4096, "
+                   "a finite focal > 0 and 8-byte aligned keys)");
+    return POCO_ERR_ARG;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  POCO_HIP_CHECK(hipMemsetAsync(d_keys, 0xFF, (size_t)B * res * res * sizeof(unsigned long long), s));
+  launch_part_labels(d_verts, B, V, d_cam_t, d_faces, F, d_face_part, focal, res, d_keys, d_labels, s);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_op_estimate_translation(const float* d_joints3d, const float* d_joints2d, int B, int J, float focal, int res,
+                                            float* d_cam_t, void* stream) {
+  if (!d_joints3d || !d_joints2d || !d_cam_t || B < 1 || J < 1 || J > POCO_EST_TRANSLATION_MAX_J || res < 1 || !(focal > 0.f) ||
+      std::isinf(focal)) {
+    poco_set_error("poco_op_estimate_translation: bad arguments (need non-null pointers, B >= 1, 1 <= J <= 64, res >= 1 and a finite "
+                   "focal > 0)");
+    return POCO_ERR_ARG;
+  }
+  launch_estimate_translation(d_joints3d, d_joints2d, B, J, focal, res, d_cam_t, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+static int segm_shape_check(const char* who, const void* a, const void* b, int B, int C, int h, int w, int H, int W) {
+  if (!a || !b || B < 1 || B > 65535 || C < 1 || C > POCO_SEGM_MAX_C || h < 1 || w < 1 || H < 1 || W < 1 || h > 4096 || w > 4096 ||
+      H > 4096 || W > 4096) {
+    poco_set_error(std::string(who) + ": bad arguments (need non-null pointers, 1 <= B <= 65535, 1 <= C <= 32 and sides in 1..4096)");
+    return POCO_ERR_ARG;
+  }
+  return POCO_OK;
+}
+
+extern "C" int poco_op_segm_score_partials(int h, int H) {
+  if (h < 1 || H < 1) return 0;
+  const int rows = segm_tile_rows(h, H);
+  return (H + rows - 1) / rows;
+}
+
+extern "C" int poco_op_segm_score(const float* d_logits, int B, int C, int h, int w, const unsigned char* d_labels, int H, int W,
+                                  unsigned long long* d_records, double* d_partials, void* stream) {
+  if (int rc = segm_shape_check("poco_op_segm_score", d_logits, d_labels, B, C, h, w, H, W)) return rc;
+  if (!d_records || !d_partials || !aligned_to(d_records, 8) || !aligned_to(d_partials, 8)) {
+    poco_set_error("poco_op_segm_score: records and partials must be non-null and 8-byte aligned");
+    return POCO_ERR_ARG;
+  }
+  if (segm_score_lds_bytes(C, w) > 60000) {
+    poco_set_error("poco_op_segm_score: four source rows of every channel must fit the LDS window (C * w <= 3750)");
+    return POCO_ERR_ARG;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t record_bytes = (size_t)B * POCO_SEGM_RECORD_WORDS(C) * sizeof(unsigned long long);
+  POCO_HIP_CHECK(hipMemsetAsync(d_records, 0, record_bytes, s));
+  launch_segm_score(d_logits, d_labels, B, C, h, w, H, W, d_records, d_partials, s);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_op_segm_argmax(const float* d_logits, int B, int C, int h, int w, int H, int W, unsigned char* d_out, void* stream) {
+  if (int rc = segm_shape_check("poco_op_segm_argmax", d_logits, d_out, B, C, h, w, H, W)) return rc;
+  launch_segm_argmax(d_logits, B, C, h, w, H, W, d_out, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

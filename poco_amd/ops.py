@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import PocoHipError, check, current_stream, fptr, lib
+from ._lib import PocoHipError, check, current_stream, fptr, iptr, lib
 
 
 def _cfg(cfg):
@@ -347,3 +347,76 @@ def stem_conv(img, weight, scale, shift, use_mfma=1):
     check(lib().poco_op_stem_conv(C.c_void_p(flat.data_ptr() + 4 * g), fptr(_f32(weight)), fptr(_f32(scale)), fptr(_f32(shift)),
                                   wo.ptr(), B, H, W, ks, int(use_mfma), current_stream()), "poco_op_stem_conv")
     return wo.get(0, 64), wo
+
+
+# ---- body-part labels, their crop camera and the segmentation score (include/poco_hip.h; poco_amd/segm.py is the user's side) -----
+def _u8(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8):
+        raise PocoHipError(f"{what} must be a CUDA uint8 tensor")
+    return t.contiguous()
+
+
+def part_labels(verts: torch.Tensor, cam_t: torch.Tensor, faces: torch.Tensor, face_part: torch.Tensor, focal: float = 5000.0,
+                res: int = 224, out: torch.Tensor = None) -> torch.Tensor:
+    """poco_op_part_labels: verts [B,V,3], cam_t [B,3] fp32, faces int32 [F,3], face_part uint8 [F] -> labels uint8 [B,res,res]
+    (0 = background, part + 1 elsewhere).  `out`: a contiguous uint8 [B,res,res] view to write into."""
+    assert verts.is_cuda and verts.dtype == torch.float32 and verts.dim() == 3 and verts.shape[2] == 3
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    assert cam_t.shape == (B, 3) and cam_t.dtype == torch.float32 and cam_t.is_cuda
+    assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+    F = int(faces.shape[0])
+    face_part = _u8(face_part, "face_part")
+    assert face_part.shape == (F,)
+    if out is None:
+        out = torch.empty((B, res, res), device=verts.device, dtype=torch.uint8)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B, res, res)
+    keys = torch.empty((B, res, res), device=verts.device, dtype=torch.int64)
+    check(lib().poco_op_part_labels(fptr(verts.contiguous()), B, V, fptr(cam_t.contiguous()), iptr(faces.contiguous()), F,
+                                    C.c_void_p(face_part.data_ptr()), C.c_float(focal), int(res), C.c_void_p(keys.data_ptr()),
+                                    C.c_void_p(out.data_ptr()), current_stream()), "poco_op_part_labels")
+    return out
+
+
+def estimate_translation(joints3d: torch.Tensor, joints2d: torch.Tensor, focal: float = 5000.0, res: int = 224) -> torch.Tensor:
+    """poco_op_estimate_translation: joints3d [B,J,3], joints2d [B,J,3] = (x, y, confidence) in crop pixels -> cam_t [B,3]."""
+    assert joints3d.is_cuda and joints3d.dtype == torch.float32 and joints3d.dim() == 3 and joints3d.shape[2] == 3
+    assert joints2d.is_cuda and joints2d.dtype == torch.float32 and joints2d.shape == joints3d.shape
+    B, J = int(joints3d.shape[0]), int(joints3d.shape[1])
+    out = torch.empty((B, 3), device=joints3d.device, dtype=torch.float32)
+    check(lib().poco_op_estimate_translation(fptr(joints3d.contiguous()), fptr(joints2d.contiguous()), B, J, C.c_float(focal), int(res),
+                                             fptr(out), current_stream()), "poco_op_estimate_translation")
+    return out
+
+
+def segm_record_words(num_classes: int) -> int:
+    return 2 + 3 * int(num_classes)
+
+
+def segm_score(logits: torch.Tensor, labels: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """poco_op_segm_score: logits [B,C,h,w] fp32, labels uint8 [B,H,W] -> records int64 [B, 2 + 3C]: word 0 holds the bits of the
+    fp64 cross-entropy sum (records[:, 0].view(torch.float64)), word 1 the correct pixels, then per class intersection / predicted /
+    ground-truth counts.  `out`: a contiguous int64 [B, 2 + 3C] view to write into."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4
+    labels = _u8(labels, "labels")
+    B, Cc, h, w = (int(x) for x in logits.shape)
+    assert labels.dim() == 3 and labels.shape[0] == B
+    H, W = int(labels.shape[1]), int(labels.shape[2])
+    words = segm_record_words(Cc)
+    if out is None:
+        out = torch.empty((B, words), device=logits.device, dtype=torch.int64)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (B, words)
+    L = lib()
+    partials = torch.empty((B, max(int(L.poco_op_segm_score_partials(h, H)), 1)), device=logits.device, dtype=torch.float64)
+    check(L.poco_op_segm_score(fptr(logits.contiguous()), B, Cc, h, w, C.c_void_p(labels.data_ptr()), H, W, C.c_void_p(out.data_ptr()),
+                               C.c_void_p(partials.data_ptr()), current_stream()), "poco_op_segm_score")
+    return out
+
+
+def segm_argmax(logits: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """poco_op_segm_argmax: logits [B,C,h,w] -> uint8 [B,H,W], the class segm_score calls predicted at every pixel."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4
+    B, Cc, h, w = (int(x) for x in logits.shape)
+    out = torch.empty((B, int(H), int(W)), device=logits.device, dtype=torch.uint8)
+    check(lib().poco_op_segm_argmax(fptr(logits.contiguous()), B, Cc, h, w, int(H), int(W), C.c_void_p(out.data_ptr()), current_stream()),
+          "poco_op_segm_argmax")
+    return out
