@@ -13,6 +13,10 @@ the confident rows of a dataset that demo.py --save_dataset wrote (its `var` arr
 segmentation head: per batch the ground-truth mesh is rasterised on the GPU into the 24 body parts plus background with the
 reference's crop camera and pred_segm_mask is scored against it - cross-entropy, pixel accuracy, mean IoU (poco_amd/segm.py,
 csrc/part_labels.hip, csrc/segm_metrics.hip); --part_mapping FILE replaces the default vertex -> part table.
+--crop dataset cuts the crops as the reference's dataset code does (crop_cv2 on the float32 image) instead of with the demo's crop,
+one launch per batch; --aug_rot / --aug_scale / --aug_flip / --aug_noise perturb every sample, --augment [--aug_seed S] draws per
+sample from the config's training-time distribution; the ground truth is transformed with the crop (poco_amd/datacrop.py,
+csrc/dataset_crop.hip).
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -52,7 +56,61 @@ def parse_args(argv=None):
     p.add_argument("--part_mapping", type=str, default=None,
                    help="with --segm: the vertex -> part table as .npy / .npz / the reference's smpl_partSegmentation_mapping.pkl "
                         "(default: each vertex's largest skinning weight)")
+    p.add_argument("--crop", choices=["demo", "dataset"], default="demo",
+                   help="demo: the demo's crop (unrounded box, cv2's uint8 path); dataset: the reference's dataset crop (crop_cv2 on "
+                        "the float32 image: rounded centre and box side, no byte rounding), one launch per batch")
+    p.add_argument("--aug_rot", type=float, default=None, metavar="DEG", help="rotate every crop by DEG degrees (implies --crop dataset)")
+    p.add_argument("--aug_scale", type=float, default=None, metavar="SC", help="scale every box by SC (implies --crop dataset)")
+    p.add_argument("--aug_flip", action="store_true", help="mirror every crop left-right (implies --crop dataset)")
+    p.add_argument("--aug_noise", type=str, default=None, metavar="R,G,B",
+                   help="multiply the channels of every crop by R,G,B, clamped to [0, 255] (implies --crop dataset)")
+    p.add_argument("--augment", action="store_true",
+                   help="per sample, draw flip, noise, rotation and scale from the config's DATASET.FLIP / NOISE_FACTOR / ROT_FACTOR / "
+                        "SCALE_FACTOR as the reference's training-time augm_params does (implies --crop dataset)")
+    p.add_argument("--aug_seed", type=int, default=0, help="seed of --augment")
     return p.parse_args(argv)
+
+
+def augmentation_spec(args):
+    """The AugSpec the augmentation flags ask for, or None without any; args.crop becomes 'dataset' when one is given.  Refuses,
+    before any GPU work: --augment together with a fixed perturbation, an unreadable --aug_noise, a non-positive --aug_scale, and
+    the dataset crop on a file that carries ready-made `img` crops."""
+    import math
+    import numpy as np
+    fixed = [n for n, on in (("--aug_rot", getattr(args, "aug_rot", None) is not None), ("--aug_scale", getattr(args, "aug_scale", None) is not None),
+                             ("--aug_flip", bool(getattr(args, "aug_flip", False))), ("--aug_noise", getattr(args, "aug_noise", None) is not None)) if on]
+    random = bool(getattr(args, "augment", False))
+    if random and fixed:
+        sys.exit(f"--augment draws every parameter per sample: it cannot be combined with {', '.join(fixed)}")
+    if getattr(args, "crop", "demo") != "dataset" and not (random or fixed):
+        return None
+    flags = ["--augment"] if random else fixed
+    args.crop = "dataset"
+    with np.load(args.dataset, allow_pickle=False) as z:
+        if "img" in z.files:
+            sys.exit(f"{args.dataset}: {' / '.join(flags) if flags else '--crop dataset'} cuts the crops from the images, but the file "
+                     "carries ready-made `img` crops: remove `img` and pass --img_dir")
+    if not (args.img_dir and os.path.isdir(args.img_dir)):
+        sys.exit("--crop dataset reads the images: --img_dir must name the folder the imgname entries are relative to")
+    from poco_amd.datacrop import AugSpec
+    if random:
+        from poco_amd.config import update_hparams
+        return AugSpec(random=True, seed=int(getattr(args, "aug_seed", 0)), cfg=update_hparams(args.cfg).DATASET)
+    noise = (1.0, 1.0, 1.0)
+    if getattr(args, "aug_noise", None) is not None:
+        try:
+            noise = tuple(float(x) for x in args.aug_noise.split(","))
+        except ValueError:
+            noise = ()
+        if len(noise) != 3 or not all(math.isfinite(x) and x >= 0 for x in noise):
+            sys.exit(f"--aug_noise needs three finite, non-negative factors R,G,B, got {args.aug_noise!r}")
+    rot = 0.0 if getattr(args, "aug_rot", None) is None else float(args.aug_rot)
+    sc = 1.0 if getattr(args, "aug_scale", None) is None else float(args.aug_scale)
+    if not math.isfinite(rot):
+        sys.exit(f"--aug_rot must be finite, got {rot}")
+    if not (math.isfinite(sc) and sc > 0):
+        sys.exit(f"--aug_scale must be finite and positive, got {sc}")
+    return AugSpec(rot=rot, scale=sc, flip=bool(getattr(args, "aug_flip", False)), noise=noise)
 
 
 def check_dataset_file(path: str) -> str:
@@ -115,6 +173,7 @@ def check_segm_inputs(args) -> None:
 
 def main(args):
     check_dataset_file(args.dataset)
+    aug = augmentation_spec(args)
     if getattr(args, "segm", False):
         check_segm_inputs(args)
     if getattr(args, "uncert_threshold", None) is not None:
@@ -127,10 +186,13 @@ def main(args):
     from poco_amd import evaluate
     from poco_amd.tester import POCOTester
     try:
+        crop_kw = dict(crop="dataset", augment=aug) if getattr(args, "crop", "demo") == "dataset" else {}
         ds = evaluate.EvalDataset(args.dataset, args.img_dir, args.dataset_name,
-                                  uncert_threshold=getattr(args, "uncert_threshold", None))
+                                  uncert_threshold=getattr(args, "uncert_threshold", None), **crop_kw)
     except ValueError as e:
         sys.exit(str(e))
+    if ds.crop == "dataset":
+        print(f"Dataset crop: {ds.augment.describe()}")
     if getattr(args, "uncert_threshold", None) is not None:
         print(f"Confident rows (uncertainty < {args.uncert_threshold}): {len(ds)} of {ds.total}")
     J = np.load(args.j_regressor).astype(np.float32)
@@ -153,6 +215,9 @@ def main(args):
     if getattr(args, "segm", False):
         for line in segm.report_lines(res):
             print(line)
+    if ds.crop == "dataset":
+        res.update(aug_rot=ds.aug_rot.astype(np.float32), aug_flip=ds.aug_flip.astype(np.int32), aug_scale=ds.aug_scale.astype(np.float32),
+                   aug_pn=ds.aug_pn.astype(np.float32))
     out = os.path.join(args.output_folder, f"evaluation_results_{args.dataset_name}.npz")
     evaluate.save_npz(out, res, args.dataset_name)
     return res

@@ -347,6 +347,36 @@ int poco_crop_normalize_f64(const unsigned char* d_frame, int H, int W, const do
 int poco_crop_normalize_multi(const unsigned char* const* d_frames, int nframes, const int* d_frame_idx, int H, int W,
                               const float* d_boxes, int N, double bbox_scale, int res, float* d_out, void* stream);
 
+/* ---- the DATASET crop (eval.py --crop dataset): rotation, flip, scale and per-channel pixel noise -------------------------------
+ * Replaces BaseDataset.rgb_processing + normalize_img (pocolib/dataset/base_dataset.py:201-221,309) and the crop_cv2 it calls
+ * (pocolib/utils/image_utils.py:189-206: gen_trans_from_patch_cv, pocolib/utils/vibe_image_utils.py:49-91, then cv2.warpAffine of
+ * the FLOAT32 image) for a whole batch cut from images of mixed sizes, in one launch; csrc/dataset_crop.hip, DESIGN.md section 22.
+ * One record per crop.  The host states gen_trans_from_patch_cv up to its three float32 source points (poco_amd/datacrop.py
+ * crop_params: integer centre and box side, float32 rotate_2d with numpy's sin / cos); the device solves getAffineTransform and
+ * inverts in double as poco_crop_normalize does, generates warpAffine's 10-bit fixed-point coordinates (1/32-pixel fractions) and
+ * blends the four byte-valued taps with cv2's float weights - raw = (sum_i v_i m_i) / 1024, integer m_i summing to 1024, a tap
+ * outside the image contributes 0: exact in float32.  Then np.fliplr (output column x shows crop column res - 1 - x), the noise
+ * min(255, max(0, raw * pn[c])) in float32, and with normalize != 0 (x / 255 - mean) / std as oracle/crop_np.normalize_np. */
+typedef struct {
+  int32_t img;      /* which of d_images the crop is cut from; the kernel clamps it into 0 .. n_images - 1              */
+  int32_t flip;     /* != 0: mirrored left-right after the warp (base_dataset.py:207-208)                               */
+  float src[6];     /* gen_trans_from_patch_cv's `src`: centre, centre + down, centre + right as (x, y) pairs           */
+  float pn[3];      /* per-channel noise factors, rounded to float32 (numpy 1.x: float32 array times float64 scalar)    */
+  int32_t bb;       /* int(round(sc * scale * 200)): the box side crop_cv2 warps, kept for the host-side validation     */
+} poco_dataset_crop_param_t;
+/* d_images: device array of n_images device pointers to uint8 [H_i, W_i, 3] RGB images, d_img_hw int32 [n_images, 2] = (H_i, W_i),
+ * d_params [N] the records on the device and h_params the host copy they were uploaded from, d_out fp32 [N, 3, res, res] NCHW:
+ * the normalised crop, or with normalize = 0 the raw float crop after noise and clamp.  POCO_ERR_ARG before any GPU work (d_out is
+ * not touched): a null pointer, N < 1, n_images < 1, res outside 1..4096, and - read from h_params, since device data cannot be
+ * validated without a round trip - a non-finite source point or noise factor, or a box side that rounds to less than 1.  That check
+ * is advisory in one sense: nothing compares h_params with d_params, so it vouches for the device records only if the caller
+ * uploaded them from h_params.  The kernel reads d_params only and is memory-safe for any RECORD: the index is clamped, coordinates
+ * saturate to int16 as cv2's maps do and every tap is bounds-checked against d_img_hw.  d_images and d_img_hw themselves are
+ * trusted, like any device pointer: a size below 1 reads as an empty image, but a size larger than the allocation behind the
+ * pointer lets taps read past it.  Enqueued on `stream`: no allocation, no synchronisation. */
+int poco_dataset_crop(const unsigned char* const* d_images, const int* d_img_hw, int n_images, const poco_dataset_crop_param_t* d_params,
+                      const poco_dataset_crop_param_t* h_params, int N, int res, int normalize, float* d_out, void* stream);
+
 /* ---- demo renderer: the uncertainty-coloured SMPL overlay of demo.py --render ----------------------------------------------
  * Replaces pyrender's offscreen render (pocolib/utils/vibe_renderer.py:33-57,88-151) as pocolib/core/tester.py:248-345 (folder
  * mode) and :482-580 (video mode) call it; csrc/render.hip.  Draws P posed meshes over an RGB uint8 frame in place.

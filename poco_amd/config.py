@@ -14,13 +14,17 @@ POCO_DEFAULTS = dict(
     USE_ITER_FEATS=False, COND_NFLOW=True, CONTEXT_DIM=512, GT_POSE_COND=False, GT_POSE_COND_DS="h36m",
     GT_POSE_COND_RATIO=0.25, KINEMATIC_UNCERT=False)
 
+# config.py:94-103: the crop size and the augmentation distribution of BaseDataset.augm_params (eval.py --augment)
+DATASET_DEFAULTS = dict(IMG_RES=224, NOISE_FACTOR=0.4, ROT_FACTOR=30, FLIP=1, SCALE_FACTOR=0.25)
+
 
 def update_hparams(cfg_file: str) -> SimpleNamespace:
     raw = yaml.safe_load(open(cfg_file)) or {}
     poco = dict(POCO_DEFAULTS)
     poco.update(raw.get("POCO", {}) or {})
-    return SimpleNamespace(METHOD=raw.get("METHOD", "poco"), POCO=SimpleNamespace(**poco),
-                           DATASET=SimpleNamespace(IMG_RES=(raw.get("DATASET", {}) or {}).get("IMG_RES", 224)))
+    ds = dict(DATASET_DEFAULTS)
+    ds.update({k: v for k, v in (raw.get("DATASET", {}) or {}).items() if k in DATASET_DEFAULTS})
+    return SimpleNamespace(METHOD=raw.get("METHOD", "poco"), POCO=SimpleNamespace(**poco), DATASET=SimpleNamespace(**ds))
 
 
 def model_kwargs(hp: SimpleNamespace) -> dict:

@@ -2,6 +2,7 @@
 // All HBM-bound elementwise / small-reduction work on L16 (channel-slice-major NHWC, common.h) fp32 with 16-byte
 // accesses; threads are ordered like the output memory.
 #include "kernels.h"
+#include "crop_affine.h"
 
 namespace {
 
@@ -285,54 +286,6 @@ void launch_avgpool(const float* in, float* dst, int B, int H, int W, int C, int
 namespace {
 constexpr int CROP_ROWS = 28;     // 8 blocks per 224-row crop: the ~3 us affine solve is paid once per 28 rows
 
-// cv::hal::LU64f (LUImpl<double>, opencv/modules/core/src/matrix_decomp.cpp) for the 6x6 system of getAffineTransform.
-__device__ __forceinline__ void lu_solve6(double (&A)[6][6], double (&b)[6]) {
-#pragma clang fp contract(off)
-  // fully unrolled with static indices (the pivot row is swapped in through selects) so that A lives in registers
-  bool singular = false;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    int k = i;
-    double best = fabs(A[i][i]);
-#pragma unroll
-    for (int j = i + 1; j < 6; ++j)
-      if (fabs(A[j][i]) > best) { best = fabs(A[j][i]); k = j; }
-    singular = singular || best < 2.220446049250313e-16 * 100;      // cv::solve returns false and leaves zeros
-#pragma unroll
-    for (int j = i + 1; j < 6; ++j) {
-      const bool sw = k == j;
-#pragma unroll
-      for (int c = i; c < 6; ++c) {
-        const double t = A[i][c];
-        A[i][c] = sw ? A[j][c] : t;
-        A[j][c] = sw ? t : A[j][c];
-      }
-      const double t = b[i];
-      b[i] = sw ? b[j] : t;
-      b[j] = sw ? t : b[j];
-    }
-    const double d = -1.0 / A[i][i];
-#pragma unroll
-    for (int j = i + 1; j < 6; ++j) {
-      const double alpha = A[j][i] * d;
-#pragma unroll
-      for (int c = i + 1; c < 6; ++c) A[j][c] = A[j][c] + alpha * A[i][c];
-      b[j] = b[j] + alpha * b[i];
-    }
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double s = b[i];
-#pragma unroll
-    for (int c = i + 1; c < 6; ++c) s = s - A[i][c] * b[c];
-    b[i] = s / A[i][i];
-  }
-  if (singular) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) b[j] = 0.0;
-  }
-}
-
 // gen_trans_from_patch_cv(rot = 0) -> getAffineTransform(src, dst) -> the inversion cv::warpAffine applies: Mi[6].
 __device__ __forceinline__ void crop_inverse_affine(double cx, double cy, double bw, double bh, double scale, int res, double (&Mi)[6]) {
 #pragma clang fp contract(off)
@@ -341,29 +294,10 @@ __device__ __forceinline__ void crop_inverse_affine(double cx, double cy, double
   const float sy[3] = {(float)cy, (float)(cy + (double)down), (float)(cy + (double)0.0f)};
   const float half = (float)(res * 0.5);
   const float dx[3] = {half, half, half + half}, dy[3] = {half, half + half, half};
-  double A[6][6], b[6];
-  for (int i = 0; i < 6; ++i)
-    for (int j = 0; j < 6; ++j) A[i][j] = 0.0;
-  for (int i = 0; i < 3; ++i) {
-    A[2 * i][0] = A[2 * i + 1][3] = sx[i];
-    A[2 * i][1] = A[2 * i + 1][4] = sy[i];
-    A[2 * i][2] = A[2 * i + 1][5] = 1.0;
-    b[2 * i] = dx[i];
-    b[2 * i + 1] = dy[i];
-  }
-  lu_solve6(A, b);
-  double D = b[0] * b[4] - b[1] * b[3];
-  D = D != 0.0 ? 1.0 / D : 0.0;
-  const double A11 = b[4] * D, A22 = b[0] * D;
-  Mi[0] = A11;
-  Mi[1] = b[1] * -D;
-  Mi[3] = b[3] * -D;
-  Mi[4] = A22;
-  Mi[2] = -Mi[0] * b[2] - Mi[1] * b[5];
-  Mi[5] = -Mi[3] * b[2] - Mi[4] * b[5];
+  crop_affine::inverse_affine_from_points(sx, sy, dx, dy, Mi);
 }
 
-__device__ __forceinline__ int cv_round(double v) { return __double2int_rn(v); }      // cvRound: round half to even
+using crop_affine::cv_round;
 
 // frames != nullptr (video / streaming batches): crop n is cut from frames[frame_idx[n]] - one launch for the crops of many frames
 template <typename BoxT>

@@ -246,9 +246,14 @@ class EvalDataset:
     kept, as base_dataset.py:59-70 keeps them (postproc.confident_frames); `total` is the file's row count."""
 
     def __init__(self, path: str, img_dir: Optional[str] = None, dataset_name: str = "3dpw", bbox_scale: float = 1.0,
-                 uncert_threshold: Optional[float] = None):
+                 uncert_threshold: Optional[float] = None, crop: str = "demo", augment=None, res: int = 224):
         if dataset_name not in DATASET_NAMES:
             raise ValueError(f"dataset_name must be one of {DATASET_NAMES}")
+        if crop not in ("demo", "dataset"):
+            raise ValueError("crop must be 'demo' or 'dataset'")
+        if augment is not None and crop != "dataset":
+            raise ValueError("an augmentation needs crop='dataset' (the demo crop has no rotation, flip or noise)")
+        self.crop, self.res = crop, int(res)
         z = np.load(path, allow_pickle=False)
         self.gt_form = check_dataset_keys(z.files)
         if uncert_threshold is not None:
@@ -272,12 +277,63 @@ class EvalDataset:
             raise ValueError("the dataset file has no `img` crops: --img_dir must name the folder its imgname entries are relative to")
         for k in ("gender", "person_id"):
             setattr(self, k, np.asarray(z[k]) if k in z.files else None)
+        if crop == "dataset":
+            self._init_dataset_crop(z, augment)
+
+    def _init_dataset_crop(self, z, augment) -> None:
+        """crop='dataset' (DESIGN.md section 22): the samples' augmentation parameters, drawn once in dataset order, and the ground
+        truth as BaseDataset.__getitem__ hands it out - pose_processing on `pose`, j3d_processing on `S` (before the joint map, as
+        base_dataset.py:317,379) - so that run_eval reads `pose` / `joints` as before.  `scale` stays the file's; batch() hands the
+        model sc * scale."""
+        from . import datacrop
+        if self.img is not None:
+            raise ValueError("crop='dataset' cuts the crops from the images: the dataset file must not carry ready-made `img` crops")
+        self.augment = augment if augment is not None else datacrop.AugSpec()
+        self.aug_flip, self.aug_pn, self.aug_rot, self.aug_scale = self.augment.draw(len(self))
+        self.scale_eff = self.aug_scale * self.scale.astype(np.float64)      # sc * scale (base_dataset.py:303,326,330)
+        if self.has_pose:
+            self.pose = np.stack([datacrop.pose_processing(p, r, f) for p, r, f in zip(self.pose, self.aug_rot, self.aug_flip)])
+        if self.gt_form == "joints":
+            jm = J24_TO_J17 if self.name == "mpi-inf-3dhp" else J24_TO_J14
+            S = np.asarray(z["S"], np.float32)
+            self.joints = np.ascontiguousarray(np.stack([datacrop.j3d_processing(s, r, f)
+                                                         for s, r, f in zip(S, self.aug_rot, self.aug_flip)])[:, jm, :3])
+
+    def part_keypoints(self, part) -> np.ndarray:
+        """`part` [N,24,3] of the dataset's rows in crop pixels: j2d_processing with the samples' sc * scale, rot and flip."""
+        from . import datacrop
+        return datacrop.crop_keypoints24(part, self.center, self.scale_eff, self.aug_rot, self.aug_flip, self.res)
+
+    def _batch_dataset_crop(self, lo: int, hi: int, device) -> Dict[str, torch.Tensor]:
+        """The reference's dataset crop for samples [lo, hi): every distinct image of the batch is read and uploaded once, all crops
+        come from one launch (datacrop.dataset_crop); scale = sc * scale, bbox_info and focal_length as base_dataset.py:325-331."""
+        from PIL import Image
+        from . import datacrop
+        from .tester import calculate_bbox_info, calculate_focal_length
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)   # noqa: E731
+        names = self.imgname[lo:hi]
+        distinct = list(dict.fromkeys(names))
+        slot = {nm: k for k, nm in enumerate(distinct)}
+        frames = [np.array(Image.open(os.path.join(self.img_dir, nm)).convert("RGB")) for nm in distinct]
+        images = [datacrop.upload_image(fr, device) for fr in frames]
+        idx = [slot[nm] for nm in names]
+        params = datacrop.batch_params(self.center[lo:hi], self.scale[lo:hi], self.aug_rot[lo:hi], self.aug_flip[lo:hi], self.aug_pn[lo:hi],
+                                       self.aug_scale[lo:hi], self.res)
+        img = datacrop.dataset_crop(images, idx, params, self.res, True)
+        shapes = np.asarray([frames[k].shape[:2] for k in idx], np.float32)
+        center, scale = self.center[lo:hi], self.scale_eff[lo:hi].astype(np.float32)      # float32, as the file's scale is held here
+        info = np.stack([calculate_bbox_info(c, s, hw) for c, s, hw in zip(center, scale, shapes)])
+        focal = np.array([calculate_focal_length(h, w) for h, w in shapes], np.float32)
+        return {"img": img, "bbox_info": t(info), "focal_length": t(focal), "scale": t(scale), "center": t(center),
+                "orig_shape": t(shapes)}
 
     def __len__(self) -> int:
         return len(self.imgname)
 
     def batch(self, lo: int, hi: int, device) -> Dict[str, torch.Tensor]:
         """Model inputs of samples [lo, hi) (the dict of tester.py:205-212) on the device."""
+        if self.crop == "dataset":
+            return self._batch_dataset_crop(lo, hi, device)
         from .tester import calculate_bbox_info, calculate_focal_length, crop_normalize
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)   # noqa: E731
         center, scale = self.center[lo:hi], self.scale[lo:hi]

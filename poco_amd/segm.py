@@ -267,7 +267,10 @@ def run_eval(model, dataset, dataset_path: str, J_regressor, smpl_path: str, par
     with np.load(dataset_path, allow_pickle=False) as z:
         check_eval_inputs("pare", z.files)
         rows = evaluate.select_confident(z, uncert_threshold, dataset_path) if uncert_threshold is not None else z
-        part = crop_keypoints24(rows["part"], dataset.center, dataset.scale, res)
+        # crop='dataset' (DESIGN.md section 22): j2d_processing with the samples' rotation, flip and scale, so that the mesh lands on
+        # the perturbed crop
+        part = dataset.part_keypoints(rows["part"]) if getattr(dataset, "crop", "demo") == "dataset" \
+            else crop_keypoints24(rows["part"], dataset.center, dataset.scale, res)
     if part.shape[0] != len(dataset):
         raise ValueError(f"`part` has {part.shape[0]} rows, the dataset {len(dataset)}")
     with np.load(smpl_path) as z:

@@ -23,6 +23,9 @@ Every stage whose inputs are missing is reported as SKIPPED (exit code 0); a sta
      pocolib/core/tester.py:324-328,552-554 calls it against the half-width table of include/poco_hip.h
      (POCO_DISC_HALF_WIDTHS, restated in tests/render_overlay_np.py) for every radius of the table, at the centre and clipped at the
      borders.  Runs only with `--keypoints`.
+  6. Dataset crop (needs `cv2` importable; licence-free; opt-in): cv2.warpAffine on the FLOAT32 image as crop_cv2 calls it
+     (pocolib/utils/image_utils.py:189-206) against the restatement tests/datacrop_np.py, bit for bit, and rot_aa's cv2.Rodrigues
+     round trip (:236-247) against its scipy restatement.  Runs only with `--dataset-crop`.
 """
 from __future__ import annotations
 
@@ -240,6 +243,46 @@ def stage_crop(args):
     return (OK if ok else FAIL), msg
 
 
+def dataset_crop_against_cv2(cv2, n: int = 48, seed: int = 0):
+    """The reference's crop_cv2 arithmetic on the real cv2 (float32 image, image_utils.py:189-206) and rot_aa (cv2.Rodrigues, :236-247)
+    vs tests/datacrop_np.py.  `cv2` is passed in, as for crop_against_cv2."""
+    from tests import datacrop_np as dn
+    from oracle import crop_np
+    r = np.random.default_rng(seed)
+    frame = r.integers(0, 256, (270, 480, 3), dtype=np.uint8)
+    worst = {"values": 0, "maxdiff": 0.0, "rot_aa": 0.0}
+    for i in range(n):
+        center, scale = (r.uniform(-30, 510), r.uniform(-30, 300)), r.uniform(0.1, 2.0)
+        rot, res = [0.0, 30.0, -47.5, 90.0, 180.0, r.uniform(-60, 60)][i % 6], (32, 224)[i % 2]
+        c_x, c_y, bb = dn.py_round(center[0]), dn.py_round(center[1]), dn.py_round(scale * 200.0)
+        src, dst = dn.patch_points(c_x, c_y, bb, res, rot)
+        M = cv2.getAffineTransform(np.float32(src), np.float32(dst))
+        ref = cv2.warpAffine(frame.astype(np.float32), M, (res, res), flags=cv2.INTER_LINEAR, borderMode=cv2.BORDER_CONSTANT)
+        mine = dn.warp_affine_f32(frame, crop_np.get_affine_transform_cv(src, dst), res)
+        worst["values"] += int((ref != mine).sum())
+        worst["maxdiff"] = max(worst["maxdiff"], float(np.abs(ref - mine).max()))
+        aa = 0.8 * r.standard_normal(3)
+        a = np.deg2rad(-rot)
+        R = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+        want = cv2.Rodrigues(np.dot(R, cv2.Rodrigues(aa)[0]))[0].T[0]
+        worst["rot_aa"] = max(worst["rot_aa"], float(np.abs(want - dn.rot_aa_np(aa, rot)).max()))
+    return worst
+
+
+def stage_dataset_crop(args):
+    try:
+        import cv2
+    except Exception as e:                                     # noqa: BLE001
+        return SKIP, f"cv2 is not importable ({type(e).__name__}); the dataset crop stays pinned to the restatement only"
+    w = dataset_crop_against_cv2(cv2)
+    msg = (f"cv2 {cv2.__version__}: 48 float crops; values differing {w['values']} (max {w['maxdiff']:.3g}), rot_aa max deviation "
+           f"{w['rot_aa']:.2e}")
+    ok = w["values"] == 0 and w["rot_aa"] < 1e-9
+    if not ok and not cv2.__version__.startswith("4.5"):
+        msg += " - note: OpenCV >= 4.11 ships a different (floating-point) warpAffine; the reference pins 4.5.5.64"
+    return (OK if ok else FAIL), msg
+
+
 def stage_keypoints(args):
     try:
         import cv2
@@ -273,8 +316,15 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--crop", action="store_true", help="only stage 4: the crop against the real cv2")
     ap.add_argument("--keypoints", action="store_true", help="only stage 5: the keypoint stamp against the real cv2.circle")
+    ap.add_argument("--dataset-crop", dest="dataset_crop", action="store_true",
+                    help="only stage 6: the dataset crop's restatement (tests/datacrop_np.py) against the real cv2.warpAffine on float32 "
+                         "images and cv2.Rodrigues")
     args = ap.parse_args(argv)
     results = []
+    if args.dataset_crop:
+        st, msg = stage_dataset_crop(args)
+        print(f"[{st:7s}] 6 dataset crop vs cv2: {msg}")
+        return 1 if st == FAIL else 0
     if args.keypoints:
         st, msg = stage_keypoints(args)
         print(f"[{st:7s}] 5 keypoint stamp vs cv2: {msg}")
