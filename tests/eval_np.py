@@ -10,6 +10,10 @@ np.float64 is the yardstick.  Each function cites the reference lines it restate
     pose_distance      eval_utils.py:154-160
     processed_uncert   poco_utils.py:21-25, 62-94
     pearson            eval_utils.py:162-165 (scipy.stats.pearsonr), centred
+
+Below the fixture's generators: solver_cases / solver_inputs (joint sets that take the rotation solver off the fixture), their second
+oracle pa_residual_invariant, pampjpe_jacobi (the device's Horn + Jacobi route in numpy, with its deliberate breaks) and slicing_cases
+(meshes and regressors on the borders of eval_partial's 1024-vertex slices) - the inputs of tests/test_eval_solver_gpu.py.
 """
 import numpy as np
 
@@ -236,3 +240,267 @@ def summary(records, sel=None):
     y = rec[:, R_UNC:R_UNC + 24][:, sel]
     return (rec.shape[0], 1000.0 * rec[:, R_MPJPE].mean(), 1000.0 * rec[:, R_PA].mean(), 1000.0 * rec[:, R_V2V].mean(),
             pearson(x, y))
+
+
+# ---- the Procrustes solve off the fixture (tests/test_eval_solver_gpu.py) ---------------------------------------------------------
+SOLVER_JOINTS = (3, 4, 14, 17, 32)
+SOLVER_MIRROR = np.array([-1.0, 1.0, 1.0])
+# (name, axis or None = a random one, angle) of the group sweep
+SOLVER_ROTATIONS = [("identity", (0, 0, 1), 0.0), ("pi_x", (1, 0, 0), np.pi), ("pi_y", (0, 1, 0), np.pi), ("pi_z", (0, 0, 1), np.pi),
+                    ("pi_111", (1, 1, 1), np.pi), ("half_pi_z", (0, 0, 1), np.pi / 2), ("third_111", (1, 1, 1), 2 * np.pi / 3),
+                    ("rand_1.0", None, 1.0), ("rand_2.0", None, 2.0), ("rand_3.0", None, 3.0), ("rand_pi-1e-3", None, np.pi - 1e-3),
+                    ("rand_pi", None, np.pi)]
+ILL_EPS = (1e-1, 1e-2, 1e-3, 1e-4, 1e-6, 0.0)
+ILL_SETS = 24
+BULK_SETS = 2000                            # over M = 14 and 17 together
+UNIT_POWERS = (-10, 0, 10)
+
+
+def rot_axis_angle(axis, angle):
+    """The textbook Rodrigues formula in float64 (rodrigues() above is the reference's variant, which moves the angle by 1e-8)."""
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    W = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.cos(angle) * np.eye(3) + np.sin(angle) * W + (1.0 - np.cos(angle)) * np.outer(a, a)
+
+
+def _rand_axis(r):
+    ax = r.standard_normal(3)
+    return ax / np.linalg.norm(ax)
+
+
+def _spread_points(r, M):
+    """[M,3] float32 normal points, sigma 0.3 m, redrawn while they are within 0.12 m (rms) of a plane: with four joints and 0.02
+    noise a flatter set's mirror image can be fitted better by a rotation, and the case would not need the reflection fix."""
+    while True:
+        g = (0.3 * r.standard_normal((M, 3))).astype(np.float32)
+        if M < 4 or np.linalg.svd(g - g.mean(0), compute_uv=False)[2] >= 0.12:
+            return g
+
+
+def _grid_points(r, M):
+    """_spread_points on the grid of multiples of 2^-10 whose three coordinate sums are multiples of M 2^-10: the points, their mean
+    and every difference of them are exact in float32 and float64."""
+    while True:
+        k = np.rint(1024.0 * _spread_points(r, M).astype(np.float64))
+        k[-1] -= k.sum(0) % M
+        g = (k / 1024.0).astype(np.float32)
+        if M < 4 or np.linalg.svd(g - g.mean(0), compute_uv=False)[2] >= 0.12:
+            return g
+
+
+def _similar(S2, R, s, t, mirrored, noise, r):
+    """float32 prediction s (mirror?)(S2) R^T + t (+ noise) of the float32 ground truth S2, formed in float64."""
+    src = S2.astype(np.float64) * (SOLVER_MIRROR if mirrored else 1.0)
+    S1 = s * src @ R.T + np.asarray(t, np.float64)
+    if noise:
+        S1 = S1 + noise * r.standard_normal(S1.shape)
+    return S1.astype(np.float32)
+
+
+def solver_cases(seed: int = 31):
+    """{M: (S1 [N,M,3] prediction, S2 [N,M,3] ground truth, tags)} for M in SOLVER_JOINTS, float32, seeded.  tags[i] is a dict:
+    cls ('group', 'exact', 'bulk', 'planar', 'units', 'ill'), rot (name of the rotation), angle, s, noise, mirrored, power (units: the data
+    are the power = 0 set times 2^power) and eps (ill).  The classes are those of DESIGN.md "Rotation solver"."""
+    out = {}
+    for M in SOLVER_JOINTS:
+        r, rx = np.random.default_rng([seed, M]), np.random.default_rng([seed, M, 1])
+        S1, S2, tags = [], [], []
+
+        def add(a, g, **tag):
+            S1.append(a)
+            S2.append(g)
+            tags.append(dict({"cls": None, "rot": "random", "angle": None, "s": 1.0, "noise": 0.0, "mirrored": False, "power": 0,
+                              "eps": None}, **tag))
+
+        # group sweep: every rotation x scale x noise x mirror
+        for name, axis, angle in SOLVER_ROTATIONS:
+            for s in (0.5, 1.3):
+                for noise in (0.0, 0.02):
+                    for mirrored in (False, True):
+                        g = _spread_points(r, M)
+                        R = rot_axis_angle(_rand_axis(r) if axis is None else axis, angle)
+                        add(_similar(g, R, s, (0.4, -2.0, 7.0), mirrored, noise, r), g, cls="group", rot=name, angle=angle, s=s,
+                            noise=noise, mirrored=mirrored)
+        # exact: coordinates on a 2^-10 grid with representable means, a power-of-two scale, sign-flip rotations and a translation on
+        # the grid - every sum of the solve is exact in fp64.  Not mirrored, K is exactly (anti)symmetric where Horn's matrix needs it:
+        # every off-diagonal entry of the optimal quaternion's row is exactly 0, its Jacobi rotations are skipped, the quaternion is a
+        # unit vector (qw = 1, or qw = 0 with the largest diagonal entry in column 1, 2 or 3) and PA is exactly 0
+        for name, flip in (("exact_identity", (1, 1, 1)), ("exact_pi_x", (1, -1, -1)), ("exact_pi_y", (-1, 1, -1)), ("exact_pi_z", (-1, -1, 1))):
+            for s in (0.5, 2.0):
+                for mirrored in (False, True):
+                    g = _grid_points(rx, M)
+                    a = s * g.astype(np.float64) * (SOLVER_MIRROR if mirrored else 1.0) * np.array(flip, np.float64) + np.array([0.5, -2.0, 7.0])
+                    assert np.array_equal(a.astype(np.float32), a)
+                    add(a.astype(np.float32), g, cls="exact", rot=name, angle=0.0 if name == "exact_identity" else np.pi, s=s, mirrored=mirrored)
+        if M in (14, 17):
+            # random bulk: a third mirrored, angles uniform in [0, pi], noise 0.02
+            for i in range(BULK_SETS // 2):
+                g = (0.3 * r.standard_normal((M, 3))).astype(np.float32)
+                angle, s = r.uniform(0.0, np.pi), r.uniform(0.5, 1.5)
+                add(_similar(g, rot_axis_angle(_rand_axis(r), angle), s, r.uniform(-3.0, 3.0, 3), i % 3 == 0, 0.02, r), g, cls="bulk",
+                    angle=angle, s=s, noise=0.02, mirrored=i % 3 == 0)
+            # planar ground truth (rank-2 K): each coordinate constant in turn; a half-turn and two random angles
+            for axis in range(3):
+                for mirrored in (False, True):
+                    for noise in (0.0, 0.02):
+                        for angle in (np.pi, r.uniform(0.5, 3.0), r.uniform(0.5, 3.0)):
+                            g = (0.3 * r.standard_normal((M, 3))).astype(np.float32)
+                            g[:, axis] = np.float32(0.15)
+                            add(_similar(g, rot_axis_angle(_rand_axis(r), angle), 0.8, (1.5, 0.3, -4.0), mirrored, noise, r), g,
+                                cls="planar", angle=angle, s=0.8, noise=noise, mirrored=mirrored,
+                                rot="rand_pi" if angle == np.pi else "random")
+            # ill conditioned: sigma(K) = 1.2 (0.25, 0.04, 0.04 (1 - eps)) with det(U V^T) < 0; the first set of a bucket is a half-turn.
+            # t stays within centimetres here: the float32 rounding of a prediction metres from the origin (1.2e-7 m) would move the
+            # conditioning by 1e-7, more than the two smallest buckets are apart
+            for eps in ILL_EPS:
+                for i in range(ILL_SETS):
+                    pts = r.standard_normal((M, 3))
+                    U = np.linalg.svd(pts - pts.mean(0), full_matrices=False)[0]
+                    g = (U * np.array([0.5, 0.2, 0.2 * np.sqrt(1.0 - eps)])).astype(np.float32)
+                    angle = np.pi if i == 0 else r.uniform(0.0, np.pi)
+                    src = g.astype(np.float64) * np.array([1.0, 1.0, -1.0])
+                    a = (1.2 * src @ rot_axis_angle(_rand_axis(r), angle).T + r.uniform(-0.05, 0.05, 3)).astype(np.float32)
+                    add(a, g, cls="ill", angle=angle, s=1.2, mirrored=True, eps=eps, rot="rand_pi" if i == 0 else "random")
+        # units: one noisy set, the same numbers times an exact power of two
+        g = (0.3 * r.standard_normal((M, 3))).astype(np.float32)
+        a = _similar(g, rot_axis_angle(_rand_axis(r), 2.2), 1.1, (0.4, -2.0, 7.0), False, 0.02, r)
+        for p in UNIT_POWERS:
+            add(a * np.float32(2.0 ** p), g * np.float32(2.0 ** p), cls="units", angle=2.2, s=1.1, noise=0.02, power=p)
+        out[M] = (np.stack(S1), np.stack(S2), tags)
+    return out
+
+
+def tag_index(tags, **want):
+    """Indices of the cases whose tag has every given value."""
+    return np.array([i for i, t in enumerate(tags) if all(t[k] == v for k, v in want.items())], np.int64)
+
+
+def solver_inputs(M, S1, S2, seed: int = 5):
+    """Keyword arguments of evaluate() that hand the solver exactly the joints S1 / S2 [N,M,3]: a J-vertex "mesh" under the identity
+    regressor (J = M with the identity map for M = 3, 4, 17; J = 32 with a shuffled map for M = 14, 32; the vertices the map leaves
+    out are at 0.25), joint ground truth, some mapped joint as the pelvis (PA does not see it), identity predicted pose, zero
+    ground-truth pose, uniform var_pose."""
+    n = len(S1)
+    J = 32 if M in (14, 32) else M
+    jmap = [int(j) for j in np.random.default_rng([seed, M]).permutation(J)[:M]] if J == 32 else list(range(M))
+    verts = np.full((n, J, 3), 0.25, np.float32)
+    verts[:, jmap] = S1
+    return dict(pred_vertices=verts, pred_pose=np.tile(np.eye(3, dtype=np.float32), (n, 24, 1, 1)), var_pose=np.full((n, 24), 0.1, np.float32),
+                gt_pose=np.zeros((n, 72), np.float32), J_regressor=np.eye(J, dtype=np.float32), jmap=jmap, gt_joints=np.asarray(S2, np.float32),
+                pelvis=jmap[M // 2])
+
+
+def pa_residual_invariant(S1, S2):
+    """sum_j PA_j^2 without a rotation: var2 - (sigma1 + sigma2 + d sigma3)^2 / var1, d = sign(det(U V^T)), var2 = sum |X2|^2,
+    in float64.  True of every maximiser of tr(R K), so it stays well conditioned where the rotation is not.  [M,3] or [N,M,3]."""
+    S1, S2 = np.asarray(S1), np.asarray(S2)
+    if S1.ndim == 3:
+        return np.array([pa_residual_invariant(a, g) for a, g in zip(S1, S2)])
+    _, _, mu2, var1, _, U, s, Vh = procrustes_parts(S1, S2, np.float64)
+    var2 = np.sum((np.asarray(S2, np.float64).T - mu2) ** 2)
+    d = np.sign(np.linalg.det(U.dot(Vh)))
+    return float(var2 - (s[0] + s[1] + d * s[2]) ** 2 / var1)
+
+
+def optimal_qw(S1, S2):
+    """|qw| of the float64 optimal rotation of one crop: the first component of the top eigenvector of Horn's 4x4 (numpy's eigh)."""
+    K = procrustes_parts(S1, S2, np.float64)[4]
+    return float(abs(np.linalg.eigh(_horn_matrix(K[None])[0])[1][0, -1]))
+
+
+def _horn_matrix(K, n13_sign=1.0):
+    N = np.empty(K.shape[:-2] + (4, 4))
+    N[..., 0, 0] = K[..., 0, 0] + K[..., 1, 1] + K[..., 2, 2]
+    N[..., 1, 1] = K[..., 0, 0] - K[..., 1, 1] - K[..., 2, 2]
+    N[..., 2, 2] = -K[..., 0, 0] + K[..., 1, 1] - K[..., 2, 2]
+    N[..., 3, 3] = -K[..., 0, 0] - K[..., 1, 1] + K[..., 2, 2]
+    N[..., 0, 1] = N[..., 1, 0] = K[..., 1, 2] - K[..., 2, 1]
+    N[..., 0, 2] = N[..., 2, 0] = K[..., 2, 0] - K[..., 0, 2]
+    N[..., 0, 3] = N[..., 3, 0] = K[..., 0, 1] - K[..., 1, 0]
+    N[..., 1, 2] = N[..., 2, 1] = K[..., 0, 1] + K[..., 1, 0]
+    N[..., 1, 3] = N[..., 3, 1] = n13_sign * (K[..., 2, 0] + K[..., 0, 2])
+    N[..., 2, 3] = N[..., 3, 2] = K[..., 1, 2] + K[..., 2, 1]
+    return N
+
+
+def pampjpe_jacobi(S1, S2, sweeps=10, n13_sign=1.0, pick="largest"):
+    """The device's route (csrc/eval_metrics.hip, eval_crop) in float64 numpy over [N,M,3]: Horn's 4x4, `sweeps` cyclic Jacobi sweeps
+    from E = I, the column of the largest diagonal entry as the quaternion.  -> per-joint PA [N,M].  The defaults are the kernel's;
+    sweeps, n13_sign = -1 and pick = 'first' are the deliberate breaks tests/test_eval_cpu.py shows the solver cases to catch."""
+    A, G = np.asarray(S1, np.float64), np.asarray(S2, np.float64)
+    n, M = A.shape[:2]
+    mu1, mu2 = A.sum(1, keepdims=True) / M, G.sum(1, keepdims=True) / M
+    X1, X2 = A - mu1, G - mu2
+    var1 = (X1 ** 2).sum((1, 2))
+    K = np.einsum("nmr,nmc->nrc", X1, X2)
+    N = _horn_matrix(K, n13_sign)
+    E = np.broadcast_to(np.eye(4), (n, 4, 4)).copy()
+    for _ in range(sweeps):
+        for p, q in ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)):
+            apq = N[:, p, q]
+            on = apq != 0.0
+            with np.errstate(over="ignore"):                            # a tiny apq: theta^2 = inf and t = 0, as on the device
+                theta = (N[:, q, q] - N[:, p, p]) / (2.0 * np.where(on, apq, 1.0))
+                t = np.where(theta >= 0.0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+            c = np.where(on, 1.0 / np.sqrt(t * t + 1.0), 1.0)[:, None]
+            s = np.where(on, t, 0.0)[:, None] * c
+            for T, cols in ((N, True), (N, False), (E, True)):
+                a, b = (T[:, :, p].copy(), T[:, :, q].copy()) if cols else (T[:, p, :].copy(), T[:, q, :].copy())
+                if cols:
+                    T[:, :, p], T[:, :, q] = c * a - s * b, s * a + c * b
+                else:
+                    T[:, p, :], T[:, q, :] = c * a - s * b, s * a + c * b
+    k = np.argmax(np.diagonal(N, axis1=1, axis2=2), 1) if pick == "largest" else np.zeros(n, np.int64)
+    qv = E[np.arange(n), :, k]
+    w, x, y, z = (qv / np.sqrt((qv ** 2).sum(1, keepdims=True))).T
+    R = np.stack([w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y),
+                  2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
+                  2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z], 1).reshape(n, 3, 3)
+    scale = np.einsum("nrc,ncr->n", R, K) / var1
+    hat = scale[:, None, None] * np.einsum("nrc,nmc->nmr", R, X1) + mu2
+    return np.sqrt(((hat - G) ** 2).sum(-1))
+
+
+# ---- slice and sub-batch edges of the mesh kernels --------------------------------------------------------------------------------
+SLICE = 1024                                # vertices per block of eval_partial
+
+
+def slice_borders(V):
+    """First and last vertex of every 1024-vertex slice of a V-vertex mesh."""
+    return sorted({v for s in range((V + SLICE - 1) // SLICE) for v in (SLICE * s, min(V, SLICE * (s + 1)) - 1)})
+
+
+def slicing_cases(seed: int = 47, meshes: bool = True, only=None):
+    """{V: case} for V = 1024, 1025, 2048 (J = 32 rows, a shuffled 32-entry map, B = 5) and 17409 (18 slices, so 227 crops per
+    launch pair; J = 5, M = 3, B = 230).  Every regressor row holds the first and the last vertex of every slice plus a few random
+    ones, except `last_only` (entries in the last slice alone) and `zero_row` (no entry: its joint is the origin; never the
+    pelvis).  case = dict(J_regressor, jmap, pelvis, last_only, zero_row, B and, with meshes, gt_vertices / pred_vertices
+    [B,V,3]: uniform in [-0.5, 0.5], prediction = ground truth + 0.02 noise).  float32, seeded per V; `only` = the V wanted."""
+    out = {}
+    for V, J, M, B in ((1024, 32, 32, 5), (1025, 32, 32, 5), (2048, 32, 32, 5), (17409, 5, 3, 230)):
+        if only is not None and V not in only:
+            continue
+        r = np.random.default_rng([seed, V])
+        rows = r.permutation(J)
+        last_only, pelvis = int(rows[0]), int(rows[1])
+        zero_row = int(rows[2]) if J == 32 else None
+        v_last = SLICE * ((V - 1) // SLICE)                       # first vertex of the last slice
+        Jr = np.zeros((J, V), np.float32)
+        for j in range(J):
+            if j == zero_row:
+                continue
+            cols = [v for v in slice_borders(V) if v >= v_last] if j == last_only else slice_borders(V)
+            lo = v_last if j == last_only else 0
+            cols = sorted(set(cols) | set((lo + r.choice(V - lo, min(5, V - lo), replace=False)).tolist()))
+            Jr[j, cols] = r.dirichlet(np.ones(len(cols))).astype(np.float32)
+        jmap = [int(j) for j in r.permutation(J)[:M]]
+        if J != 32:
+            jmap = [last_only] + [int(j) for j in rows[2:2 + M - 1]]
+        case = {"J_regressor": Jr, "jmap": jmap, "pelvis": pelvis, "last_only": last_only, "zero_row": zero_row, "B": B}
+        if meshes:
+            gt = r.random((B, V, 3), np.float32) - np.float32(0.5)
+            case["gt_vertices"] = gt
+            case["pred_vertices"] = gt + np.float32(0.02) * r.standard_normal(gt.shape, np.float32)
+        out[V] = case
+    return out
