@@ -16,7 +16,8 @@ csrc/part_labels.hip, csrc/segm_metrics.hip); --part_mappi
 --crop dataset cuts the crops as the reference's dataset code does (crop_cv2 on the float32 image) instead of with the demo's crop,
 one launch per batch; --aug_rot / --aug_scale / --aug_flip / --aug_noise perturb every sample, --augment [--aug_seed S] draws per
 sample from the config's training-time distribution; the ground truth is transformed with the crop (poco_amd/datacrop.py,
-csrc/dataset_crop.hip).
+csrc/dataset_crop.hip).  --aug_occlude FILE pastes the reference's synthetic occluders over every crop inside
+that launch and reports how the uncertainty follows the covered area.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -67,7 +68,11 @@ def parse_args(argv=None):
     p.add_argument("--augment", action="store_true",
                    help="per sample, draw flip, noise, rotation and scale from the config's DATASET.FLIP / NOISE_FACTOR / ROT_FACTOR / "
                         "SCALE_FACTOR as the reference's training-time augm_params does (implies --crop dataset)")
-    p.add_argument("--aug_seed", type=int, default=0, help="seed of --augment")
+    p.add_argument("--aug_seed", type=int, default=0, help="seed of --augment and --aug_occlude")
+    p.add_argument("--aug_occlude", type=str, default=None, metavar="FILE",
+                   help="paste 1..7 synthetic occluders per crop over the ground-truth keypoints as the reference's training dataset "
+                        "does (occlude_with_pascal_objects_kp); FILE: its pascal_occluders.pkl or an .npz of uint8 [h,w,4] RGBA cut-outs; "
+                        "needs `part` in the dataset; composes with the other --aug_* flags and --augment (implies --crop dataset)")
     return p.parse_args(argv)
 
 
@@ -80,11 +85,12 @@ def augmentation_spec(args):
     fixed = [n for n, on in (("--aug_rot", getattr(args, "aug_rot", None) is not None), ("--aug_scale", getattr(args, "aug_scale", None) is not None),
                              ("--aug_flip", bool(getattr(args, "aug_flip", False))), ("--aug_noise", getattr(args, "aug_noise", None) is not None)) if on]
     random = bool(getattr(args, "augment", False))
+    occlude = getattr(args, "aug_occlude", None) is not None
     if random and fixed:
         sys.exit(f"--augment draws every parameter per sample: it cannot be combined with {', '.join(fixed)}")
-    if getattr(args, "crop", "demo") != "dataset" and not (random or fixed):
+    if getattr(args, "crop", "demo") != "dataset" and not (random or fixed or occlude):
         return None
-    flags = ["--augment"] if random else fixed
+    flags = (["--augment"] if random else fixed) + (["--aug_occlude"] if occlude else [])
     args.crop = "dataset"
     with np.load(args.dataset, allow_pickle=False) as z:
         if "img" in z.files:
@@ -111,6 +117,27 @@ def augmentation_spec(args):
     if not (math.isfinite(sc) and sc > 0):
         sys.exit(f"--aug_scale must be finite and positive, got {sc}")
     return AugSpec(rot=rot, scale=sc, flip=bool(getattr(args, "aug_flip", False)), noise=noise)
+
+
+def occlusion_spec(args):
+    """The OcclusionSpec --aug_occlude asks for, or None without the flag.  Refuses, before any GPU work: a dataset file without
+    `part` (the occluders are centred on the ground-truth keypoints) and a FILE that is missing or holds anything but uint8 RGBA
+    cut-outs.  augmentation_spec, which runs first, has refused ready-made `img` crops and a missing --img_dir."""
+    path = getattr(args, "aug_occlude", None)
+    if path is None:
+        return None
+    import numpy as np
+    from poco_amd import datacrop
+    from poco_amd.evaluate import check_occlusion_keys
+    with np.load(args.dataset, allow_pickle=False) as z:
+        try:
+            check_occlusion_keys(z.files)
+        except ValueError as e:
+            sys.exit(f"{args.dataset}: --aug_occlude: {e}")
+    try:
+        return datacrop.OcclusionSpec(datacrop.load_occluders(path), seed=int(getattr(args, "aug_seed", 0)), source=path)
+    except ValueError as e:
+        sys.exit(f"--aug_occlude: {e}")
 
 
 def check_dataset_file(path: str) -> str:
@@ -174,6 +201,7 @@ def check_segm_inputs(args) -> None:
 def main(args):
     check_dataset_file(args.dataset)
     aug = augmentation_spec(args)
+    occ = occlusion_spec(args)
     if getattr(args, "segm", False):
         check_segm_inputs(args)
     if getattr(args, "uncert_threshold", None) is not None:
@@ -187,12 +215,16 @@ def main(args):
     from poco_amd.tester import POCOTester
     try:
         crop_kw = dict(crop="dataset", augment=aug) if getattr(args, "crop", "demo") == "dataset" else {}
+        if occ is not None:
+            crop_kw["occlude"] = occ
         ds = evaluate.EvalDataset(args.dataset, args.img_dir, args.dataset_name,
                                   uncert_threshold=getattr(args, "uncert_threshold", None), **crop_kw)
     except ValueError as e:
         sys.exit(str(e))
     if ds.crop == "dataset":
         print(f"Dataset crop: {ds.augment.describe()}")
+    if occ is not None:
+        print(f"Synthetic occluders: {occ.describe()}")
     if getattr(args, "uncert_threshold", None) is not None:
         print(f"Confident rows (uncertainty < {args.uncert_threshold}): {len(ds)} of {ds.total}")
     J = np.load(args.j_regressor).astype(np.float32)
@@ -215,6 +247,10 @@ def main(args):
     if getattr(args, "segm", False):
         for line in segm.report_lines(res):
             print(line)
+    if occ is not None:
+        for line in evaluate.occlusion_lines(ds, res):
+            print(line)
+        res.update(occ_count=ds.occ_count.astype(np.int32), occ_cover=ds.occ_cover.astype(np.float32))
     if ds.crop == "dataset":
         res.update(aug_rot=ds.aug_rot.astype(np.float32), aug_flip=ds.aug_flip.astype(np.int32), aug_scale=ds.aug_scale.astype(np.float32),
                    aug_pn=ds.aug_pn.astype(np.float32))

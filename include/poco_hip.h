@@ -377,6 +377,51 @@ typedef struct {
 int poco_dataset_crop(const unsigned char* const* d_images, const int* d_img_hw, int n_images, const poco_dataset_crop_param_t* d_params,
                       const poco_dataset_crop_param_t* h_params, int N, int res, int normalize, float* d_out, void* stream);
 
+/* ---- the dataset crop with synthetic occluders (eval.py --aug_occlude) ---------------------------------------------------------
+ * rgb_processing's occluder step (base_dataset.py:210-213: occlude_with_pascal_objects_kp, pocolib/dataset/occlusion.py:109-149)
+ * inside the launch of poco_dataset_crop, between the flip and the pixel noise, where the reference has it; DESIGN.md section 23,
+ * numpy restatement tests/occlude_np.py.  The host makes the reference's draws (poco_amd/datacrop.py occlusion_params): per crop up
+ * to 7 objects, each a cut-out, the size resize_by_factor gives it and the centre paste_over receives.  The device computes, per
+ * output pixel and object whose paste rectangle [c - size // 2, c - size // 2 + size) holds the pixel, the one texel of
+ * cv2.resize(cut-out, (dst_w, dst_h), interpolation=INTER_AREA) on uint8 RGBA that the pixel needs:
+ *   both axes with an integer scale src / dst: sums over the sx x sy source block, (s + 2) >> 2 for 2 x 2, otherwise
+ *     round-half-to-even of float32(s) * float32(1.f / (sx * sy)); 1 x 1 is the copy;
+ *   otherwise cv::computeResizeAreaTab's entries per axis, derived in double, and ResizeArea_'s float32 sequence: per source row
+ *     buf += S * alpha in table order, then sum = beta * buf for the first row and sum += beta * buf after it, each multiply and
+ *     add rounded on its own; the result round-half-to-even, saturated to a byte.
+ * and blends as paste_over does: alpha = float32(a) / 255, out = alpha * colour + (1 - alpha) * dst per channel in float32, two
+ * products and one sum, objects in drawn order (later ones cover earlier ones).  Then noise, clamp and Normalize as above.  A record
+ * with count = 0 leaves the crop bit for bit what poco_dataset_crop gives. */
+#define POCO_OCC_MAX_OBJECTS 7
+typedef struct {
+  int32_t offset;   /* first texel of the cut-out in the atlas, in texels (4 bytes: R, G, B, A)                        */
+  int32_t h, w;     /* its size; rows are packed                                                                       */
+} poco_occluder_t;
+typedef struct {
+  int32_t id;       /* which cut-out; the kernel clamps it into the table                                              */
+  int32_t dst_w;    /* resize_by_factor's new_size: np.round([w, h] * factor).astype(int)                              */
+  int32_t dst_h;
+  int32_t cx, cy;   /* paste_over's centre after np.round(center).astype(np.int32), in crop pixels                     */
+} poco_occ_object_t;
+typedef struct {
+  int32_t count;                                /* objects of this crop, 0 .. POCO_OCC_MAX_OBJECTS                     */
+  poco_occ_object_t obj[POCO_OCC_MAX_OBJECTS];  /* in drawn order                                                      */
+} poco_occ_record_t;                            /* 144 bytes                                                           */
+/* The arguments of poco_dataset_crop, then: d_atlas = all cut-outs as packed uint8 RGBA on the device (4-byte aligned, uploaded
+ * once per run), atlas_texels its size in texels, d_occluders [n_occluders] the table on the device and h_occluders its host copy,
+ * d_occ [N] the per-crop records on the device and h_occ their host copy, d_cover = null or int32 [N, ceil(res/32)^2]: every block
+ * writes, unconditionally, the number of its pixels that a pasted texel with alpha > 0 touched - no memset, no atomics; the caller
+ * sums a crop's cells.  POCO_ERR_ARG before any GPU work (d_out and d_cover are not touched): everything poco_dataset_crop refuses,
+ * a null or misaligned atlas, table or record pointer, res > 256 (a larger crop could ask for an upscaled cut-out: INTER_LINEAR is
+ * not built), an empty atlas, a cut-out side outside 1..4096 or a cut-out that does not lie inside the atlas, a count outside
+ * 0..7, an occluder id outside the table, a destination side below 1 or above the source side.  As for the crop records the host
+ * copies are what is checked; the kernel is memory-safe for any device record or table: count, id and sizes are clamped, every tap
+ * is clamped into its cut-out and checked against atlas_texels.  Enqueued on `stream`: no allocation, no synchronisation. */
+int poco_dataset_crop_occ(const unsigned char* const* d_images, const int* d_img_hw, int n_images, const poco_dataset_crop_param_t* d_params,
+                          const poco_dataset_crop_param_t* h_params, int N, int res, int normalize, const unsigned char* d_atlas,
+                          long long atlas_texels, const poco_occluder_t* d_occluders, const poco_occluder_t* h_occluders, int n_occluders,
+                          const poco_occ_record_t* d_occ, const poco_occ_record_t* h_occ, float* d_out, int* d_cover, void* stream);
+
 /* ---- demo renderer: the uncertainty-coloured SMPL overlay of demo.py --render ----------------------------------------------
  * Replaces pyrender's offscreen render (pocolib/utils/vibe_renderer.py:33-57,88-151) as pocolib/core/tester.py:248-345 (folder
  * mode) and :482-580 (video mode) call it; csrc/render.hip.  Draws P posed meshes over an RGB uint8 frame in place.

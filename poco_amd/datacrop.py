@@ -5,11 +5,16 @@ ground-truth transforms that go with them (pocolib/dataset/base_dataset.py:172-2
 The pixels are made by ONE launch per batch (poco_dataset_crop, csrc/dataset_crop.hip): crops of mixed image sizes with rotation,
 flip, scale and per-channel noise.  The host states gen_trans_from_patch_cv up to its three float32 source points (crop_params);
 everything after that runs on the device.  The ground truth - 72 or 24 x 3 numbers per sample - is transformed on the host in
-float64 numpy: dataset loading, not a hot path.  DESIGN.md section 22; tests/datacrop_np.py restates the contract."""
+float64 numpy: dataset loading, not a hot path.  DESIGN.md section 22; tests/datacrop_np.py restates the contract.
+
+Synthetic occluders (eval.py --aug_occlude): occlusion_params restates the draws of
+occlude_with_pascal_objects_kp (pocolib/dataset/occlusion.py:109-149) on the host; the resize of the cut-outs and the alpha blend run
+inside the same launch (poco_dataset_crop_occ), from an atlas of the cut-outs that is uploaded once."""
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+import random as pyrandom
+from dataclasses import dataclass, field
 from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
@@ -25,6 +30,15 @@ J24_FLIP_PERM = [5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13, 14, 15, 16, 17, 1
 # poco_dataset_crop_param_t (include/poco_hip.h): 48 bytes
 PARAM_DTYPE = np.dtype([("img", np.int32), ("flip", np.int32), ("src", np.float32, (6,)), ("pn", np.float32, (3,)), ("bb", np.int32)])
 assert PARAM_DTYPE.itemsize == 48
+
+# poco_occluder_t, poco_occ_object_t, poco_occ_record_t (include/poco_hip.h)
+OCCLUDER_DTYPE = np.dtype([("offset", np.int32), ("h", np.int32), ("w", np.int32)])
+OCC_OBJECT_DTYPE = np.dtype([("id", np.int32), ("dst_w", np.int32), ("dst_h", np.int32), ("cx", np.int32), ("cy", np.int32)])
+OCC_MAX_OBJECTS = 7
+OCC_DTYPE = np.dtype([("count", np.int32), ("obj", OCC_OBJECT_DTYPE, (OCC_MAX_OBJECTS,))])
+assert OCC_DTYPE.itemsize == 144 and OCCLUDER_DTYPE.itemsize == 12
+OCC_MAX_RES = 256                                       # above it resize_by_factor could upscale: INTER_LINEAR is not built
+OCC_MAX_SIDE = 4096
 
 upload_count = 0                                        # images sent to the device by upload_image since import
 upload_hook: Optional[Callable[[np.ndarray], None]] = None    # called with every image upload_image sends (tests count with it)
@@ -142,12 +156,187 @@ def _bind():
     return L
 
 
+def _bind_occ():
+    L = _bind()
+    if not getattr(L, "_datacrop_occ_bound", False):
+        L.poco_dataset_crop_occ.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]
+        L._datacrop_occ_bound = True
+    return L
+
+
+# ---- synthetic occluders: the host side --------------------------------------------------------------------------------------------
+def _check_cutout(a, where: str) -> np.ndarray:
+    if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 4 and 1 <= a.shape[0] <= OCC_MAX_SIDE
+            and 1 <= a.shape[1] <= OCC_MAX_SIDE):
+        what = f"{a.dtype} {a.shape}" if isinstance(a, np.ndarray) else type(a).__name__
+        raise ValueError(f"{where} is not a uint8 [h, w, 4] RGBA cut-out with sides in 1..{OCC_MAX_SIDE}: {what}")
+    return np.ascontiguousarray(a)
+
+
+def load_occluders(path: str) -> list:
+    """The reference's pascal_occluders.pkl (joblib: a list of uint8 [h, w, 4] RGBA cut-outs, occlusion.py:43-98) or an .npz whose
+    arrays are such cut-outs, taken in sorted key order.  Anything else is a ValueError that names the offending entry."""
+    import os
+    if not os.path.isfile(path):
+        raise ValueError(f"occluder file not found: {path}")
+    if path.endswith(".npz"):
+        try:
+            with np.load(path, allow_pickle=False) as z:
+                items = [(f"{path}: array {k!r}", z[k]) for k in sorted(z.files)]
+        except ValueError:
+            raise
+        except Exception as e:
+            raise ValueError(f"{path}: not a readable .npz ({e})")
+    else:
+        import joblib
+        try:
+            obj = joblib.load(path)
+        except Exception as e:
+            raise ValueError(f"{path}: not a joblib file of cut-outs ({type(e).__name__}: {e})")
+        if not isinstance(obj, (list, tuple)):
+            raise ValueError(f"{path}: a list of cut-outs is expected, got {type(obj).__name__}")
+        items = [(f"{path}: entry {i}", a) for i, a in enumerate(obj)]
+    if not items:
+        raise ValueError(f"{path}: no cut-out in the file")
+    return [_check_cutout(a, where) for where, a in items]
+
+
+def occlusion_params(np_rng: np.random.RandomState, py_rng: pyrandom.Random, kp24, scale, occluder_hw, res: int = 224) -> dict:
+    """The draws of occlude_with_pascal_objects_kp (occlusion.py:109-149) for one sample, up to the two calls that touch pixels, with
+    the reference's draw order and dtype chain: count = randint(1, 8); per object random.choice (Python's generator), choice among the
+    visible keypoints, two randn, one uniform(0.2, 1.0).  kp24: the 24 ground-truth keypoints after j2d_processing (normalised crop
+    coordinates, float32; the reference's kp2d[25:]), brought to pixels with the reference's literal 224; scale = sc * scale;
+    occluder_hw: (h, w) per cut-out.  Returns dict(count = the count drawn, objects = [(id, dst_w, dst_h, cx, cy)] kept, skipped,
+    no_visible).  Where the reference raises: no keypoint with confidence > 0.3 -> the sample stays unoccluded after its count draw;
+    a new size with a zero side -> that object is skipped after its draws."""
+    res = int(res)
+    if not 1 <= res <= OCC_MAX_RES:
+        raise ValueError(f"occlusion_params: res must be in 1..{OCC_MAX_RES} (above it a cut-out could be upscaled: INTER_LINEAR is not built)")
+    if len(occluder_hw) < 1:
+        raise ValueError("occlusion_params: no cut-out")
+    im_w = im_h = res
+    im_scale_factor = min(im_w, im_h) / 256
+    count = int(np_rng.randint(1, 8))
+    kp = np.array(kp24, np.float32).reshape(24, 3)
+    kp[:, :-1] = np.float32(0.5 * 224) * (kp[:, :-1] + np.float32(1))
+    visible = kp[kp[..., -1] > 0.3]
+    if len(visible) == 0:
+        return dict(count=count, objects=[], skipped=0, no_visible=True)
+    objects, skipped = [], 0
+    for _ in range(count):
+        oid = py_rng.choice(range(len(occluder_hw)))
+        x, y = visible[np_rng.choice(range(len(visible)), 1)[0]][:2]
+        delta_x = np.float64((np_rng.randn() * 0.1) * scale)
+        delta_y = np.float64((np_rng.randn() * 0.1) * scale)
+        cx = int(np.clip(np.float64(x) + delta_x, 0, im_w))           # truncates, does not round
+        cy = int(np.clip(np.float64(y) + delta_y, 0, im_h))
+        factor = np_rng.uniform(0.2, 1.0) * im_scale_factor + 1e-8
+        h, w = occluder_hw[oid]
+        new = np.round(np.array([int(w), int(h)]) * factor).astype(int)   # resize_by_factor
+        if new[0] < 1 or new[1] < 1:
+            skipped += 1
+            continue
+        objects.append((int(oid), int(new[0]), int(new[1]), cx, cy))
+    return dict(count=count, objects=objects, skipped=skipped, no_visible=False)
+
+
+def occ_records(objects) -> np.ndarray:
+    """OCC_DTYPE [N] from per-sample lists of (id, dst_w, dst_h, cx, cy)."""
+    rec = np.zeros(len(objects), OCC_DTYPE)
+    for n, objs in enumerate(objects):
+        if len(objs) > OCC_MAX_OBJECTS:
+            raise ValueError(f"occ_records: sample {n} has {len(objs)} objects, at most {OCC_MAX_OBJECTS} fit a record")
+        rec["count"][n] = len(objs)
+        for k, o in enumerate(objs):
+            rec["obj"][n, k] = tuple(int(v) for v in o)
+    return rec
+
+
+class OccluderAtlas:
+    """All cut-outs as one packed uint8 RGBA buffer on the device with the (offset, h, w) table: uploaded once, read by every batch."""
+
+    def __init__(self, occluders, device):
+        cut = [_check_cutout(a, f"cut-out {i}") for i, a in enumerate(occluders)]
+        if not cut:
+            raise ValueError("OccluderAtlas: no cut-out")
+        self.table = np.zeros(len(cut), OCCLUDER_DTYPE)
+        off = 0
+        for i, a in enumerate(cut):
+            self.table[i] = (off, a.shape[0], a.shape[1])
+            off += a.shape[0] * a.shape[1]
+        if off >= 2 ** 31:
+            raise ValueError(f"OccluderAtlas: {off} texels do not fit the table's int32 offsets")
+        self.texels = off
+        self.device = torch.device(device)
+        self.d_atlas = torch.from_numpy(np.concatenate([a.reshape(-1) for a in cut])).to(self.device)
+        self.d_table = torch.from_numpy(self.table.view(np.uint8).copy()).to(self.device)
+
+
+@dataclass
+class OcclusionSpec:
+    """What eval.py --aug_occlude asks for: the cut-outs and the seed of the two generators (numpy's and Python's, as the reference
+    uses both).  draw() makes every sample's objects once, in dataset order; atlas() uploads the cut-outs once per device."""
+    occluders: Sequence[np.ndarray]
+    seed: int = 0
+    source: str = ""
+    _atlas: dict = field(default_factory=dict, repr=False)
+
+    def __post_init__(self):
+        self.occluders = [_check_cutout(a, f"cut-out {i}") for i, a in enumerate(self.occluders)]
+        if not self.occluders:
+            raise ValueError("OcclusionSpec: no cut-out")
+
+    @property
+    def sizes(self):
+        return [(a.shape[0], a.shape[1]) for a in self.occluders]
+
+    def atlas(self, device) -> OccluderAtlas:
+        key = str(torch.device(device))
+        if key not in self._atlas:
+            self._atlas[key] = OccluderAtlas(self.occluders, device)
+        return self._atlas[key]
+
+    def draw(self, aug: "AugSpec", part, center, scale, res: int = 224):
+        """Per sample, in dataset order and from ONE RandomState(seed) as BaseDataset.__getitem__ draws: augm_params first (only a
+        random AugSpec draws anything), then the sample's occlusion draws on its keypoints after j2d_processing with sc * scale, rot
+        and flip.  part [N,24,3], center [N,2], scale [N] (the file's).  Returns (flip, pn, rot, sc) as AugSpec.draw does and a dict:
+        objects (per-sample lists), count int32 [N] (objects kept), skipped and no_visible (totals)."""
+        part = np.asarray(part, np.float64).reshape(-1, 24, 3)
+        n = len(part)
+        if aug.random and int(aug.seed) != int(self.seed):
+            raise ValueError(f"OcclusionSpec.draw: one generator makes the augmentation and the occlusion draws, but the seeds differ "
+                             f"({aug.seed} and {self.seed})")
+        np_rng, py_rng = np.random.RandomState(self.seed), pyrandom.Random(self.seed)
+        flip, pn, rot, sc = aug.draw(n) if not aug.random else (np.zeros(n, np.int32), np.ones((n, 3)), np.zeros(n), np.ones(n))
+        objects, skipped, no_visible = [], 0, 0
+        sizes = self.sizes
+        for i in range(n):
+            if aug.random:
+                flip[i], pn[i], rot[i], sc[i] = augm_params(np_rng, aug.cfg, True)
+            s_eff = np.float64(sc[i]) * np.float64(scale[i])
+            kp = j2d_processing(part[i], center[i], float(s_eff), float(rot[i]), int(flip[i]), res)
+            d = occlusion_params(np_rng, py_rng, kp, s_eff, sizes, res)
+            objects.append(d["objects"])
+            skipped += d["skipped"]
+            no_visible += int(d["no_visible"])
+        return (flip, pn, rot, sc), dict(objects=objects, count=np.asarray([len(o) for o in objects], np.int32), skipped=skipped,
+                                         no_visible=no_visible)
+
+    def describe(self) -> str:
+        return f"{len(self.occluders)} cut-outs{' from ' + self.source if self.source else ''}, seed {self.seed}"
+
+
 def dataset_crop(images: Sequence[torch.Tensor], img_index, params: np.ndarray, res: int = 224, normalize: bool = True,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, occlusion=None):
     """images: uint8 [H_i,W_i,3] RGB tensors on one device; img_index [N]: which of them crop n is cut from (an index outside the
     list is clamped into it by the kernel); params: PARAM_DTYPE [N] (crop_params / batch_params) -> fp32 [N,3,res,res] on that
     device: the normalised crop, or with normalize=False the raw float crop after noise and clamp.
-    One small upload (pointer table, image sizes and records in one buffer) and one launch on the current stream."""
+    One small upload (pointer table, image sizes and records in one buffer) and one launch on the current stream.
+    occlusion = (OccluderAtlas on the same device, OCC_DTYPE [N] records from occ_records): the synthetic occluders are pasted between
+    flip and noise in the same launch (poco_dataset_crop_occ), the records travel in the same upload, and the result is (crops,
+    cover) with cover int32 [N] on the device = the crop's pixels that a pasted texel with alpha > 0 touched."""
     if len(images) < 1:
         raise ValueError("dataset_crop: no image")
     dev = images[0].device
@@ -161,15 +350,38 @@ def dataset_crop(images: Sequence[torch.Tensor], img_index, params: np.ndarray, 
     if idx.shape[0] != N:
         raise ValueError(f"dataset_crop: {idx.shape[0]} image indices for {N} records")
     params["img"] = np.clip(idx, -2 ** 31, 2 ** 31 - 1)
-    # [pointers 8 n_img | (H, W) 8 n_img | records 48 N]: every part starts on a multiple of 8 bytes
-    host = np.zeros(16 * n_img + 48 * N, np.uint8)
+    occ = None
+    if occlusion is not None:
+        atlas, occ = occlusion
+        occ = np.array(occ, dtype=OCC_DTYPE).reshape(-1)
+        if not isinstance(atlas, OccluderAtlas) or atlas.device != dev:
+            raise ValueError("dataset_crop: occlusion needs an OccluderAtlas on the images' device")
+        if occ.shape[0] != N:
+            raise ValueError(f"dataset_crop: {occ.shape[0]} occlusion records for {N} crops")
+    # [pointers 8 n_img | (H, W) 8 n_img | records 48 N | occlusion records 144 N]: every part starts on a multiple of 8 bytes
+    host = np.zeros(16 * n_img + 48 * N + (144 * N if occ is not None else 0), np.uint8)
     host[:8 * n_img].view(np.int64)[:] = [im.data_ptr() for im in images]
     host[8 * n_img:16 * n_img].view(np.int32)[:] = [v for im in images for v in (im.shape[0], im.shape[1])]
-    host[16 * n_img:] = params.view(np.uint8)
+    host[16 * n_img:16 * n_img + 48 * N] = params.view(np.uint8)
+    if occ is not None:
+        host[16 * n_img + 48 * N:] = occ.view(np.uint8)
     if out is None:
         out = torch.empty((N, 3, res, res), dtype=torch.float32, device=dev)
     elif not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (N, 3, res, res)):
         raise ValueError(f"dataset_crop: out must be a contiguous float32 [{N},3,{res},{res}] tensor on the images' device")
+    if occ is not None:
+        groups = (int(res) + 31) // 32
+        with torch.cuda.device(dev):
+            d = torch.from_numpy(host).to(dev)
+            base = d.data_ptr()
+            cover = torch.empty((N, groups * groups), dtype=torch.int32, device=dev)
+            check(_bind_occ().poco_dataset_crop_occ(
+                C.c_void_p(base), C.c_void_p(base + 8 * n_img), n_img, C.c_void_p(base + 16 * n_img), C.c_void_p(params.ctypes.data), N, int(res),
+                int(bool(normalize)), C.c_void_p(atlas.d_atlas.data_ptr()), atlas.texels, C.c_void_p(atlas.d_table.data_ptr()),
+                C.c_void_p(atlas.table.ctypes.data), len(atlas.table), C.c_void_p(base + 16 * n_img + 48 * N), C.c_void_p(occ.ctypes.data),
+                C.c_void_p(out.data_ptr()), C.c_void_p(cover.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                "poco_dataset_crop_occ")
+            return out, cover.sum(dim=1, dtype=torch.int32)
     with torch.cuda.device(dev):
         d = torch.from_numpy(host).to(dev)
         base = d.data_ptr()

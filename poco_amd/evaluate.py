@@ -246,16 +246,20 @@ class EvalDataset:
     kept, as base_dataset.py:59-70 keeps them (postproc.confident_frames); `total` is the file's row count."""
 
     def __init__(self, path: str, img_dir: Optional[str] = None, dataset_name: str = "3dpw", bbox_scale: float = 1.0,
-                 uncert_threshold: Optional[float] = None, crop: str = "demo", augment=None, res: int = 224):
+                 uncert_threshold: Optional[float] = None, crop: str = "demo", augment=None, res: int = 224, occlude=None):
         if dataset_name not in DATASET_NAMES:
             raise ValueError(f"dataset_name must be one of {DATASET_NAMES}")
         if crop not in ("demo", "dataset"):
             raise ValueError("crop must be 'demo' or 'dataset'")
         if augment is not None and crop != "dataset":
             raise ValueError("an augmentation needs crop='dataset' (the demo crop has no rotation, flip or noise)")
-        self.crop, self.res = crop, int(res)
+        if occlude is not None and crop != "dataset":
+            raise ValueError("synthetic occluders need crop='dataset' (they are pasted inside the dataset crop's launch)")
+        self.crop, self.res, self.occlude = crop, int(res), occlude
         z = np.load(path, allow_pickle=False)
         self.gt_form = check_dataset_keys(z.files)
+        if occlude is not None:
+            check_occlusion_keys(z.files)
         if uncert_threshold is not None:
             z = select_confident(z, uncert_threshold, path)
         self.name, self.img_dir, self.bbox_scale = dataset_name, img_dir, float(bbox_scale)
@@ -289,7 +293,16 @@ class EvalDataset:
         if self.img is not None:
             raise ValueError("crop='dataset' cuts the crops from the images: the dataset file must not carry ready-made `img` crops")
         self.augment = augment if augment is not None else datacrop.AugSpec()
-        self.aug_flip, self.aug_pn, self.aug_rot, self.aug_scale = self.augment.draw(len(self))
+        if self.occlude is not None:
+            # one generator for both, per sample: augm_params, then the occlusion draws (BaseDataset.__getitem__)
+            (self.aug_flip, self.aug_pn, self.aug_rot, self.aug_scale), d = self.occlude.draw(self.augment, z["part"], self.center, self.scale,
+                                                                                              self.res)
+            self.occ_records = datacrop.occ_records(d["objects"])
+            self.occ_count, self.occ_skipped, self.occ_no_visible = d["count"], int(d["skipped"]), int(d["no_visible"])
+            self._occ_cover = np.full(len(self), np.nan)
+            self._occ_pending = []
+        else:
+            self.aug_flip, self.aug_pn, self.aug_rot, self.aug_scale = self.augment.draw(len(self))
         self.scale_eff = self.aug_scale * self.scale.astype(np.float64)      # sc * scale (base_dataset.py:303,326,330)
         if self.has_pose:
             self.pose = np.stack([datacrop.pose_processing(p, r, f) for p, r, f in zip(self.pose, self.aug_rot, self.aug_flip)])
@@ -298,6 +311,15 @@ class EvalDataset:
             S = np.asarray(z["S"], np.float32)
             self.joints = np.ascontiguousarray(np.stack([datacrop.j3d_processing(s, r, f)
                                                          for s, r, f in zip(S, self.aug_rot, self.aug_flip)])[:, jm, :3])
+
+    @property
+    def occ_cover(self) -> np.ndarray:
+        """Per sample, the fraction of the crop's pixels that a pasted texel with alpha > 0 touched (NaN until its batch was made).
+        The counts stay on the device until they are asked for, so that making a batch does not wait for the launch."""
+        for lo, hi, cover in self._occ_pending:
+            self._occ_cover[lo:hi] = cover.cpu().numpy().astype(np.float64) / float(self.res * self.res)
+        self._occ_pending.clear()
+        return self._occ_cover
 
     def part_keypoints(self, part) -> np.ndarray:
         """`part` [N,24,3] of the dataset's rows in crop pixels: j2d_processing with the samples' sc * scale, rot and flip."""
@@ -319,7 +341,12 @@ class EvalDataset:
         idx = [slot[nm] for nm in names]
         params = datacrop.batch_params(self.center[lo:hi], self.scale[lo:hi], self.aug_rot[lo:hi], self.aug_flip[lo:hi], self.aug_pn[lo:hi],
                                        self.aug_scale[lo:hi], self.res)
-        img = datacrop.dataset_crop(images, idx, params, self.res, True)
+        if self.occlude is not None:
+            img, cover = datacrop.dataset_crop(images, idx, params, self.res, True,
+                                               occlusion=(self.occlude.atlas(device), self.occ_records[lo:hi]))
+            self._occ_pending.append((lo, hi, cover))
+        else:
+            img = datacrop.dataset_crop(images, idx, params, self.res, True)
         shapes = np.asarray([frames[k].shape[:2] for k in idx], np.float32)
         center, scale = self.center[lo:hi], self.scale_eff[lo:hi].astype(np.float32)      # float32, as the file's scale is held here
         info = np.stack([calculate_bbox_info(c, s, hw) for c, s, hw in zip(center, scale, shapes)])
@@ -392,6 +419,36 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
     res["imgname"] = np.asarray(dataset.imgname)
     ev.close()
     return res
+
+
+def check_occlusion_keys(files) -> None:
+    """Synthetic occluders are centred on the ground-truth 2-D keypoints: refuse a dataset file without `part` or with ready-made
+    `img` crops (ValueError)."""
+    if "img" in files:
+        raise ValueError("synthetic occluders are pasted inside the dataset crop, but the file carries ready-made `img` crops: remove "
+                         "`img` and pass --img_dir")
+    if "part" not in files:
+        raise ValueError("synthetic occluders are centred on the ground-truth 2-D keypoints: the dataset file needs `part` [N,24,3] "
+                         "(x, y, confidence in image pixels)")
+
+
+def cover_uncert_corr(occ_cover, corr_y) -> float:
+    """Pearson correlation, in float64 on the host, between the covered fraction of each crop and the crop's mean of corr_y (the
+    uncertainty of the selected joints, flattened [N * J] as Evaluator.finish hands it out).  NaN when either side is constant."""
+    c = np.asarray(occ_cover, np.float64).reshape(-1)
+    u = np.asarray(corr_y, np.float64).reshape(len(c), -1).mean(axis=1)
+    dc, du = c - c.mean(), u - u.mean()
+    den = np.sqrt((dc * dc).sum() * (du * du).sum())
+    return float((dc * du).sum() / den) if den > 0 else float("nan")
+
+
+def occlusion_lines(dataset: "EvalDataset", res: Dict[str, object]):
+    """eval.py --aug_occlude: mean objects per crop, mean cover, and the correlation the paper's argument predicts to be positive."""
+    lines = [f"Occluders per crop: {float(np.mean(dataset.occ_count))} (skipped objects {dataset.occ_skipped}, crops without a visible "
+             f"keypoint {dataset.occ_no_visible})", f"Occluder cover: {float(np.mean(dataset.occ_cover))}"]
+    if "corr_y" in res:
+        lines.append(f"Corr(cover, uncertainty): {cover_uncert_corr(dataset.occ_cover, res['corr_y'])}")
+    return lines
 
 
 def report_lines(res: Dict[str, object]):

@@ -26,6 +26,8 @@ Every stage whose inputs are missing is reported as SKIPPED (exit code 0); a sta
   6. Dataset crop (needs `cv2` importable; licence-free; opt-in): cv2.warpAffine on the FLOAT32 image as crop_cv2 calls it
      (pocolib/utils/image_utils.py:189-206) against the restatement tests/datacrop_np.py, bit for bit, and rot_aa's cv2.Rodrigues
      round trip (:236-247) against its scipy restatement.  Runs only with `--dataset-crop`.
+  7. the synthetic occluders: the restated cv2.resize(INTER_AREA) on uint8 RGBA and whole occluded crops
+     against the real cv2; prints the number of differing bytes.  Runs only with `--occlusion`.
 """
 from __future__ import annotations
 
@@ -283,6 +285,58 @@ def stage_dataset_crop(args):
     return (OK if ok else FAIL), msg
 
 
+def occlusion_against_cv2(cv2, seed: int = 0):
+    """The restated cv2.resize(uint8 RGBA, INTER_AREA) of tests/occlude_np.py against the real one over every path (copy, integer
+    blocks, generic, mixed axes), and whole occluded crops against the reference's arithmetic on the real cv2: crop_cv2's warp on
+    float32, then resize_by_factor and paste_over per drawn object (pocolib/dataset/occlusion.py:247-288, restated call for call so
+    that the reference tree is not needed).  Returns the numbers of differing bytes / float values."""
+    from tests import datacrop_np as dn, occlude_cases, occlude_np as on
+    from oracle import crop_np
+    r = np.random.default_rng(seed)
+    cuts = occlude_cases.cutouts() + [r.integers(0, 256, (int(h), int(w), 4), dtype=np.uint8) for h, w in r.integers(20, 200, (6, 2))]
+    out = {"resizes": 0, "resize_bytes": 0, "resize_max": 0, "crops": 0, "crop_values": 0}
+    for c in cuts:
+        h, w = c.shape[:2]
+        sizes = {(w, h), (max(w // 2, 1), max(h // 2, 1)), (max(w // 3, 1), max(h // 3, 1)), (max(w // 2, 1), max(int(h / 3.2), 1)), (1, 1)}
+        sizes |= {(max(int(round(w * f)), 1), max(int(round(h * f)), 1)) for f in r.uniform(0.175, 0.875, 12)}
+        for dw, dh in sorted(sizes):
+            ref, mine = cv2.resize(c, (dw, dh), interpolation=cv2.INTER_AREA), on.resize_area(c, (dw, dh))
+            d = np.abs(ref.astype(np.int32) - mine.astype(np.int32))
+            out["resizes"] += 1
+            out["resize_bytes"] += int((d != 0).sum())
+            out["resize_max"] = max(out["resize_max"], int(d.max()))
+    frame = r.integers(0, 256, (270, 480, 3), dtype=np.uint8)
+    kp = np.concatenate([r.uniform(-0.8, 0.8, (24, 2)), np.ones((24, 1))], 1).astype(np.float32)
+    for i in range(8):
+        res = (224, 32)[i % 2]
+        src, dst = dn.patch_points(240, 135, 200, res, 30.0 * (i % 3))
+        crop = cv2.warpAffine(frame.astype(np.float32), cv2.getAffineTransform(np.float32(src), np.float32(dst)), (res, res),
+                              flags=cv2.INTER_LINEAR, borderMode=cv2.BORDER_CONSTANT)
+        np.random.seed(i)
+        __import__("random").seed(i)
+        objs = on.occlusion_draws_np(kp, 1.0, [c.shape[:2] for c in cuts], res)["objects"]
+        ref = crop.copy()
+        for oid, dw, dh, cx, cy in objs:
+            on.paste_over_np(cv2.resize(cuts[oid], (dw, dh), interpolation=cv2.INTER_AREA), ref, np.array([cx, cy]))
+        mine, _ = on.apply_objects_np(dn.warp_affine_f32(frame, crop_np.get_affine_transform_cv(src, dst), res), cuts, objs)
+        out["crops"] += 1
+        out["crop_values"] += int((ref.view(np.uint32) != mine.view(np.uint32)).sum())
+    return out
+
+
+def stage_occlusion(args):
+    try:
+        import cv2
+    except Exception as e:                                     # noqa: BLE001
+        return SKIP, f"cv2 is not importable ({type(e).__name__}); the occluder resize stays pinned to the restatement only"
+    w = occlusion_against_cv2(cv2)
+    msg = (f"cv2 {cv2.__version__}: {w['resizes']} INTER_AREA resizes, bytes differing {w['resize_bytes']} (max {w['resize_max']} grey "
+           f"levels); {w['crops']} occluded crops, float values differing {w['crop_values']}")
+    if w["resize_bytes"] and w["resize_max"] <= 1:
+        msg += " - one grey level at rounding ties is what a build that fuses the row accumulation (FMA dispatch) gives"
+    return (OK if w["resize_bytes"] == 0 and w["crop_values"] == 0 else FAIL), msg
+
+
 def stage_keypoints(args):
     try:
         import cv2
@@ -319,8 +373,15 @@ def main(argv=None):
     ap.add_argument("--dataset-crop", dest="dataset_crop", action="store_true",
                     help="only stage 6: the dataset crop's restatement (tests/datacrop_np.py) against the real cv2.warpAffine on float32 "
                          "images and cv2.Rodrigues")
+    ap.add_argument("--occlusion", action="store_true",
+                    help="only stage 7: the synthetic occluders' restatement (tests/occlude_np.py) against the real cv2.resize(INTER_AREA) "
+                         "and whole occluded crops; prints the number of differing bytes")
     args = ap.parse_args(argv)
     results = []
+    if args.occlusion:
+        st, msg = stage_occlusion(args)
+        print(f"[{st:7s}] 7 occluders vs cv2: {msg}")
+        return 1 if st == FAIL else 0
     if args.dataset_crop:
         st, msg = stage_dataset_crop(args)
         print(f"[{st:7s}] 6 dataset crop vs cv2: {msg}")
