@@ -314,6 +314,58 @@ int poco_bench_part_attention(const float* d_heat, int heat_cs, const float* d_f
 int poco_op_lc2d_pose(const float* d_x, const float* d_w, float* d_pose6d, int B, void* stream);
 /* rot6d_to_rotmat == pocolib/utils/geometry.py:247-261: d_in [B,24,3,2] (144 floats per crop) -> d_rotmat [B,24,3,3]. */
 int poco_op_rot6d(const float* d_in, float* d_rotmat, int B, void* stream);
+
+/* ---- head kernels on their own, at any stride (parity tests: tests/test_head_kernels_gpu.py) ---------------------------------
+ * Row-vector data: a "row" is one crop's floats, `*_stride` the distance between rows in floats.  Argument errors - a null
+ * pointer, B < 1, a stride smaller than the row, 2^31 floats or more - are POCO_ERR_ARG before any GPU work; each entry
+ * synchronises `stream` before it returns. */
+/* poco_op_rot6d with the launcher's operands: d_in rows of in_stride >= 144 floats; the 216 floats of a crop go to d_dst0 and
+ * d_dst1 (rows of stride0 / stride1 >= 216; either may be NULL, not both). */
+int poco_op_rot6d_ex(const float* d_in, int in_stride, float* d_dst0, int stride0, float* d_dst1, int stride1, int B,
+                     void* stream);
+/* poco_op_lc2d_pose with d_x rows of x_stride >= 3072 floats. */
+int poco_op_lc2d_pose_ex(const float* d_x, int x_stride, const float* d_w, float* d_pose6d, int B, void* stream);
+/* d_dst[b * dst_stride + i] = d_src[b * src_stride + i], i < n (1 <= n <= both strides). */
+int poco_op_copy_rows(const float* d_src, int src_stride, float* d_dst, int dst_stride, int n, int B, void* stream);
+/* d_dst[b * dst_stride + i] = d_src[i], i < n (the regressor's init vectors). */
+int poco_op_broadcast_rows(const float* d_src, float* d_dst, int dst_stride, int n, int B, void* stream);
+/* The first C channels of an L16 buffer [B,H,cs/16,W,16] -> dense NCHW d_out [B,C,H,W] (1 <= C <= cs, cs a multiple of 16). */
+int poco_op_nhwc_to_nchw(const float* d_in, int cs, float* d_out, int B, int H, int W, int C, void* stream);
+/* poco_outputs_t.record on its own: d_rec [B,254] = [rotmat 216 | betas 10 | cam 3 | var 24 | confidence 1] from rows of
+ * rot_stride >= 216, betas_stride >= 10, cam_stride >= 3, var_stride >= 24 floats.  confidence = poco_utils.py:21-25,50-60 and
+ * the clip of tester.py:245: cliff 0 | 1 (root value against 2 thr | mean over the joints against thr), kinematic 0 | 1. */
+int poco_op_pack_record(const float* d_rot, int rot_stride, const float* d_betas, int betas_stride, const float* d_cam,
+                        int cam_stride, const float* d_var, int var_stride, float* d_rec, int cliff, int kinematic, float thr,
+                        int B, void* stream);
+/* Camera conversion and projection of the 49 joints (smpl_head.py:63-78; cliff = 1: smplcam_head.py:65-90,123-139):
+ * d_cam rows (s, tx, ty) of cam_stride >= 3 floats, d_joints49 [B,49,3] -> d_cam_t [B,3], d_joints2d [B,49,2] and, cliff only,
+ * d_fullimg_cam_t [B,3] (nullable: then not written).  cliff = 1 needs d_focal [B], d_scale [B], d_center [B,2] = (x, y) and
+ * d_orig_shape [B,2] = (h, w); with cliff = 0 they are not read. */
+int poco_op_camera(const float* d_cam, int cam_stride, const float* d_joints49, int cliff, const float* d_focal,
+                   const float* d_scale, const float* d_center, const float* d_orig_shape, float* d_cam_t,
+                   float* d_fullimg_cam_t, float* d_joints2d, int B, void* stream);
+/* The fused regressor's persistent kernel (csrc/mlp_chain.hip) on a caller-described PROGRAM: stages of independent jobs with a
+ * grid barrier between consecutive stages.  Every operand is a column slice of one of nbuf caller-owned device buffers
+ * (d_bufs[i], 16-byte aligned, buf_floats[i] floats): rows r < B at d_bufs[buf] + off + r * rs.
+ *   layers [nlayers][POCO_MLP_LAYER_INTS] = {K, N, act, in_buf, in_off, in_rs, res_buf, res_off, res_rs, out_buf, out_off, out_rs}:
+ *     out[r][n] = act(bias[n] + sum_k W[n][k] in[r][k] (+ res[r][n])), act 0 none | 1 ReLU | 2 sigmoid, res_buf = -1: no residual;
+ *     K, N multiples of 16, offsets and strides multiples of 4; h_weights[l] = host [N][K] (packed as the engine packs a Linear),
+ *     h_bias[l] = host [N].
+ *   rows [nrows][POCO_MLP_ROW_INTS] = {kind, src_buf, src_off, src_rs, dst_buf, dst_off, dst_rs, dst2_buf, dst2_off, dst2_rs, n}:
+ *     kind 0 copy (dst[r][i] = src[r][i], i < n) | 1 broadcast (dst[r][i] = src[i]) | 2 rot6d (144 -> 216 floats into dst and
+ *     dst2; a buffer index of -1 = none, at least one; n is ignored).
+ *   stages [nstages][4] = {layer0, nlayers, row0, nrows}: index ranges into the two arrays above.
+ * max_blocks >= 1 bounds the grid (the launcher also bounds it by poco_op_mlp_chain_resident_blocks()); results do not depend
+ * on it.  The entry owns the kernel's counters and its time-out word for the duration of the call.  POCO_ERR_ARG before any GPU
+ * work: null arrays, B < 1, more than 16 layers / 12 row jobs / 14 stages, K or N no multiple of 16, misaligned offsets, an
+ * operand that does not fit its buffer, a stage range outside the arrays.  Returns 6 if a grid barrier timed out. */
+#define POCO_MLP_LAYER_INTS 12
+#define POCO_MLP_ROW_INTS 11
+int poco_op_mlp_chain(const int* layers, int nlayers, const float* const* h_weights, const float* const* h_bias,
+                      const int* rows, int nrows, const int* stages, int nstages, float* const* d_bufs,
+                      const long long* buf_floats, int nbuf, int B, int max_blocks, void* stream);
+/* Blocks of that kernel the device holds at once (needs the GPU). */
+int poco_op_mlp_chain_resident_blocks(void);
 /* batch_rodrigues == pocolib/utils/geometry.py:207-244 (through quat_to_rotmat, with the reference's `theta + 1e-8` inside the
  * norm; not a textbook Rodrigues): d_axis_angle [N,3] -> d_rotmat [N,3,3].  Evaluated in fp64, stored as fp32.  The same device
  * function gives poco_evaluator_step its pose distance; this entry turns a ground-truth axis-angle pose [B,72] (N = 24 B) into

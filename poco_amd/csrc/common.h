@@ -22,7 +22,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
   } while (0)
 
 enum { POCO_OK = 0, POCO_ERR_ARG = 1, POCO_ERR_HIP = 2, POCO_ERR_STATE = 3, POCO_ERR_MISSING = 4,
-       POCO_ERR_SHAPE = 5 };
+       POCO_ERR_SHAPE = 5, POCO_ERR_TIMEOUT = 6 /* poco_op_mlp_chain: a grid barrier's bounded wait ran out */ };
 
 void poco_set_error(const std::string& msg);
 // Compute units of the current device (hipDeviceAttributeMultiprocessorCount; 256 on MI355X), cached per thread and device.

@@ -522,6 +522,201 @@ extern "C" int poco_op_stem_conv(const float* d_img, const float* h_weight, cons
   return op_finish(who, (hipStream_t)stream);
 }
 
+// ---- head kernels on their own, at any stride (tests/test_head_kernels_gpu.py) ----------------------------------------------
+namespace {
+// B rows of `width` floats, `stride` apart
+bool rows_ok(int stride, int width, int B) { return stride >= width && (long)B * stride < (1L << 31); }
+}  // namespace
+
+extern "C" int poco_op_rot6d_ex(const float* d_in, int in_stride, float* d_dst0, int stride0, float* d_dst1, int stride1, int B,
+                                void* stream) {
+  const char* who = "rot6d_ex";
+  if (!d_in || (!d_dst0 && !d_dst1)) return op_bad(who, "null pointer (d_in, or both destinations)");
+  if (B < 1) return op_bad(who, "needs B >= 1");
+  if (!rows_ok(in_stride, 144, B)) return op_bad(who, "in_stride must be at least 144 and B * in_stride below 2^31");
+  if ((d_dst0 && !rows_ok(stride0, 216, B)) || (d_dst1 && !rows_ok(stride1, 216, B)))
+    return op_bad(who, "a destination's stride must be at least 216 and B * stride below 2^31");
+  launch_rot6d(d_in, in_stride, d_dst0, stride0, d_dst1, stride1, B, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_lc2d_pose_ex(const float* d_x, int x_stride, const float* d_w, float* d_pose6d, int B, void* stream) {
+  const char* who = "lc2d_pose_ex";
+  if (!d_x || !d_w || !d_pose6d) return op_bad(who, "null pointer");
+  if (B < 1) return op_bad(who, "needs B >= 1");
+  if (!rows_ok(x_stride, 128 * 24, B)) return op_bad(who, "x_stride must be at least 3072 and B * x_stride below 2^31");
+  launch_lc2d_pose(d_x, x_stride, d_w, d_pose6d, B, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_copy_rows(const float* d_src, int src_stride, float* d_dst, int dst_stride, int n, int B, void* stream) {
+  const char* who = "copy_rows";
+  if (!d_src || !d_dst) return op_bad(who, "null pointer");
+  if (B < 1 || n < 1) return op_bad(who, "needs B, n >= 1");
+  if (!rows_ok(src_stride, n, B) || !rows_ok(dst_stride, n, B)) return op_bad(who, "strides must be at least n and B * stride below 2^31");
+  launch_copy_rows(d_src, src_stride, d_dst, dst_stride, n, B, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_broadcast_rows(const float* d_src, float* d_dst, int dst_stride, int n, int B, void* stream) {
+  const char* who = "broadcast_rows";
+  if (!d_src || !d_dst) return op_bad(who, "null pointer");
+  if (B < 1 || n < 1) return op_bad(who, "needs B, n >= 1");
+  if (!rows_ok(dst_stride, n, B)) return op_bad(who, "dst_stride must be at least n and B * dst_stride below 2^31");
+  launch_broadcast_rows(d_src, d_dst, dst_stride, n, B, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_nhwc_to_nchw(const float* d_in, int cs, float* d_out, int B, int H, int W, int C, void* stream) {
+  const char* who = "nhwc_to_nchw";
+  if (!d_in || !d_out) return op_bad(who, "null pointer");
+  if (B < 1 || H < 1 || W < 1 || C < 1) return op_bad(who, "needs B, H, W, C >= 1");
+  if (cs < C || (cs & 15)) return op_bad(who, "cs must be a multiple of 16 and at least C");
+  if ((double)B * H * W * cs >= 2147483648.0) return op_bad(who, "buffer of 2^31 floats or more");
+  launch_nhwc_to_nchw(d_in, cs, d_out, B, H, W, C, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_pack_record(const float* d_rot, int rot_stride, const float* d_betas, int betas_stride, const float* d_cam,
+                                   int cam_stride, const float* d_var, int var_stride, float* d_rec, int cliff, int kinematic,
+                                   float thr, int B, void* stream) {
+  const char* who = "pack_record";
+  if (!d_rot || !d_betas || !d_cam || !d_var || !d_rec) return op_bad(who, "null pointer");
+  if (B < 1 || (long)B * 254 >= (1L << 31)) return op_bad(who, "needs B >= 1 and fewer than 2^31 floats of records");
+  if (!rows_ok(rot_stride, 216, B) || !rows_ok(betas_stride, 10, B) || !rows_ok(cam_stride, 3, B) || !rows_ok(var_stride, 24, B))
+    return op_bad(who, "strides must be at least 216 (rot), 10 (betas), 3 (cam), 24 (var) and B * stride below 2^31");
+  if ((cliff != 0 && cliff != 1) || (kinematic != 0 && kinematic != 1)) return op_bad(who, "cliff and kinematic must be 0 or 1");
+  launch_pack_record(d_rot, rot_stride, d_betas, betas_stride, d_cam, cam_stride, d_var, var_stride, d_rec, cliff, kinematic, thr, B,
+                     (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_camera(const float* d_cam, int cam_stride, const float* d_joints49, int cliff, const float* d_focal,
+                              const float* d_scale, const float* d_center, const float* d_orig_shape, float* d_cam_t,
+                              float* d_fullimg_cam_t, float* d_joints2d, int B, void* stream) {
+  const char* who = "camera";
+  if (!d_cam || !d_joints49 || !d_cam_t || !d_joints2d) return op_bad(who, "null pointer");
+  if (cliff != 0 && cliff != 1) return op_bad(who, "cliff must be 0 or 1");
+  if (cliff && (!d_focal || !d_scale || !d_center || !d_orig_shape)) return op_bad(who, "cliff = 1 needs d_focal, d_scale, d_center and d_orig_shape");
+  if (B < 1 || (long)B * 147 >= (1L << 31)) return op_bad(who, "needs B >= 1 and fewer than 2^31 floats of joints");
+  if (!rows_ok(cam_stride, 3, B)) return op_bad(who, "cam_stride must be at least 3 and B * cam_stride below 2^31");
+  CamArgs c{};
+  c.cam = d_cam; c.cam_stride = cam_stride; c.joints49 = d_joints49; c.cliff = cliff;
+  if (cliff) { c.focal = d_focal; c.scale = d_scale; c.center = d_center; c.orig_shape = d_orig_shape; }
+  c.cam_t = d_cam_t; c.fullimg_cam_t = d_fullimg_cam_t; c.joints2d = d_joints2d;
+  launch_camera(c, B, (hipStream_t)stream);
+  return op_finish(who, (hipStream_t)stream);
+}
+
+extern "C" int poco_op_mlp_chain_resident_blocks(void) { return mlp_chain_resident_blocks(); }
+
+static_assert(POCO_MLP_LAYER_INTS == 12 && POCO_MLP_ROW_INTS == 11, "poco_op_mlp_chain reads 12 ints per layer and 11 per row job");
+
+extern "C" int poco_op_mlp_chain(const int* layers, int nlayers, const float* const* h_weights, const float* const* h_bias,
+                                 const int* rows, int nrows, const int* stages, int nstages, float* const* d_bufs,
+                                 const long long* buf_floats, int nbuf, int B, int max_blocks, void* stream) {
+  const char* who = "mlp_chain";
+  if (!stages || !d_bufs || !buf_floats || (nlayers > 0 && (!layers || !h_weights || !h_bias)) || (nrows > 0 && !rows))
+    return op_bad(who, "null pointer");
+  if (B < 1 || max_blocks < 1) return op_bad(who, "needs B >= 1 and max_blocks >= 1");
+  if (nlayers < 0 || nlayers > MLP_MAX_LAYERS || nrows < 0 || nrows > MLP_MAX_ROWS || nstages < 1 || nstages > MLP_MAX_STAGES)
+    return op_bad(who, "a program holds at most " + std::to_string(MLP_MAX_LAYERS) + " layers, " + std::to_string(MLP_MAX_ROWS) +
+                       " row jobs and 1 to " + std::to_string(MLP_MAX_STAGES) + " stages");
+  if (nbuf < 1 || nbuf > 64) return op_bad(who, "1 to 64 buffers");
+  for (int i = 0; i < nbuf; ++i)
+    if (!d_bufs[i] || !aligned16(d_bufs[i]) || buf_floats[i] < 1 || buf_floats[i] >= (1LL << 31))
+      return op_bad(who, "buffer " + std::to_string(i) + " is null, not 16-byte aligned, empty or holds 2^31 floats or more");
+  // rows [0, nr) of `width` floats at d_bufs[buf] + off + r * rs lie inside the buffer; `quad`: the kernel moves them as float4
+  auto slice = [&](int buf, int off, int rs, int width, int nr, bool quad) {
+    if (buf < 0 || buf >= nbuf || off < 0 || rs < width) return false;
+    if (quad && ((off | rs) & 3)) return false;
+    return (long long)off + (long long)(nr - 1) * rs + width <= buf_floats[buf];
+  };
+  MlpProgram p{};
+  p.B = B; p.nstages = nstages;
+  for (int l = 0; l < nlayers; ++l) {
+    const int* q = layers + (size_t)l * POCO_MLP_LAYER_INTS;
+    const std::string nm = "layer " + std::to_string(l);
+    const int K = q[0], N = q[1], act = q[2];
+    if (K < 16 || N < 16 || (K & 15) || (N & 15)) return op_bad(who, nm + ": K and N must be multiples of 16");
+    if (act < 0 || act > 2) return op_bad(who, nm + ": act must be 0, 1 or 2");
+    if (!h_weights[l] || !h_bias[l]) return op_bad(who, nm + ": null weights or bias");
+    if (!slice(q[3], q[4], q[5], K, B, true)) return op_bad(who, nm + ": the input does not fit its buffer, or its offset / stride is no multiple of 4");
+    if (q[6] >= 0 && !slice(q[6], q[7], q[8], N, B, true)) return op_bad(who, nm + ": the residual does not fit its buffer, or its offset / stride is no multiple of 4");
+    if (!slice(q[9], q[10], q[11], N, B, true)) return op_bad(who, nm + ": the output does not fit its buffer, or its offset / stride is no multiple of 4");
+    MlpLayer& L = p.layer[l];
+    L.in = d_bufs[q[3]] + q[4]; L.in_rs = q[5];
+    if (q[6] >= 0) { L.res = d_bufs[q[6]] + q[7]; L.res_rs = q[8]; }
+    L.out = d_bufs[q[9]] + q[10]; L.out_rs = q[11];
+    L.nC16 = K / 16; L.nT16 = N / 16; L.act = act;
+  }
+  for (int j = 0; j < nrows; ++j) {
+    const int* q = rows + (size_t)j * POCO_MLP_ROW_INTS;
+    const std::string nm = "row job " + std::to_string(j);
+    const int kind = q[0];
+    MlpRowJob& J = p.row[j];
+    J = MlpRowJob{};
+    J.kind = kind;
+    if (kind == MLP_ROW_COPY || kind == MLP_ROW_BCAST) {
+      const int n = q[10];
+      if (n < 1) return op_bad(who, nm + ": n must be at least 1");
+      if (!slice(q[1], q[2], kind == MLP_ROW_BCAST ? n : q[3], n, kind == MLP_ROW_BCAST ? 1 : B, false) || !slice(q[4], q[5], q[6], n, B, false))
+        return op_bad(who, nm + ": source or destination does not fit its buffer");
+      J.src = d_bufs[q[1]] + q[2]; J.src_rs = kind == MLP_ROW_BCAST ? 0 : q[3];
+      J.dst = d_bufs[q[4]] + q[5]; J.dst_rs = q[6]; J.n = n;
+    } else if (kind == MLP_ROW_ROT6D) {
+      if (q[4] < 0 && q[7] < 0) return op_bad(who, nm + ": rot6d needs a destination");
+      if (!slice(q[1], q[2], q[3], 144, B, false) || (q[4] >= 0 && !slice(q[4], q[5], q[6], 216, B, false)) ||
+          (q[7] >= 0 && !slice(q[7], q[8], q[9], 216, B, false)))
+        return op_bad(who, nm + ": source or destination does not fit its buffer");
+      J.src = d_bufs[q[1]] + q[2]; J.src_rs = q[3];
+      if (q[4] >= 0) { J.dst = d_bufs[q[4]] + q[5]; J.dst_rs = q[6]; }
+      if (q[7] >= 0) { J.dst2 = d_bufs[q[7]] + q[8]; J.dst2_rs = q[9]; }
+    } else {
+      return op_bad(who, nm + ": kind must be 0 (copy), 1 (broadcast) or 2 (rot6d)");
+    }
+  }
+  for (int s = 0; s < nstages; ++s) {
+    const int* q = stages + (size_t)s * 4;
+    if (q[0] < 0 || q[1] < 0 || q[0] + q[1] > nlayers || q[2] < 0 || q[3] < 0 || q[2] + q[3] > nrows)
+      return op_bad(who, "stage " + std::to_string(s) + " names layers or row jobs outside the arrays");
+    p.stage[s] = MlpStage{q[0], q[1], q[2], q[3]};
+  }
+  // weights packed the way the engine's builder packs a Linear (a 1x1 conv on a 1x1 plane)
+  DevBuf wdev[MLP_MAX_LAYERS], bdev[MLP_MAX_LAYERS];
+  for (int l = 0; l < nlayers; ++l) {
+    const int K = p.layer[l].nC16 * 16, N = p.layer[l].nT16 * 16;
+    std::vector<float> packed(conv_packed_weight_floats(K, N, 1));
+    conv_pack_weights(h_weights[l], nullptr, N, K, 1, N, packed.data());
+    POCO_HIP_CHECK(wdev[l].upload(packed));
+    POCO_HIP_CHECK(bdev[l].upload(std::vector<float>(h_bias[l], h_bias[l] + N)));
+    p.layer[l].wfrag = reinterpret_cast<const float4*>(wdev[l].p);
+    p.layer[l].bias = bdev[l].p;
+  }
+  // the 1 KiB of barrier counters and the pinned time-out word live for this call only
+  struct Sync {
+    unsigned* dev = nullptr;
+    unsigned* host = nullptr;
+    ~Sync() {
+      if (dev) (void)hipFree(dev);
+      if (host) (void)hipHostFree(host);
+    }
+  } sy;
+  POCO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&sy.dev), 1024));
+  POCO_HIP_CHECK(hipMemsetAsync(sy.dev, 0, 1024, (hipStream_t)stream));
+  POCO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sy.host), 64, hipHostMallocMapped));
+  *sy.host = 0;
+  p.sync = sy.dev; p.err_host = sy.host;
+  const int rc = launch_mlp_chain(p, max_blocks, (hipStream_t)stream);
+  const int rs = op_finish(who, (hipStream_t)stream);
+  if (rc != POCO_OK || rs != POCO_OK) return rc != POCO_OK ? rc : rs;
+  if (*reinterpret_cast<volatile unsigned*>(sy.host)) {
+    poco_set_error(std::string(who) + ": a grid barrier timed out");
+    return POCO_ERR_TIMEOUT;
+  }
+  return POCO_OK;
+}
+
 // ---- demo renderer (csrc/render.hip) ------------------------------------------------------------------------------------
 struct poco_renderer {
   int F = 0, V = 0;

@@ -100,6 +100,50 @@ class Wide:
         return C.c_void_p(self.body.data_ptr())
 
 
+class Rows:
+    """The flat form of Wide for row-vector data at any stride: `B + extra_rows` rows of `stride` floats in one allocation with a
+    guard band (at least one row, a multiple of 4 floats: the body stays 16-byte aligned) before and after them.  fill = "nan"
+    (operands: whatever the kernel may not read is NaN) or "poison" (POISON_BITS).  put() writes an operand into a column slice of
+    the first B rows, mark() makes a slice NaN (an output the kernel must write: an element it leaves out shows), untouched()
+    compares everything else - guard bands, the other columns, the rows from B on - bitwise with the fill."""
+
+    def __init__(self, B, stride, device, fill, extra_rows=0):
+        assert fill in ("nan", "poison") and B >= 1 and stride >= 1
+        self.B, self.stride, self.rows = B, stride, B + extra_rows
+        self.guard = (max(stride, 64) + 3) // 4 * 4
+        n = self.rows * stride
+        self.flat = torch.empty(n + 2 * self.guard, device=device, dtype=torch.float32)
+        if fill == "nan":
+            self.flat.fill_(float("nan"))
+        else:
+            self.flat.view(torch.int32).fill_(POISON_BITS)
+        self.fill_bits = int(self.flat[:1].view(torch.int32).item())
+        self.body = self.flat[self.guard:self.guard + n].view(self.rows, stride)
+
+    def put(self, off, x):
+        x = x.reshape(self.B, -1)
+        self.body[:self.B, off:off + x.shape[1]].copy_(x)
+        return self
+
+    def mark(self, off, n):
+        self.body[:self.B, off:off + n].fill_(float("nan"))
+        return self
+
+    def get(self, off, n):
+        return self.body[:self.B, off:off + n].contiguous()
+
+    def untouched(self, slices):
+        """True if nothing outside the column slices [(off, n), ...] of the first B rows differs from the fill (bitwise)."""
+        keep = torch.ones_like(self.flat, dtype=torch.bool)
+        kb = keep[self.guard:self.guard + self.rows * self.stride].view(self.rows, self.stride)
+        for off, n in slices:
+            kb[:self.B, off:off + n] = False
+        return bool((self.flat.view(torch.int32)[keep] == self.fill_bits).all())
+
+    def ptr(self, off=0):
+        return C.c_void_p(self.body.data_ptr() + 4 * off)
+
+
 def _out_hw(H, W, ks, stride):
     pad = (ks - 1) // 2
     return (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
@@ -186,21 +230,34 @@ def bench_conv2d(x: torch.Tensor, weight: np.ndarray, stride=1, cfg=None, iters=
     return ms.value, flops / (ms.value * 1e-3) / 1e12, tuple(used)
 
 
-def part_attention(feat_nchw: torch.Tensor, heat_nchw: torch.Tensor) -> torch.Tensor:
+def part_attention(feat_nchw: torch.Tensor, heat_nchw: torch.Tensor, *, heat_cs: int = 32, poison: bool = False) -> torch.Tensor:
     """KeypointAttention as the PARE head uses it: feat [B,C,H,W], heat [B,24,H,W] (the 24 part maps, no background channel)
-    -> [B,C,24].  Channels are padded to the library's L16 layout here (tests only; the engine never leaves L16)."""
+    -> [B,C,24].  Channels are padded to the library's L16 layout here (tests only; the engine never leaves L16).  The heat map
+    is channels 1..24 of a buffer with heat_cs channels per pixel.  poison: every other channel of that buffer (the background
+    channel 0, 25 and above) and the guard rows around both inputs are NaN, and the output lies between poisoned guard bands
+    (a store outside it raises)."""
     B, Cc, H, W = feat_nchw.shape
-    assert heat_nchw.shape == (B, 24, H, W) and feat_nchw.is_cuda
+    assert heat_nchw.shape == (B, 24, H, W) and feat_nchw.is_cuda and heat_cs >= 32 and heat_cs % 16 == 0
+    dev = feat_nchw.device
     C16 = (Cc + 15) // 16 * 16
-    f = torch.zeros((B, H, W, C16), device=feat_nchw.device)
+    f = torch.zeros((B, H, W, C16), device=dev)
     f[..., :Cc] = feat_nchw.permute(0, 2, 3, 1)
-    h = torch.zeros((B, H, W, 32), device=feat_nchw.device)
+    h = torch.full((B, H, W, heat_cs), float("nan") if poison else 0.0, device=dev)
     h[..., 1:25] = heat_nchw.permute(0, 2, 3, 1)            # channel 0 = background, skipped by the kernel
-    fl, hl = to_l16(f), to_l16(h)
-    out = torch.empty((B, C16, 24), device=feat_nchw.device)
-    check(lib().poco_op_part_attention(fptr(hl), 32, fptr(fl), C16, B, H, W, fptr(out), current_stream()),
+    if not poison:
+        fl, hl = to_l16(f), to_l16(h)
+        out = torch.empty((B, C16, 24), device=dev)
+        check(lib().poco_op_part_attention(fptr(hl), heat_cs, fptr(fl), C16, B, H, W, fptr(out), current_stream()),
+              "poco_op_part_attention")
+        return out[:, :Cc]
+    wh = Wide(B, H, W, heat_cs, dev, "nan").put(0, h)
+    wf = Wide(B, H, W, C16, dev, "nan").put(0, f)
+    wo = Rows(B, C16 * 24, dev, "poison").mark(0, C16 * 24)
+    check(lib().poco_op_part_attention(wh.base(), heat_cs, wf.base(), C16, B, H, W, wo.ptr(), current_stream()),
           "poco_op_part_attention")
-    return out[:, :Cc]
+    if not wo.untouched([(0, C16 * 24)]):
+        raise PocoHipError("poco_op_part_attention wrote outside its output tensor (guard band changed)")
+    return wo.get(0, C16 * 24).view(B, C16, 24)[:, :Cc]
 
 
 def lc2d_pose(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -420,3 +477,130 @@ def segm_argmax(logits: torch.Tensor, H: int, W: int) -> torch.Tensor:
     check(lib().poco_op_segm_argmax(fptr(logits.contiguous()), B, Cc, h, w, int(H), int(W), C.c_void_p(out.data_ptr()), current_stream()),
           "poco_op_segm_argmax")
     return out
+
+
+# ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
+# Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
+# that the caller can check `untouched`.
+def rot6d_ex(x, *, in_stride=144, stride0=216, stride1=216, dst0=True, dst1=False):
+    """poco_op_rot6d_ex: x [B,144] cuda -> (out0 | None, out1 | None, buffer 0 | None, buffer 1 | None), outputs [B,216]."""
+    B = x.shape[0]
+    wi = Rows(B, in_stride, x.device, "nan").put(0, x)
+    w0 = Rows(B, stride0, x.device, "poison").mark(0, 216) if dst0 else None
+    w1 = Rows(B, stride1, x.device, "poison").mark(0, 216) if dst1 else None
+    check(lib().poco_op_rot6d_ex(wi.ptr(), in_stride, w0.ptr() if w0 else C.c_void_p(0), stride0, w1.ptr() if w1 else C.c_void_p(0),
+                                 stride1, B, current_stream()), "poco_op_rot6d_ex")
+    return (w0.get(0, 216) if w0 else None), (w1.get(0, 216) if w1 else None), w0, w1
+
+
+def lc2d_pose_ex(x, w, *, x_stride=3072):
+    """poco_op_lc2d_pose_ex: x [B,128,24], w [6,128,24] -> ([B,24,6], output buffer)."""
+    B = x.shape[0]
+    wi = Rows(B, x_stride, x.device, "nan").put(0, x)
+    ww = Rows(1, 6 * 128 * 24, x.device, "nan").put(0, w)
+    wo = Rows(B, 144, x.device, "poison").mark(0, 144)
+    check(lib().poco_op_lc2d_pose_ex(wi.ptr(), x_stride, ww.ptr(), wo.ptr(), B, current_stream()), "poco_op_lc2d_pose_ex")
+    return wo.get(0, 144).view(B, 24, 6), wo
+
+
+def copy_rows(x, *, src_stride, dst_stride):
+    """poco_op_copy_rows: x [B,n] -> ([B,n], output buffer)."""
+    B, n = x.shape
+    wi = Rows(B, src_stride, x.device, "nan").put(0, x)
+    wo = Rows(B, dst_stride, x.device, "poison").mark(0, n)
+    check(lib().poco_op_copy_rows(wi.ptr(), src_stride, wo.ptr(), dst_stride, n, B, current_stream()), "poco_op_copy_rows")
+    return wo.get(0, n), wo
+
+
+def broadcast_rows(v, B, *, dst_stride):
+    """poco_op_broadcast_rows: v [n] -> ([B,n], output buffer)."""
+    n = v.numel()
+    wi = Rows(1, n, v.device, "nan").put(0, v)
+    wo = Rows(B, dst_stride, v.device, "poison").mark(0, n)
+    check(lib().poco_op_broadcast_rows(wi.ptr(), wo.ptr(), dst_stride, n, B, current_stream()), "poco_op_broadcast_rows")
+    return wo.get(0, n), wo
+
+
+def nhwc_to_nchw(x, *, cs, C_out=None):
+    """poco_op_nhwc_to_nchw: x NHWC [B,H,W,Cx] at channel 0 of an L16 buffer with cs channels; its first C_out (default Cx)
+    channels -> (NCHW [B,C_out,H,W], output buffer)."""
+    B, H, W, Cx = x.shape
+    Cc = Cx if C_out is None else C_out
+    wi = Wide(B, H, W, cs, x.device, "nan").put(0, x)
+    wo = Rows(1, B * Cc * H * W, x.device, "poison").mark(0, B * Cc * H * W)
+    check(lib().poco_op_nhwc_to_nchw(wi.base(), cs, wo.ptr(), B, H, W, Cc, current_stream()), "poco_op_nhwc_to_nchw")
+    return wo.get(0, B * Cc * H * W).view(B, Cc, H, W), wo
+
+
+def pack_record(rot, betas, cam, var, *, cliff, kinematic, thr=0.4, rot_stride=216, betas_stride=10, cam_stride=3, var_stride=24):
+    """poco_op_pack_record: rot [B,216], betas [B,10], cam [B,3], var [B,24] -> (records [B,254], output buffer)."""
+    B = rot.shape[0]
+    wr = Rows(B, rot_stride, rot.device, "nan").put(0, rot)
+    wb = Rows(B, betas_stride, rot.device, "nan").put(0, betas)
+    wc = Rows(B, cam_stride, rot.device, "nan").put(0, cam)
+    wv = Rows(B, var_stride, rot.device, "nan").put(0, var)
+    wo = Rows(B, 254, rot.device, "poison").mark(0, 254)
+    check(lib().poco_op_pack_record(wr.ptr(), rot_stride, wb.ptr(), betas_stride, wc.ptr(), cam_stride, wv.ptr(), var_stride, wo.ptr(),
+                                    int(cliff), int(kinematic), C.c_float(thr), B, current_stream()), "poco_op_pack_record")
+    return wo.get(0, 254), wo
+
+
+def camera(cam, joints49, *, cliff=False, focal=None, scale=None, center=None, orig_shape=None, cam_stride=3, fullimg=True):
+    """poco_op_camera: cam [B,3] = (s, tx, ty), joints49 [B,49,3]; cliff: focal [B], scale [B], center [B,2], orig_shape [B,2] ->
+    dict(cam_t [B,3], fullimg_cam_t [B,3] | None, joints2d [B,49,2], bufs = the three output buffers).  fullimg = False passes a
+    null d_fullimg_cam_t."""
+    B, dev = cam.shape[0], cam.device
+    wc = Rows(B, cam_stride, dev, "nan").put(0, cam)
+    wj = Rows(1, B * 147, dev, "nan").put(0, joints49.reshape(1, -1))
+    side = [None if t is None else Rows(1, t.numel(), dev, "nan").put(0, t.reshape(1, -1)) for t in (focal, scale, center, orig_shape)]
+    wt = Rows(1, B * 3, dev, "poison").mark(0, B * 3)
+    wf = Rows(1, B * 3, dev, "poison")
+    if cliff and fullimg:
+        wf.mark(0, B * 3)
+    w2 = Rows(1, B * 98, dev, "poison").mark(0, B * 98)
+    null = C.c_void_p(0)
+    check(lib().poco_op_camera(wc.ptr(), cam_stride, wj.ptr(), int(cliff), *[null if w is None else w.ptr() for w in side], wt.ptr(),
+                               wf.ptr() if fullimg else null, w2.ptr(), B, current_stream()), "poco_op_camera")
+    return dict(cam_t=wt.get(0, B * 3).view(B, 3), fullimg_cam_t=wf.get(0, B * 3).view(B, 3) if cliff and fullimg else None,
+                joints2d=w2.get(0, B * 98).view(B, 49, 2), bufs=(wt, wf, w2))
+
+
+def mlp_chain_resident_blocks() -> int:
+    return int(lib().poco_op_mlp_chain_resident_blocks())
+
+
+def mlp_chain(layers, rows, stages, bufs, B, max_blocks=256):
+    """poco_op_mlp_chain on Rows buffers (the row stride of an operand is its buffer's):
+    layers = [dict(W=[N,K] numpy, b=[N] numpy, act=0|1|2, src=(buf, off), res=(buf, off) | None, dst=(buf, off)), ...],
+    rows   = [dict(kind=0|1|2, src=(buf, off), dst=(buf, off) | None, dst2=(buf, off) | None, n=...), ...] (a broadcast source is
+             one row: its buffer's stride is not used),
+    stages = [(layer0, nlayers, row0, nrows), ...].  Returns the status (0 = ok); PocoHipError on a refused program."""
+    li, ws, bs = [], [], []
+    for L in layers:
+        W = np.ascontiguousarray(L["W"], dtype=np.float32)
+        b = np.ascontiguousarray(L["b"], dtype=np.float32)
+        N, K = W.shape
+        res = L.get("res")
+        li += [K, N, int(L.get("act", 0)), L["src"][0], L["src"][1], bufs[L["src"][0]].stride]
+        li += [-1, 0, 0] if res is None else [res[0], res[1], bufs[res[0]].stride]
+        li += [L["dst"][0], L["dst"][1], bufs[L["dst"][0]].stride]
+        ws.append(W)
+        bs.append(b)
+    ri = []
+    for J in rows:
+        ri += [int(J["kind"]), J["src"][0], J["src"][1], bufs[J["src"][0]].stride]
+        for key in ("dst", "dst2"):
+            d = J.get(key)
+            ri += [-1, 0, 0] if d is None else [d[0], d[1], bufs[d[0]].stride]
+        ri.append(int(J.get("n", 0)))
+    si = [int(v) for st in stages for v in st]
+    nl, nr, ns, nb = len(layers), len(rows), len(stages), len(bufs)
+    arr = lambda v: (C.c_int * max(len(v), 1))(*v)
+    wp = (C.c_void_p * max(nl, 1))(*[w.ctypes.data for w in ws])
+    bp = (C.c_void_p * max(nl, 1))(*[b.ctypes.data for b in bs])
+    dp = (C.c_void_p * nb)(*[w.ptr().value for w in bufs])
+    # what the entry may touch: the rows and nothing of the guard bands
+    sizes = (C.c_longlong * nb)(*[w.rows * w.stride for w in bufs])
+    rc = lib().poco_op_mlp_chain(arr(li), nl, wp, bp, arr(ri), nr, arr(si), ns, dp, sizes, nb, int(B), int(max_blocks), current_stream())
+    check(rc, "poco_op_mlp_chain")
+    return rc

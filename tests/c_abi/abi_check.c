@@ -38,7 +38,11 @@ int main(int argc, char** argv) {
     /* the stand-alone operators of the view conv and the backbone side kernels (additions to ABI 4) */
     const char* ops[] = {"poco_op_conv2d", "poco_op_conv2d_ex", "poco_op_bneck_chain", "poco_op_bneck_chain_resident_tiles",
                          "poco_op_conv1x1_dual", "poco_op_fuse_sum", "poco_op_bilinear_up2x", "poco_op_maxpool3x3s2",
-                         "poco_op_avgpool", "poco_op_stem_conv"};
+                         "poco_op_avgpool", "poco_op_stem_conv",
+                         /* the head kernels on their own (additions to ABI 4 too) */
+                         "poco_op_camera", "poco_op_mlp_chain", "poco_op_mlp_chain_resident_blocks", "poco_op_rot6d_ex",
+                         "poco_op_lc2d_pose_ex", "poco_op_copy_rows", "poco_op_broadcast_rows", "poco_op_nhwc_to_nchw",
+                         "poco_op_pack_record"};
     size_t k;
     for (k = 0; k < sizeof ops / sizeof ops[0]; ++k)
       if (!dlsym(so, ops[k])) { fprintf(stderr, "missing %s\n", ops[k]); return 28; }

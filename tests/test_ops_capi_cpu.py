@@ -9,7 +9,10 @@ import pytest
 from poco_amd import _lib
 
 NEW = ["poco_op_conv2d_ex", "poco_op_bneck_chain", "poco_op_bneck_chain_resident_tiles", "poco_op_conv1x1_dual", "poco_op_fuse_sum",
-       "poco_op_bilinear_up2x", "poco_op_maxpool3x3s2", "poco_op_avgpool", "poco_op_stem_conv"]
+       "poco_op_bilinear_up2x", "poco_op_maxpool3x3s2", "poco_op_avgpool", "poco_op_stem_conv",
+       # the head kernels on their own (tests/test_head_kernels_gpu.py)
+       "poco_op_camera", "poco_op_mlp_chain", "poco_op_mlp_chain_resident_blocks", "poco_op_rot6d_ex", "poco_op_lc2d_pose_ex",
+       "poco_op_copy_rows", "poco_op_broadcast_rows", "poco_op_nhwc_to_nchw", "poco_op_pack_record"]
 FAKE = C.c_void_p(4096)          # never dereferenced: every call below is refused before a pointer is used
 NULL = C.c_void_p(0)
 ERR_ARG = 1
@@ -114,6 +117,49 @@ def test_side_kernel_argument_errors(L):
     assert L.poco_op_stem_conv(FAKE, pw, NULL, NULL, FAKE, 1, 224, 224, 5, 1, NULL) == ERR_ARG
     assert L.poco_op_stem_conv(FAKE, pw, NULL, NULL, FAKE, 1, 224, 224, 7, 2, NULL) == ERR_ARG
     assert L.poco_op_stem_conv(FAKE, pw, NULL, NULL, FAKE, 0, 224, 224, 7, 1, NULL) == ERR_ARG
+
+
+def test_head_kernel_argument_errors(L):
+    """The list tests/test_head_kernels_gpu.py runs on device buffers, here with fake pointers: each call is refused with
+    POCO_ERR_ARG and a message that names the entry before anything is dereferenced or launched."""
+    from tests.test_head_kernels_gpu import bad_calls
+    calls = bad_calls(L, FAKE, FAKE)
+    assert len(calls) > 40 and {w for w, _ in calls} == {"rot6d_ex", "lc2d_pose_ex", "copy_rows", "broadcast_rows", "nhwc_to_nchw",
+                                                         "pack_record", "camera", "mlp_chain"}
+    for who, rc in calls:
+        assert rc == ERR_ARG, who
+    # the message names the entry and what is wrong
+    assert L.poco_op_camera(FAKE, 3, FAKE, 1, FAKE, FAKE, NULL, FAKE, FAKE, NULL, FAKE, 1, NULL) == ERR_ARG
+    assert "camera" in _msg(L) and "d_center" in _msg(L)
+    assert L.poco_op_rot6d_ex(FAKE, 100, FAKE, 216, NULL, 0, 1, NULL) == ERR_ARG and "rot6d_ex" in _msg(L) and "144" in _msg(L)
+    layer = (C.c_int * 12)(16, 16, 0, 0, 2, 16, -1, 0, 0, 0, 16, 32)           # input offset 2: no multiple of 4
+    w = np.zeros(256, np.float32)
+    ptr = (C.c_void_p * 1)(w.ctypes.data)
+    assert L.poco_op_mlp_chain(layer, 1, ptr, ptr, None, 0, (C.c_int * 4)(0, 1, 0, 0), 1, (C.c_void_p * 1)(4096), (C.c_longlong * 1)(64), 1,
+                               1, 4, NULL) == ERR_ARG
+    assert "mlp_chain" in _msg(L) and "layer 0" in _msg(L) and "multiple of 4" in _msg(L)
+    rowj = (C.c_int * 11)(3, 0, 0, 16, 0, 16, 16, -1, 0, 0, 8)                 # kind 3
+    assert L.poco_op_mlp_chain(None, 0, None, None, rowj, 1, (C.c_int * 4)(0, 0, 0, 1), 1, (C.c_void_p * 1)(4096), (C.c_longlong * 1)(64), 1,
+                               1, 4, NULL) == ERR_ARG and "row job 0" in _msg(L)
+    assert L.poco_op_mlp_chain(None, 0, None, None, None, 0, (C.c_int * 4)(0, 1, 0, 0), 1, (C.c_void_p * 1)(4096), (C.c_longlong * 1)(64), 1,
+                               1, 4, NULL) == ERR_ARG and "stage 0" in _msg(L)
+
+
+def test_rows_buffer_poisoning_helper():
+    """ops.Rows on the CPU: slices round-trip at an odd stride; a write to a guard, another column or a row >= B is noticed."""
+    import torch
+    from poco_amd import ops
+    x = torch.randn(3, 5)
+    for fill in ("nan", "poison"):
+        w = ops.Rows(3, 7, "cpu", fill, extra_rows=2).put(1, x)
+        assert torch.equal(w.get(1, 5), x) and w.untouched([(1, 5)]) and not w.untouched([(1, 4)])
+        assert w.guard % 4 == 0 and w.guard >= 64 and w.flat.numel() == 5 * 7 + 2 * w.guard
+        assert w.ptr(3).value - w.ptr().value == 12 and w.ptr().value == w.flat.data_ptr() + 4 * w.guard
+        for idx in (0, w.flat.numel() - 1, w.guard, w.guard + 3 * 7 + 2):      # guards, column 0 of row 0, a row >= B
+            v = ops.Rows(3, 7, "cpu", fill, extra_rows=2).put(1, x)
+            v.flat[idx] = 1.0
+            assert not v.untouched([(1, 5)])
+    assert bool(torch.isnan(ops.Rows(2, 4, "cpu", "poison").mark(0, 4).get(0, 4)).all())
 
 
 def test_wide_buffer_poisoning_helper():
