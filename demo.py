@@ -37,6 +37,12 @@ The printed JSON line gains dataset_offered, dataset_kept and dataset_threshold.
 coloured argmax of the upsampled pred_segm_mask and, beside it, the same crop blended with the 24 body parts of the predicted mesh
 rasterised at pred_cam_t (poco_amd/segm.py, csrc/part_labels.hip, csrc/segm_metrics.hip); --part_mapping FILE replaces the default
 vertex -> part table (each vertex's largest skinning weight).
+--infill THRESH (video mode) puts the per-joint uncertainty to work: per track and per joint, a rotation whose post-processed
+uncertainty exceeds THRESH is replaced by the shortest-arc interpolation between the nearest confident frames on either side, if
+those are at most --infill_max_gap frames apart, else by the nearer one if it is at most half of that away, else left alone; betas
+and orig_cam follow the root joint, the touched frames are re-posed, --smooth then filters the repaired pose (poco_amd/infill.py,
+csrc/track_infill.hip).  The result gains infill [T,24] (0 reliable, 1 interpolated, 2 held, 3 left) and pose_net / betas_net /
+orig_cam_net, the values before in-filling.  No default threshold: it is the user's statement of what they trust.  Not with --gpus N > 1.
 """
 import argparse
 import json
@@ -141,6 +147,13 @@ def parse_args(argv=None):
     p.add_argument("--part_mapping", type=str, default=None,
                    help="with --save_segm: the vertex -> part table as .npy / .npz / the reference's smpl_partSegmentation_mapping.pkl "
                         "(default: each vertex's largest skinning weight)")
+    p.add_argument("--infill", type=float, default=None, metavar="THRESH",
+                   help="video mode: replace every joint rotation whose uncertainty (the result's `var`) exceeds THRESH by the "
+                        "shortest-arc interpolation between the track's nearest confident frames on either side (made on the GPU, "
+                        "before --smooth); the result gains infill, pose_net, betas_net and orig_cam_net")
+    p.add_argument("--infill_max_gap", type=int, default=30,
+                   help="--infill: the most frames between the two confident frames of an interpolation (one second at the default "
+                        "--fps); a single confident frame is held for at most half of it")
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
@@ -207,6 +220,25 @@ def _check_dataset(args) -> None:
                  "them across the ranks in source order is a later change; run with --gpus 1")
 
 
+def _check_infill(args) -> None:
+    """--infill / --infill_max_gap: refuse them outside video mode and with --gpus N > 1 before the engine is built."""
+    thr = getattr(args, "infill", None)
+    gap = getattr(args, "infill_max_gap", 30)
+    if thr is None:
+        if gap != 30:
+            sys.exit("--infill_max_gap bounds the gaps --infill bridges: it needs --infill THRESH")
+        return
+    if args.mode != "video":
+        sys.exit("--infill repairs the tracks of video mode: it needs --mode video")
+    if args.gpus > 1:
+        sys.exit("--infill with --gpus N > 1 is not supported: the packed record the ranks exchange has no room for the in-fill "
+                 "flags; run with --gpus 1")
+    if not thr == thr:
+        sys.exit("--infill must be a number")
+    if gap < 1:
+        sys.exit(f"--infill_max_gap must be >= 1, got {gap}")
+
+
 def _check_segm(args) -> None:
     """--save_segm: refuse video mode, a head without a segmentation mask, a body model without triangles and an unreadable
     --part_mapping before the engine is built."""
@@ -249,6 +281,7 @@ def main(args):
     _check_occlusion(args)
     _check_dataset(args)
     _check_segm(args)
+    _check_infill(args)
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")

@@ -402,7 +402,7 @@ int poco_crop_normalize_multi(const unsigned char* const* d_frames, int nframes,
 /* ---- the DATASET crop (eval.py --crop dataset): rotation, flip, scale and per-channel pixel noise -------------------------------
  * Replaces BaseDataset.rgb_processing + normalize_img (pocolib/dataset/base_dataset.py:201-221,309) and the crop_cv2 it calls
  * (pocolib/utils/image_utils.py:189-206: gen_trans_from_patch_cv, pocolib/utils/vibe_image_utils.py:49-91, then cv2.warpAffine of
- * the FLOAT32 image) for a whole batch cut from images of mixed sizes, in one launch; csrc/dataset_crop.hip, DESIGN.md section 22.
+ * the FLOAT32 image) for a whole batch cut from images of mixed sizes, in one launch; csrc/dataset_crop.hip, DESIGN.md section 24.
  * One record per crop.  The host states gen_trans_from_patch_cv up to its three float32 source points (poco_amd/datacrop.py
  * crop_params: integer centre and box side, float32 rotate_2d with numpy's sin / cos); the device solves getAffineTransform and
  * inverts in double as poco_crop_normalize does, generates warpAffine's 10-bit fixed-point coordinates (1/32-pixel fractions) and
@@ -981,6 +981,42 @@ int poco_op_segm_score(const float* d_logits, int B, int C, int h, int w, const 
                        unsigned long long* d_records, double* d_partials, void* stream);
 /* d_out uint8 [B,H,W] <- the argmax poco_op_segm_score takes at every pixel (the same interpolation and tie rule). */
 int poco_op_segm_argmax(const float* d_logits, int B, int C, int h, int w, int H, int W, unsigned char* d_out, void* stream);
+
+/* ---- video mode's in-fill: unreliable joint rotations of a track from the confident frames around them -------------------------
+ * demo.py --mode video --infill THRESH; csrc/track_infill.hip; tests/infill_np.py restates it in float64
+ * numpy.  No counterpart in the reference's code (the paper repairs occluded frames with external motion models).
+ *
+ * poco_op_track_infill: P tracks concatenated into N rows, track p = rows [d_offsets[p], d_offsets[p + 1]).
+ *   d_offsets int32 [P+1] (0 = first, N = last, strictly increasing: the CALLER checks this; the kernel only clamps it to 0..N),
+ *   d_frames int32 [N] (the tracks' frame indices, strictly increasing within a track, holes allowed), d_pose [N,24,3,3] (proper
+ *   rotations), d_u [N,24] (the post-processed uncertainty), d_lin [N,L] with 0 <= L <= POCO_INFILL_MAX_LIN (NULL iff L = 0;
+ *   the demo passes betas | orig_cam, L = 14), thresh, max_gap >= 1, d_scratch = 24 * N int32 words (set and consumed by the call).
+ *   Reliable: entry (t, j) is reliable iff u[t][j] <= thresh; a NaN compares false and counts as unreliable.
+ *   Per unreliable entry, within its own track only: a = the last reliable row before t in column j, b = the first after (either
+ *   may be absent).
+ *     1. both exist and frames[b] - frames[a] <= max_gap: R' = R(slerp(q_a, q_b, s)), s = (frames[t] - frames[a]) / (frames[b] -
+ *        frames[a]); flag 1.
+ *     2. otherwise c = the existing anchor nearer in frames (a tie goes to a); if |frames[t] - frames[c]| <= max_gap / 2 (integer
+ *        division): R' = R[c], copied bit for bit; flag 2.
+ *     3. otherwise the entry is copied bit for bit from the input; flag 3.
+ *   Reliable entries: flag 0, copied bit for bit.
+ *   Arithmetic: fp64, rounded once to fp32 on store (as poco_op_rotmat_to_aa).  Matrix -> quaternion by the largest of (trace, m00,
+ *   m11, m22), the first of equals, then normalised; q_b is negated when q_a.q_b < 0; |q_a.q_b| > 1 - 1e-12: the normalised linear
+ *   blend, else sin((1 - s) th) / sin(th) and sin(s th) / sin(th) with th = acos(q_a.q_b); quaternion -> matrix in the standard form.
+ *   Linear block: row t of d_lin follows column 0's decision: flag 1: lin[a] + s (lin[b] - lin[a]) in fp64; flag 2: a copy of
+ *   lin[c]; else a copy of the row.
+ *   Outputs (every element is written; none may alias an input): d_pose_out [N,24,3,3], d_lin_out [N,L], d_flags uint8 [N,24],
+ *   d_touched uint8 [N] = 1 where any flag of the row is 1 or 2, and - both or neither - d_rows int32 [N] whose first *d_count
+ *   words are the touched rows in ascending order (the rest is left alone) and d_count int32 [1].
+ *   Two launches on `stream` whatever P is (one wave per (track, joint) column, then one block over the rows); no allocation, no
+ *   synchronisation, no atomics: the same input gives the same bits on every run and for every split into calls.
+ *   POCO_ERR_ARG before any GPU work: a null pointer, P < 1, N < P, 24 * 9 * N >= 2^31, L outside 0..16, max_gap < 1, one of
+ *   d_rows / d_count without the other. */
+#define POCO_INFILL_MAX_LIN 16
+int poco_op_track_infill(const float* d_pose, const float* d_u, const int32_t* d_frames, const int32_t* d_offsets, int P, int N,
+                         const float* d_lin, int L, float thresh, int max_gap, int32_t* d_scratch, float* d_pose_out,
+                         float* d_lin_out, unsigned char* d_flags, unsigned char* d_touched, int32_t* d_rows, int32_t* d_count,
+                         void* stream);
 
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /

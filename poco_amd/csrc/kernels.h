@@ -255,3 +255,12 @@ void launch_segm_score(const float* logits, const unsigned char* labels, int B, 
                        unsigned long long* records, double* partials, hipStream_t s);
 // out uint8 [B,H,W] <- the argmax over the C channels of the upsampled logits (the scorer's interpolation and tie rule)
 void launch_segm_argmax(const float* logits, int B, int C, int h, int w, int H, int W, unsigned char* out, hipStream_t s);
+
+// ---- video mode's in-fill of unreliable joint rotations (track_infill.hip) -------------------------------------------
+// include/poco_hip.h poco_op_track_infill: P tracks = rows [offsets[p], offsets[p + 1]) of N; pose [N,24,3,3], u [N,24], frames [N],
+// lin [N,L]; scratch = 24 * N ints; outputs pose_out, lin_out, flags uint8 [N,24], touched uint8 [N]; rows [N] / count [1] nullable.
+// Columns are dealt to at most TRACK_INFILL_MAX_BLOCKS one-wave blocks by a grid-stride loop.
+constexpr int TRACK_INFILL_MAX_BLOCKS = 4096;
+void launch_track_infill(const float* pose, const float* u, const int* frames, const int* offsets, int P, int N, const float* lin, int L,
+                         float thresh, int max_gap, int* scratch, float* pose_out, float* lin_out, unsigned char* flags,
+                         unsigned char* touched, int* rows, int* count, hipStream_t s);

@@ -984,3 +984,24 @@ extern "C" int poco_op_segm_argmax(const float* d_logits, int B, int C, int h, i
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- video mode's in-fill (track_infill.hip) --------------------------------------------------------------------------------
+extern "C" int poco_op_track_infill(const float* d_pose, const float* d_u, const int32_t* d_frames, const int32_t* d_offsets, int P, int N,
+                                    const float* d_lin, int L, float thresh, int max_gap, int32_t* d_scratch, float* d_pose_out,
+                                    float* d_lin_out, unsigned char* d_flags, unsigned char* d_touched, int32_t* d_rows,
+                                    int32_t* d_count, void* stream) {
+  const char* who = "poco_op_track_infill";
+  if (!d_pose || !d_u || !d_frames || !d_offsets || !d_scratch || !d_pose_out || !d_flags || !d_touched)
+    return op_bad(who, "null pointer (pose, u, frames, offsets, scratch, pose_out, flags and touched are needed)");
+  if (P < 1 || N < P || (long long)N * 216 >= (1LL << 31))
+    return op_bad(who, "needs 1 <= P <= N (no empty track) and fewer than 2^31 floats of pose");
+  if (L < 0 || L > POCO_INFILL_MAX_LIN) return op_bad(who, "L must be in 0..16");
+  if ((L > 0) != (d_lin != nullptr) || (L > 0) != (d_lin_out != nullptr)) return op_bad(who, "lin and lin_out are needed iff L > 0");
+  if (max_gap < 1) return op_bad(who, "max_gap must be >= 1");
+  if ((d_rows != nullptr) != (d_count != nullptr)) return op_bad(who, "rows and count come together or not at all");
+  if (d_pose_out == d_pose || (L > 0 && d_lin_out == d_lin)) return op_bad(who, "an output may not alias its input");
+  launch_track_infill(d_pose, d_u, d_frames, d_offsets, P, N, d_lin, L, thresh, max_gap, d_scratch, d_pose_out, d_lin_out, d_flags,
+                      d_touched, d_rows, d_count, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

@@ -479,6 +479,57 @@ def segm_argmax(logits: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return out
 
 
+# ---- video mode's in-fill of unreliable joint rotations (include/poco_hip.h; poco_amd/infill.py is the user's side) -------------
+INFILL_MAX_LIN = 16
+
+
+def track_infill(pose: torch.Tensor, u: torch.Tensor, frames: torch.Tensor, offsets: torch.Tensor, lin: torch.Tensor, thresh: float,
+                 max_gap: int, *, rows: bool = False, out=None):
+    """poco_op_track_infill on device tensors: pose [N,24,3,3], u [N,24] fp32, frames int32 [N], offsets int32 [P+1] (0 .. N,
+    strictly increasing; a host tensor is taken as it is, a device tensor is read back once for the check), lin [N,L] fp32, L <= 16
+    -> (pose', lin', flags uint8 [N,24], touched uint8 [N]); rows=True adds (rows int32 [N], count int32 [1]): the first `count`
+    words of rows are the touched rows in ascending order.  out = (pose', lin', flags, touched[, rows, count]): contiguous tensors
+    to write into (tests: views into guarded buffers).  Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"track_infill: {what}")
+    for name, t, dt in (("pose", pose, torch.float32), ("u", u, torch.float32), ("frames", frames, torch.int32),
+                        ("lin", lin, torch.float32)):
+        need(torch.is_tensor(t) and t.is_cuda, f"{name} must be a CUDA tensor")
+        need(t.dtype == dt, f"{name} must be {dt}, got {t.dtype}")
+    need(torch.is_tensor(offsets) and offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.numel() >= 2,
+         "offsets must be an int32 tensor [P+1], P >= 1")
+    need(pose.dim() == 4 and tuple(pose.shape[1:]) == (24, 3, 3) and pose.shape[0] >= 1, f"pose must be [N,24,3,3], got {tuple(pose.shape)}")
+    N, P = int(pose.shape[0]), int(offsets.numel()) - 1
+    need(tuple(u.shape) == (N, 24), f"u must be [{N},24], got {tuple(u.shape)}")
+    need(tuple(frames.shape) == (N,), f"frames must be [{N}], got {tuple(frames.shape)}")
+    need(lin.dim() == 2 and lin.shape[0] == N, f"lin must be [{N},L], got {tuple(lin.shape)}")
+    L = int(lin.shape[1])
+    need(L <= INFILL_MAX_LIN, f"L = {L} exceeds {INFILL_MAX_LIN}")
+    need(isinstance(max_gap, (int, np.integer)) and max_gap >= 1, f"max_gap must be an integer >= 1, got {max_gap!r}")
+    off = offsets.cpu().numpy()
+    need(off[0] == 0 and off[-1] == N and bool(np.all(np.diff(off) > 0)), "offsets must start at 0, end at N and increase strictly")
+    dev = pose.device
+    if out is None:
+        out = [torch.empty_like(pose), torch.empty_like(lin), torch.empty((N, 24), device=dev, dtype=torch.uint8),
+               torch.empty((N,), device=dev, dtype=torch.uint8)]
+        if rows:
+            out += [torch.empty((N,), device=dev, dtype=torch.int32), torch.empty((1,), device=dev, dtype=torch.int32)]
+    need(len(out) == (6 if rows else 4), "out must hold pose', lin', flags, touched (and rows, count with rows=True)")
+    shapes = [((N, 24, 3, 3), torch.float32), ((N, L), torch.float32), ((N, 24), torch.uint8), ((N,), torch.uint8), ((N,), torch.int32),
+              ((1,), torch.int32)]
+    for t, (shp, dt) in zip(out, shapes):
+        need(t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt, f"an output must be a contiguous CUDA {dt} {shp}")
+    scratch = torch.empty((24 * N,), device=dev, dtype=torch.int32)
+    p = lambda t: C.c_void_p(t.data_ptr())                                    # noqa: E731
+    null = C.c_void_p(0)
+    check(lib().poco_op_track_infill(p(pose.contiguous()), p(u.contiguous()), p(frames.contiguous()), p(offsets.to(dev).contiguous()), P, N,
+                                     p(lin.contiguous()) if L else null, L, C.c_float(thresh), int(max_gap), p(scratch), p(out[0]),
+                                     p(out[1]) if L else null, p(out[2]), p(out[3]), p(out[4]) if rows else null,
+                                     p(out[5]) if rows else null, current_stream()), "poco_op_track_infill")
+    return tuple(out)
+
+
 # ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
 # Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
 # that the caller can check `untouched`.

@@ -500,7 +500,31 @@ class POCOTester:
         stacked = {pid: {k: np.stack(v) for k, v in store[pid].items()} for pid in tracking_results}
         if raw:
             return stacked
+        if getattr(self.args, "infill", None) is not None:
+            return self._finish_tracks_infilled(tracking_results, stacked, orig_width, orig_height)
         return {pid: self._finish_track(tr, stacked[pid], orig_width, orig_height) for pid, tr in tracking_results.items()}
+
+    def _finish_tracks_infilled(self, tracking_results: dict, stacked: dict, orig_width: int, orig_height: int) -> dict:
+        """--infill THRESH: the tracks are finished unsmoothed (video_uncert, convert_crop_cam_to_orig_img), then ONE call of
+        infill.infill_tracks over all of them replaces the rotations whose `var` exceeds THRESH (betas and orig_cam follow the root
+        joint, the touched frames are re-posed), and only then does --smooth filter the in-filled pose - its LBS call supplies the
+        meshes.  Each result gains `infill` [T,24] and `pose_net` / `betas_net` / `orig_cam_net`, the values before in-filling; var,
+        var_global, pred_cam and smpl_joints2d stay those of the raw prediction."""
+        from . import infill
+        res = {pid: self._finish_track(tr, stacked[pid], orig_width, orig_height, smooth=False) for pid, tr in tracking_results.items()}
+        filled = infill.infill_tracks(self.model, res, float(self.args.infill), int(getattr(self.args, "infill_max_gap", 30)))
+        for pid, r in res.items():
+            f = filled[pid]
+            r["pose_net"], r["betas_net"], r["orig_cam_net"] = r["pose"], r["betas"], r["orig_cam"]
+            for k in ("pose", "betas", "orig_cam", "verts", "smpl_joints3d", "infill"):
+                r[k] = f[k]
+            if getattr(self.args, "smooth", False):
+                from .smooth import smooth_pose
+                r["verts"], r["pose"], r["smpl_joints3d"] = smooth_pose(self.model, r["pose"], r["betas"],
+                                                                        getattr(self.args, "min_cutoff", 0.004),
+                                                                        getattr(self.args, "beta", 1.5))
+        print(infill.summary_line(filled))
+        return res
 
     def _finish_track(self, tr: dict, st: Dict[str, np.ndarray], orig_width: int, orig_height: int,
                       smooth: Optional[bool] = None) -> dict:
