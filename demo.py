@@ -43,6 +43,12 @@ those are at most --infill_max_gap frames apart, else by the nearer one if it is
 and orig_cam follow the root joint, the touched frames are re-posed, --smooth then filters the repaired pose (poco_amd/infill.py,
 csrc/track_infill.hip).  The result gains infill [T,24] (0 reliable, 1 interpolated, 2 held, 3 left) and pose_net / betas_net /
 orig_cam_net, the values before in-filling.  No default threshold: it is the user's statement of what they trust.  Not with --gpus N > 1.
+--cfg2 FILE --ckpt2 FILE [--inf_model2 best] [--select crop|joint] [--select_scale S] runs a second model on the same crops on the
+same GPU and lets the uncertainty choose (poco_amd/select.py, csrc/select_regressor.hip): per crop the model
+whose global uncertainty (the reference's get_global_uncert of its own head) is lower, S times the second model's against the
+first's, a tie to the first; or with --select joint per joint rotation, shape, camera and 2-D joints following the root joint and
+the mixed rows re-posed.  Folder and video mode; the result gains select [n,24] and select_score [n,2].  Not with --gpus N > 1,
+--occlusion_map, --save_dataset or --save_segm.
 """
 import argparse
 import json
@@ -154,6 +160,17 @@ def parse_args(argv=None):
     p.add_argument("--infill_max_gap", type=int, default=30,
                    help="--infill: the most frames between the two confident frames of an interpolation (one second at the default "
                         "--fps); a single confident frame is held for at most half of it")
+    p.add_argument("--cfg2", type=str, default=None,
+                   help="a second model's config: with --ckpt2, both engines regress every crop on the one GPU and the per-joint "
+                        "uncertainty decides whose result is written (poco_amd/select.py); the result gains select and select_score")
+    p.add_argument("--ckpt2", type=str, default=None, help="the second model's checkpoint (needs --cfg2)")
+    p.add_argument("--inf_model2", type=str, default="best", help="--inf_model of the second model")
+    p.add_argument("--select", default=None, choices=["crop", "joint"],
+                   help="with --cfg2 --ckpt2: crop (default) = each crop from the model with the lower global uncertainty; joint = "
+                        "each joint rotation from the model with the lower uncertainty of that joint, shape and camera from the "
+                        "root's model, mixed rows re-posed")
+    p.add_argument("--select_scale", type=float, default=None,
+                   help="with --cfg2 --ckpt2: multiplies the second model's uncertainty before the comparison (default 1.0)")
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
@@ -239,6 +256,14 @@ def _check_infill(args) -> None:
         sys.exit(f"--infill_max_gap must be >= 1, got {gap}")
 
 
+def _check_select(args) -> None:
+    """--cfg2 / --ckpt2 / --select / --select_scale: refuse what cannot work before an engine is built."""
+    from poco_amd.select import flag_error
+    msg = flag_error(args, ("occlusion_map", "save_dataset", "save_segm"))
+    if msg:
+        sys.exit(msg)
+
+
 def _check_segm(args) -> None:
     """--save_segm: refuse video mode, a head without a segmentation mask, a body model without triangles and an unreadable
     --part_mapping before the engine is built."""
@@ -278,6 +303,7 @@ def main(args):
         sys.exit(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
     if getattr(args, "save_video", False) and not (args.mode == "video" and render_enabled(args)):
         sys.exit("--save_video writes the rendered frames of video mode: it needs --mode video and --render")
+    _check_select(args)
     _check_occlusion(args)
     _check_dataset(args)
     _check_segm(args)

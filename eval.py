@@ -18,6 +18,11 @@ one launch per batch; --aug_rot / --aug_scale / --aug_flip / --aug_noise perturb
 sample from the config's training-time distribution; the ground truth is transformed with the crop (poco_amd/datacrop.py,
 csrc/dataset_crop.hip).  --aug_occlude FILE pastes the reference's synthetic occluders over every crop inside
 that launch and reports how the uncertainty follows the covered area.
+--cfg2 FILE --ckpt2 FILE [--inf_model2 best] [--select crop|joint] [--select_scale S] evaluates a second model on the same crops and
+the selection between the two by their own uncertainty (demo.py's flags): the lines above for model 1, model 2
+and the selection, Oracle MPJPE / PA-MPJPE (per crop the better model: the bound no selection beats), the selection accuracy and the
+share of crops taken from model 2; the .npz holds the selection under the usual keys and gains the models' mpjpe / pampjpe / v2v as
+*_m1 / *_m2, select and select_score.  Not with --segm or --likelihood.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -73,6 +78,16 @@ def parse_args(argv=None):
                    help="paste 1..7 synthetic occluders per crop over the ground-truth keypoints as the reference's training dataset "
                         "does (occlude_with_pascal_objects_kp); FILE: its pascal_occluders.pkl or an .npz of uint8 [h,w,4] RGBA cut-outs; "
                         "needs `part` in the dataset; composes with the other --aug_* flags and --augment (implies --crop dataset)")
+    p.add_argument("--cfg2", type=str, default=None,
+                   help="a second model's config: with --ckpt2, both engines regress every crop and model 1, model 2 and the selection "
+                        "by uncertainty are evaluated side by side (poco_amd/select.py, evaluate.run_eval_pair)")
+    p.add_argument("--ckpt2", type=str, default=None, help="the second model's checkpoint (needs --cfg2)")
+    p.add_argument("--inf_model2", type=str, default="best")
+    p.add_argument("--select", default=None, choices=["crop", "joint"],
+                   help="with --cfg2 --ckpt2: crop (default) = each crop from the model with the lower global uncertainty; joint = "
+                        "each joint rotation from the model with the lower uncertainty of that joint, mixed rows re-posed")
+    p.add_argument("--select_scale", type=float, default=None,
+                   help="with --cfg2 --ckpt2: multiplies the second model's uncertainty before the comparison (default 1.0)")
     return p.parse_args(argv)
 
 
@@ -198,7 +213,16 @@ def check_segm_inputs(args) -> None:
                      "triangles)")
 
 
+def check_select(args) -> None:
+    """--cfg2 / --ckpt2 / --select / --select_scale: refuse what cannot work before an engine is built."""
+    from poco_amd.select import flag_error
+    msg = flag_error(args, ("segm", "likelihood"))
+    if msg:
+        sys.exit(msg)
+
+
 def main(args):
+    check_select(args)
     check_dataset_file(args.dataset)
     aug = augmentation_spec(args)
     occ = occlusion_spec(args)
@@ -238,11 +262,15 @@ def main(args):
                                 uncert_threshold=getattr(args, "uncert_threshold", None), res=tester.model_cfg.DATASET.IMG_RES)
         except ValueError as e:
             sys.exit(str(e))
+    elif tester.pair is not None:
+        res = evaluate.run_eval_pair(tester.pair, ds, J, batch_size=max(int(args.batch_size), 1),
+                                     kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
     else:
         res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
                                 kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
                                 likelihood=args.likelihood)
-    for line in (evaluate.likelihood_lines(res) if args.likelihood else []) + evaluate.report_lines(res):
+    lines = evaluate.pair_report_lines(res, tester.pair.mode) if tester.pair is not None else evaluate.report_lines(res)
+    for line in (evaluate.likelihood_lines(res) if args.likelihood else []) + lines:
         print(line)
     if getattr(args, "segm", False):
         for line in segm.report_lines(res):

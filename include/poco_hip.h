@@ -1018,6 +1018,50 @@ int poco_op_track_infill(const float* d_pose, const float* d_u, const int32_t* d
                          float* d_lin_out, unsigned char* d_flags, unsigned char* d_touched, int32_t* d_rows, int32_t* d_count,
                          void* stream);
 
+/* ---- choosing between two regressors by their own uncertainty ---------------------------------------------------------------------
+ * demo.py / eval.py --cfg2 --ckpt2 --select crop|joint; csrc/select_regressor.hip; tests/select_np.py restates
+ * it in float64 numpy with plain loops.  No counterpart in the reference's code (the paper's comparison was offline); the
+ * uncertainty post-processing it decides on is pocolib/utils/poco_utils.py:21-25,50-60.
+ *
+ * poco_op_select_regressor: models m = 0, 1 over B rows.  d_pose_m [B,24,3,3], d_var_m [B,24] (the raw var_pose), kind_m: 0 = the
+ *   "mean" rule (pare), 1 = the "root" rule (cliff); kinematic 0 | 1, thr, scale > 0 (multiplies model 1's uncertainty), mode 0 =
+ *   crop, 1 = joint; `payloads`: up to POCO_SELECT_MAX_PAYLOADS arrays of `width` floats per row, each with its two sources and
+ *   its destination.  All buffers dense and caller-owned; no output may alias an input.
+ *   Processed uncertainty: u_m[t][j] = var_m[t][j]; with kinematic u[child] = var[child] + u[parent] in child order 1..23, fp32
+ *   additions (poco_utils.py:21-25).
+ *   Crop score, fp64 from the fp32 u: kind 1: g = u[0] > 2 thr ? 1 : u[0]; kind 0: g = u[0] > thr ? 1 : (u[0] + ... + u[23], in
+ *   joint order) / 24 (poco_utils.py:50-60; the fp64 mean and comparison differ from numpy's fp32 pairwise mean by at most one
+ *   rounding: chosen so that kernel and restatement agree bit for bit).  s_0 = g_0, s_1 = scale g_1.
+ *   mode 0: row t takes model 1 iff s_1 < s_0 (a tie and a NaN on either side: model 0); all 24 entries of choice[t] are that.
+ *   mode 1: entry (t, j) takes model 1 iff scale (double)u_1[t][j] < (double)u_0[t][j], same tie and NaN rule, no 1.0 rule.
+ *   Outputs (every element is written): d_pose_out [B,24,3,3] and d_var_out [B,24] = the chosen model's nine floats / one float
+ *   per entry, bit for bit; every payload row = a bit-for-bit copy from the model chosen for joint 0; d_choice uint8 [B,24];
+ *   d_score fp32 [B,2] = s_0, s_1 rounded once (a NaN is stored as 0x7fc00000), in both modes; d_mixed uint8 [B] = 1 where the
+ *   24 choices of the row are not all equal (never in mode 0); and - both or neither - d_rows int32 [B] whose first *d_count
+ *   words are the mixed rows in ascending order (the rest is left alone) and d_count int32 [1].
+ *   max_blocks: 0 = the default grid, > 0 bounds the first launch's grid; the result does not depend on it.
+ *   Two launches on `stream` (one block per row, grid-stride; one block over the rows); no allocation, no synchronisation, no
+ *   atomics.  Payload rows are copied with the widest accesses the row's own addresses allow (16, 8 or 4 bytes): no alignment
+ *   beyond a float's is assumed.
+ *   POCO_ERR_ARG before any GPU work: a null pointer (a payload's included), B outside 1..2^24, mode, kind or kinematic
+ *   outside {0, 1}, scale not finite or <= 0, a payload count outside 0..8, a payload width outside 1..2^24, an output equal to
+ *   an input, one of d_rows / d_count without the other. */
+#define POCO_SELECT_MAX_PAYLOADS 8
+typedef struct {
+  const float* src0;  /* [B, width] of model 0                                                                           */
+  const float* src1;  /* [B, width] of model 1                                                                           */
+  float* dst;         /* [B, width]                                                                                      */
+  int64_t width;      /* floats per row, 1 .. 2^24                                                                       */
+} poco_select_payload_t;
+typedef struct {
+  int64_t count;                                        /* payloads in use, 0 .. POCO_SELECT_MAX_PAYLOADS               */
+  poco_select_payload_t p[POCO_SELECT_MAX_PAYLOADS];
+} poco_select_payloads_t;                               /* passed by value                                              */
+int poco_op_select_regressor(const float* d_pose0, const float* d_var0, int kind0, const float* d_pose1, const float* d_var1,
+                             int kind1, int B, int kinematic, double thr, double scale, int mode, poco_select_payloads_t payloads,
+                             float* d_pose_out, float* d_var_out, unsigned char* d_choice, float* d_score, unsigned char* d_mixed,
+                             int32_t* d_rows, int32_t* d_count, int max_blocks, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

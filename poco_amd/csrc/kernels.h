@@ -264,3 +264,24 @@ constexpr int TRACK_INFILL_MAX_BLOCKS = 4096;
 void launch_track_infill(const float* pose, const float* u, const int* frames, const int* offsets, int P, int N, const float* lin, int L,
                          float thresh, int max_gap, int* scratch, float* pose_out, float* lin_out, unsigned char* flags,
                          unsigned char* touched, int* rows, int* count, hipStream_t s);
+
+// ---- choosing between two regressors by their uncertainty (select_regressor.hip) ------------------------------------------
+// include/poco_hip.h poco_op_select_regressor: B rows of two models' pose [B,24,3,3] / var [B,24] and up to SELECT_MAX_PAYLOADS
+// payload arrays of `width` floats per row (src0, src1 -> dst); outputs pose_out, var_out, choice uint8 [B,24], score [B,2],
+// mixed uint8 [B]; rows [B] / count [1] nullable.  Rows are dealt to at most SELECT_MAX_BLOCKS blocks (max_blocks > 0: at most
+// that many) by a grid-stride loop.
+constexpr int SELECT_MAX_BLOCKS = 1024;
+constexpr int SELECT_MAX_PAYLOADS = 8;
+struct SelectPayload {
+  const float *src0, *src1;
+  float* dst;
+  int width;
+};
+struct SelectPayloads {
+  int count;
+  SelectPayload p[SELECT_MAX_PAYLOADS];
+};
+void launch_select_regressor(const float* pose0, const float* var0, int kind0, const float* pose1, const float* var1, int kind1, int B,
+                             int kinematic, double thr, double scale, int mode, const SelectPayloads& payloads, float* pose_out,
+                             float* var_out, unsigned char* choice, float* score, unsigned char* mixed, int* rows, int* count,
+                             int max_blocks, hipStream_t s);

@@ -1005,3 +1005,35 @@ extern "C" int poco_op_track_infill(const float* d_pose, const float* d_u, const
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- choosing between two regressors (select_regressor.hip) ------------------------------------------------------------------
+extern "C" int poco_op_select_regressor(const float* d_pose0, const float* d_var0, int kind0, const float* d_pose1, const float* d_var1,
+                                        int kind1, int B, int kinematic, double thr, double scale, int mode,
+                                        poco_select_payloads_t payloads, float* d_pose_out, float* d_var_out, unsigned char* d_choice,
+                                        float* d_score, unsigned char* d_mixed, int32_t* d_rows, int32_t* d_count, int max_blocks,
+                                        void* stream) {
+  const char* who = "poco_op_select_regressor";
+  if (!d_pose0 || !d_var0 || !d_pose1 || !d_var1 || !d_pose_out || !d_var_out || !d_choice || !d_score || !d_mixed)
+    return op_bad(who, "null pointer (both models' pose and var, pose_out, var_out, choice, score and mixed are needed)");
+  if (B < 1 || B > (1 << 24)) return op_bad(who, "B must be in 1..2^24");
+  if ((mode | 1) != 1 || (kind0 | 1) != 1 || (kind1 | 1) != 1 || (kinematic | 1) != 1)
+    return op_bad(who, "mode, kind0, kind1 and kinematic must be 0 or 1");
+  if (!std::isfinite(scale) || !(scale > 0.0)) return op_bad(who, "scale must be finite and > 0");
+  if (payloads.count < 0 || payloads.count > POCO_SELECT_MAX_PAYLOADS) return op_bad(who, "at most 8 payloads");
+  if ((d_rows != nullptr) != (d_count != nullptr)) return op_bad(who, "rows and count come together or not at all");
+  if (d_pose_out == d_pose0 || d_pose_out == d_pose1 || d_var_out == d_var0 || d_var_out == d_var1)
+    return op_bad(who, "an output may not alias an input");
+  SelectPayloads pl{};
+  pl.count = (int)payloads.count;
+  for (int k = 0; k < pl.count; ++k) {
+    const poco_select_payload_t& p = payloads.p[k];
+    if (!p.src0 || !p.src1 || !p.dst) return op_bad(who, "null pointer in payload " + std::to_string(k));
+    if (p.width < 1 || p.width > (1 << 24)) return op_bad(who, "the width of payload " + std::to_string(k) + " must be in 1..2^24");
+    if (p.dst == p.src0 || p.dst == p.src1) return op_bad(who, "an output may not alias an input (payload " + std::to_string(k) + ")");
+    pl.p[k] = SelectPayload{p.src0, p.src1, p.dst, (int)p.width};
+  }
+  launch_select_regressor(d_pose0, d_var0, kind0, d_pose1, d_var1, kind1, B, kinematic, thr, scale, mode, pl, d_pose_out, d_var_out,
+                          d_choice, d_score, d_mixed, d_rows, d_count, max_blocks, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

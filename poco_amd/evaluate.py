@@ -7,6 +7,7 @@ restates that and is the yardstick of tests/test_eval_*.py."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, Optional, Sequence
 
@@ -421,6 +422,77 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
     return res
 
 
+PAIR_SCALARS = ("val_oracle_mpjpe", "val_oracle_pampjpe", "select_accuracy", "select_share_m2")
+
+
+def selection_summary(crop_mpjpe, crop_pampjpe, select) -> Dict[str, float]:
+    """What the records of two models say about a selection, in float64 on the host.  crop_mpjpe / crop_pampjpe: ([N], [N]) = the
+    two models' per-crop values (record words 0 and 1, metres); select [N,24].  val_oracle_* = 1000 x the mean over the crops of the
+    smaller of the two values - the bound no selection beats; select_accuracy = the share of crops whose chosen model (the model of
+    the root joint) is not the worse one in MPJPE (equal values count as right); select_share_m2 = the share taken from model 2."""
+    root = np.asarray(select).reshape(-1, 24)[:, 0] != 0
+    a1, a2 = (np.asarray(x, np.float64) for x in crop_mpjpe)
+    p1, p2 = (np.asarray(x, np.float64) for x in crop_pampjpe)
+    n = float(len(root))
+    # 1000.0 * sum / n as eval_finish forms its means, the sum rounded once: where one model is the better on every crop the oracle
+    # is that model's own mean whenever the device's fp64 sum of the fp32 values is exact, not one rounding above it
+    return {"val_oracle_mpjpe": 1000.0 * math.fsum(np.minimum(a1, a2)) / n, "val_oracle_pampjpe": 1000.0 * math.fsum(np.minimum(p1, p2)) / n,
+            "select_accuracy": float(np.where(root, a2 <= a1, a1 <= a2).mean()), "select_share_m2": float(root.mean())}
+
+
+@torch.no_grad()
+def run_eval_pair(pair, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
+                  sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False) -> Dict[str, object]:
+    """run_eval with a second model (eval.py --cfg2 --ckpt2): per batch RegressorPair.forward_all, then three
+    Evaluators - model 1, model 2, selected - stepped against the same ground truth on the same stream; the choices are kept in
+    device buffers, so nothing goes to the host between the forward and the three finish() calls.  Returns the selected result
+    under run_eval's keys, the two models' mpjpe / pampjpe / v2v and val_* with suffixes _m1 and _m2, their per-crop record values
+    crop_mpjpe_m* / crop_pampjpe_m* [N], select [N,24] uint8, select_score [N,2] and selection_summary of them."""
+    from . import ops
+    dev, n = pair.device, len(dataset)
+    evs = [Evaluator(J_regressor, joint_map(dataset.name), capacity=n, sel_uncert_part=sel_uncert_part, kinematic=kinematic, device=dev)
+           for _ in range(3)]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+    select = torch.zeros(n, 24, dtype=torch.uint8, device=dev)
+    score = torch.zeros(n, 2, dtype=torch.float32, device=dev)
+    for lo in range(0, n, batch_size):
+        hi = min(lo + batch_size, n)
+        outs = pair.forward_all(dataset.batch(lo, hi, dev))
+        select[lo:hi].copy_(outs[2]["select"])
+        score[lo:hi].copy_(outs[2]["select_score"])
+        gt_pose = t(dataset.pose[lo:hi])
+        if dataset.gt_form == "smpl":
+            gt = {"gt_vertices": pair.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))[0]}
+        else:
+            gt = {"gt_joints": t(dataset.joints[lo:hi])}
+        for ev, out in zip(evs, outs):
+            ev.step(out, gt_pose, **gt)
+    solo = [ev.finish(return_records=True) for ev in evs[:2]]
+    res = evs[2].finish(save_results=save_results)
+    for tag, r in zip(("_m1", "_m2"), solo):
+        res.update({k + tag: r[k] for k in ("mpjpe", "pampjpe", "v2v", "val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")})
+        res["crop_mpjpe" + tag], res["crop_pampjpe" + tag] = r["records"][:, R_MPJPE].copy(), r["records"][:, R_PA].copy()
+    res["select"], res["select_score"] = select.cpu().numpy(), score.cpu().numpy()
+    res.update(selection_summary((res["crop_mpjpe_m1"], res["crop_mpjpe_m2"]), (res["crop_pampjpe_m1"], res["crop_pampjpe_m2"]),
+                                 res["select"]))
+    pair.check_status()
+    res["imgname"] = np.asarray(dataset.imgname)
+    for ev in evs:
+        ev.close()
+    return res
+
+
+def pair_report_lines(res: Dict[str, object], mode: str = "crop"):
+    """report_lines for model 1, model 2 and the selection, labelled, then the oracle, the selection accuracy and model 2's share."""
+    lines = []
+    for label, tag in (("Model 1", "_m1"), ("Model 2", "_m2")):
+        lines += [f"{label} MPJPE: {res['val_mpjpe' + tag]}", f"{label} PA-MPJPE: {res['val_pampjpe' + tag]}",
+                  f"{label} V2V (mm): {res['val_v2v' + tag]}", f"{label} Uncert Error Correlation: {res['val_corr' + tag]}"]
+    lines += [f"Selected ({mode}) {line}" for line in report_lines(res)]
+    return lines + [f"Oracle MPJPE: {res['val_oracle_mpjpe']}", f"Oracle PA-MPJPE: {res['val_oracle_pampjpe']}",
+                    f"Selection accuracy: {res['select_accuracy']}", f"Crops from model 2: {res['select_share_m2']}"]
+
+
 def check_occlusion_keys(files) -> None:
     """Synthetic occluders are centred on the ground-truth 2-D keypoints: refuse a dataset file without `part` or with ready-made
     `img` crops (ValueError)."""
@@ -469,5 +541,7 @@ def save_npz(path: str, res: Dict[str, object], dataset_name: str) -> None:
     keep.update({k: np.float64(res[k]) for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")})
     keep["N"] = np.int64(res["N"])
     keep.update({k: np.float64(res[k]) for k in ("val_nll", "val_log_phi", "val_log_sigma", "val_mpjpe_var", "val_var") if k in res})
+    pair = PAIR_SCALARS + tuple(k + tag for tag in ("_m1", "_m2") for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr"))
+    keep.update({k: np.float64(res[k]) for k in pair if k in res})           # eval.py --cfg2 --ckpt2 (run_eval_pair)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     np.savez(path, **keep)

@@ -530,6 +530,97 @@ def track_infill(pose: torch.Tensor, u: torch.Tensor, frames: torch.Tensor, offs
     return tuple(out)
 
 
+# ---- choosing between two regressors by their uncertainty (include/poco_hip.h; poco_amd/select.py is the user's side) -----------
+SELECT_MAX_PAYLOADS = 8
+SELECT_MODES = {"crop": 0, "joint": 1}
+
+
+class _SelectPayload(C.Structure):
+    _fields_ = [("src0", C.c_void_p), ("src1", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int64)]
+
+
+class _SelectPayloads(C.Structure):
+    _fields_ = [("count", C.c_int64), ("p", _SelectPayload * SELECT_MAX_PAYLOADS)]
+
+
+SELECT_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                   _SelectPayloads] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
+
+
+def select_payloads(triples):
+    """The by-value descriptor of poco_op_select_regressor from [(src0 pointer, src1 pointer, dst pointer, width), ...]; more than
+    SELECT_MAX_PAYLOADS entries keep their count (the entry refuses it) but only the first eight are stored."""
+    d = _SelectPayloads()
+    d.count = len(triples)
+    for k, (a, b, o, w) in enumerate(triples[:SELECT_MAX_PAYLOADS]):
+        d.p[k] = _SelectPayload(a, b, o, int(w))
+    return d
+
+
+def select_regressor(pose0: torch.Tensor, var0: torch.Tensor, kind0: int, pose1: torch.Tensor, var1: torch.Tensor, kind1: int,
+                     payloads=(), *, kinematic: bool = True, thr: float = 0.40, scale: float = 1.0, mode="crop", rows: bool = False,
+                     out=None, max_blocks: int = 0) -> dict:
+    """poco_op_select_regressor on device tensors: pose_m [B,24,3,3], var_m [B,24] fp32 (the raw var_pose), kind_m 0 = the mean rule
+    (pare) | 1 = the root rule (cliff), payloads = [(src0, src1), ...] of up to 8 pairs of contiguous fp32 tensors with B rows each
+    (any trailing shape, the same in a pair), mode "crop" | "joint" (or 0 | 1)
+    -> dict(pose, var, choice uint8 [B,24], score [B,2], mixed uint8 [B], payloads = [dst, ...]); rows=True adds rows int32 [B] and
+    count int32 [1]: the first `count` words of rows are the mixed rows in ascending order.  out = a dict with the same keys:
+    contiguous tensors to write into (tests: views into guarded buffers).  max_blocks > 0 bounds the grid of the first launch (the
+    result does not depend on it).  Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"select_regressor: {what}")
+    for name, t in (("pose0", pose0), ("var0", var0), ("pose1", pose1), ("var1", var1)):
+        need(torch.is_tensor(t) and t.is_cuda, f"{name} must be a CUDA tensor")
+        need(t.dtype == torch.float32, f"{name} must be float32, got {t.dtype}")
+    need(pose0.dim() == 4 and tuple(pose0.shape[1:]) == (24, 3, 3) and pose0.shape[0] >= 1, f"pose0 must be [B,24,3,3], got {tuple(pose0.shape)}")
+    B = int(pose0.shape[0])
+    need(tuple(pose1.shape) == (B, 24, 3, 3), f"pose1 must be [{B},24,3,3], got {tuple(pose1.shape)}")
+    for name, t in (("var0", var0), ("var1", var1)):
+        need(tuple(t.shape) == (B, 24), f"{name} must be [{B},24] (SIGMA_DIM 1), got {tuple(t.shape)}")
+    mode = SELECT_MODES.get(mode, mode)
+    need(mode in (0, 1), "mode must be 'crop' or 'joint'")
+    need(kind0 in (0, 1) and kind1 in (0, 1), "kind0 and kind1 must be 0 (mean rule) or 1 (root rule)")
+    need(isinstance(scale, (int, float)) and np.isfinite(scale) and scale > 0, f"scale must be finite and > 0, got {scale!r}")
+    payloads = list(payloads)
+    need(len(payloads) <= SELECT_MAX_PAYLOADS, f"at most {SELECT_MAX_PAYLOADS} payloads, got {len(payloads)}")
+    for k, (a, b) in enumerate(payloads):
+        for t in (a, b):
+            need(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(),
+                 f"payload {k} must be a pair of contiguous float32 CUDA tensors")
+        need(a.shape == b.shape and a.dim() >= 1 and a.shape[0] == B and a.numel() >= B, f"payload {k} must be two [{B}, ...] tensors of one shape")
+    dev = pose0.device
+    if out is None:
+        out = {"pose": torch.empty_like(pose0), "var": torch.empty_like(var0), "choice": torch.empty((B, 24), device=dev, dtype=torch.uint8),
+               "score": torch.empty((B, 2), device=dev, dtype=torch.float32), "mixed": torch.empty((B,), device=dev, dtype=torch.uint8),
+               "payloads": [torch.empty_like(a) for a, _ in payloads]}
+        if rows:
+            out["rows"] = torch.empty((B,), device=dev, dtype=torch.int32)
+            out["count"] = torch.empty((1,), device=dev, dtype=torch.int32)
+    shapes = {"pose": ((B, 24, 3, 3), torch.float32), "var": ((B, 24), torch.float32), "choice": ((B, 24), torch.uint8),
+              "score": ((B, 2), torch.float32), "mixed": ((B,), torch.uint8)}
+    if rows:
+        shapes.update(rows=((B,), torch.int32), count=((1,), torch.int32))
+    for key, (shp, dt) in shapes.items():
+        t = out.get(key)
+        need(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt,
+             f"out[{key!r}] must be a contiguous CUDA {dt} {shp}")
+    need(len(out.get("payloads", [])) == len(payloads), "out['payloads'] must hold one destination per payload")
+    for k, ((a, _), o) in enumerate(zip(payloads, out["payloads"])):
+        need(torch.is_tensor(o) and o.is_cuda and o.is_contiguous() and o.shape == a.shape and o.dtype == torch.float32,
+             f"out['payloads'][{k}] must be a contiguous float32 CUDA tensor of the payload's shape")
+    p = lambda t: t.data_ptr()                                                # noqa: E731
+    pose0, var0, pose1, var1 = pose0.contiguous(), var0.contiguous(), pose1.contiguous(), var1.contiguous()
+    desc = select_payloads([(p(a), p(b), p(o), a.numel() // B) for (a, b), o in zip(payloads, out["payloads"])])
+    fn = lib().poco_op_select_regressor
+    fn.argtypes = SELECT_ARGTYPES
+    check(fn(p(pose0), p(var0), int(kind0), p(pose1), p(var1), int(kind1), B, int(bool(kinematic)), float(thr), float(scale), int(mode),
+             desc, p(out["pose"]), p(out["var"]), p(out["choice"]), p(out["score"]), p(out["mixed"]),
+             p(out["rows"]) if rows else None, p(out["count"]) if rows else None, int(max_blocks), current_stream()),
+          "poco_op_select_regressor")
+    return out
+
+
 # ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
 # Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
 # that the caller can check `untouched`.

@@ -73,6 +73,7 @@ def crop_keypoints(joints2d, box, res: int = 224, bbox_scale: float = 1.0) -> np
 
 class POCOTester:
     _pseudo = None                      # --save_dataset: the device-side labeler of the current run (pseudo_begin), else None
+    pair = None                         # --cfg2 / --ckpt2: the RegressorPair that stands where self.model is used for forwards, else None
 
     def __init__(self, args):
         self.args = args
@@ -85,10 +86,19 @@ class POCOTester:
         ndev = max(torch.cuda.device_count(), 1)
         self.device = torch.device(f"cuda:{int(os.environ.get('LOCAL_RANK', '0')) % ndev}")
         torch.cuda.set_device(self.device)
-        kw = model_kwargs(self.model_cfg)
-        self.model = POCO(**kw, pretrained=args.ckpt, inf_model=getattr(args, "inf_model", "best"),
-                          max_batch=max(int(args.batch_size), 1), smpl=args.smpl, device=str(self.device),
-                          keep_state_dict=False).finalize()     # (state_dict() re-reads the checkpoint file on demand)
+        self.model = self._build_engine(self.model_cfg, args.ckpt, getattr(args, "inf_model", "best"))
+        if getattr(args, "cfg2", None):
+            from .select import RegressorPair
+            cfg2 = update_hparams(args.cfg2)
+            if cfg2.DATASET.IMG_RES != self.model_cfg.DATASET.IMG_RES:
+                raise ValueError(f"--cfg2: DATASET.IMG_RES {cfg2.DATASET.IMG_RES} differs from --cfg's {self.model_cfg.DATASET.IMG_RES}")
+            # POCO.KINEMATIC_UNCERT is neither config's: --no_kinematic_uncert decides it (above), for both models alike
+            second = self._build_engine(cfg2, args.ckpt2, getattr(args, "inf_model2", "best"))
+            self.model = self.pair = RegressorPair(self.model, second, mode=getattr(args, "select", None) or "crop",
+                                                   scale=float(getattr(args, "select_scale", None) or 1.0),
+                                                   kinematic=self.model_cfg.POCO.KINEMATIC_UNCERT)
+            self._select_rows = []              # the `select` of every batch, for the printed line
+            self._select_mixed = 0
         self.faces = None                       # triangle list for --save_obj / --render, if the body-model file carries one
         if isinstance(args.smpl, str) and os.path.isfile(args.smpl):
             with np.load(args.smpl) as z:
@@ -96,6 +106,27 @@ class POCOTester:
                     self.faces = np.asarray(z["faces"], np.int64)
         self._renderer = None
         self._pseudo_src = []                   # --save_dataset: the label of every crop offered to the labeler
+
+    def _build_engine(self, model_cfg, ckpt, inf_model):
+        """One finalized engine for a config and a checkpoint, with this tester's --smpl, batch size and device."""
+        return POCO(**model_kwargs(model_cfg), pretrained=ckpt, inf_model=inf_model, max_batch=max(int(self.args.batch_size), 1),
+                    smpl=self.args.smpl, device=str(self.device),
+                    keep_state_dict=False).finalize()     # (state_dict() re-reads the checkpoint file on demand)
+
+    # ---- --cfg2 / --ckpt2 -------------------------------------------------------------------------------------------
+    def _select_note(self, out) -> None:
+        """Keep a forward's choices for the printed line (host copies of [B,24] and [B] bytes)."""
+        self._select_rows.append(np.asarray(out["select"].cpu().numpy() if torch.is_tensor(out["select"]) else out["select"]))
+        self._select_mixed += int(np.asarray(out["select_mixed"].cpu().numpy() if torch.is_tensor(out["select_mixed"])
+                                             else out["select_mixed"]).sum())
+
+    def select_summary(self) -> None:
+        """Print the one line of a run with a second model and forget its counts."""
+        if self.pair is None or not self._select_rows:
+            return
+        from .select import summary_line
+        print(summary_line(np.concatenate(self._select_rows), self._select_mixed, self.pair.mode))
+        self._select_rows, self._select_mixed = [], 0
 
     # ---- --save_dataset ---------------------------------------------------------------------------------------------
     def pseudo_begin(self, capacity: int) -> None:
@@ -359,6 +390,15 @@ class POCOTester:
                "betas": output["pred_shape"].cpu().numpy(), "joints3d": output["smpl_joints3d"].cpu().numpy(),
                "bboxes": dets}
         j2d = output["smpl_joints2d"].cpu().numpy()
+        if self.pair is not None:                                                    # the same two steps, per row by the root's model
+            from . import select
+            sel = output["select"].cpu().numpy()
+            j2d = select.pair_joints2d(j2d, sel, self.pair.backbones, dets, self.model_cfg.DATASET.IMG_RES)
+            res["smpl_joints2d"] = np.concatenate([j2d, np.ones((len(dets), 49, 1), np.float32)], -1)
+            res["var"], res["var_global"] = select.pair_uncert(output["var_pose"], sel, self.pair.backbones,
+                                                               self.model_cfg.POCO.KINEMATIC_UNCERT, clip=True)
+            res["select"], res["select_score"] = sel, output["select_score"].cpu().numpy()
+            return res
         if "cliff" not in self.backbone:                                             # tester.py:225-230
             j2d = postproc.convert_crop_coords_to_orig_img(dets, j2d, self.model_cfg.DATASET.IMG_RES)
         res["smpl_joints2d"] = np.concatenate([j2d, np.ones((len(dets), 49, 1), np.float32)], -1)
@@ -394,6 +434,8 @@ class POCOTester:
             # downstream uses), sliced per frame below
             out = {n: v.cpu() for n, v in out.items() if torch.is_tensor(v) and n not in DEVICE_ONLY_KEYS}
             self.model.check_status()          # (the copies above synchronised the stream) a timed-out in-kernel wait = invalid rows: raise, write nothing
+            if self.pair is not None:
+                self._select_note(out)
             off = 0
             for e, lo, k in pieces:
                 sl = {n: (v[off:off + k] if torch.is_tensor(v) else v) for n, v in out.items()}
@@ -457,6 +499,8 @@ class POCOTester:
         # (frame, person, slot in that person's track), frame-major
         items = sorted((int(f), pid, k) for pid, tr in tracking_results.items() for k, f in enumerate(tr["frames"]))
         keys = ("pred_cam", "smpl_vertices", "pred_pose", "pred_shape", "smpl_joints3d", "smpl_joints2d", "var_pose")
+        if self.pair is not None:
+            keys += ("select", "select_score")
         store = {pid: {k: [None] * len(tr["frames"]) for k in keys} for pid, tr in tracking_results.items()}
         pend_batches, pend_meta, pend_dets = [], [], []
 
@@ -469,6 +513,8 @@ class POCOTester:
                 self._pseudo_offer(out, np.concatenate(pend_dets), list(pend_meta))
             host = {k: out[k].cpu().numpy() for k in keys}
             self.model.check_status()          # after the synchronising copies, before the rows are stored
+            if self.pair is not None:
+                self._select_note(out)
             for row, (pid, slot) in enumerate(pend_meta):
                 for k in keys:
                     store[pid][k][slot] = host[k][row]
@@ -498,6 +544,7 @@ class POCOTester:
         flush()
 
         stacked = {pid: {k: np.stack(v) for k, v in store[pid].items()} for pid in tracking_results}
+        self.select_summary()
         if raw:
             return stacked
         if getattr(self.args, "infill", None) is not None:
@@ -540,9 +587,17 @@ class POCOTester:
             from .smooth import smooth_pose
             verts, pose, j3d = smooth_pose(self.model, pose, betas, getattr(self.args, "min_cutoff", 0.004),
                                            getattr(self.args, "beta", 1.5))
-        var, var_global = postproc.video_uncert(st["var_pose"], self.backbone,
-                                                self.model_cfg.POCO.KINEMATIC_UNCERT)    # tester.py:416-419
+        extra = {}
+        if "select" in st:                      # --cfg2 / --ckpt2: var_global per row by the rule of the model chosen for the root
+            from .select import pair_uncert
+            var, var_global = pair_uncert(st["var_pose"], st["select"], self.pair.backbones, self.model_cfg.POCO.KINEMATIC_UNCERT,
+                                          clip=False)
+            extra = {"select": st["select"], "select_score": st["select_score"]}
+        else:
+            var, var_global = postproc.video_uncert(st["var_pose"], self.backbone,
+                                                    self.model_cfg.POCO.KINEMATIC_UNCERT)    # tester.py:416-419
         return {
+            **extra,
             "pred_cam": st["pred_cam"],
             "orig_cam": postproc.convert_crop_cam_to_orig_img(st["pred_cam"], bboxes, orig_width, orig_height),
             "verts": verts, "pose": pose, "betas": betas, "joints2d": tr.get("joints2d"),
@@ -696,6 +751,7 @@ class POCOTester:
             for w in writes:
                 w.result()                                      # re-raises a failed write
         dataset = self.pseudo_finish(lambda x: picked[x[0]][1], lambda x: x[1])   # imgname = the file name, person_id = detection index
+        self.select_summary()
         torch.cuda.synchronize()
         dt = time.time() - t0
         n_crops = int(sum(counts))
