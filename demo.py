@@ -49,6 +49,13 @@ whose global uncertainty (the reference's get_global_uncert of its own head) is 
 first's, a tie to the first; or with --select joint per joint rotation, shape, camera and 2-D joints following the root joint and
 the mixed rows re-posed.  Folder and video mode; the result gains select [n,24] and select_score [n,2].  Not with --gpus N > 1,
 --occlusion_map, --save_dataset or --save_segm.
+--tta VIEWS [--tta_weight uncert|uniform] (folder mode) regresses K views of every detection - VIEWS is a comma-separated list of
+'+'-joined flip, rot:<degrees>, scale:<factor>; the untransformed crop is always the first view - in one forward and fuses them per
+joint by the model's own uncertainty (poco_amd/tta.py, csrc/tta_fuse.hip).  With the flag every view, the base
+view included, is cut with the DATASET crop from the detection's box (centre (cx, cy), scale max(w, h) / 200: rounded centre and
+side, no byte rounding), not with the demo's crop.  Pose, betas, verts, joints3d and var / var_global are the fused ones; camera and
+2-D joints stay the base view's; the result gains tta_spread [n,24].  Not with video, directory or webcam mode, --cfg2,
+--occlusion_map, --save_dataset, --save_segm or --gpus N > 1.
 """
 import argparse
 import json
@@ -171,6 +178,14 @@ def parse_args(argv=None):
                         "root's model, mixed rows re-posed")
     p.add_argument("--select_scale", type=float, default=None,
                    help="with --cfg2 --ckpt2: multiplies the second model's uncertainty before the comparison (default 1.0)")
+    p.add_argument("--tta", type=str, default=None, metavar="VIEWS",
+                   help="folder mode: test-time augmentation: comma-separated views, each a '+'-joined set of flip, rot:<degrees>, "
+                        "scale:<factor> (at most 8 with the untransformed crop, which is always there); every view is cut with the "
+                        "dataset crop, all go through one forward and are fused per joint on the GPU; the result gains tta_spread; a forward "
+                        "takes the views of max(1, batch_size // K) crops, so with --batch_size below the K views the engine is built for "
+                        "a batch of K")
+    p.add_argument("--tta_weight", default=None, choices=["uncert", "uniform"],
+                   help="with --tta: weigh each view's joint by 1 / its uncertainty (default) or uniformly")
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
@@ -264,6 +279,14 @@ def _check_select(args) -> None:
         sys.exit(msg)
 
 
+def _check_tta(args) -> None:
+    """--tta / --tta_weight: refuse what cannot work before an engine is built."""
+    from poco_amd.tta import flag_error
+    msg = flag_error(args, "demo")
+    if msg:
+        sys.exit(msg)
+
+
 def _check_segm(args) -> None:
     """--save_segm: refuse video mode, a head without a segmentation mask, a body model without triangles and an unreadable
     --part_mapping before the engine is built."""
@@ -304,6 +327,7 @@ def main(args):
     if getattr(args, "save_video", False) and not (args.mode == "video" and render_enabled(args)):
         sys.exit("--save_video writes the rendered frames of video mode: it needs --mode video and --render")
     _check_select(args)
+    _check_tta(args)
     _check_occlusion(args)
     _check_dataset(args)
     _check_segm(args)

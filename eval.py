@@ -23,6 +23,13 @@ the selection between the two by their own uncertainty (demo.py's flags, DESIGN.
 and the selection, Oracle MPJPE / PA-MPJPE (per crop the better model: the bound no selection beats), the selection accuracy and the
 share of crops taken from model 2; the .npz holds the selection under the usual keys and gains the models' mpjpe / pampjpe / v2v as
 *_m1 / *_m2, select and select_score.  Not with --segm or --likelihood.
+--tta VIEWS [--tta_weight uncert|uniform] (with --crop dataset) regresses K views of every crop - VIEWS is a comma-separated list
+of '+'-joined flip, rot:<degrees>, scale:<factor>, e.g. flip,rot:-15,rot:15; the untransformed crop is always the first view - in
+one forward, takes every view's rotations back into the crop's frame and fuses them per joint, weighted by the model's own
+uncertainty or uniformly (poco_amd/tta.py, csrc/tta_fuse.hip).  Printed: the lines above for the base view and
+the fused result, and Corr(view spread, pose distance), the disagreement baseline a learnt uncertainty is compared against; the .npz
+holds the fused result under the usual keys and gains *_base, tta_spread [N,24] and tta_views.  Not with --aug_*, --augment, --cfg2,
+--segm or --likelihood.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -88,6 +95,13 @@ def parse_args(argv=None):
                         "each joint rotation from the model with the lower uncertainty of that joint, mixed rows re-posed")
     p.add_argument("--select_scale", type=float, default=None,
                    help="with --cfg2 --ckpt2: multiplies the second model's uncertainty before the comparison (default 1.0)")
+    p.add_argument("--tta", type=str, default=None, metavar="VIEWS",
+                   help="test-time augmentation: comma-separated views, each a '+'-joined set of flip, rot:<degrees>, scale:<factor> "
+                        "(e.g. flip,rot:-15,rot:15,flip+scale:1.1; at most 8 with the untransformed crop, which is always there); all "
+                        "views go through one forward and are fused per joint on the GPU (needs --crop dataset); a forward takes the views of "
+                        "max(1, batch_size // K) crops, so with --batch_size below the K views the engine is built for a batch of K")
+    p.add_argument("--tta_weight", default=None, choices=["uncert", "uniform"],
+                   help="with --tta: weigh each view's joint by 1 / its uncertainty (default) or uniformly")
     return p.parse_args(argv)
 
 
@@ -221,8 +235,17 @@ def check_select(args) -> None:
         sys.exit(msg)
 
 
+def check_tta(args) -> None:
+    """--tta / --tta_weight: refuse what cannot work before an engine is built."""
+    from poco_amd.tta import flag_error
+    msg = flag_error(args, "eval")
+    if msg:
+        sys.exit(msg)
+
+
 def main(args):
     check_select(args)
+    check_tta(args)
     check_dataset_file(args.dataset)
     aug = augmentation_spec(args)
     occ = occlusion_spec(args)
@@ -262,6 +285,10 @@ def main(args):
                                 uncert_threshold=getattr(args, "uncert_threshold", None), res=tester.model_cfg.DATASET.IMG_RES)
         except ValueError as e:
             sys.exit(str(e))
+    elif tester.tta is not None:
+        print(f"Test-time views: {tester.tta_text} ({tester.tta.weight} weights)")
+        res = evaluate.run_eval_tta(tester.tta, ds, J, batch_size=max(int(args.batch_size), 1),
+                                    kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
     elif tester.pair is not None:
         res = evaluate.run_eval_pair(tester.pair, ds, J, batch_size=max(int(args.batch_size), 1),
                                      kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
@@ -270,6 +297,8 @@ def main(args):
                                 kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
                                 likelihood=args.likelihood)
     lines = evaluate.pair_report_lines(res, tester.pair.mode) if tester.pair is not None else evaluate.report_lines(res)
+    if tester.tta is not None:
+        lines = evaluate.tta_report_lines(res)
     for line in (evaluate.likelihood_lines(res) if args.likelihood else []) + lines:
         print(line)
     if getattr(args, "segm", False):

@@ -1062,6 +1062,45 @@ int poco_op_select_regressor(const float* d_pose0, const float* d_var0, int kind
                              float* d_pose_out, float* d_var_out, unsigned char* d_choice, float* d_score, unsigned char* d_mixed,
                              int32_t* d_rows, int32_t* d_count, int max_blocks, void* stream);
 
+/* ---- test-time augmentation: fusing K views of a crop by their uncertainty -----------------------------------------------------------
+ * eval.py / demo.py --tta VIEWS [--tta_weight uncert|uniform]; csrc/tta_fuse.hip; poco_amd/tta.py; DESIGN.md section 26;
+ * tests/tta_np.py restates it in float64 numpy with plain loops.  No counterpart in the reference's code; the transforms it undoes
+ * are flip_pose and rot_aa (pocolib/utils/image_utils.py:236-247,269-278) in the order of pose_processing (base_dataset.py:253-262).
+ *
+ * poco_op_tta_fuse: K views of B crops, view-major: row k * B + b is view k of crop b.  d_pose [K*B,24,3,3], d_var [K*B,24] (the
+ *   raw var_pose), d_betas [K*B,10], all fp32, dense and caller-owned.  `views` (by value): K in 2..8 and per view flip (0 | 1) and
+ *   c, s = cos and sin of +rot degrees, formed by the host in float64 (rot = 0: exactly 1 and 0).  View 0 is the identity.
+ *   weight: 0 = uniform, 1 = uncertainty.
+ *   Per (b, j), in fp64, nothing fused, views in order:
+ *     js = flip_k ? SMPL_JOINTS_FLIP_PERM[j] : j;  R_k = pose[k,b,js];  flip: R_k[i][c] *= m_i m_c, m = (1,-1,-1);
+ *     j = 0 and (c_k, s_k) != (1, 0): R_k = Rz R_k, Rz = [[c,-s,0],[s,c,0],[0,0,1]] (after the un-flip);
+ *     v_k = var[k,b,js];  w_k = 1 (uniform) | 1 / ((double)v_k + 1e-9) (uncertainty);  w_k = 0 where v_k is not finite or is
+ *     negative or R_k holds a non-finite value (such a view enters no sum);
+ *     M = sum w_k R_k, W = sum w_k;  R' = argmax over SO(3) of tr(R^T M) (Horn's quaternion form, the largest eigenvector of a
+ *     symmetric 4x4 by cyclic Jacobi with the 10 fixed sweeps of csrc/eval_metrics.hip);
+ *     var' = (sum w_k v_k) / W;  spread = (sum_k w_k mean9((R_k - R')^2)) / W.
+ *     W = 0 (every view dropped): pose' and var' are the base view's words, bit for bit, and spread is NaN (0x7fc00000).
+ *   Per crop: betas' = (sum g_k betas_k) / sum g_k with g_k the joint-0 weight of view k; sum g_k = 0: the base view's words.
+ *   Outputs, fp32, each rounded once, every element written: d_pose_out [B,24,3,3], d_var_out [B,24], d_spread [B,24],
+ *   d_betas_out [B,10].
+ *   max_blocks: 0 = the default grid, > 0 bounds it; the result does not depend on it.
+ *   One launch on `stream` (one lane per (crop, joint), grid-stride); no allocation, no synchronisation, no atomics.
+ *   POCO_ERR_ARG before any GPU work: a null pointer, K outside 2..8, B outside 1..2^24, weight outside {0, 1}, a flip outside
+ *   {0, 1}, c or s not finite or |c^2 + s^2 - 1| > 1e-12, view 0 not the identity, an output that overlaps an input or another
+ *   output. */
+#define POCO_TTA_MAX_VIEWS 8
+typedef struct {
+  int32_t flip;       /* 0 | 1: the view was mirrored left-right                                                          */
+  int32_t pad_;
+  double c, s;        /* cos and sin of +rot degrees                                                                      */
+} poco_tta_view_t;
+typedef struct {
+  int64_t count;                                        /* views in use, 2 .. POCO_TTA_MAX_VIEWS; view 0 is the identity  */
+  poco_tta_view_t v[POCO_TTA_MAX_VIEWS];
+} poco_tta_views_t;                                     /* passed by value                                                */
+int poco_op_tta_fuse(const float* d_pose, const float* d_var, const float* d_betas, int B, poco_tta_views_t views, int weight,
+                     float* d_pose_out, float* d_var_out, float* d_spread, float* d_betas_out, int max_blocks, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

@@ -285,3 +285,18 @@ void launch_select_regressor(const float* pose0, const float* var0, int kind0, c
                              int kinematic, double thr, double scale, int mode, const SelectPayloads& payloads, float* pose_out,
                              float* var_out, unsigned char* choice, float* score, unsigned char* mixed, int* rows, int* count,
                              int max_blocks, hipStream_t s);
+
+// ---- test-time augmentation: fusing K views of a crop by their uncertainty (tta_fuse.hip) -------------------------------------
+// include/poco_hip.h poco_op_tta_fuse: K views of B crops, view-major (row k * B + b): pose [K*B,24,3,3], var [K*B,24], betas
+// [K*B,10] -> pose_out [B,24,3,3], var_out / spread [B,24], betas_out [B,10].  One lane per (crop, joint), dealt to at most
+// TTA_MAX_BLOCKS blocks of TTA_THREADS (max_blocks > 0: at most that many) by a grid-stride loop.
+constexpr int TTA_MAX_BLOCKS = 1024;
+constexpr int TTA_THREADS = 256;
+constexpr int TTA_MAX_VIEWS = 8;
+struct TtaViews {
+  int count;
+  int flip[TTA_MAX_VIEWS];
+  double c[TTA_MAX_VIEWS], s[TTA_MAX_VIEWS];
+};
+void launch_tta_fuse(const float* pose, const float* var, const float* betas, int B, const TtaViews& views, int weight, float* pose_out,
+                     float* var_out, float* spread, float* betas_out, int max_blocks, hipStream_t s);

@@ -1037,3 +1037,36 @@ extern "C" int poco_op_select_regressor(const float* d_pose0, const float* d_var
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- test-time augmentation: fusing K views of a crop (tta_fuse.hip) ------------------------------------------------------------
+extern "C" int poco_op_tta_fuse(const float* d_pose, const float* d_var, const float* d_betas, int B, poco_tta_views_t views, int weight,
+                                float* d_pose_out, float* d_var_out, float* d_spread, float* d_betas_out, int max_blocks, void* stream) {
+  const char* who = "poco_op_tta_fuse";
+  if (!d_pose || !d_var || !d_betas || !d_pose_out || !d_var_out || !d_spread || !d_betas_out)
+    return op_bad(who, "null pointer (pose, var, betas, pose_out, var_out, spread and betas_out are needed)");
+  if (views.count < 2 || views.count > POCO_TTA_MAX_VIEWS) return op_bad(who, "K must be in 2..8");
+  if (B < 1 || B > (1 << 24)) return op_bad(who, "B must be in 1..2^24");
+  if ((weight | 1) != 1) return op_bad(who, "weight must be 0 (uniform) or 1 (uncertainty)");
+  TtaViews tv{};
+  tv.count = (int)views.count;
+  for (int k = 0; k < tv.count; ++k) {
+    const poco_tta_view_t& v = views.v[k];
+    if ((v.flip | 1) != 1) return op_bad(who, "the flip of view " + std::to_string(k) + " must be 0 or 1");
+    if (!std::isfinite(v.c) || !std::isfinite(v.s) || !(std::fabs(v.c * v.c + v.s * v.s - 1.0) <= 1e-12))
+      return op_bad(who, "c and s of view " + std::to_string(k) + " must be the finite cos and sin of one angle (|c^2 + s^2 - 1| <= 1e-12)");
+    tv.flip[k] = v.flip; tv.c[k] = v.c; tv.s[k] = v.s;
+  }
+  if (tv.flip[0] != 0 || tv.c[0] != 1.0 || tv.s[0] != 0.0) return op_bad(who, "view 0 must be the identity (flip 0, c 1, s 0)");
+  // [begin, end) in bytes of the three inputs and the four outputs: no output may overlap an input or another output
+  const size_t K = (size_t)tv.count, n = (size_t)B;
+  const struct { const float* p; size_t floats; } buf[7] = {{d_pose, K * n * 216}, {d_var, K * n * 24}, {d_betas, K * n * 10},
+                                                            {d_pose_out, n * 216}, {d_var_out, n * 24}, {d_spread, n * 24}, {d_betas_out, n * 10}};
+  for (int o = 3; o < 7; ++o)
+    for (int i = 0; i < o; ++i) {
+      const uintptr_t a0 = (uintptr_t)buf[o].p, a1 = a0 + 4 * buf[o].floats, b0 = (uintptr_t)buf[i].p, b1 = b0 + 4 * buf[i].floats;
+      if (a0 < b1 && b0 < a1) return op_bad(who, "an output may not overlap an input or another output");
+    }
+  launch_tta_fuse(d_pose, d_var, d_betas, B, tv, weight, d_pose_out, d_var_out, d_spread, d_betas_out, max_blocks, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

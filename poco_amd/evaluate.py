@@ -493,6 +493,77 @@ def pair_report_lines(res: Dict[str, object], mode: str = "crop"):
                     f"Selection accuracy: {res['select_accuracy']}", f"Crops from model 2: {res['select_share_m2']}"]
 
 
+TTA_SCALARS = tuple(k + "_base" for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")) + ("val_corr_spread",)
+TTA_OUTPUT_KEYS = ("pred_pose", "var_pose", "pred_shape", "smpl_vertices", "smpl_joints3d", "smpl_joints2d", "pred_cam")
+
+
+@torch.no_grad()
+def run_eval_tta(tta_model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
+                 sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_outputs: bool = False) -> Dict[str, object]:
+    """run_eval with test-time views (eval.py --tta, DESIGN.md section 26): per batch of b = max(1, batch_size // K) crops the K * b
+    views are cut in one launch (tta.dataset_batch), TTAModel.forward_all regresses and fuses them, and three Evaluators are
+    stepped against the base frame's ground truth on the same stream: the base view, the fused result, and the fused result with
+    var_pose := tta_spread and kinematic off, whose correlation is Corr(view spread, pose distance).  Nothing goes to the host
+    between the forward and the three finish() calls.  Returns the fused result under run_eval's keys, the base view's mpjpe /
+    pampjpe / v2v and val_* with suffix _base, val_corr_spread, tta_spread [N,24] and tta_views [K,3] (flip, rot, scale).
+    return_outputs (tests): also `outputs` = per batch (the K per-view dicts, the fused dict) of host arrays."""
+    from . import ops, tta
+    if dataset.crop != "dataset":
+        raise ValueError("run_eval_tta cuts its views with the dataset crop: the dataset needs crop='dataset'")
+    if dataset.occlude is not None or dataset.augment.random or np.any(dataset.aug_flip) or np.any(dataset.aug_rot) or np.any(dataset.aug_scale != 1) \
+            or np.any(dataset.aug_pn != 1):
+        raise ValueError("run_eval_tta makes its own views of the unperturbed crop: the dataset may carry no augmentation")
+    dev, n, views = tta_model.device, len(dataset), tta_model.views
+    b = max(1, min(int(batch_size) // len(views), tta_model.max_batch))
+    kw = dict(capacity=n, sel_uncert_part=sel_uncert_part, device=dev)
+    evs = [Evaluator(J_regressor, joint_map(dataset.name), kinematic=kinematic, **kw), Evaluator(J_regressor, joint_map(dataset.name), kinematic=kinematic, **kw),
+           Evaluator(J_regressor, joint_map(dataset.name), kinematic=False, **kw)]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+    spread = torch.zeros(n, 24, dtype=torch.float32, device=dev)
+    outputs = []
+    for lo in range(0, n, b):
+        hi = min(lo + b, n)
+        per_view, fused = tta_model.forward_all(tta.dataset_batch(dataset, lo, hi, views, dev))
+        spread[lo:hi].copy_(fused["tta_spread"])
+        gt_pose = t(dataset.pose[lo:hi])
+        if dataset.gt_form == "smpl":
+            gt = {"gt_vertices": tta_model.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))[0]}
+        else:
+            gt = {"gt_joints": t(dataset.joints[lo:hi])}
+        by_spread = dict(fused)
+        by_spread["var_pose"] = fused["tta_spread"]
+        for ev, out in zip(evs, (per_view[0], fused, by_spread)):
+            ev.step(out, gt_pose, **gt)
+        if return_outputs:
+            host = lambda d: {k: d[k].cpu().numpy() for k in TTA_OUTPUT_KEYS + ("tta_spread",) if k in d}   # noqa: E731
+            outputs.append(([host(v) for v in per_view], host(fused)))
+    base = evs[0].finish()
+    by_spread = evs[2].finish()
+    res = evs[1].finish(save_results=save_results)
+    res.update({k + "_base": base[k] for k in ("mpjpe", "pampjpe", "v2v", "val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")})
+    res["val_corr_spread"] = by_spread["val_corr"]
+    res["tta_spread"] = spread.cpu().numpy()
+    res["tta_views"] = np.asarray([[float(v.flip), float(v.rot), float(v.scale)] for v in views], np.float64)
+    res["tta_weight"] = tta_model.weight
+    if return_outputs:
+        res["outputs"] = outputs
+    tta_model.check_status()
+    res["imgname"] = np.asarray(dataset.imgname)
+    for ev in evs:
+        ev.close()
+    return res
+
+
+def tta_report_lines(res: Dict[str, object]):
+    """The reference's lines for the base view and the fused result, then the correlation between the views' spread and the pose
+    distance - the baseline a learnt uncertainty is compared against."""
+    lines = [f"Base view MPJPE: {res['val_mpjpe_base']}", f"Base view PA-MPJPE: {res['val_pampjpe_base']}",
+             f"Base view V2V (mm): {res['val_v2v_base']}", f"Base view Uncert Error Correlation: {res['val_corr_base']}"]
+    label = f"Fused ({res['tta_weight']}, {len(res['tta_views'])} views)"
+    lines += [f"{label} {line}" for line in report_lines(res)]
+    return lines + [f"Corr(view spread, pose distance): {res['val_corr_spread']}"]
+
+
 def check_occlusion_keys(files) -> None:
     """Synthetic occluders are centred on the ground-truth 2-D keypoints: refuse a dataset file without `part` or with ready-made
     `img` crops (ValueError)."""
@@ -543,5 +614,6 @@ def save_npz(path: str, res: Dict[str, object], dataset_name: str) -> None:
     keep.update({k: np.float64(res[k]) for k in ("val_nll", "val_log_phi", "val_log_sigma", "val_mpjpe_var", "val_var") if k in res})
     pair = PAIR_SCALARS + tuple(k + tag for tag in ("_m1", "_m2") for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr"))
     keep.update({k: np.float64(res[k]) for k in pair if k in res})           # eval.py --cfg2 --ckpt2 (run_eval_pair)
+    keep.update({k: np.float64(res[k]) for k in TTA_SCALARS if k in res})        # eval.py --tta (run_eval_tta)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     np.savez(path, **keep)

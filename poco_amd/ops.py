@@ -621,6 +621,84 @@ def select_regressor(pose0: torch.Tensor, var0: torch.Tensor, kind0: int, pose1:
     return out
 
 
+# ---- test-time augmentation: fusing K views of a crop (include/poco_hip.h; poco_amd/tta.py is the user's side) ---------------------
+TTA_MAX_VIEWS = 8
+TTA_WEIGHTS = {"uniform": 0, "uncert": 1}
+
+
+class _TtaView(C.Structure):
+    _fields_ = [("flip", C.c_int32), ("pad_", C.c_int32), ("c", C.c_double), ("s", C.c_double)]
+
+
+class _TtaViews(C.Structure):
+    _fields_ = [("count", C.c_int64), ("v", _TtaView * TTA_MAX_VIEWS)]
+
+
+TTA_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _TtaViews, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+
+
+def tta_view_cs(rot: float):
+    """(cos, sin) of +rot degrees in float64, exact at the quarter turns: rot = 0 gives (1.0, 0.0).  tests/tta_np.view_cs restates this
+    on purpose instead of importing it; what pins both is the comparison with cos / sin of pi / 12 in tests/test_tta_cpu.py."""
+    import math
+    q, r = divmod(float(rot), 90.0)
+    if r == 0.0:
+        return ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(q) % 4]
+    a = math.radians(float(rot))
+    return math.cos(a), math.sin(a)
+
+
+def tta_views(views):
+    """The by-value view table of poco_op_tta_fuse from [(flip, c, s), ...]; more than TTA_MAX_VIEWS entries keep their count (the
+    entry refuses it) but only the first eight are stored."""
+    d = _TtaViews()
+    d.count = len(views)
+    for k, (f, c, s) in enumerate(views[:TTA_MAX_VIEWS]):
+        d.v[k] = _TtaView(int(f), 0, float(c), float(s))
+    return d
+
+
+def tta_fuse(pose: torch.Tensor, var: torch.Tensor, betas: torch.Tensor, views, weight="uncert", *, out=None, max_blocks: int = 0) -> dict:
+    """poco_op_tta_fuse on device tensors: K views of B crops, view-major (row k * B + b): pose [K*B,24,3,3], var [K*B,24] (the raw
+    var_pose), betas [K*B,10], fp32 and contiguous; views = [(flip, rot degrees), ...] with view 0 = (0, 0); weight "uncert" |
+    "uniform" (or 1 | 0) -> dict(pose [B,24,3,3], var [B,24], spread [B,24], betas [B,10]).  out = a dict with the same keys:
+    contiguous tensors to write into (tests: views into guarded buffers).  max_blocks > 0 bounds the grid (the result does not
+    depend on it).  Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"tta_fuse: {what}")
+    for name, t in (("pose", pose), ("var", var), ("betas", betas)):
+        need(torch.is_tensor(t) and t.is_cuda, f"{name} must be a CUDA tensor")
+        need(t.dtype == torch.float32 and t.is_contiguous(), f"{name} must be contiguous float32, got {t.dtype}")
+    views = list(views)
+    K = len(views)
+    need(2 <= K <= TTA_MAX_VIEWS, f"2 to {TTA_MAX_VIEWS} views are needed, got {K}")
+    need(all(len(v) == 2 and v[0] in (0, 1, False, True) and np.isfinite(float(v[1])) for v in views), "a view is (flip 0 | 1, rot in finite degrees)")
+    need(int(views[0][0]) == 0 and float(views[0][1]) == 0.0, "view 0 must be the identity (flip 0, rot 0)")
+    need(pose.dim() == 4 and tuple(pose.shape[1:]) == (24, 3, 3) and pose.shape[0] >= K and pose.shape[0] % K == 0,
+         f"pose must be [K*B,24,3,3] with K = {K}, got {tuple(pose.shape)}")
+    B = int(pose.shape[0]) // K
+    need(tuple(var.shape) == (K * B, 24), f"var must be [{K * B},24] (SIGMA_DIM 1), got {tuple(var.shape)}")
+    need(tuple(betas.shape) == (K * B, 10), f"betas must be [{K * B},10], got {tuple(betas.shape)}")
+    weight = TTA_WEIGHTS.get(weight, weight)
+    need(weight in (0, 1), "weight must be 'uncert' or 'uniform'")
+    dev = pose.device
+    shapes = {"pose": (B, 24, 3, 3), "var": (B, 24), "spread": (B, 24), "betas": (B, 10)}
+    if out is None:
+        out = {k: torch.empty(s, device=dev, dtype=torch.float32) for k, s in shapes.items()}
+    for key, shp in shapes.items():
+        t = out.get(key)
+        need(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == torch.float32,
+             f"out[{key!r}] must be a contiguous CUDA float32 {shp}")
+    p = lambda t: t.data_ptr()                                                # noqa: E731
+    fn = lib().poco_op_tta_fuse
+    fn.argtypes = TTA_ARGTYPES
+    with torch.cuda.device(dev):
+        check(fn(p(pose), p(var), p(betas), B, tta_views([(int(f), *tta_view_cs(r)) for f, r in views]), int(weight), p(out["pose"]),
+                 p(out["var"]), p(out["spread"]), p(out["betas"]), int(max_blocks), current_stream()), "poco_op_tta_fuse")
+    return out
+
+
 # ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
 # Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
 # that the caller can check `untouched`.

@@ -74,6 +74,7 @@ def crop_keypoints(joints2d, box, res: int = 224, bbox_scale: float = 1.0) -> np
 class POCOTester:
     _pseudo = None                      # --save_dataset: the device-side labeler of the current run (pseudo_begin), else None
     pair = None                         # --cfg2 / --ckpt2: the RegressorPair that stands where self.model is used for forwards, else None
+    tta = None                          # --tta: the TTAModel that stands where self.model is used for forwards, else None
 
     def __init__(self, args):
         self.args = args
@@ -86,7 +87,15 @@ class POCOTester:
         ndev = max(torch.cuda.device_count(), 1)
         self.device = torch.device(f"cuda:{int(os.environ.get('LOCAL_RANK', '0')) % ndev}")
         torch.cuda.set_device(self.device)
-        self.model = self._build_engine(self.model_cfg, args.ckpt, getattr(args, "inf_model", "best"))
+        views = None
+        if getattr(args, "tta", None):
+            from . import tta
+            views = tta.parse_views(args.tta)
+        # --tta: a forward takes the K views of max(1, batch_size // K) crops, so the engine holds at least the K views of one crop
+        self.model = self._build_engine(self.model_cfg, args.ckpt, getattr(args, "inf_model", "best"), min_batch=len(views) if views else 1)
+        if views:
+            self.model = self.tta = tta.TTAModel(self.model, views, getattr(args, "tta_weight", None) or "uncert")
+            self.tta_text = tta.views_text(views)
         if getattr(args, "cfg2", None):
             from .select import RegressorPair
             cfg2 = update_hparams(args.cfg2)
@@ -107,9 +116,9 @@ class POCOTester:
         self._renderer = None
         self._pseudo_src = []                   # --save_dataset: the label of every crop offered to the labeler
 
-    def _build_engine(self, model_cfg, ckpt, inf_model):
+    def _build_engine(self, model_cfg, ckpt, inf_model, min_batch: int = 1):
         """One finalized engine for a config and a checkpoint, with this tester's --smpl, batch size and device."""
-        return POCO(**model_kwargs(model_cfg), pretrained=ckpt, inf_model=inf_model, max_batch=max(int(self.args.batch_size), 1),
+        return POCO(**model_kwargs(model_cfg), pretrained=ckpt, inf_model=inf_model, max_batch=max(int(self.args.batch_size), min_batch),
                     smpl=self.args.smpl, device=str(self.device),
                     keep_state_dict=False).finalize()     # (state_dict() re-reads the checkpoint file on demand)
 
@@ -369,6 +378,9 @@ class POCOTester:
 
     # ---- one batch of detections of one frame ---------------------------------------------------
     def make_batch(self, frame_u8: torch.Tensor, dets: np.ndarray, bbox_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+        if self.tta is not None:            # --tta: the K views of every detection, view-major, cut with the dataset crop from its box
+            from .tta import frame_batch
+            return frame_batch(frame_u8, dets, self.tta.views, self.model_cfg.DATASET.IMG_RES)
         H, W = int(frame_u8.shape[0]), int(frame_u8.shape[1])
         raw = np.asarray(dets)
         # the crop follows the detections' own dtype (float64 tracks stay float64: cv2 sees float32(cx) etc. of THOSE values)
@@ -399,6 +411,8 @@ class POCOTester:
                                                                self.model_cfg.POCO.KINEMATIC_UNCERT, clip=True)
             res["select"], res["select_score"] = sel, output["select_score"].cpu().numpy()
             return res
+        if "tta_spread" in output:                                                   # --tta: the views' disagreement per joint
+            res["tta_spread"] = output["tta_spread"].cpu().numpy()
         if "cliff" not in self.backbone:                                             # tester.py:225-230
             j2d = postproc.convert_crop_coords_to_orig_img(dets, j2d, self.model_cfg.DATASET.IMG_RES)
         res["smpl_joints2d"] = np.concatenate([j2d, np.ones((len(dets), 49, 1), np.float32)], -1)
@@ -425,7 +439,11 @@ class POCOTester:
             nonlocal npend
             if not pieces:
                 return
-            batch = batches[0] if len(batches) == 1 else {k: torch.cat([b[k] for b in batches], 0) for k in batches[0]}
+            if self.tta is not None:           # view-major batches join per view
+                from .tta import cat_view_batches
+                batch = cat_view_batches(batches, self.tta.K)
+            else:
+                batch = batches[0] if len(batches) == 1 else {k: torch.cat([b[k] for b in batches], 0) for k in batches[0]}
             out = self.model(batch, want_segm=False)
             if self._pseudo is not None:       # --save_dataset: from the device outputs, before they are copied for the result files
                 self._pseudo_offer(out, np.concatenate([e["dets"][lo:lo + k] for e, lo, k in pieces]),
