@@ -30,6 +30,12 @@ uncertainty or uniformly (poco_amd/tta.py, csrc/tta_fuse.hip, DESIGN.md section 
 the fused result, and Corr(view spread, pose distance), the disagreement baseline a learnt uncertainty is compared against; the .npz
 holds the fused result under the usual keys and gains *_base, tta_spread [N,24] and tta_views.  Not with --aug_*, --augment, --cfg2,
 --segm or --likelihood.
+--rank_metrics [--rank_bins K] measures the uncertainty as a ranking, which is how --uncert_threshold, --infill and --select use it:
+the records are sorted by uncertainty on the GPU (csrc/rank_curve.hip, poco_amd/ranking.py) and Spearman's
+rho is printed beside Pearson's r, then AUSE / AURG (area of the sparsification curve against the oracle ranking / a random one) of
+MPJPE, PA-MPJPE, V2V and the pose distance, then per kept fraction the uncertainty threshold and the errors of the crops kept; the
+.npz gains rank_spars_*, rank_oracle_*, rank_reliab_*, rank_thresholds and rank_summary.  Not with --cfg2, --tta, --segm or
+--likelihood.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -102,6 +108,13 @@ def parse_args(argv=None):
                         "max(1, batch_size // K) crops, so with --batch_size below the K views the engine is built for a batch of K")
     p.add_argument("--tta_weight", default=None, choices=["uncert", "uniform"],
                    help="with --tta: weigh each view's joint by 1 / its uncertainty (default) or uniformly")
+    p.add_argument("--rank_metrics", action="store_true",
+                   help="also rank-based measures of the uncertainty, sorted and summed on the GPU (poco_amd/ranking.py): Spearman's rho "
+                        "beside Pearson's r, AUSE / AURG of MPJPE, PA-MPJPE, V2V and the pose distance, and the table of what "
+                        "--uncert_threshold keeps at what error; the .npz gains rank_spars_*, rank_oracle_*, rank_reliab_*, "
+                        "rank_thresholds and rank_summary")
+    p.add_argument("--rank_bins", type=int, default=None, metavar="K",
+                   help="with --rank_metrics: cuts of the sparsification curves = bins of the tables, 1..1024 (default 20)")
     return p.parse_args(argv)
 
 
@@ -230,7 +243,15 @@ def check_segm_inputs(args) -> None:
 def check_select(args) -> None:
     """--cfg2 / --ckpt2 / --select / --select_scale: refuse what cannot work before an engine is built."""
     from poco_amd.select import flag_error
-    msg = flag_error(args, ("segm", "likelihood"))
+    msg = flag_error(args, ("segm", "likelihood", "rank_metrics"))
+    if msg:
+        sys.exit(msg)
+
+
+def check_rank(args) -> None:
+    """--rank_metrics / --rank_bins: refuse what cannot work before an engine is built."""
+    from poco_amd.ranking import flag_error
+    msg = flag_error(args)
     if msg:
         sys.exit(msg)
 
@@ -246,6 +267,7 @@ def check_tta(args) -> None:
 def main(args):
     check_select(args)
     check_tta(args)
+    check_rank(args)
     check_dataset_file(args.dataset)
     aug = augmentation_spec(args)
     occ = occlusion_spec(args)
@@ -295,7 +317,8 @@ def main(args):
     else:
         res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
                                 kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
-                                likelihood=args.likelihood)
+                                likelihood=args.likelihood,
+                                rank_metrics=(args.rank_bins or 20) if getattr(args, "rank_metrics", False) else None)
     lines = evaluate.pair_report_lines(res, tester.pair.mode) if tester.pair is not None else evaluate.report_lines(res)
     if tester.tta is not None:
         lines = evaluate.tta_report_lines(res)
@@ -303,6 +326,9 @@ def main(args):
         print(line)
     if getattr(args, "segm", False):
         for line in segm.report_lines(res):
+            print(line)
+    if getattr(args, "rank_metrics", False):
+        for line in evaluate.rank_lines(res):
             print(line)
     if occ is not None:
         for line in evaluate.occlusion_lines(ds, res):

@@ -886,6 +886,18 @@ int poco_evaluator_finish(poco_evaluator_t e, double* h_summary8, float* h_recor
  * in fp64 from the stored fp32 fields, in metres (the reference does not scale these two by 1000).  One block, fixed order.
  * Synchronises `stream`.  No step yet is POCO_ERR_STATE. */
 int poco_evaluator_uncert_summary(poco_evaluator_t e, double* h_summary2, void* stream);
+/* Keys and value planes for poco_op_rank_curve from the N records written so far, which are only read; nothing leaves the device.
+ *   mode 0 (per crop):  n = N, E = 3.  d_key[i] = u_i of poco_evaluator_uncert_summary (the 24 stored values added in joint order
+ *                       in fp64, divided by 24, rounded once to fp32); d_vals = [MPJPE | PA-MPJPE | V2V] of the crop, [3][n], in
+ *                       the records' units (metres).
+ *   mode 1 (per joint): n = N * |sel|, E = 1.  d_key = the processed uncertainty and d_vals the pose distance of the selected
+ *                       joints, flattened crop-major (entry i * |sel| + k = selected joint k of crop i): the corr_y / corr_x of
+ *                       poco_evaluator_finish's records.
+ * d_key holds `cap` floats and d_vals E planes of n floats, dense; *h_n and *h_E (host) are written before the call returns.
+ * One launch on `stream`, no synchronisation.  POCO_ERR_ARG: a null pointer, a mode outside {0, 1}, cap < n (then *h_n and *h_E
+ * are still written, so that the caller learns the size).  No step yet is POCO_ERR_STATE. */
+int poco_evaluator_rank_inputs(poco_evaluator_t e, int mode, float* d_key, float* d_vals, int64_t cap, int64_t* h_n, int* h_E,
+                               void* stream);
 /* Rewind: the next step writes record 0. */
 int poco_evaluator_reset(poco_evaluator_t e);
 void poco_evaluator_destroy(poco_evaluator_t e);
@@ -1100,6 +1112,42 @@ typedef struct {
 } poco_tta_views_t;                                     /* passed by value                                                */
 int poco_op_tta_fuse(const float* d_pose, const float* d_var, const float* d_betas, int B, poco_tta_views_t views, int weight,
                      float* d_pose_out, float* d_var_out, float* d_spread, float* d_betas_out, int max_blocks, void* stream);
+
+/* ---- rank-based uncertainty metrics: stable key sort, midranks, fp64 sums at K + 1 cuts ------------------------------------------------
+ * eval.py --rank_metrics [--rank_bins K]; csrc/rank_curve.hip; poco_amd/ranking.py; tests/rank_np.py restates
+ * it in float64 with plain loops.  No counterpart in the reference's code, which reports Pearson's r only (trainer.py:380).
+ *
+ * poco_op_rank_curve: n keys (fp32) and E value planes d_vals [E][n] (fp32; NULL if E = 0), dense, caller-owned, on the device.
+ *   A key is canonicalised first: -0.0 becomes +0.0 and every NaN becomes 0x7fc00000, so NaN sorts last; its order-preserving
+ *   uint32 image is ~bits for a negative key and bits | 0x80000000 otherwise.
+ *   d_order [n] int32 = the stable ascending order of the canonical keys: numpy.argsort(key, kind="stable").  Least-significant-
+ *     digit radix sort, 4 passes of 8 bits, row index as payload, tiles of POCO_RANK_TILE rows.
+ *   d_rank [n] fp64 = the 1-based midrank of row i: rows with equal canonical keys share the mean of their sorted positions
+ *     (scipy.stats.rankdata(method="average")).
+ *   d_cuts [E + 1][K + 1] fp64: cuts[e][k] = the sum of plane e over the sorted positions [0, c_k), c_k = floor(k n / K) in 64-bit
+ *     integers.  Plane 0 = the canonical key widened to fp64, plane e >= 1 = d_vals[e - 1].  prefix(c) = (scan of the totals of the
+ *     tiles before tile c / T) + (strided per-lane sums and a halving tree over the first c % T rows of that tile): the summation
+ *     tree is a function of c and n alone.  fp64 additions only, no floating-point atomics.
+ *   d_cut_keys [K + 1] fp32: the canonical sorted key at position max(c_k, 1) - 1 = the threshold that keeps the first c_k rows.
+ *   d_scratch: at least poco_op_rank_curve_scratch_bytes(n, E) bytes (0 = n or E out of range), 8-byte aligned; its contents
+ *     before and after the call mean nothing.
+ *   max_blocks: 0 = the default grid, > 0 bounds it.  All four outputs are bitwise independent of it and equal from run to run.
+ *   16 launches on `stream`; no allocation, no synchronisation, the inputs are only read.
+ *   POCO_ERR_ARG before any GPU work: a null pointer, n outside 1..2^24, E outside 0..4, K outside 1..1024, max_blocks < 0, a
+ *   scratch buffer that is too small, misaligned buffers, scratch or outputs that overlap an input or each other.
+ *
+ * poco_op_pearson64: d_r[0] = Pearson's r of the fp64 device arrays d_x and d_y [n], n in 1..2^24: means first, then the three
+ *   centred sums and one division, clipped to [-1, 1] as poco_evaluator_finish clips; NaN if every element of either array equals
+ *   its first.  One block of 1024 lanes in a fixed order, so the result cannot depend on max_blocks (>= 0, accepted so that the
+ *   call reads like its neighbours).  Spearman's rho = poco_op_pearson64 of two d_rank arrays.  One launch on `stream`. */
+#define POCO_RANK_TILE 2048
+#define POCO_RANK_MAX_N (1 << 24)
+#define POCO_RANK_MAX_PLANES 4
+#define POCO_RANK_MAX_CUTS 1024
+size_t poco_op_rank_curve_scratch_bytes(int64_t n, int E);
+int poco_op_rank_curve(const float* d_key, const float* d_vals, int64_t n, int E, int K, void* d_scratch, size_t scratch_bytes,
+                       int32_t* d_order, double* d_rank, double* d_cuts, float* d_cut_keys, int max_blocks, void* stream);
+int poco_op_pearson64(const double* d_x, const double* d_y, int64_t n, double* d_r, int max_blocks, void* stream);
 
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /

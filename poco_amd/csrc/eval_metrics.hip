@@ -342,6 +342,28 @@ __global__ __launch_bounds__(EV_FIN_THREADS) void eval_finish(EvalDev d, long lo
   }
 }
 
+// poco_evaluator_rank_inputs: keys and value planes for poco_op_rank_curve from the records, one lane per output row.
+// mode 0: row = crop, key = u_i as eval_uncert_summary_kernel forms it, planes MPJPE | PA-MPJPE | V2V.
+// mode 1: row = crop * nsel + k, key = the processed uncertainty, plane = the pose distance of selected joint k.
+__global__ __launch_bounds__(256) void eval_rank_inputs(EvalDev d, int mode, long long rows, float* __restrict__ key, float* __restrict__ vals) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows) return;
+  if (mode == 0) {
+    const float* r = d.rec + (size_t)i * EV_REC;
+    double m = 0.0;
+    for (int j = 0; j < 24; ++j) m += (double)r[R_UNC + j];
+    m /= 24.0;
+    key[i] = (float)m;
+    vals[i] = r[R_MPJPE]; vals[rows + i] = r[R_PA]; vals[2 * rows + i] = r[R_V2V];
+  } else {
+    const long long crop = i / d.nsel;
+    const int j = d.sel[(int)(i % d.nsel)];
+    const float* r = d.rec + (size_t)crop * EV_REC;
+    key[i] = r[R_UNC + j];
+    vals[i] = r[R_POSE + j];
+  }
+}
+
 }  // namespace
 
 extern "C" int poco_op_rodrigues(const float* d_axis_angle, float* d_rotmat, int N, void* stream) {
@@ -499,6 +521,26 @@ extern "C" int poco_evaluator_uncert_summary(poco_evaluator_t e, double* h_summa
   POCO_HIP_CHECK(hipGetLastError());
   POCO_HIP_CHECK(hipMemcpyAsync(h_summary2, e->d_summary + 8, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   POCO_HIP_CHECK(hipStreamSynchronize(s));
+  return POCO_OK;
+}
+
+extern "C" int poco_evaluator_rank_inputs(poco_evaluator_t e, int mode, float* d_key, float* d_vals, int64_t cap, int64_t* h_n, int* h_E,
+                                          void* stream) {
+  if (!e || !d_key || !d_vals || !h_n || !h_E || (mode | 1) != 1) {
+    poco_set_error("poco_evaluator_rank_inputs: bad arguments (need a handle, key, vals, n and E, and mode 0 or 1)");
+    return POCO_ERR_ARG;
+  }
+  if (e->first < 1) { poco_set_error("poco_evaluator_rank_inputs: no crop has been stepped"); return POCO_ERR_STATE; }
+  const long long rows = mode == 0 ? e->first : e->first * (long long)e->sel.size();
+  *h_n = rows;
+  *h_E = mode == 0 ? 3 : 1;
+  if (cap < rows) {
+    poco_set_error("poco_evaluator_rank_inputs: " + std::to_string(rows) + " rows do not fit a capacity of " + std::to_string(cap));
+    return POCO_ERR_ARG;
+  }
+  if (int rc = evaluator_upload(e)) return rc;
+  eval_rank_inputs<<<(unsigned)((rows + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->dev(), mode, rows, d_key, d_vals);
+  POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
 

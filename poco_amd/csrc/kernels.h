@@ -300,3 +300,20 @@ struct TtaViews {
 };
 void launch_tta_fuse(const float* pose, const float* var, const float* betas, int B, const TtaViews& views, int weight, float* pose_out,
                      float* var_out, float* spread, float* betas_out, int max_blocks, hipStream_t s);
+
+// ---- rank-based uncertainty metrics: stable key sort, midranks, fp64 cut sums (rank_curve.hip) ------------------------------------
+// include/poco_hip.h poco_op_rank_curve / poco_op_pearson64: key [n], vals [E][n] -> order int32 [n], rank fp64 [n], cuts fp64
+// [E+1][K+1], cut_keys [K+1].  Tiles of RANK_TILE positions are dealt to at most RANK_MAX_BLOCKS blocks of RANK_THREADS (max_blocks
+// > 0: at most that many) by a grid-stride loop.  The scratch buffer is the caller's: rank_scratch_layout gives the byte offset of
+// every part of it (each a multiple of 256) and the total.
+constexpr int RANK_TILE = 2048;
+constexpr int RANK_THREADS = 256;
+constexpr int RANK_MAX_BLOCKS = 1024;
+struct RankScratch {
+  int NT;                                                  // tiles
+  size_t key_a, key_b, order_a, hist, totals, last_head, first_end, fwd, bwd, tsum, tprefix, bytes;
+};
+RankScratch rank_scratch_layout(long long n, int E);
+void launch_rank_curve(const float* key, const float* vals, long long n, int E, int K, void* scratch, int32_t* order, double* rank,
+                       double* cuts, float* cut_keys, int max_blocks, hipStream_t s);
+void launch_pearson64(const double* x, const double* y, long long n, double* r, hipStream_t s);

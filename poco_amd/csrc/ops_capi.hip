@@ -1070,3 +1070,57 @@ extern "C" int poco_op_tta_fuse(const float* d_pose, const float* d_var, const f
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- rank-based uncertainty metrics: sort, midranks, cut sums (rank_curve.hip) ---------------------------------------------------
+static_assert(POCO_RANK_TILE == RANK_TILE, "include/poco_hip.h and csrc/kernels.h disagree on the sort's tile");
+static bool rank_shape_ok(int64_t n, int E) { return n >= 1 && n <= POCO_RANK_MAX_N && E >= 0 && E <= POCO_RANK_MAX_PLANES; }
+
+extern "C" size_t poco_op_rank_curve_scratch_bytes(int64_t n, int E) {
+  return rank_shape_ok(n, E) ? rank_scratch_layout(n, E).bytes : 0;
+}
+
+extern "C" int poco_op_rank_curve(const float* d_key, const float* d_vals, int64_t n, int E, int K, void* d_scratch, size_t scratch_bytes,
+                                  int32_t* d_order, double* d_rank, double* d_cuts, float* d_cut_keys, int max_blocks, void* stream) {
+  const char* who = "poco_op_rank_curve";
+  if (!rank_shape_ok(n, E)) return op_bad(who, "n must be in 1..2^24 and E in 0..4");
+  if (K < 1 || K > POCO_RANK_MAX_CUTS) return op_bad(who, "K must be in 1..1024");
+  if (max_blocks < 0) return op_bad(who, "max_blocks must be >= 0");
+  if (!d_key || !d_scratch || !d_order || !d_rank || !d_cuts || !d_cut_keys || (E > 0 && !d_vals))
+    return op_bad(who, "null pointer (key, scratch, order, rank, cuts and cut_keys are needed, and vals if E > 0)");
+  if (!aligned_to(d_scratch, 8) || !aligned_to(d_rank, 8) || !aligned_to(d_cuts, 8) || !aligned_to(d_key, 4) || !aligned_to(d_order, 4) ||
+      !aligned_to(d_cut_keys, 4) || (E > 0 && !aligned_to(d_vals, 4)))
+    return op_bad(who, "scratch, rank and cuts must be 8-byte aligned, the fp32 and int32 buffers 4-byte aligned");
+  const size_t need = rank_scratch_layout(n, E).bytes;
+  if (scratch_bytes < need)
+    return op_bad(who, "the scratch buffer holds " + std::to_string(scratch_bytes) + " bytes, poco_op_rank_curve_scratch_bytes asks for " +
+                           std::to_string(need));
+  // [begin, end) in bytes: the two inputs, then the scratch and the four outputs, none of which may overlap anything before it
+  const size_t N = (size_t)n, cuts = (size_t)K + 1;
+  const struct { const void* p; size_t bytes; } buf[7] = {{d_key, N * 4}, {d_vals, (size_t)E * N * 4}, {d_scratch, need}, {d_order, N * 4},
+                                                          {d_rank, N * 8}, {d_cuts, ((size_t)E + 1) * cuts * 8}, {d_cut_keys, cuts * 4}};
+  for (int o = 2; o < 7; ++o)
+    for (int i = 0; i < o; ++i) {
+      if (!buf[i].bytes) continue;
+      const uintptr_t a0 = (uintptr_t)buf[o].p, a1 = a0 + buf[o].bytes, b0 = (uintptr_t)buf[i].p, b1 = b0 + buf[i].bytes;
+      if (a0 < b1 && b0 < a1) return op_bad(who, "the scratch and the outputs may not overlap an input or each other");
+    }
+  launch_rank_curve(d_key, d_vals, n, E, K, d_scratch, d_order, d_rank, d_cuts, d_cut_keys, max_blocks, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_op_pearson64(const double* d_x, const double* d_y, int64_t n, double* d_r, int max_blocks, void* stream) {
+  const char* who = "poco_op_pearson64";
+  if (!d_x || !d_y || !d_r) return op_bad(who, "null pointer (x, y and r are needed)");
+  if (n < 1 || n > POCO_RANK_MAX_N) return op_bad(who, "n must be in 1..2^24");
+  if (max_blocks < 0) return op_bad(who, "max_blocks must be >= 0");
+  if (!aligned_to(d_x, 8) || !aligned_to(d_y, 8) || !aligned_to(d_r, 8)) return op_bad(who, "x, y and r must be 8-byte aligned");
+  const uintptr_t r0 = (uintptr_t)d_r, r1 = r0 + 8;
+  for (const double* in : {d_x, d_y}) {
+    const uintptr_t b0 = (uintptr_t)in, b1 = b0 + (size_t)n * 8;
+    if (r0 < b1 && b0 < r1) return op_bad(who, "r may not overlap an input");
+  }
+  launch_pearson64(d_x, d_y, n, d_r, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

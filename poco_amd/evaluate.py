@@ -41,6 +41,8 @@ def _bind():
     L.poco_evaluator_step.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
     L.poco_evaluator_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.poco_evaluator_uncert_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.poco_evaluator_rank_inputs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int), C.c_void_p]
     L.poco_evaluator_reset.argtypes = [C.c_void_p]
     L.poco_evaluator_destroy.argtypes = [C.c_void_p]
     L.poco_evaluator_destroy.restype = None
@@ -133,6 +135,24 @@ class Evaluator:
             check(_bind().poco_evaluator_uncert_summary(self._h, summ.ctypes.data, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
                   "poco_evaluator_uncert_summary")
         return {"val_mpjpe_var": float(summ[0]), "val_var": float(summ[1])}
+
+    def rank_inputs(self, mode: int):
+        """Keys and value planes for ops.rank_curve from the records written so far, as device tensors (key [n], vals [E,n]); the
+        records are only read and nothing goes to the host.  mode 0 = per crop: key = the mean of the crop's 24 processed
+        uncertainties (the u_i of uncert_summary), vals = MPJPE, PA-MPJPE, V2V.  mode 1 = per selected joint, crop-major: key =
+        corr_y, vals = corr_x of finish().  Enqueued on the current stream."""
+        if mode not in (0, 1):
+            raise PocoHipError("Evaluator.rank_inputs: mode must be 0 (per crop) or 1 (per joint)")
+        n, E = (self.count, 3) if mode == 0 else (self.count * int(self.sel.size), 1)
+        key = torch.empty(max(n, 1), device=self.device, dtype=torch.float32)
+        vals = torch.empty((E, max(n, 1)), device=self.device, dtype=torch.float32)
+        hn, hE = C.c_int64(0), C.c_int(0)
+        with torch.cuda.device(self.device):
+            check(_bind().poco_evaluator_rank_inputs(self._h, int(mode), key.data_ptr(), vals.data_ptr(), n, C.byref(hn), C.byref(hE),
+                                                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                  "poco_evaluator_rank_inputs")
+        assert (hn.value, hE.value) == (n, E), (hn.value, hE.value, n, E)
+        return key, vals
 
     def finish(self, save_results: bool = False, return_records: bool = False) -> Dict[str, object]:
         """Summary under the reference's log names (trainer.py:397-403) plus the per-sample arrays of
@@ -387,12 +407,14 @@ class EvalDataset:
 @torch.no_grad()
 def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
              sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_records: bool = False,
-             likelihood: bool = False) -> Dict[str, object]:
+             likelihood: bool = False, rank_metrics: Optional[int] = None) -> Dict[str, object]:
     """trainer.py:298-336 over a whole dataset: forward, then the metrics of every batch (the ragged last one included) on the
     device.  SMPL ground truth: gt_vertices = POCO.smpl_lbs(shape, poco_op_rodrigues(pose)) (base_dataset.py:353-366, neutral
     model), also on the device.  Returns Evaluator.finish() plus `imgname`.  likelihood=True (needs `pose` in the dataset and
     cond_layer in the checkpoint): also the held-out flow NLL of every batch on the same stream (LikelihoodAccumulator: val_nll,
-    val_log_phi, val_log_sigma, log_phi / log_sigma / bar_pose [N,24]) and Evaluator.uncert_summary() (val_mpjpe_var, val_var)."""
+    val_log_phi, val_log_sigma, log_phi / log_sigma / bar_pose [N,24]) and Evaluator.uncert_summary() (val_mpjpe_var, val_var).
+    rank_metrics=K (eval.py --rank_metrics --rank_bins K): also ranking.RankMetrics of the records with K cuts - the
+    ranking.RANK_NPZ_KEYS arrays; everything else is what it is without the argument."""
     from . import ops
     dev = model.device
     ev = Evaluator(J_regressor, joint_map(dataset.name), capacity=len(dataset), sel_uncert_part=sel_uncert_part, kinematic=kinematic,
@@ -416,6 +438,9 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
     if lk is not None:
         res.update(ev.uncert_summary())
         res.update(lk.finish())
+    if rank_metrics is not None:
+        from .ranking import RankMetrics
+        res.update(RankMetrics(ev, int(rank_metrics)).result)
     model.check_status()
     res["imgname"] = np.asarray(dataset.imgname)
     ev.close()
@@ -598,6 +623,12 @@ def report_lines(res: Dict[str, object]):
     """The lines of trainer.py:386-391 this port computes."""
     return [f"MPJPE: {res['val_mpjpe']}", f"PA-MPJPE: {res['val_pampjpe']}", f"V2V (mm): {res['val_v2v']}",
             f"Uncert Error Correlation: {res['val_corr']}", f"N: {res['N']}"]
+
+
+def rank_lines(res: Dict[str, object]):
+    """eval.py --rank_metrics: Spearman beside Pearson, AUSE / AURG of the four errors and the threshold table (ranking.rank_lines)."""
+    from .ranking import rank_lines as lines
+    return lines(res)
 
 
 def likelihood_lines(res: Dict[str, object]):

@@ -699,6 +699,81 @@ def tta_fuse(pose: torch.Tensor, var: torch.Tensor, betas: torch.Tensor, views, 
     return out
 
 
+# ---- rank-based uncertainty metrics: sort, midranks, cut sums (include/poco_hip.h; poco_amd/ranking.py is the user's side) ----------
+RANK_TILE = 2048                  # POCO_RANK_TILE: rows per tile of the sort (tests sit on its edges)
+RANK_MAX_N, RANK_MAX_PLANES, RANK_MAX_CUTS = 1 << 24, 4, 1024
+RANK_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+PEARSON64_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+
+
+def rank_curve_scratch_bytes(n: int, E: int) -> int:
+    """poco_op_rank_curve_scratch_bytes: the bytes of scratch poco_op_rank_curve needs for n rows and E planes (0: out of range)."""
+    fn = lib().poco_op_rank_curve_scratch_bytes
+    fn.argtypes, fn.restype = [C.c_int64, C.c_int], C.c_size_t
+    return int(fn(int(n), int(E)))
+
+
+def rank_curve(key: torch.Tensor, vals=None, K: int = 20, max_blocks: int = 0, *, out=None, scratch=None) -> dict:
+    """poco_op_rank_curve on device tensors: key [n] fp32 and vals [E,n] fp32 (None or E = 0: no planes) -> dict(order int32 [n] =
+    the stable argsort of the canonical keys, rank float64 [n] = 1-based midranks, cuts float64 [E+1,K+1] = sums of the key (plane 0)
+    and of each value plane over the first floor(k n / K) sorted rows, cut_keys fp32 [K+1]).  out = a dict with the same keys:
+    contiguous tensors to write into; scratch = a uint8 CUDA tensor of at least rank_curve_scratch_bytes(n, E) bytes (default: one
+    is allocated here, before the call).  max_blocks > 0 bounds the grid (the result does not depend on it).  Argument errors raise
+    PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"rank_curve: {what}")
+    need(torch.is_tensor(key) and key.is_cuda and key.dtype == torch.float32 and key.is_contiguous() and key.dim() == 1,
+         "key must be a contiguous float32 CUDA vector")
+    n = int(key.shape[0])
+    E = 0 if vals is None else int(vals.shape[0]) if torch.is_tensor(vals) and vals.dim() == 2 else -1
+    need(E >= 0, "vals must be None or [E,n]")
+    if E > 0:
+        need(vals.is_cuda and vals.dtype == torch.float32 and vals.is_contiguous() and int(vals.shape[1]) == n,
+             f"vals must be a contiguous float32 CUDA [E,{n}], got {tuple(vals.shape)} {vals.dtype}")
+    need(1 <= n <= RANK_MAX_N, f"n must be in 1..2^24, got {n}")
+    need(E <= RANK_MAX_PLANES, f"at most {RANK_MAX_PLANES} value planes, got {E}")
+    need(isinstance(K, (int, np.integer)) and 1 <= K <= RANK_MAX_CUTS, f"K must be in 1..{RANK_MAX_CUTS}, got {K}")
+    dev = key.device
+    shapes = {"order": ((n,), torch.int32), "rank": ((n,), torch.float64), "cuts": ((E + 1, K + 1), torch.float64),
+              "cut_keys": ((K + 1,), torch.float32)}
+    if out is None:
+        out = {k: torch.empty(s, device=dev, dtype=dt) for k, (s, dt) in shapes.items()}
+    for k, (shp, dt) in shapes.items():
+        t = out.get(k)
+        need(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt,
+             f"out[{k!r}] must be a contiguous CUDA {dt} {shp}")
+    nbytes = rank_curve_scratch_bytes(n, E)
+    if scratch is None:
+        scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    need(torch.is_tensor(scratch) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous(),
+         "scratch must be a contiguous uint8 CUDA tensor")
+    p = lambda t: t.data_ptr()                                                # noqa: E731
+    fn = lib().poco_op_rank_curve
+    fn.argtypes = RANK_ARGTYPES
+    with torch.cuda.device(dev):
+        check(fn(p(key), p(vals) if E > 0 else None, n, E, int(K), p(scratch), int(scratch.numel()), p(out["order"]), p(out["rank"]),
+                 p(out["cuts"]), p(out["cut_keys"]), int(max_blocks), current_stream()), "poco_op_rank_curve")
+    return out
+
+
+def pearson64(x: torch.Tensor, y: torch.Tensor, max_blocks: int = 0, *, out=None) -> torch.Tensor:
+    """poco_op_pearson64: Pearson's r of two float64 CUDA vectors of one length, as a float64 CUDA tensor [1] (clipped to [-1, 1];
+    NaN where either side is constant).  Applied to two `rank` arrays of rank_curve it is Spearman's rho.  Nothing is read back."""
+    for name, t in (("x", x), ("y", y)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1):
+            raise PocoHipError(f"pearson64: {name} must be a contiguous float64 CUDA vector")
+    if x.shape != y.shape or not 1 <= int(x.shape[0]) <= RANK_MAX_N:
+        raise PocoHipError(f"pearson64: x and y must have one length in 1..2^24, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if out is None:
+        out = torch.empty(1, device=x.device, dtype=torch.float64)
+    fn = lib().poco_op_pearson64
+    fn.argtypes = PEARSON64_ARGTYPES
+    with torch.cuda.device(x.device):
+        check(fn(x.data_ptr(), y.data_ptr(), int(x.shape[0]), out.data_ptr(), int(max_blocks), current_stream()), "poco_op_pearson64")
+    return out
+
+
 # ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
 # Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
 # that the caller can check `untouched`.

@@ -102,7 +102,7 @@ def flag_error(args, script: str):
                          ("--augment", bool(getattr(args, "augment", False))), ("--aug_occlude", getattr(args, "aug_occlude", None) is not None)):
             if on:
                 return f"--tta makes its own views of the unperturbed crop: it cannot be combined with {flag}"
-        for flag in ("segm", "likelihood"):
+        for flag in ("segm", "likelihood", "rank_metrics"):
             if getattr(args, flag, False):
                 return f"--{flag} reads one forward's outputs: it cannot be combined with --tta"
         return None
