@@ -43,6 +43,13 @@ those are at most --infill_max_gap frames apart, else by the nearer one if it is
 and orig_cam follow the root joint, the touched frames are re-posed, --smooth then filters the repaired pose (poco_amd/infill.py,
 csrc/track_infill.hip).  The result gains infill [T,24] (0 reliable, 1 interpolated, 2 held, 3 left) and pose_net / betas_net /
 orig_cam_net, the values before in-filling.  No default threshold: it is the user's statement of what they trust.  Not with --gpus N > 1.
+--smooth_uncert LAMBDA (video mode) is the continuous counterpart of --smooth and --infill: per track and per joint a non-causal
+penalised least-squares fit over time, its data term weighted by the precision (--smooth_uncert_ref / var)^2, its penalty LAMBDA
+times the squared second difference over the frame indices (none across a hole wider than --smooth_uncert_max_gap frames), each
+solved matrix taken back onto SO(3); betas and orig_cam are smoothed with the root joint's weights, every frame is re-posed
+(poco_amd/usmooth.py, csrc/track_smooth.hip).  The result gains smooth_shift [T,24] (degrees) and pose_net /
+betas_net / orig_cam_net; var stays as regressed.  After --infill it works on the in-filled pose.  Not with --smooth (two
+smoothers) and not with --gpus N > 1.
 --cfg2 FILE --ckpt2 FILE [--inf_model2 best] [--select crop|joint] [--select_scale S] runs a second model on the same crops on the
 same GPU and lets the uncertainty choose (poco_amd/select.py, csrc/select_regressor.hip): per crop the model
 whose global uncertainty (the reference's get_global_uncert of its own head) is lower, S times the second model's against the
@@ -186,6 +193,14 @@ def parse_args(argv=None):
                         "a batch of K")
     p.add_argument("--tta_weight", default=None, choices=["uncert", "uniform"],
                    help="with --tta: weigh each view's joint by 1 / its uncertainty (default) or uniformly")
+    p.add_argument("--smooth_uncert", type=float, default=None, metavar="LAMBDA",
+                   help="video mode: smooth every track over time, weighting each frame's joint rotation by the model's own "
+                        "precision (made on the GPU, after --infill); LAMBDA in (0, 1e4] is the stiffness; the result gains "
+                        "smooth_shift, pose_net, betas_net and orig_cam_net")
+    p.add_argument("--smooth_uncert_ref", type=float, default=0.3,
+                   help="--smooth_uncert: the uncertainty (`var`) at which a frame's weight is 1")
+    p.add_argument("--smooth_uncert_max_gap", type=int, default=30,
+                   help="--smooth_uncert: curvature is not penalised across a hole of more than this many frames")
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
@@ -287,6 +302,30 @@ def _check_tta(args) -> None:
         sys.exit(msg)
 
 
+def _check_smooth_uncert(args) -> None:
+    """--smooth_uncert and its two companions: refuse them outside video mode, with --smooth and with --gpus N > 1 before the engine
+    is built."""
+    lam = getattr(args, "smooth_uncert", None)
+    ref, gap = getattr(args, "smooth_uncert_ref", 0.3), getattr(args, "smooth_uncert_max_gap", 30)
+    if lam is None:
+        if ref != 0.3 or gap != 30:
+            sys.exit("--smooth_uncert_ref and --smooth_uncert_max_gap tune --smooth_uncert: they need --smooth_uncert LAMBDA")
+        return
+    if args.mode != "video":
+        sys.exit("--smooth_uncert smooths the tracks of video mode: it needs --mode video")
+    if getattr(args, "smooth", False):
+        sys.exit("--smooth_uncert with --smooth: two smoothers; choose one")
+    if args.gpus > 1:
+        sys.exit("--smooth_uncert with --gpus N > 1 is not supported: the packed record the ranks exchange has no room for the "
+                 "shifts; run with --gpus 1")
+    if not 0.0 < lam <= 1e4:
+        sys.exit(f"--smooth_uncert LAMBDA must be in (0, 1e4], got {lam}")
+    if not (ref > 0.0 and ref < float("inf")):
+        sys.exit(f"--smooth_uncert_ref must be finite and > 0, got {ref}")
+    if gap < 1:
+        sys.exit(f"--smooth_uncert_max_gap must be >= 1, got {gap}")
+
+
 def _check_segm(args) -> None:
     """--save_segm: refuse video mode, a head without a segmentation mask, a body model without triangles and an unreadable
     --part_mapping before the engine is built."""
@@ -332,6 +371,7 @@ def main(args):
     _check_dataset(args)
     _check_segm(args)
     _check_infill(args)
+    _check_smooth_uncert(args)
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")

@@ -1149,6 +1149,44 @@ int poco_op_rank_curve(const float* d_key, const float* d_vals, int64_t n, int E
                        int32_t* d_order, double* d_rank, double* d_cuts, float* d_cut_keys, int max_blocks, void* stream);
 int poco_op_pearson64(const double* d_x, const double* d_y, int64_t n, double* d_r, int max_blocks, void* stream);
 
+/* ---- video mode's uncertainty-weighted smoother: each track smoothed over time, the data term weighted by the precision -------
+ * demo.py --mode video --smooth_uncert LAMBDA; csrc/track_smooth.hip; tests/usmooth_np.py restates it in
+ * float64 numpy with a dense solve.  No counterpart in the reference (its --smooth is the causal one-euro filter on the host).
+ *
+ * poco_op_track_smooth: P tracks concatenated into N rows as for poco_op_track_infill: d_offsets int32 [P+1] (0 = first, N = last,
+ *   strictly increasing: the CALLER checks this; the kernel only clamps it to 0..N), d_frames int32 [N] (strictly increasing within
+ *   a track, holes allowed), d_pose [N,24,3,3] (finite), d_u [N,24] (the post-processed uncertainty), d_lin [N,L] with 0 <= L <=
+ *   POCO_SMOOTH_MAX_LIN (NULL iff L = 0; the demo passes betas | orig_cam, L = 14), lam in (0, 1e4], u_ref finite and > 0,
+ *   max_gap >= 1.
+ *   Per track (rows t = 0 .. T-1, frames f_t) and per joint j:
+ *     weight     w_t = clamp((u_ref / max(u[t][j], 1e-6))^2, 1e-6, 1e6); a NaN or an infinity of either sign gives 1e-6.
+ *     curvature  for 1 <= t <= T-2 with h1 = f_t - f_(t-1) and h2 = f_(t+1) - f_t both in 1..max_gap: row t of D is
+ *                (2 / (h1 (h1 + h2)), -2 / (h1 h2), 2 / (h2 (h1 + h2))) at columns t-1, t, t+1, its weight omega_t = (h1 + h2) / 2
+ *                (unit spacing: (1, -2, 1), omega 1).  Every other row of D is zero: no penalty across a hole wider than max_gap.
+ *     solve      A = diag(w) + lam D^T Omega D (pentadiagonal, symmetric positive definite whatever the data); A X = diag(w) Y for
+ *                the nine entries of joint j's matrices; each solved 3x3 M is replaced by the rotation nearest to it: Horn's
+ *                quaternion, the largest eigenvector of the symmetric 4x4 by cyclic Jacobi with 10 fixed sweeps, as
+ *                poco_op_tta_fuse.  T <= 2 has no penalty row: the output is the projected input.
+ *     shift      the angle in degrees between the input matrix A and the output R (before its rounding):
+ *                atan2(|skew(A^T R)| / 2, (trace(A^T R) - 1) / 2), skew = (Q21 - Q12, Q02 - Q20, Q10 - Q01).
+ *   Linear block: the L columns of d_lin are solved with joint 0's A and are not projected.
+ *   Arithmetic: fp64 throughout, rounded once to fp32 on store; banded L D L^T without pivoting (two sub-diagonals), forward and
+ *   backward substitution.  lam is capped at 1e4 because the factor's deviation from a dense fp64 solve grows with it (1e-12 for
+ *   lam <= 100, 1.2e-10 at 1e4, 1.4e-8 at 1e6 on random tracks).
+ *   Outputs (every element is written; none may alias an input): d_pose_out [N,24,3,3], d_lin_out [N,L], d_shift [N,24].
+ *   d_scratch: POCO_SMOOTH_SCRATCH_DOUBLES(N, L) doubles, caller-owned, set and consumed by the call (per row the 216 + L substituted
+ *   right-hand sides, then the solution in their place, and two sub-diagonal words for each of the 24 joints and the linear block).
+ *   One launch on `stream` whatever P is (a block per (track, 7 joints): one wave solves, one lane per column; four waves project);
+ *   max_blocks > 0 caps the grid (tests).  No allocation, no synchronisation, no atomics: a track's output bits do not depend on
+ *   the other tracks in the buffer or on the grid, and two runs give the same bits.
+ *   POCO_ERR_ARG before any GPU work: a null pointer, P < 1, N < P, 24 * 9 * N >= 2^31, L outside 0..16, max_gap < 1, lam not in
+ *   (0, 1e4], u_ref not finite and positive, an output that is its own input. */
+#define POCO_SMOOTH_MAX_LIN 16
+#define POCO_SMOOTH_SCRATCH_DOUBLES(N, L) ((size_t)(N) * (size_t)(266 + (L)))
+int poco_op_track_smooth(const float* d_pose, const float* d_u, const int32_t* d_frames, const int32_t* d_offsets, int P, int N,
+                         const float* d_lin, int L, double lam, double u_ref, int max_gap, double* d_scratch, float* d_pose_out,
+                         float* d_lin_out, float* d_shift, int max_blocks, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

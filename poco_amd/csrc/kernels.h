@@ -317,3 +317,15 @@ RankScratch rank_scratch_layout(long long n, int E);
 void launch_rank_curve(const float* key, const float* vals, long long n, int E, int K, void* scratch, int32_t* order, double* rank,
                        double* cuts, float* cut_keys, int max_blocks, hipStream_t s);
 void launch_pearson64(const double* x, const double* y, long long n, double* r, hipStream_t s);
+
+// ---- video mode's uncertainty-weighted smoother (track_smooth.hip) ------------------------------------------------------------
+// include/poco_hip.h poco_op_track_smooth: P tracks = rows [offsets[p], offsets[p + 1]) of N; pose [N,24,3,3], u [N,24], frames [N],
+// lin [N,L]; scratch = N * (TRACK_SMOOTH_ROW_DOUBLES + L) doubles (a row: 216 + L solution columns, then 25 x 2 factor words);
+// outputs pose_out, lin_out, shift [N,24].  (track, group of 7 joints) pairs are dealt to at most TRACK_SMOOTH_MAX_BLOCKS blocks of
+// TRACK_SMOOTH_THREADS (max_blocks > 0: at most that many) by a grid-stride loop.
+constexpr int TRACK_SMOOTH_MAX_BLOCKS = 4096;
+constexpr int TRACK_SMOOTH_THREADS = 256;
+constexpr int TRACK_SMOOTH_ROW_DOUBLES = 266;
+void launch_track_smooth(const float* pose, const float* u, const int* frames, const int* offsets, int P, int N, const float* lin, int L,
+                         double lam, double u_ref, int max_gap, double* scratch, float* pose_out, float* lin_out, float* shift,
+                         int max_blocks, hipStream_t s);

@@ -1124,3 +1124,24 @@ extern "C" int poco_op_pearson64(const double* d_x, const double* d_y, int64_t n
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- video mode's uncertainty-weighted smoother (track_smooth.hip) -----------------------------------------------------------
+extern "C" int poco_op_track_smooth(const float* d_pose, const float* d_u, const int32_t* d_frames, const int32_t* d_offsets, int P, int N,
+                                    const float* d_lin, int L, double lam, double u_ref, int max_gap, double* d_scratch,
+                                    float* d_pose_out, float* d_lin_out, float* d_shift, int max_blocks, void* stream) {
+  const char* who = "poco_op_track_smooth";
+  if (!d_pose || !d_u || !d_frames || !d_offsets || !d_scratch || !d_pose_out || !d_shift)
+    return op_bad(who, "null pointer (pose, u, frames, offsets, scratch, pose_out and shift are needed)");
+  if (P < 1 || N < P || (long long)N * 216 >= (1LL << 31))
+    return op_bad(who, "needs 1 <= P <= N (no empty track) and fewer than 2^31 floats of pose");
+  if (L < 0 || L > POCO_SMOOTH_MAX_LIN) return op_bad(who, "L must be in 0..16");
+  if ((L > 0) != (d_lin != nullptr) || (L > 0) != (d_lin_out != nullptr)) return op_bad(who, "lin and lin_out are needed iff L > 0");
+  if (max_gap < 1) return op_bad(who, "max_gap must be >= 1");
+  if (!(lam > 0.0) || !(lam <= 1e4)) return op_bad(who, "lambda must be in (0, 1e4]");
+  if (!std::isfinite(u_ref) || !(u_ref > 0.0)) return op_bad(who, "u_ref must be finite and > 0");
+  if (d_pose_out == d_pose || (L > 0 && d_lin_out == d_lin)) return op_bad(who, "an output may not alias its input");
+  launch_track_smooth(d_pose, d_u, d_frames, d_offsets, P, N, d_lin, L, lam, u_ref, max_gap, d_scratch, d_pose_out, d_lin_out, d_shift,
+                      max_blocks, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

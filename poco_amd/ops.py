@@ -774,6 +774,61 @@ def pearson64(x: torch.Tensor, y: torch.Tensor, max_blocks: int = 0, *, out=None
     return out
 
 
+# ---- video mode's uncertainty-weighted smoother (include/poco_hip.h; poco_amd/usmooth.py is the user's side) --------------------
+SMOOTH_MAX_LIN = 16
+SMOOTH_MAX_LAMBDA = 1e4
+
+
+def smooth_scratch_doubles(N: int, L: int) -> int:
+    """POCO_SMOOTH_SCRATCH_DOUBLES of include/poco_hip.h."""
+    return int(N) * (266 + int(L))
+
+
+def track_smooth(pose: torch.Tensor, u: torch.Tensor, frames: torch.Tensor, offsets: torch.Tensor, lin: torch.Tensor, lam: float,
+                 u_ref: float, max_gap: int, *, out=None, max_blocks: int = 0):
+    """poco_op_track_smooth on device tensors: pose [N,24,3,3], u [N,24] fp32, frames int32 [N], offsets int32 [P+1] (0 .. N,
+    strictly increasing; a host tensor is taken as it is, a device tensor is read back once for the check), lin [N,L] fp32, L <= 16
+    -> (pose', lin', shift [N,24] in degrees).  out = (pose', lin', shift): contiguous tensors to write into (tests: poisoned
+    buffers); max_blocks > 0 caps the grid.  Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"track_smooth: {what}")
+    for name, t, dt in (("pose", pose, torch.float32), ("u", u, torch.float32), ("frames", frames, torch.int32),
+                        ("lin", lin, torch.float32)):
+        need(torch.is_tensor(t) and t.is_cuda, f"{name} must be a CUDA tensor")
+        need(t.dtype == dt, f"{name} must be {dt}, got {t.dtype}")
+    need(torch.is_tensor(offsets) and offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.numel() >= 2,
+         "offsets must be an int32 tensor [P+1], P >= 1")
+    need(pose.dim() == 4 and tuple(pose.shape[1:]) == (24, 3, 3) and pose.shape[0] >= 1, f"pose must be [N,24,3,3], got {tuple(pose.shape)}")
+    N, P = int(pose.shape[0]), int(offsets.numel()) - 1
+    need(tuple(u.shape) == (N, 24), f"u must be [{N},24], got {tuple(u.shape)}")
+    need(tuple(frames.shape) == (N,), f"frames must be [{N}], got {tuple(frames.shape)}")
+    need(lin.dim() == 2 and lin.shape[0] == N, f"lin must be [{N},L], got {tuple(lin.shape)}")
+    L = int(lin.shape[1])
+    need(L <= SMOOTH_MAX_LIN, f"L = {L} exceeds {SMOOTH_MAX_LIN}")
+    need(isinstance(max_gap, (int, np.integer)) and max_gap >= 1, f"max_gap must be an integer >= 1, got {max_gap!r}")
+    lam, u_ref = float(lam), float(u_ref)
+    need(0.0 < lam <= SMOOTH_MAX_LAMBDA, f"lambda must be in (0, {SMOOTH_MAX_LAMBDA:g}], got {lam!r}")
+    need(np.isfinite(u_ref) and u_ref > 0.0, f"u_ref must be finite and > 0, got {u_ref!r}")
+    off = offsets.cpu().numpy()
+    need(off[0] == 0 and off[-1] == N and bool(np.all(np.diff(off) > 0)), "offsets must start at 0, end at N and increase strictly")
+    dev = pose.device
+    if out is None:
+        out = [torch.empty_like(pose), torch.empty_like(lin), torch.empty((N, 24), device=dev, dtype=torch.float32)]
+    need(len(out) == 3, "out must hold pose', lin' and shift")
+    for t, shp in zip(out, ((N, 24, 3, 3), (N, L), (N, 24))):
+        need(t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == torch.float32,
+             f"an output must be a contiguous CUDA float32 {shp}")
+    scratch = torch.empty((smooth_scratch_doubles(N, L),), device=dev, dtype=torch.float64)
+    p = lambda t: C.c_void_p(t.data_ptr())                                    # noqa: E731
+    null = C.c_void_p(0)
+    check(lib().poco_op_track_smooth(p(pose.contiguous()), p(u.contiguous()), p(frames.contiguous()), p(offsets.to(dev).contiguous()), P, N,
+                                     p(lin.contiguous()) if L else null, L, C.c_double(lam), C.c_double(u_ref), int(max_gap), p(scratch),
+                                     p(out[0]), p(out[1]) if L else null, p(out[2]), int(max_blocks), current_stream()),
+          "poco_op_track_smooth")
+    return tuple(out)
+
+
 # ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
 # Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
 # that the caller can check `untouched`.

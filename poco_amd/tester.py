@@ -565,9 +565,31 @@ class POCOTester:
         self.select_summary()
         if raw:
             return stacked
+        lam = getattr(self.args, "smooth_uncert", None)
         if getattr(self.args, "infill", None) is not None:
-            return self._finish_tracks_infilled(tracking_results, stacked, orig_width, orig_height)
+            res = self._finish_tracks_infilled(tracking_results, stacked, orig_width, orig_height)
+            return res if lam is None else self._smooth_tracks_uncert(res, lam)
+        if lam is not None:
+            return self._smooth_tracks_uncert({pid: self._finish_track(tr, stacked[pid], orig_width, orig_height, smooth=False)
+                                               for pid, tr in tracking_results.items()}, lam)
         return {pid: self._finish_track(tr, stacked[pid], orig_width, orig_height) for pid, tr in tracking_results.items()}
+
+    def _smooth_tracks_uncert(self, res: dict, lam: float) -> dict:
+        """--smooth_uncert LAMBDA on finished, unsmoothed tracks (after --infill where that is given: its output is what is
+        smoothed, with the `var` as regressed): ONE call of usmooth.smooth_tracks over all tracks replaces pose, betas and orig_cam
+        by the smoothed values and re-poses every frame.  Each result gains `smooth_shift` [T,24] (degrees) and, unless --infill
+        put them there already, `pose_net` / `betas_net` / `orig_cam_net`; var, var_global, pred_cam and smpl_joints2d stay those
+        of the raw prediction."""
+        from . import usmooth
+        sm = usmooth.smooth_tracks(self.model, res, float(lam), float(getattr(self.args, "smooth_uncert_ref", 0.3)),
+                                   int(getattr(self.args, "smooth_uncert_max_gap", 30)))
+        for pid, r in res.items():
+            for net, k in (("pose_net", "pose"), ("betas_net", "betas"), ("orig_cam_net", "orig_cam")):
+                r.setdefault(net, r[k])
+            for k in ("pose", "betas", "orig_cam", "verts", "smpl_joints3d", "smooth_shift"):
+                r[k] = sm[pid][k]
+        print(usmooth.summary_line(sm, res))
+        return res
 
     def _finish_tracks_infilled(self, tracking_results: dict, stacked: dict, orig_width: int, orig_height: int) -> dict:
         """--infill THRESH: the tracks are finished unsmoothed (video_uncert, convert_crop_cam_to_orig_img), then ONE call of
