@@ -36,6 +36,15 @@ rho is printed beside Pearson's r, then AUSE / AURG (area of the sparsification 
 MPJPE, PA-MPJPE, V2V and the pose distance, then per kept fraction the uncertainty threshold and the errors of the crops kept; the
 .npz gains rank_spars_*, rank_oracle_*, rank_reliab_*, rank_thresholds and rank_summary.  Not with --cfg2, --tta, --segm or
 --likelihood.
+--sequences treats the dataset's rows as the consecutive frames they are in 3DPW and Human3.6M: the rows are grouped into tracks by
+folder, person and frame number (poco_amd/sequences.py) and the records are scored on the GPU for Accel, the prediction's own
+jitter, and Accel error, the acceleration error of the video papers, both in mm / frame^2 (csrc/track_accel.hip, DESIGN.md section
+29).  --seq_post LIST runs up to four pipelines of video mode's post-processing - infill:<thresh>, smooth_uncert:<lambda> and smooth,
+joined with '+' - on the device and prints for each MPJPE, PA-MPJPE, V2V, Accel and Accel error with their differences to the raw
+prediction: what --infill and --smooth_uncert do to the error against ground truth.  --seq_max_gap, --seq_uncert_ref, --min_cutoff
+and --beta carry the operators' remaining parameters (defaults: demo.py's).  The .npz gains seq_track, seq_frame, seq_accel,
+seq_accel_err, seq_track_names, seq_pipelines and seq_summary.  Not with --cfg2, --tta, --segm, --likelihood, --rank_metrics, --aug_*
+or --augment.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -115,6 +124,21 @@ def parse_args(argv=None):
                         "rank_thresholds and rank_summary")
     p.add_argument("--rank_bins", type=int, default=None, metavar="K",
                    help="with --rank_metrics: cuts of the sparsification curves = bins of the tables, 1..1024 (default 20)")
+    p.add_argument("--sequences", action="store_true",
+                   help="the dataset's rows are consecutive frames: group them into tracks by folder, person and frame number and "
+                        "also print Accel and Accel error (mm / frame^2), scored on the GPU (poco_amd/sequences.py, "
+                        "csrc/track_accel.hip); the .npz gains seq_track, seq_frame, seq_accel, seq_accel_err, seq_track_names, "
+                        "seq_pipelines and seq_summary")
+    p.add_argument("--seq_post", type=str, default=None, metavar="LIST",
+                   help="with --sequences: at most four comma-separated pipelines of video mode's post-processing, each a '+'-joined "
+                        "chain of infill:<thresh>, smooth_uncert:<lambda> and smooth (e.g. infill:0.3,smooth_uncert:10,"
+                        "infill:0.3+smooth_uncert:10); each is run on the device and scored like the raw prediction")
+    p.add_argument("--seq_max_gap", type=int, default=None,
+                   help="with --seq_post: the max_gap of infill and smooth_uncert, in frames (default 30, as demo.py)")
+    p.add_argument("--seq_uncert_ref", type=float, default=None,
+                   help="with --seq_post: the uncertainty at which smooth_uncert weighs a frame 1 (default 0.3, as demo.py)")
+    p.add_argument("--min_cutoff", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 0.004)")
+    p.add_argument("--beta", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 1.5)")
     return p.parse_args(argv)
 
 
@@ -264,7 +288,25 @@ def check_tta(args) -> None:
         sys.exit(msg)
 
 
+def check_sequences(args) -> None:
+    """--sequences / --seq_*: refuse what cannot work before an engine is built - the flags it excludes, an unreadable --seq_post,
+    and a dataset whose image names do not group into tracks."""
+    from poco_amd.sequences import flag_error, group_tracks
+    msg = flag_error(args)
+    if msg:
+        sys.exit(msg)
+    if getattr(args, "sequences", False) and os.path.isfile(args.dataset):
+        import numpy as np
+        with np.load(args.dataset, allow_pickle=False) as z:
+            if "imgname" in z.files and getattr(args, "uncert_threshold", None) is None:
+                try:
+                    group_tracks(z["imgname"], z["person_id"] if "person_id" in z.files else None)
+                except ValueError as e:
+                    sys.exit(f"{args.dataset}: --sequences: {e}")
+
+
 def main(args):
+    check_sequences(args)
     check_select(args)
     check_tta(args)
     check_rank(args)
@@ -314,6 +356,17 @@ def main(args):
     elif tester.pair is not None:
         res = evaluate.run_eval_pair(tester.pair, ds, J, batch_size=max(int(args.batch_size), 1),
                                      kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
+    elif getattr(args, "sequences", False):
+        from poco_amd.sequences import parse_pipelines
+        opt = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)   # noqa: E731
+        try:
+            res = evaluate.run_eval_sequences(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
+                                              kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
+                                              pipelines=parse_pipelines(getattr(args, "seq_post", None)),
+                                              max_gap=int(opt("seq_max_gap", 30)), uncert_ref=float(opt("seq_uncert_ref", 0.3)),
+                                              min_cutoff=float(opt("min_cutoff", 0.004)), beta=float(opt("beta", 1.5)))
+        except ValueError as e:
+            sys.exit(f"--sequences: {e}")
     else:
         res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
                                 kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
@@ -329,6 +382,9 @@ def main(args):
             print(line)
     if getattr(args, "rank_metrics", False):
         for line in evaluate.rank_lines(res):
+            print(line)
+    if getattr(args, "sequences", False):
+        for line in evaluate.sequence_lines(res):
             print(line)
     if occ is not None:
         for line in evaluate.occlusion_lines(ds, res):

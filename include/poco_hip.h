@@ -1187,6 +1187,44 @@ int poco_op_track_smooth(const float* d_pose, const float* d_u, const int32_t* d
                          const float* d_lin, int L, double lam, double u_ref, int max_gap, double* d_scratch, float* d_pose_out,
                          float* d_lin_out, float* d_shift, int max_blocks, void* stream);
 
+/* ---- eval.py --sequences: the acceleration and the acceleration error of every row of a ragged buffer of tracks --------------------
+ * eval.py --sequences [--seq_post LIST]; csrc/track_accel.hip; poco_amd/sequences.py; tests/accel_np.py
+ * restates it in float64 with plain loops.  The acceleration error is compute_error_accel of the VIBE line of work (not in the
+ * reference's code, which reports no temporal metric).
+ *
+ * poco_op_track_accel: P tracks concatenated into N rows as for poco_op_track_smooth: d_offsets int32 [P+1] (0 = first, N = last,
+ *   strictly increasing: the CALLER checks this; the kernels only clamp it to 0..N), d_frames int32 [N].  d_pred and d_gt: fp32
+ *   joints [N,M,3], row i at d_x + i * stride floats, 1 <= M <= POCO_ACCEL_MAX_JOINTS, stride >= 3 M; only the first 3 M floats of
+ *   a row are read (the evaluator's records in place: d_records + 116 and d_records + 212 at stride POCO_EVAL_RECORD_FLOATS).
+ *   d_gt may be NULL: then d_accel_err is not written (it may be NULL too) and the sums of the acceleration error are 0.
+ *   Row i is VALID when rows i-1, i, i+1 lie in one track and frames[i-1] + 1 == frames[i] == frames[i+1] - 1.
+ *     a_m        = p[i-1][m] - 2 p[i][m] + p[i+1][m] (and g_m the same of the ground truth), formed as (x0 - 2 x1) + x2 in fp64
+ *     accel[i]     = (sum_m |a_m|) / M           accel_err[i] = (sum_m |a_m - g_m|) / M      |v| = sqrt((x^2 + y^2) + z^2)
+ *   in the units of the joints per frame^2 (metres per frame^2; nothing is divided by a frame rate), all in fp64 and rounded once
+ *   to fp32; the sum over the joints is a halving tree over 32 slots.  An invalid row gets the quiet NaN 0x7fc00000 in both.
+ *   d_track_sums fp64 [P,3] = per track the sum of accel_err, the sum of accel (the fp64 values before their rounding) and the
+ *   number of valid rows; d_total fp64 [3] = the same over all tracks.  A track's sum adds its rows t, t + 256, ... per lane in
+ *   ascending order and then a halving tree over the 256 lanes; the total does the same over the tracks' sums: the summation tree
+ *   is a function of the track lengths alone.  fp64 additions only, no floating-point atomics: all four outputs are bitwise
+ *   independent of max_blocks (0 = the default grid, > 0 bounds it) and equal from run to run.
+ *   d_scratch: POCO_ACCEL_SCRATCH_DOUBLES(N) doubles, caller-owned, set and consumed by the call (per row the two fp64 terms and
+ *   the valid flag).  Every element of the outputs is written; none may overlap an input.
+ *   Three launches on `stream` (a block per 64 rows: the 66 rows it needs are read once, coalesced, into LDS; one half-wave per
+ *   row, one lane per joint; then a block per track; then one block); no allocation, no synchronisation.
+ *   POCO_ERR_ARG before any GPU work: a null pointer (d_gt and, with it, d_accel_err excepted), M outside 1..32, stride < 3 M or
+ *   > 65536, P < 1, N < P, N > 2^24, max_blocks < 0. */
+#define POCO_ACCEL_MAX_JOINTS 32
+#define POCO_ACCEL_SCRATCH_DOUBLES(N) ((size_t)(N) * 3)
+int poco_op_track_accel(const float* d_pred, const float* d_gt, int stride, int M, const int32_t* d_frames, const int32_t* d_offsets,
+                        int P, int N, double* d_scratch, float* d_accel, float* d_accel_err, double* d_track_sums, double* d_total,
+                        int max_blocks, void* stream);
+/* The records of an evaluator, copied on the device: d_out [n, POCO_EVAL_RECORD_FLOATS] fp32 (16-byte aligned) <- record
+ * d_order[i] for i in [0, n) (d_order int32 [n] on the device, entries in [0, N written so far), checked by the CALLER: a row whose
+ * entry is outside gets zeros); d_order NULL: the first n records in their own order.  One launch on `stream`; the records are
+ * only read.  POCO_ERR_ARG: a null handle or d_out, n < 1, n > N without an order, a misaligned d_out; no step yet is
+ * POCO_ERR_STATE. */
+int poco_evaluator_copy_records(poco_evaluator_t e, const int32_t* d_order, int64_t n, float* d_out, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

@@ -364,6 +364,21 @@ __global__ __launch_bounds__(256) void eval_rank_inputs(EvalDev d, int mode, lon
   }
 }
 
+// poco_evaluator_copy_records: record order[i] (or i) -> row i of out, 16 bytes per lane; an entry outside [0, have) gives zeros
+__global__ __launch_bounds__(256) void eval_copy_records(const float* __restrict__ rec, const int* __restrict__ order, long long n,
+                                                         long long have, float* __restrict__ out) {
+  constexpr int Q = EV_REC / 4;                                       // float4 words of a record
+  static_assert(EV_REC % 4 == 0, "a record is a whole number of 16-byte words");
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n * Q) return;
+  const long long row = i / Q;
+  const int q = (int)(i - row * Q);
+  const long long src = order ? (long long)order[row] : row;
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (src >= 0 && src < have) v = reinterpret_cast<const float4*>(rec + (size_t)src * EV_REC)[q];
+  reinterpret_cast<float4*>(out + (size_t)row * EV_REC)[q] = v;
+}
+
 }  // namespace
 
 extern "C" int poco_op_rodrigues(const float* d_axis_angle, float* d_rotmat, int N, void* stream) {
@@ -540,6 +555,23 @@ extern "C" int poco_evaluator_rank_inputs(poco_evaluator_t e, int mode, float* d
   }
   if (int rc = evaluator_upload(e)) return rc;
   eval_rank_inputs<<<(unsigned)((rows + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->dev(), mode, rows, d_key, d_vals);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_evaluator_copy_records(poco_evaluator_t e, const int32_t* d_order, int64_t n, float* d_out, void* stream) {
+  if (!e || !d_out || n < 1 || ((uintptr_t)d_out & 15) != 0 || n > (1ll << 24)) {
+    poco_set_error("poco_evaluator_copy_records: bad arguments (need a handle, a 16-byte aligned output and 1 <= n <= 2^24)");
+    return POCO_ERR_ARG;
+  }
+  if (e->first < 1) { poco_set_error("poco_evaluator_copy_records: no crop has been stepped"); return POCO_ERR_STATE; }
+  if (!d_order && n > e->first) {
+    poco_set_error("poco_evaluator_copy_records: " + std::to_string(n) + " rows asked for, " + std::to_string(e->first) + " written");
+    return POCO_ERR_ARG;
+  }
+  if (int rc = evaluator_upload(e)) return rc;
+  const long long words = (long long)n * (EV_REC / 4);
+  eval_copy_records<<<(unsigned)((words + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d_rec, d_order, n, e->first, d_out);
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }

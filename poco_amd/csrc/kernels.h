@@ -329,3 +329,16 @@ constexpr int TRACK_SMOOTH_ROW_DOUBLES = 266;
 void launch_track_smooth(const float* pose, const float* u, const int* frames, const int* offsets, int P, int N, const float* lin, int L,
                          double lam, double u_ref, int max_gap, double* scratch, float* pose_out, float* lin_out, float* shift,
                          int max_blocks, hipStream_t s);
+
+// ---- the temporal metric of eval.py --sequences: acceleration and acceleration error per row (track_accel.hip) -------------------
+// include/poco_hip.h poco_op_track_accel: P tracks = rows [offsets[p], offsets[p + 1]) of N; pred / gt [N,M,3] at a row stride in
+// floats (gt nullable); scratch = TRACK_ACCEL_ROW_DOUBLES doubles per row (acceleration error, acceleration, valid: the fp64 terms
+// of the sums); outputs accel / accel_err [N], track_sums fp64 [P,3], total fp64 [3].  Tiles of TRACK_ACCEL_TILE rows, then tracks,
+// are dealt to at most TRACK_ACCEL_MAX_BLOCKS blocks of TRACK_ACCEL_THREADS (max_blocks > 0: at most that many) by grid-stride loops.
+constexpr int TRACK_ACCEL_MAX_BLOCKS = 4096;
+constexpr int TRACK_ACCEL_THREADS = 256;
+constexpr int TRACK_ACCEL_TILE = 64;
+constexpr int TRACK_ACCEL_MAX_JOINTS = 32;
+constexpr int TRACK_ACCEL_ROW_DOUBLES = 3;
+void launch_track_accel(const float* pred, const float* gt, int stride, int M, const int* frames, const int* offsets, int P, int N,
+                        double* scratch, float* accel, float* accel_err, double* track_sums, double* total, int max_blocks, hipStream_t s);

@@ -1145,3 +1145,22 @@ extern "C" int poco_op_track_smooth(const float* d_pose, const float* d_u, const
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- eval.py --sequences: acceleration and acceleration error per row (track_accel.hip) ----------------------------------------
+static_assert(POCO_ACCEL_MAX_JOINTS == TRACK_ACCEL_MAX_JOINTS && POCO_ACCEL_SCRATCH_DOUBLES(1) == TRACK_ACCEL_ROW_DOUBLES,
+              "include/poco_hip.h and csrc/kernels.h disagree on the acceleration operator");
+extern "C" int poco_op_track_accel(const float* d_pred, const float* d_gt, int stride, int M, const int32_t* d_frames,
+                                   const int32_t* d_offsets, int P, int N, double* d_scratch, float* d_accel, float* d_accel_err,
+                                   double* d_track_sums, double* d_total, int max_blocks, void* stream) {
+  const char* who = "poco_op_track_accel";
+  if (!d_pred || !d_frames || !d_offsets || !d_scratch || !d_accel || !d_track_sums || !d_total || (d_gt && !d_accel_err))
+    return op_bad(who, "null pointer (pred, frames, offsets, scratch, accel, track_sums and total are needed, and accel_err with gt)");
+  if (M < 1 || M > POCO_ACCEL_MAX_JOINTS) return op_bad(who, "M must be in 1..32");
+  if (stride < 3 * M || stride > 65536) return op_bad(who, "the row stride must be at least 3 M floats and at most 65536");
+  if (P < 1 || N < P || N > (1 << 24)) return op_bad(who, "needs 1 <= P <= N <= 2^24 (no empty track)");
+  if (max_blocks < 0) return op_bad(who, "max_blocks must be >= 0");
+  launch_track_accel(d_pred, d_gt, stride, M, d_frames, d_offsets, P, N, d_scratch, d_accel, d_accel_err, d_track_sums, d_total,
+                     max_blocks, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

@@ -154,6 +154,23 @@ class Evaluator:
         assert (hn.value, hE.value) == (n, E), (hn.value, hE.value, n, E)
         return key, vals
 
+    def copy_records(self, order: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The records written so far as a device tensor [n, RECORD_FLOATS], copied on the device: record order[i] in row i (order
+        int32 [n] on the device, entries in [0, count)), or all of them in their own order.  Enqueued on the current stream; nothing
+        goes to the host."""
+        if order is not None and not (torch.is_tensor(order) and order.is_cuda and order.dtype == torch.int32 and order.dim() == 1
+                                      and order.numel() >= 1):
+            raise PocoHipError("Evaluator.copy_records: order must be a CUDA int32 tensor [n], n >= 1")
+        n = self.count if order is None else int(order.numel())
+        out = torch.empty((max(n, 1), RECORD_FLOATS), device=self.device, dtype=torch.float32)
+        L = _bind()
+        L.poco_evaluator_copy_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        with torch.cuda.device(self.device):
+            check(L.poco_evaluator_copy_records(self._h, None if order is None else order.contiguous().data_ptr(), n, out.data_ptr(),
+                                                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                  "poco_evaluator_copy_records")
+        return out
+
     def finish(self, save_results: bool = False, return_records: bool = False) -> Dict[str, object]:
         """Summary under the reference's log names (trainer.py:397-403) plus the per-sample arrays of
         SaveResults.evaluation_results (save_results.py:23-43): mpjpe / pampjpe [N,M], v2v [N], corr_x / corr_y (flattened over
@@ -447,6 +464,153 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
     return res
 
 
+SEQ_NPZ_KEYS = ("seq_track", "seq_frame", "seq_accel", "seq_accel_err", "seq_track_names", "seq_pipelines", "seq_summary")
+
+
+def _seq_accel(ev: "Evaluator", order_d, frames_d, offsets):
+    """ops.track_accel on the evaluator's records gathered into track-major rows: the joints are read where they lie in the
+    records (row stride RECORD_FLOATS).  -> (the gathered records, the operator's result)."""
+    from . import ops
+    rec = ev.copy_records(order_d)
+    W = 3 * ev.M
+    return rec, ops.track_accel(rec[:, R_PRED:R_PRED + W], rec[:, R_GT:R_GT + W], frames_d, offsets)
+
+
+def _seq_row(res: Dict[str, object], total: np.ndarray, changed: float, n: int) -> np.ndarray:
+    """One row of seq_summary (sequences.SUMMARY_FIELDS): MPJPE, PA-MPJPE, V2V, then Accel and Accel error x 1000 as means over the
+    valid rows (NaN without one), the share of changed joint-frames and the share of valid rows."""
+    cnt = float(total[2])
+    acc, err = (1000.0 * float(total[1]) / cnt, 1000.0 * float(total[0]) / cnt) if cnt > 0 else (float("nan"), float("nan"))
+    return np.array([res["val_mpjpe"], res["val_pampjpe"], res["val_v2v"], acc, err, changed, cnt / max(n, 1)], np.float64)
+
+
+@torch.no_grad()
+def run_eval_sequences(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
+                       sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_records: bool = False,
+                       pipelines=(), max_gap: int = 30, uncert_ref: float = 0.3, min_cutoff: float = 0.004,
+                       beta: float = 1.5) -> Dict[str, object]:
+    """run_eval on a dataset whose rows are consecutive frames (eval.py --sequences, DESIGN.md section 29).  The loop is run_eval's;
+    what it returns under run_eval's keys is bit for bit what run_eval returns.  The rows are grouped into tracks
+    (sequences.group_tracks), the records are gathered track-major on the device and ops.track_accel scores them: seq_track /
+    seq_frame / seq_accel / seq_accel_err [N] in file order (NaN where a row has no two neighbours at consecutive frames),
+    seq_track_names, and seq_summary [1 + pipelines, 7] (sequences.SUMMARY_FIELDS; row 0 = the raw prediction).
+    pipelines (sequences.parse_pipelines): each chain of video mode's post-processing operators is run on the device tensors of
+    pose, shape and processed uncertainty kept from the loop - ops.track_infill, ops.track_smooth, the one-euro filter on the host -
+    re-posed with model.smpl_lbs (the rows the in-fill touched; every row after a smoother) and scored with a second Evaluator
+    stepped over the same batches against the same ground truth, and with ops.track_accel."""
+    from . import ops
+    from .sequences import group_tracks, pipeline_text
+    dev, n = model.device, len(dataset)
+    pipelines = list(pipelines)
+    new_ev = lambda: Evaluator(J_regressor, joint_map(dataset.name), capacity=n, sel_uncert_part=sel_uncert_part,   # noqa: E731
+                               kinematic=kinematic, device=dev)
+    ev = new_ev()
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+    g = group_tracks(dataset.imgname, dataset.person_id)                # refuses before any GPU work
+
+    def ground_truth(lo, hi):
+        gt_pose = t(dataset.pose[lo:hi])
+        if dataset.gt_form == "smpl":
+            return gt_pose, {"gt_vertices": model.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))[0]}
+        return gt_pose, {"gt_joints": t(dataset.joints[lo:hi])}
+
+    keep = None
+    for lo in range(0, n, batch_size):
+        hi = min(lo + batch_size, n)
+        out = model(dataset.batch(lo, hi, dev), want_segm=False)
+        gt_pose, gt = ground_truth(lo, hi)
+        ev.step(out, gt_pose, **gt)
+        if pipelines:
+            if keep is None:
+                keep = {k: torch.empty((n,) + tuple(out[k].shape[1:]), device=dev, dtype=torch.float32)
+                        for k in ("pred_pose", "pred_shape", "var_pose", "smpl_vertices")}
+            for k, buf in keep.items():
+                buf[lo:hi].copy_(out[k])
+    res = ev.finish(save_results=save_results, return_records=return_records)
+    order_d, frames_d = torch.from_numpy(g["order"]).to(dev), torch.from_numpy(g["frames"]).to(dev)
+    offsets = torch.from_numpy(g["offsets"])
+    rec, acc = _seq_accel(ev, order_d, frames_d, offsets)
+    P = len(g["names"])
+    order = g["order"].astype(np.int64)
+
+    def to_file_order(x, fill):
+        a = np.full(n, fill, x.dtype)
+        a[order] = x
+        return a
+    res["seq_track"] = to_file_order(np.repeat(np.arange(P, dtype=np.int32), np.diff(g["offsets"])), 0)
+    res["seq_frame"] = to_file_order(g["frames"], 0)
+    res["seq_accel"] = to_file_order(acc["accel"].cpu().numpy(), np.float32(np.nan))
+    res["seq_accel_err"] = to_file_order(acc["accel_err"].cpu().numpy(), np.float32(np.nan))
+    res["seq_track_sums"], res["seq_total"] = acc["track_sums"].cpu().numpy(), acc["total"].cpu().numpy()
+    res["seq_track_names"] = np.asarray(g["names"])
+    res["seq_pipelines"] = np.asarray([pipeline_text(p) for p in pipelines], dtype=str)
+    rows = [_seq_row(res, res["seq_total"], 0.0, n)]
+    if pipelines:
+        order_l = order_d.long()
+        u = rec[:, R_UNC:R_UNC + 24].contiguous()                       # the processed uncertainty, as regressed, for every step
+        pose_t, betas_t = keep["pred_pose"].index_select(0, order_l), keep["pred_shape"].index_select(0, order_l)
+        bs = max(int(model.max_batch), 1)
+        res["seq_post"] = []
+    for steps in pipelines:
+        pose, betas = pose_t, betas_t
+        stale = torch.zeros(n, dtype=torch.bool, device=dev)            # track-major rows whose mesh no longer fits their pose
+        for name, val in steps:
+            if name == "infill":
+                pose, betas, _, touched = ops.track_infill(pose, u, frames_d, offsets, betas, float(val), int(max_gap))
+                stale |= touched.bool()
+            elif name == "smooth_uncert":
+                pose, betas, _ = ops.track_smooth(pose, u, frames_d, offsets, betas, float(val), float(uncert_ref), int(max_gap))
+                stale[:] = True
+            else:
+                from .smooth import one_euro_rotmats
+                host = pose.cpu().numpy()
+                pose = torch.from_numpy(np.concatenate([one_euro_rotmats(host[a:b], min_cutoff, beta)
+                                                        for a, b in zip(g["offsets"][:-1], g["offsets"][1:])]).astype(np.float32)).to(dev)
+                stale[:] = True
+        verts = keep["smpl_vertices"].clone()                           # file order
+        sel_all = torch.nonzero(stale).reshape(-1)                      # ascending, re-posed as infill.py / usmooth.py do
+        for lo in range(0, int(sel_all.numel()), bs):
+            sel = sel_all[lo:lo + bs]
+            v, _ = model.smpl_lbs(betas.index_select(0, sel).contiguous(), pose.index_select(0, sel))
+            verts.index_copy_(0, order_l.index_select(0, sel), v)
+        pose_f = torch.empty_like(pose)
+        pose_f.index_copy_(0, order_l, pose)
+        ev2 = new_ev()
+        for lo in range(0, n, batch_size):
+            hi = min(lo + batch_size, n)
+            gt_pose, gt = ground_truth(lo, hi)
+            ev2.step({"smpl_vertices": verts[lo:hi], "pred_pose": pose_f[lo:hi], "var_pose": keep["var_pose"][lo:hi]}, gt_pose, **gt)
+        r2 = ev2.finish(save_results=save_results)
+        _, acc2 = _seq_accel(ev2, order_d, frames_d, offsets)
+        changed = float((pose != pose_t).reshape(n, 24, 9).any(-1).sum().item()) / float(n * 24)
+        r2["seq_accel"] = to_file_order(acc2["accel"].cpu().numpy(), np.float32(np.nan))
+        r2["seq_accel_err"] = to_file_order(acc2["accel_err"].cpu().numpy(), np.float32(np.nan))
+        r2["seq_total"] = acc2["total"].cpu().numpy()
+        r2["pose"] = pose_f.cpu().numpy()
+        rows.append(_seq_row(r2, r2["seq_total"], changed, n))
+        res["seq_post"].append(r2)
+        ev2.close()
+    res["seq_summary"] = np.stack(rows)
+    model.check_status()
+    res["imgname"] = np.asarray(dataset.imgname)
+    ev.close()
+    return res
+
+
+def sequence_lines(res: Dict[str, object]):
+    """eval.py --sequences: Accel and Accel error (mm / frame^2) of the raw prediction, the tracks and the share of valid rows, then
+    one line per --seq_post pipeline with every figure's difference to the raw prediction."""
+    s = res["seq_summary"]
+    lines = [f"Accel: {s[0, 3]}", f"Accel error: {s[0, 4]}",
+             f"Tracks: {len(res['seq_track_names'])} (rows with both neighbours at consecutive frames: {100.0 * s[0, 6]:.2f} %)"]
+    for name, row in zip(res["seq_pipelines"], s[1:]):
+        d = row - s[0]
+        lines.append(f"Post {name}: MPJPE {row[0]:.4f} ({d[0]:+.4f}), PA-MPJPE {row[1]:.4f} ({d[1]:+.4f}), V2V {row[2]:.4f} ({d[2]:+.4f}), "
+                     f"Accel {row[3]:.4f} ({d[3]:+.4f}), Accel error {row[4]:.4f} ({d[4]:+.4f}), changed {100.0 * row[5]:.2f} % of "
+                     "joint-frames")
+    return lines
+
+
 PAIR_SCALARS = ("val_oracle_mpjpe", "val_oracle_pampjpe", "select_accuracy", "select_share_m2")
 
 
@@ -646,5 +810,6 @@ def save_npz(path: str, res: Dict[str, object], dataset_name: str) -> None:
     pair = PAIR_SCALARS + tuple(k + tag for tag in ("_m1", "_m2") for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr"))
     keep.update({k: np.float64(res[k]) for k in pair if k in res})           # eval.py --cfg2 --ckpt2 (run_eval_pair)
     keep.update({k: np.float64(res[k]) for k in TTA_SCALARS if k in res})        # eval.py --tta (run_eval_tta)
+    keep.update({k: res[k] for k in ("seq_track_names", "seq_pipelines") if k in res})   # eval.py --sequences (run_eval_sequences)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     np.savez(path, **keep)

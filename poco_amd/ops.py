@@ -829,6 +829,72 @@ def track_smooth(pose: torch.Tensor, u: torch.Tensor, frames: torch.Tensor, offs
     return tuple(out)
 
 
+ACCEL_MAX_JOINTS = 32             # POCO_ACCEL_MAX_JOINTS
+
+
+def accel_scratch_doubles(N: int) -> int:
+    """POCO_ACCEL_SCRATCH_DOUBLES of include/poco_hip.h."""
+    return int(N) * 3
+
+
+def _joint_rows(t, name, need):
+    """(N, M, row stride in floats) of joints given as [N,M,3] or as [N,3M] rows; the rows may be a view into wider rows (the
+    evaluator's records: records[:, 116:116 + 3 * M]), the floats of a row must be adjacent."""
+    need(torch.is_tensor(t) and t.dtype == torch.float32, f"{name} must be a float32 tensor")
+    need(t.dim() in (2, 3) and t.shape[0] >= 1, f"{name} must be [N,M,3] or [N,3M], got {tuple(t.shape)}")
+    if t.dim() == 3:
+        need(t.shape[2] == 3 and t.stride(2) == 1 and t.stride(1) == 3, f"{name} [N,M,3]: the floats of a row must be adjacent")
+        M = int(t.shape[1])
+    else:
+        need(t.shape[1] % 3 == 0 and t.stride(1) == 1, f"{name} [N,3M]: 3M floats per row, adjacent")
+        M = int(t.shape[1]) // 3
+    need(1 <= M <= ACCEL_MAX_JOINTS, f"{name}: M = {M} is outside 1..{ACCEL_MAX_JOINTS}")
+    stride = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), 3 * M)
+    need(3 * M <= stride <= 65536, f"{name}: the row stride {stride} must be in 3M = {3 * M} .. 65536")
+    return int(t.shape[0]), M, stride
+
+
+def track_accel(pred: torch.Tensor, gt, frames: torch.Tensor, offsets: torch.Tensor, *, out=None, max_blocks: int = 0):
+    """poco_op_track_accel on device tensors: pred and gt (or None) fp32 joints of track-major rows, [N,M,3] or [N,3M] rows that may
+    be a view into wider rows (both at the same row stride), frames int32 [N], offsets int32 [P+1] (0 .. N, strictly increasing; a
+    host tensor is taken as it is, a device tensor is read back once for the check) -> dict(accel [N], accel_err [N] | None,
+    track_sums float64 [P,3], total float64 [3]): per track and over all tracks the sum of accel_err, the sum of accel and the
+    number of valid rows.  out = (accel, accel_err | None, track_sums, total): contiguous tensors to write into (tests: guarded
+    buffers); max_blocks > 0 caps the grids.  Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"track_accel: {what}")
+    N, M, stride = _joint_rows(pred, "pred", need)
+    if gt is not None:
+        need(_joint_rows(gt, "gt", need) == (N, M, stride), "gt must have pred's shape and row stride")
+    need(torch.is_tensor(frames) and frames.dtype == torch.int32 and tuple(frames.shape) == (N,), f"frames must be int32 [{N}]")
+    need(torch.is_tensor(offsets) and offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.numel() >= 2,
+         "offsets must be an int32 tensor [P+1], P >= 1")
+    need(isinstance(max_blocks, (int, np.integer)) and max_blocks >= 0, f"max_blocks must be an integer >= 0, got {max_blocks!r}")
+    P = int(offsets.numel()) - 1
+    off = offsets.cpu().numpy()
+    need(off[0] == 0 and off[-1] == N and bool(np.all(np.diff(off) > 0)), "offsets must start at 0, end at N and increase strictly")
+    for name, t in (("pred", pred), ("gt", gt), ("frames", frames)):
+        need(t is None or t.is_cuda, f"{name} must be a CUDA tensor")
+    dev = pred.device
+    if out is None:
+        out = (torch.empty(N, device=dev, dtype=torch.float32), None if gt is None else torch.empty(N, device=dev, dtype=torch.float32),
+               torch.empty((P, 3), device=dev, dtype=torch.float64), torch.empty(3, device=dev, dtype=torch.float64))
+    need(len(out) == 4, "out must hold accel, accel_err, track_sums and total")
+    for t, shp, dt in zip(out, ((N,), (N,), (P, 3), (3,)), (torch.float32, torch.float32, torch.float64, torch.float64)):
+        if t is None and shp == (N,) and gt is None:
+            continue
+        need(t is not None and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt,
+             f"an output must be a contiguous CUDA {dt} {shp}")
+    need(out[0] is not None, "accel is needed")
+    scratch = torch.empty((accel_scratch_doubles(N),), device=dev, dtype=torch.float64)
+    p = lambda t: C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+    check(lib().poco_op_track_accel(p(pred), p(gt), stride, M, p(frames.contiguous()), p(offsets.to(dev).contiguous()), P, N, p(scratch),
+                                    p(out[0]), p(out[1] if gt is not None else None), p(out[2]), p(out[3]), int(max_blocks),
+                                    current_stream()), "poco_op_track_accel")
+    return {"accel": out[0], "accel_err": out[1] if gt is not None else None, "track_sums": out[2], "total": out[3]}
+
+
 # ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
 # Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
 # that the caller can check `untouched`.
