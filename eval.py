@@ -45,6 +45,14 @@ prediction: what --infill and --smooth_uncert do to the error against ground tru
 and --beta carry the operators' remaining parameters (defaults: demo.py's).  The .npz gains seq_track, seq_frame, seq_accel,
 seq_accel_err, seq_track_names, seq_pipelines and seq_summary.  Not with --cfg2, --tta, --segm, --likelihood, --rank_metrics, --aug_*
 or --augment.
+--visibility [--vis_margin M] [--vis_bins K] states the paper's claim - a joint's uncertainty rises when its body part cannot be seen -
+per joint: per batch the ground-truth mesh is placed in the crop as --segm places it and counted on the GPU (csrc/part_visibility.hip,
+poco_amd/visibility.py) - per crop and body part the pixels in a window of M pixels around the crop (default
+res / 2), inside the crop, in front of the rest of the body, and not touched by the occluders of --aug_occlude.  Printed: the mean
+visibility per joint, Pearson's and Spearman's Corr(1 - visibility, uncertainty) pooled, per joint and for each of truncation,
+self-occlusion and object occlusion, Corr(1 - visibility, per-joint error), and uncertainty and error over K visibility bins (default
+5); the .npz gains vis_counts, vis, vis_summary, vis_joint and vis_bins.  Needs `pose`, `shape` and `part`; works for every model and
+with --crop dataset, --aug_*, --augment, --segm and --part_mapping.  Not with --cfg2, --tta, --sequences, --rank_metrics or --likelihood.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -137,6 +145,16 @@ def parse_args(argv=None):
                    help="with --seq_post: the max_gap of infill and smooth_uncert, in frames (default 30, as demo.py)")
     p.add_argument("--seq_uncert_ref", type=float, default=None,
                    help="with --seq_post: the uncertainty at which smooth_uncert weighs a frame 1 (default 0.3, as demo.py)")
+    p.add_argument("--visibility", action="store_true",
+                   help="also the per-joint visibility of the ground-truth body, counted on the GPU (poco_amd/visibility.py, "
+                        "csrc/part_visibility.hip): mean visibility per joint, Corr(1 - visibility, uncertainty) pooled, per joint and "
+                        "split into truncation, self-occlusion and object occlusion, and a table over visibility bins (needs `pose`, "
+                        "`shape` and `part` in the dataset and `faces` in the --smpl file; with --aug_occlude the occluders count); the "
+                        ".npz gains vis_counts, vis, vis_summary, vis_joint and vis_bins")
+    p.add_argument("--vis_margin", type=int, default=None, metavar="M",
+                   help="with --visibility: pixels around the crop in which the body still counts, 0..res (default res / 2); it bounds "
+                        "the truncation that can be measured")
+    p.add_argument("--vis_bins", type=int, default=None, metavar="K", help="with --visibility: bins of the table, 2..20 (default 5)")
     p.add_argument("--min_cutoff", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 0.004)")
     p.add_argument("--beta", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 1.5)")
     return p.parse_args(argv)
@@ -305,7 +323,37 @@ def check_sequences(args) -> None:
                     sys.exit(f"{args.dataset}: --sequences: {e}")
 
 
+def check_visibility(args) -> None:
+    """--visibility / --vis_margin / --vis_bins: refuse what cannot work before an engine is built - the flags it excludes, a bin
+    count or margin out of range, a dataset without pose / shape / part, a body model without triangles, an unreadable
+    --part_mapping."""
+    from poco_amd import visibility
+    msg = visibility.flag_error(args)
+    if msg:
+        sys.exit(msg)
+    if not getattr(args, "visibility", False):
+        return
+    import numpy as np
+    from poco_amd import segm
+    if not os.path.isfile(args.dataset):
+        sys.exit(f"dataset file not found: {args.dataset}")
+    try:
+        with np.load(args.dataset, allow_pickle=False) as z:
+            visibility.check_dataset_keys(z.files)
+        if getattr(args, "part_mapping", None):
+            segm.load_part_mapping(args.part_mapping)
+    except ValueError as e:
+        sys.exit(f"{args.dataset}: {e}")
+    if not os.path.isfile(args.smpl):
+        sys.exit(f"--visibility: body-model file not found: {args.smpl}")
+    with np.load(args.smpl) as z:
+        if "faces" not in z.files:
+            sys.exit(f"--visibility: {args.smpl} has no `faces` array (convert the SMPL .pkl with tools/convert_smpl.py, which keeps "
+                     "its triangles)")
+
+
 def main(args):
+    check_visibility(args)
     check_sequences(args)
     check_select(args)
     check_tta(args)
@@ -340,13 +388,24 @@ def main(args):
         print(f"Confident rows (uncertainty < {args.uncert_threshold}): {len(ds)} of {ds.total}")
     J = np.load(args.j_regressor).astype(np.float32)
     tester = POCOTester(args)                       # builds the engine from --cfg / --ckpt / --smpl exactly as demo.py does
+    vis_kw = {}
+    if getattr(args, "visibility", False):
+        from poco_amd import visibility
+        try:
+            vis_kw["visibility"] = visibility.prepare(tester.model, ds, args.dataset, args.smpl, part_mapping=args.part_mapping,
+                                                      batch_size=max(int(args.batch_size), 1),
+                                                      uncert_threshold=getattr(args, "uncert_threshold", None),
+                                                      res=tester.model_cfg.DATASET.IMG_RES, margin=getattr(args, "vis_margin", None),
+                                                      bins=getattr(args, "vis_bins", None) or 5)
+        except ValueError as e:
+            sys.exit(str(e))
     if getattr(args, "segm", False):
         from poco_amd import segm
         try:
             res = segm.run_eval(tester.model, ds, args.dataset, J, args.smpl, part_mapping=args.part_mapping,
                                 batch_size=max(int(args.batch_size), 1), kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT),
                                 save_results=args.save_results, likelihood=args.likelihood,
-                                uncert_threshold=getattr(args, "uncert_threshold", None), res=tester.model_cfg.DATASET.IMG_RES)
+                                uncert_threshold=getattr(args, "uncert_threshold", None), res=tester.model_cfg.DATASET.IMG_RES, **vis_kw)
         except ValueError as e:
             sys.exit(str(e))
     elif tester.tta is not None:
@@ -371,7 +430,7 @@ def main(args):
         res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
                                 kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
                                 likelihood=args.likelihood,
-                                rank_metrics=(args.rank_bins or 20) if getattr(args, "rank_metrics", False) else None)
+                                rank_metrics=(args.rank_bins or 20) if getattr(args, "rank_metrics", False) else None, **vis_kw)
     lines = evaluate.pair_report_lines(res, tester.pair.mode) if tester.pair is not None else evaluate.report_lines(res)
     if tester.tta is not None:
         lines = evaluate.tta_report_lines(res)
@@ -385,6 +444,9 @@ def main(args):
             print(line)
     if getattr(args, "sequences", False):
         for line in evaluate.sequence_lines(res):
+            print(line)
+    if getattr(args, "visibility", False):
+        for line in visibility.report_lines(res):
             print(line)
     if occ is not None:
         for line in evaluate.occlusion_lines(ds, res):

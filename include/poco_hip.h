@@ -473,6 +473,16 @@ int poco_dataset_crop_occ(const unsigned char* const* d_images, const int* d_img
                           const poco_dataset_crop_param_t* h_params, int N, int res, int normalize, const unsigned char* d_atlas,
                           long long atlas_texels, const poco_occluder_t* d_occluders, const poco_occluder_t* h_occluders, int n_occluders,
                           const poco_occ_record_t* d_occ, const poco_occ_record_t* h_occ, float* d_out, int* d_cover, void* stream);
+/* poco_dataset_crop_occ with one more output (eval.py --visibility --aug_occlude): d_mask uint8 [N,res,res] <-
+ * 1 where a pasted texel with alpha > 0 touched the pixel - the condition d_cover counts, so a crop's mask sums to its cells - and 0
+ * elsewhere; every byte is written, by the same launch, and it may not be null (else POCO_ERR_ARG, as for every argument
+ * poco_dataset_crop_occ refuses).  A third instantiation of the one kernel body: d_out and d_cover are bit for bit what
+ * poco_dataset_crop_occ gives, and the two older entries keep their own kernels. */
+int poco_dataset_crop_occ_mask(const unsigned char* const* d_images, const int* d_img_hw, int n_images,
+                               const poco_dataset_crop_param_t* d_params, const poco_dataset_crop_param_t* h_params, int N, int res,
+                               int normalize, const unsigned char* d_atlas, long long atlas_texels, const poco_occluder_t* d_occluders,
+                               const poco_occluder_t* h_occluders, int n_occluders, const poco_occ_record_t* d_occ,
+                               const poco_occ_record_t* h_occ, float* d_out, int* d_cover, unsigned char* d_mask, void* stream);
 
 /* ---- demo renderer: the uncertainty-coloured SMPL overlay of demo.py --render ----------------------------------------------
  * Replaces pyrender's offscreen render (pocolib/utils/vibe_renderer.py:33-57,88-151) as pocolib/core/tester.py:248-345 (folder
@@ -967,6 +977,37 @@ void poco_pseudo_destroy(poco_pseudo_t p);
 int poco_op_part_labels(const float* d_verts, int B, int V, const float* d_cam_t, const int32_t* d_faces, int F,
                         const unsigned char* d_face_part, float focal, int res, unsigned long long* d_keys, unsigned char* d_labels,
                         void* stream);
+/* poco_op_part_visibility (eval.py --visibility; csrc/part_visibility.hip; tests/visibility_np.py restates it):
+ *   d_counts int32 [B,24,4] <- per crop and body part p the pixel counts (total, area, front, seen).
+ *   d_verts, d_cam_t, d_faces, d_face_part, focal, res: as for poco_op_part_labels, and so are the camera, the pixel-centre sampling,
+ *   the coverage rule (both windings filled), the face exclusions (a non-finite vertex, Z < 0.1, zero area, an index outside
+ *   [0, V)) and the depth rule (the nearest fragment wins, at equal depth the lower face index).  A fragment is a covered centre
+ *   whose interpolated depth is finite and positive, as poco_op_part_labels draws it.
+ *   Window and frame: the frame is the crop, the pixel lattice [0, res)^2; the window is the lattice [-margin, res + margin)^2,
+ *   0 <= margin <= res.  A face is walked over its bounding box clipped to the WINDOW: body outside the window is not counted at
+ *   all, so `margin` bounds the truncation that can be measured - a part of which more than the margin lies beyond the crop's
+ *   border has a `total` that is too small and a vis_frame = area / total that is too large.
+ *     total[p]  window pixel centres covered by at least one fragment of part p.  No depth test; a centre covered by several faces
+ *               of p (front and back surface, faces that meet in an edge) counts once.
+ *     area[p]   the same count restricted to the frame.
+ *     front[p]  frame pixels whose nearest fragment belongs to part p = the pixels with label p + 1 in poco_op_part_labels' output
+ *               for the same input.
+ *     seen[p]   the front pixels at which d_occ_mask (uint8 [B,res,res], e.g. poco_dataset_crop_occ_mask's) is 0; NULL = all zeros.
+ *   A part that covers nothing gives four zeros.  seen <= front <= area <= total.
+ *   h_face_part: the host copy of d_face_part, or NULL.  Given, a part above 23 is POCO_ERR_ARG; the kernel clamps a part above 23
+ *   to 23 either way, so it is memory-safe for any device content (indices, parts, vertices, mask).
+ *   d_scratch: poco_op_part_visibility_scratch_bytes(B, res, margin) bytes, 8-byte aligned, set and consumed by the call (the depth
+ *   keys of the frame, then one 32-bit word of part bits per window pixel); the helper returns 0 for arguments the operator refuses.
+ *   POCO_ERR_ARG before any GPU work, outputs untouched: a null pointer (but h_face_part, d_occ_mask), B outside 1..65535, V or F
+ *   outside 1..2^24, res outside 1..4096, margin outside 0..res, a focal that is not finite and > 0, a misaligned scratch.
+ *   Three memsets (keys, bits, counts) and two launches (per (crop, face): atomicOr of 1 << part per covered window pixel, atomicMin
+ *   of the depth key per covered frame pixel; per window pixel: wave ballots and popcounts, one global integer add per (part,
+ *   counter) and block) on `stream`; no allocation, no synchronisation.  Every output word is written; integer sums, so two runs
+ *   give equal bits. */
+size_t poco_op_part_visibility_scratch_bytes(int B, int res, int margin);
+int poco_op_part_visibility(const float* d_verts, int B, int V, const float* d_cam_t, const int32_t* d_faces, int F,
+                            const unsigned char* d_face_part, const unsigned char* h_face_part, float focal, int res, int margin,
+                            const unsigned char* d_occ_mask, void* d_scratch, int32_t* d_counts, void* stream);
 /* geometry.py:511-551 estimate_translation_np per crop: d_cam_t [B,3] <- the translation that brings d_joints3d [B,J,3] closest to
  * d_joints2d [B,J,3] = (x, y, confidence) in crop pixels under the camera above, by the weighted 3x3 normal equations.  The weight
  * sqrt(confidence) is taken in float32 as the reference takes it; products and sums are fp64, added in joint order; the system is

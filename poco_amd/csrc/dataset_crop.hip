@@ -21,6 +21,8 @@
 // the decimation tables are derived on the fly in double, the accumulation is cv2's float32 sequence with no contraction - then blends
 // as paste_over does.  No scratch image of resized occluders exists: each resized texel is used by exactly one pixel.  The two entries
 // share one kernel body; the plain one instantiates it without the occluder code and keeps its arguments and arithmetic.
+// poco_dataset_crop_occ_mask is a third instantiation: it also stores, per pixel, whether a pasted texel with
+// alpha > 0 touched it - the condition `cover` counts - as one byte of a [N, res, res] mask.
 #include "../../include/poco_hip.h"
 #include "common.h"
 #include "crop_affine.h"
@@ -38,6 +40,7 @@ struct OccArgs {
   int n_occ;
   const poco_occ_record_t* recs;
   int* cover;                                // [N, groups^2] or null
+  unsigned char* mask;                       // [N, res, res]: written by the DC_OCC_MASK instantiation only
 };
 
 // One axis of cv::computeResizeAreaTab (opencv/modules/imgproc/src/resize.cpp) for destination index d: the entries are the
@@ -128,11 +131,15 @@ __device__ unsigned int resized_texel(const OccArgs& oa, long long off, int h, i
   return byte_of(sum[0]) | (byte_of(sum[1]) << 8) | (byte_of(sum[2]) << 16) | (byte_of(sum[3]) << 24);
 }
 
-template <bool OCC>
+// which of the three kernels the body is instantiated for: the plain crop, the crop with occluders, and that with the mask output
+constexpr int DC_PLAIN = 0, DC_OCC = 1, DC_OCC_MASK = 2;
+
+template <int MODE>
 __device__ __forceinline__ void dataset_crop_body(const unsigned char* const* __restrict__ images, const int* __restrict__ img_hw, int n_images,
                                                   const poco_dataset_crop_param_t* __restrict__ params, float* __restrict__ out, int res,
                                                   int groups_x, int normalize, const OccArgs& oa) {
 #pragma clang fp contract(off)
+  constexpr bool OCC = MODE != DC_PLAIN;
   const int n = blockIdx.y;
   const poco_dataset_crop_param_t p = params[n];
   // (device data cannot be validated on the host: an index outside the table is clamped into it, as poco_crop_normalize_multi does)
@@ -214,6 +221,7 @@ __device__ __forceinline__ void dataset_crop_body(const unsigned char* const* __
           raw[c] = alpha * (float)((texel >> (8 * c)) & 255u) + rest * raw[c];
       }
       touched += hit ? 1 : 0;
+      if (MODE == DC_OCC_MASK) oa.mask[((size_t)n * res + y) * res + x] = hit ? 1 : 0;
     }
     float* o = out + (((size_t)n * 3) * res + y) * res + x;
 #pragma unroll
@@ -239,17 +247,24 @@ __device__ __forceinline__ void dataset_crop_body(const unsigned char* const* __
 __global__ void __launch_bounds__(256)
 dataset_crop_kernel(const unsigned char* const* __restrict__ images, const int* __restrict__ img_hw, int n_images,
                     const poco_dataset_crop_param_t* __restrict__ params, float* __restrict__ out, int res, int groups_x, int normalize) {
-  dataset_crop_body<false>(images, img_hw, n_images, params, out, res, groups_x, normalize, OccArgs{});
+  dataset_crop_body<DC_PLAIN>(images, img_hw, n_images, params, out, res, groups_x, normalize, OccArgs{});
 }
 
 __global__ void __launch_bounds__(256)
 dataset_crop_occ_kernel(const unsigned char* const* __restrict__ images, const int* __restrict__ img_hw, int n_images,
                         const poco_dataset_crop_param_t* __restrict__ params, float* __restrict__ out, int res, int groups_x, int normalize,
                         OccArgs oa) {
-  dataset_crop_body<true>(images, img_hw, n_images, params, out, res, groups_x, normalize, oa);
+  dataset_crop_body<DC_OCC>(images, img_hw, n_images, params, out, res, groups_x, normalize, oa);
 }
 
-// the checks the two entries share; `who` names the entry in the message
+__global__ void __launch_bounds__(256)
+dataset_crop_occ_mask_kernel(const unsigned char* const* __restrict__ images, const int* __restrict__ img_hw, int n_images,
+                             const poco_dataset_crop_param_t* __restrict__ params, float* __restrict__ out, int res, int groups_x,
+                             int normalize, OccArgs oa) {
+  dataset_crop_body<DC_OCC_MASK>(images, img_hw, n_images, params, out, res, groups_x, normalize, oa);
+}
+
+// the checks the entries share; `who` names the entry in the message
 int check_crop_args(const char* who, const void* d_images, const void* d_img_hw, int n_images, const void* d_params,
                     const poco_dataset_crop_param_t* h_params, int N, int res, const void* d_out) {
   const std::string w(who);
@@ -286,12 +301,13 @@ extern "C" int poco_dataset_crop(const unsigned char* const* d_images, const int
   return POCO_OK;
 }
 
-extern "C" int poco_dataset_crop_occ(const unsigned char* const* d_images, const int* d_img_hw, int n_images,
-                                     const poco_dataset_crop_param_t* d_params, const poco_dataset_crop_param_t* h_params, int N, int res,
-                                     int normalize, const unsigned char* d_atlas, long long atlas_texels, const poco_occluder_t* d_occluders,
-                                     const poco_occluder_t* h_occluders, int n_occluders, const poco_occ_record_t* d_occ,
-                                     const poco_occ_record_t* h_occ, float* d_out, int* d_cover, void* stream) {
-  const std::string who = "poco_dataset_crop_occ";
+// poco_dataset_crop_occ (want_mask = false: d_mask is not looked at) and poco_dataset_crop_occ_mask behind one set of checks
+static int crop_occ_entry(const std::string& who, bool want_mask, const unsigned char* const* d_images, const int* d_img_hw, int n_images,
+                          const poco_dataset_crop_param_t* d_params, const poco_dataset_crop_param_t* h_params, int N, int res,
+                          int normalize, const unsigned char* d_atlas, long long atlas_texels, const poco_occluder_t* d_occluders,
+                          const poco_occluder_t* h_occluders, int n_occluders, const poco_occ_record_t* d_occ,
+                          const poco_occ_record_t* h_occ, float* d_out, int* d_cover, unsigned char* d_mask, void* stream) {
+  if (want_mask && !d_mask) { poco_set_error(who + ": null pointer"); return POCO_ERR_ARG; }
   if (!d_atlas || !d_occluders || !h_occluders || !d_occ || !h_occ) { poco_set_error(who + ": null pointer"); return POCO_ERR_ARG; }
   if (reinterpret_cast<uintptr_t>(d_atlas) & 3) { poco_set_error(who + ": the atlas must be 4-byte aligned"); return POCO_ERR_ARG; }
   if (int rc = check_crop_args(who.c_str(), d_images, d_img_hw, n_images, d_params, h_params, N, res, d_out)) return rc;
@@ -330,11 +346,34 @@ extern "C" int poco_dataset_crop_occ(const unsigned char* const* d_images, const
   for (int n0 = 0; n0 < N; n0 += 65535) {             // gridDim.y limit
     const int nn = N - n0 < 65535 ? N - n0 : 65535;
     OccArgs oa{reinterpret_cast<const unsigned int*>(d_atlas), atlas_texels, d_occluders, n_occluders, d_occ + n0,
-               d_cover ? d_cover + (size_t)n0 * groups * groups : nullptr};
-    hipLaunchKernelGGL(dataset_crop_occ_kernel, dim3(groups * groups, nn), dim3(256), 0, (hipStream_t)stream, d_images, d_img_hw, n_images,
-                       d_params + n0, d_out + (size_t)n0 * 3 * res * res, res, groups, normalize ? 1 : 0, oa);
+               d_cover ? d_cover + (size_t)n0 * groups * groups : nullptr, want_mask ? d_mask + (size_t)n0 * res * res : nullptr};
+    if (want_mask)
+      hipLaunchKernelGGL(dataset_crop_occ_mask_kernel, dim3(groups * groups, nn), dim3(256), 0, (hipStream_t)stream, d_images, d_img_hw,
+                         n_images, d_params + n0, d_out + (size_t)n0 * 3 * res * res, res, groups, normalize ? 1 : 0, oa);
+    else
+      hipLaunchKernelGGL(dataset_crop_occ_kernel, dim3(groups * groups, nn), dim3(256), 0, (hipStream_t)stream, d_images, d_img_hw, n_images,
+                         d_params + n0, d_out + (size_t)n0 * 3 * res * res, res, groups, normalize ? 1 : 0, oa);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { poco_set_error(who + ": " + hipGetErrorString(e)); return POCO_ERR_HIP; }
   return POCO_OK;
+}
+
+extern "C" int poco_dataset_crop_occ(const unsigned char* const* d_images, const int* d_img_hw, int n_images,
+                                     const poco_dataset_crop_param_t* d_params, const poco_dataset_crop_param_t* h_params, int N, int res,
+                                     int normalize, const unsigned char* d_atlas, long long atlas_texels, const poco_occluder_t* d_occluders,
+                                     const poco_occluder_t* h_occluders, int n_occluders, const poco_occ_record_t* d_occ,
+                                     const poco_occ_record_t* h_occ, float* d_out, int* d_cover, void* stream) {
+  return crop_occ_entry("poco_dataset_crop_occ", false, d_images, d_img_hw, n_images, d_params, h_params, N, res, normalize, d_atlas,
+                        atlas_texels, d_occluders, h_occluders, n_occluders, d_occ, h_occ, d_out, d_cover, nullptr, stream);
+}
+
+extern "C" int poco_dataset_crop_occ_mask(const unsigned char* const* d_images, const int* d_img_hw, int n_images,
+                                          const poco_dataset_crop_param_t* d_params, const poco_dataset_crop_param_t* h_params, int N,
+                                          int res, int normalize, const unsigned char* d_atlas, long long atlas_texels,
+                                          const poco_occluder_t* d_occluders, const poco_occluder_t* h_occluders, int n_occluders,
+                                          const poco_occ_record_t* d_occ, const poco_occ_record_t* h_occ, float* d_out, int* d_cover,
+                                          unsigned char* d_mask, void* stream) {
+  return crop_occ_entry("poco_dataset_crop_occ_mask", true, d_images, d_img_hw, n_images, d_params, h_params, N, res, normalize, d_atlas,
+                        atlas_texels, d_occluders, h_occluders, n_occluders, d_occ, h_occ, d_out, d_cover, d_mask, stream);
 }

@@ -244,6 +244,13 @@ void launch_part_labels(const float* verts, int B, int V, const float* cam_t, co
 constexpr int POCO_EST_MAX_JOINTS = 64;
 void launch_estimate_translation(const float* j3d, const float* j2d, int B, int J, float focal, int res, float* cam_t, hipStream_t s);
 
+// ---- per-part visibility counts (part_visibility.hip) ---------------------------------------------------------------
+// counts int32 [B,24,4] += (total, area, front, seen) of every part: they must be zero on entry, as bits [B, (res + 2 margin)^2];
+// keys [B*res*res] must hold all ones; occ_mask uint8 [B,res,res] or null.
+void launch_part_visibility(const float* verts, int B, int V, const float* cam_t, const int* faces, int F, const unsigned char* face_part,
+                            float focal, int res, int margin, const unsigned char* occ_mask, unsigned long long* keys, unsigned int* bits,
+                            int* counts, hipStream_t s);
+
 // ---- segmentation scoring (segm_metrics.hip) ---------------------------------------------------------------------
 constexpr int POCO_SEGM_MAX_CLASSES = 32;
 // label rows one block owns / blocks per crop = ceil(H / rows); dynamic LDS bytes of a launch

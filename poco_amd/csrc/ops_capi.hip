@@ -931,6 +931,40 @@ extern "C" int poco_op_part_labels(const float* d_verts, int B, int V, const flo
   return POCO_OK;
 }
 
+// ---- per-part visibility counts (part_visibility.hip) ----------------------------------------------------------------------
+extern "C" size_t poco_op_part_visibility_scratch_bytes(int B, int res, int margin) {
+  if (B < 1 || B > 65535 || res < 1 || res > 4096 || margin < 0 || margin > res) return 0;
+  const size_t W = (size_t)res + 2 * (size_t)margin;
+  return (size_t)B * ((size_t)res * res * sizeof(unsigned long long) + W * W * sizeof(unsigned int));
+}
+
+extern "C" int poco_op_part_visibility(const float* d_verts, int B, int V, const float* d_cam_t, const int32_t* d_faces, int F,
+                                       const unsigned char* d_face_part, const unsigned char* h_face_part, float focal, int res,
+                                       int margin, const unsigned char* d_occ_mask, void* d_scratch, int32_t* d_counts, void* stream) {
+  const char* who = "poco_op_part_visibility";
+  if (!d_verts || !d_cam_t || !d_faces || !d_face_part || !d_scratch || !d_counts)
+    return op_bad(who, "null pointer (only h_face_part and occ_mask may be null)");
+  if (B < 1 || B > 65535 || V < 1 || V > (1 << 24) || F < 1 || F > (1 << 24)) return op_bad(who, "needs 1 <= B <= 65535 and 1 <= V, F <= 2^24");
+  if (res < 1 || res > 4096) return op_bad(who, "res must be in 1..4096");
+  if (margin < 0 || margin > res) return op_bad(who, "margin must be in 0..res");
+  if (!(focal > 0.f) || std::isinf(focal)) return op_bad(who, "needs a finite focal > 0");
+  if (!aligned_to(d_scratch, 8) || !aligned_to(d_counts, 4)) return op_bad(who, "the scratch must be 8-byte, the counts 4-byte aligned");
+  if (h_face_part)
+    for (int f = 0; f < F; ++f)
+      if (h_face_part[f] > 23) return op_bad(who, "face " + std::to_string(f) + " has part " + std::to_string((int)h_face_part[f]) + " (0..23)");
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t key_bytes = (size_t)B * res * res * sizeof(unsigned long long);
+  const size_t W = (size_t)res + 2 * (size_t)margin;
+  unsigned long long* keys = static_cast<unsigned long long*>(d_scratch);
+  unsigned int* bits = reinterpret_cast<unsigned int*>(static_cast<unsigned char*>(d_scratch) + key_bytes);
+  POCO_HIP_CHECK(hipMemsetAsync(keys, 0xFF, key_bytes, s));
+  POCO_HIP_CHECK(hipMemsetAsync(bits, 0, (size_t)B * W * W * sizeof(unsigned int), s));
+  POCO_HIP_CHECK(hipMemsetAsync(d_counts, 0, (size_t)B * 24 * 4 * sizeof(int32_t), s));
+  launch_part_visibility(d_verts, B, V, d_cam_t, d_faces, F, d_face_part, focal, res, margin, d_occ_mask, keys, bits, d_counts, s);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
 extern "C" int poco_op_estimate_translation(const float* d_joints3d, const float* d_joints2d, int B, int J, float focal, int res,
                                             float* d_cam_t, void* stream) {
   if (!d_joints3d || !d_joints2d || !d_cam_t || B < 1 || J < 1 || J > POCO_EST_TRANSLATION_MAX_J || res < 1 || !(focal > 0.f) ||

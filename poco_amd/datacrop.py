@@ -162,6 +162,7 @@ def _bind_occ():
         L.poco_dataset_crop_occ.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
+        L.poco_dataset_crop_occ_mask.argtypes = L.poco_dataset_crop_occ.argtypes[:-1] + [C.c_void_p, C.c_void_p]
         L._datacrop_occ_bound = True
     return L
 
@@ -329,16 +330,20 @@ class OcclusionSpec:
 
 
 def dataset_crop(images: Sequence[torch.Tensor], img_index, params: np.ndarray, res: int = 224, normalize: bool = True,
-                 out: Optional[torch.Tensor] = None, occlusion=None):
+                 out: Optional[torch.Tensor] = None, occlusion=None, want_mask: bool = False):
     """images: uint8 [H_i,W_i,3] RGB tensors on one device; img_index [N]: which of them crop n is cut from (an index outside the
     list is clamped into it by the kernel); params: PARAM_DTYPE [N] (crop_params / batch_params) -> fp32 [N,3,res,res] on that
     device: the normalised crop, or with normalize=False the raw float crop after noise and clamp.
     One small upload (pointer table, image sizes and records in one buffer) and one launch on the current stream.
     occlusion = (OccluderAtlas on the same device, OCC_DTYPE [N] records from occ_records): the synthetic occluders are pasted between
     flip and noise in the same launch (poco_dataset_crop_occ), the records travel in the same upload, and the result is (crops,
-    cover) with cover int32 [N] on the device = the crop's pixels that a pasted texel with alpha > 0 touched."""
+    cover) with cover int32 [N] on the device = the crop's pixels that a pasted texel with alpha > 0 touched.  want_mask=True (with
+    occlusion): the launch is poco_dataset_crop_occ_mask and the result (crops, cover, mask) with mask uint8 [N,res,res] on the device =
+    1 at exactly those pixels."""
     if len(images) < 1:
         raise ValueError("dataset_crop: no image")
+    if want_mask and occlusion is None:
+        raise ValueError("dataset_crop: want_mask needs occlusion (the mask marks the pixels the occluders touched)")
     dev = images[0].device
     for im in images:
         if not (torch.is_tensor(im) and im.is_cuda and im.device == dev and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3
@@ -375,6 +380,15 @@ def dataset_crop(images: Sequence[torch.Tensor], img_index, params: np.ndarray, 
             d = torch.from_numpy(host).to(dev)
             base = d.data_ptr()
             cover = torch.empty((N, groups * groups), dtype=torch.int32, device=dev)
+            if want_mask:
+                mask = torch.empty((N, int(res), int(res)), dtype=torch.uint8, device=dev)
+                check(_bind_occ().poco_dataset_crop_occ_mask(
+                    C.c_void_p(base), C.c_void_p(base + 8 * n_img), n_img, C.c_void_p(base + 16 * n_img), C.c_void_p(params.ctypes.data), N,
+                    int(res), int(bool(normalize)), C.c_void_p(atlas.d_atlas.data_ptr()), atlas.texels, C.c_void_p(atlas.d_table.data_ptr()),
+                    C.c_void_p(atlas.table.ctypes.data), len(atlas.table), C.c_void_p(base + 16 * n_img + 48 * N), C.c_void_p(occ.ctypes.data),
+                    C.c_void_p(out.data_ptr()), C.c_void_p(cover.data_ptr()), C.c_void_p(mask.data_ptr()),
+                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "poco_dataset_crop_occ_mask")
+                return out, cover.sum(dim=1, dtype=torch.int32), mask
             check(_bind_occ().poco_dataset_crop_occ(
                 C.c_void_p(base), C.c_void_p(base + 8 * n_img), n_img, C.c_void_p(base + 16 * n_img), C.c_void_p(params.ctypes.data), N, int(res),
                 int(bool(normalize)), C.c_void_p(atlas.d_atlas.data_ptr()), atlas.texels, C.c_void_p(atlas.d_table.data_ptr()),

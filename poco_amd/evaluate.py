@@ -294,6 +294,9 @@ class EvalDataset:
         if occlude is not None and crop != "dataset":
             raise ValueError("synthetic occluders need crop='dataset' (they are pasted inside the dataset crop's launch)")
         self.crop, self.res, self.occlude = crop, int(res), occlude
+        # want_occ_mask: set by the visibility step; with occluders, batch() then leaves the batch's mask uint8 [n,res,res] of the
+        # pixels they touched in last_occ_mask (None without occluders), on the device
+        self.want_occ_mask, self.last_occ_mask = False, None
         z = np.load(path, allow_pickle=False)
         self.gt_form = check_dataset_keys(z.files)
         if occlude is not None:
@@ -379,7 +382,13 @@ class EvalDataset:
         idx = [slot[nm] for nm in names]
         params = datacrop.batch_params(self.center[lo:hi], self.scale[lo:hi], self.aug_rot[lo:hi], self.aug_flip[lo:hi], self.aug_pn[lo:hi],
                                        self.aug_scale[lo:hi], self.res)
-        if self.occlude is not None:
+        self.last_occ_mask = None
+        if self.occlude is not None and self.want_occ_mask:
+            # eval.py --visibility: the same crops and cover from the launch that also writes the per-pixel mask
+            img, cover, self.last_occ_mask = datacrop.dataset_crop(images, idx, params, self.res, True, want_mask=True,
+                                                                   occlusion=(self.occlude.atlas(device), self.occ_records[lo:hi]))
+            self._occ_pending.append((lo, hi, cover))
+        elif self.occlude is not None:
             img, cover = datacrop.dataset_crop(images, idx, params, self.res, True,
                                                occlusion=(self.occlude.atlas(device), self.occ_records[lo:hi]))
             self._occ_pending.append((lo, hi, cover))
@@ -424,14 +433,17 @@ class EvalDataset:
 @torch.no_grad()
 def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
              sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_records: bool = False,
-             likelihood: bool = False, rank_metrics: Optional[int] = None) -> Dict[str, object]:
+             likelihood: bool = False, rank_metrics: Optional[int] = None, visibility=None) -> Dict[str, object]:
     """trainer.py:298-336 over a whole dataset: forward, then the metrics of every batch (the ragged last one included) on the
     device.  SMPL ground truth: gt_vertices = POCO.smpl_lbs(shape, poco_op_rodrigues(pose)) (base_dataset.py:353-366, neutral
     model), also on the device.  Returns Evaluator.finish() plus `imgname`.  likelihood=True (needs `pose` in the dataset and
     cond_layer in the checkpoint): also the held-out flow NLL of every batch on the same stream (LikelihoodAccumulator: val_nll,
     val_log_phi, val_log_sigma, log_phi / log_sigma / bar_pose [N,24]) and Evaluator.uncert_summary() (val_mpjpe_var, val_var).
     rank_metrics=K (eval.py --rank_metrics --rank_bins K): also ranking.RankMetrics of the records with K cuts - the
-    ranking.RANK_NPZ_KEYS arrays; everything else is what it is without the argument."""
+    ranking.RANK_NPZ_KEYS arrays; everything else is what it is without the argument.
+    visibility (eval.py --visibility): a visibility.VisibilityEval from visibility.prepare(); behind the metrics of every batch, on
+    the same stream, it counts the visible pixels of every body part of the ground-truth mesh; the result gains the
+    visibility.NPZ_KEYS arrays and `vis_stats`.  Needs SMPL ground truth; without the argument nothing changes."""
     from . import ops
     dev = model.device
     ev = Evaluator(J_regressor, joint_map(dataset.name), capacity=len(dataset), sel_uncert_part=sel_uncert_part, kinematic=kinematic,
@@ -447,8 +459,10 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
         if lk is not None:
             lk.step(out, gt_pose)
         if dataset.gt_form == "smpl":
-            gt_verts, _ = model.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))
+            gt_verts, gt_j49 = model.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))
             ev.step(out, gt_pose, gt_vertices=gt_verts)
+            if visibility is not None:
+                visibility.step(lo, hi, gt_verts, gt_j49, dataset.last_occ_mask)
         else:
             ev.step(out, gt_pose, gt_joints=t(dataset.joints[lo:hi]))
     res = ev.finish(save_results=save_results, return_records=return_records)
@@ -458,6 +472,8 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
     if rank_metrics is not None:
         from .ranking import RankMetrics
         res.update(RankMetrics(ev, int(rank_metrics)).result)
+    if visibility is not None:
+        res.update(visibility.finish(res["corr_x"], res["corr_y"]))
     model.check_status()
     res["imgname"] = np.asarray(dataset.imgname)
     ev.close()

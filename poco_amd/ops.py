@@ -434,6 +434,62 @@ def part_labels(verts: torch.Tensor, cam_t: torch.Tensor, faces: torch.Tensor, f
     return out
 
 
+VIS_TOTAL, VIS_AREA, VIS_FRONT, VIS_SEEN = 0, 1, 2, 3      # the last axis of part_visibility's counts
+
+
+def part_visibility_scratch_bytes(B: int, res: int, margin: int) -> int:
+    """poco_op_part_visibility_scratch_bytes: the scratch a call needs; 0 for a shape the operator refuses."""
+    L = lib()
+    L.poco_op_part_visibility_scratch_bytes.restype = C.c_size_t
+    return int(L.poco_op_part_visibility_scratch_bytes(int(B), int(res), int(margin)))
+
+
+def part_visibility(verts: torch.Tensor, cam_t: torch.Tensor, faces: torch.Tensor, face_part: torch.Tensor, focal: float = 5000.0,
+                    res: int = 224, margin: int = 112, occ_mask: torch.Tensor = None, out: torch.Tensor = None,
+                    scratch: torch.Tensor = None, h_face_part=None) -> torch.Tensor:
+    """poco_op_part_visibility: verts [B,V,3], cam_t [B,3] fp32, faces int32 [F,3], face_part uint8 [F] -> counts int32 [B,24,4] =
+    (total, area, front, seen) per crop and part: pixels of the part in the window [-margin, res + margin)^2, of those inside the
+    crop, of those nearest to the camera, of those where occ_mask (uint8 [B,res,res] or None = nothing occluded) is 0.
+    `out`: a contiguous int32 [B,24,4] view to write into; `scratch`: a uint8 tensor of at least part_visibility_scratch_bytes
+    bytes (allocated here when None); h_face_part: the host copy of face_part (numpy uint8 [F]) for the argument check.
+    Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"part_visibility: {what}")
+    need(torch.is_tensor(verts) and verts.is_cuda and verts.dtype == torch.float32 and verts.dim() == 3 and verts.shape[2] == 3,
+         "verts must be a CUDA float32 tensor [B,V,3]")
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    need(torch.is_tensor(cam_t) and cam_t.is_cuda and cam_t.dtype == torch.float32 and tuple(cam_t.shape) == (B, 3), "cam_t must be a CUDA float32 tensor [B,3]")
+    need(torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3,
+         "faces must be a CUDA int32 tensor [F,3]")
+    F = int(faces.shape[0])
+    face_part = _u8(face_part, "face_part")
+    need(tuple(face_part.shape) == (F,), "face_part must be [F]")
+    res, margin = int(res), int(margin)
+    nbytes = part_visibility_scratch_bytes(B, res, margin)
+    need(nbytes > 0, f"needs 1 <= B <= 65535, 1 <= res <= 4096 and 0 <= margin <= res, got B {B}, res {res}, margin {margin}")
+    if occ_mask is not None:
+        occ_mask = _u8(occ_mask, "occ_mask")
+        need(tuple(occ_mask.shape) == (B, res, res), f"occ_mask must be [{B},{res},{res}], got {tuple(occ_mask.shape)}")
+    if out is None:
+        out = torch.empty((B, 24, 4), device=verts.device, dtype=torch.int32)
+    need(out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (B, 24, 4), "out must be a contiguous CUDA int32 [B,24,4]")
+    if scratch is None:
+        scratch = torch.empty(nbytes, device=verts.device, dtype=torch.uint8)
+    need(scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= nbytes,
+         f"scratch must be a contiguous CUDA uint8 tensor of at least {nbytes} bytes")
+    hfp = None
+    if h_face_part is not None:
+        hfp = np.ascontiguousarray(np.asarray(h_face_part, np.uint8).reshape(-1))
+        need(hfp.shape[0] == F, "h_face_part must be [F]")
+    check(lib().poco_op_part_visibility(fptr(verts.contiguous()), B, V, fptr(cam_t.contiguous()), iptr(faces.contiguous()), F,
+                                        C.c_void_p(face_part.data_ptr()), C.c_void_p(hfp.ctypes.data if hfp is not None else 0),
+                                        C.c_float(focal), res, margin, C.c_void_p(occ_mask.data_ptr() if occ_mask is not None else 0),
+                                        C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), current_stream()),
+          "poco_op_part_visibility")
+    return out
+
+
 def estimate_translation(joints3d: torch.Tensor, joints2d: torch.Tensor, focal: float = 5000.0, res: int = 224) -> torch.Tensor:
     """poco_op_estimate_translation: joints3d [B,J,3], joints2d [B,J,3] = (x, y, confidence) in crop pixels -> cam_t [B,3]."""
     assert joints3d.is_cuda and joints3d.dtype == torch.float32 and joints3d.dim() == 3 and joints3d.shape[2] == 3

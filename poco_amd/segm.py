@@ -255,12 +255,13 @@ class SegmEval:
 @torch.no_grad()
 def run_eval(model, dataset, dataset_path: str, J_regressor, smpl_path: str, part_mapping: Optional[str] = None, batch_size: int = 64,
              kinematic: bool = True, save_results: bool = False, likelihood: bool = False, uncert_threshold: Optional[float] = None,
-             res: int = 224, return_labels: bool = False) -> Dict[str, object]:
+             res: int = 224, return_labels: bool = False, visibility=None) -> Dict[str, object]:
     """eval.py --segm: evaluate.run_eval's loop (trainer.py:298-336) with the forward asked for pred_segm_mask and, behind the
     metrics of every batch on the same stream, the segmentation step.  dataset: the evaluate.EvalDataset of dataset_path (SMPL
     ground truth); its `part` rows are read here, restricted like the dataset's own rows.  Returns run_eval's result plus
     SegmAccumulator.finish() and `segm_summary` = [CE, pixel accuracy, mIoU, mIoU without background]; with save_results the
-    per-crop records `segm_ce` / `segm_counts`; with return_labels `segm_labels` uint8 [N,res,res] (tests)."""
+    per-crop records `segm_ce` / `segm_counts`; with return_labels `segm_labels` uint8 [N,res,res] (tests).  visibility: as
+    evaluate.run_eval's (eval.py --visibility --segm)."""
     from . import evaluate
     if dataset.gt_form != "smpl" or dataset.shape is None:
         raise ValueError("--segm needs SMPL ground truth (`pose` and `shape`) in the dataset")
@@ -290,6 +291,8 @@ def run_eval(model, dataset, dataset_path: str, J_regressor, smpl_path: str, par
         gt_verts, gt_j49 = model.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))
         ev.step(out, gt_pose, gt_vertices=gt_verts)
         sg.step(out, gt_verts, gt_j49, part[lo:hi])
+        if visibility is not None:
+            visibility.step(lo, hi, gt_verts, gt_j49, dataset.last_occ_mask)
         if return_labels:
             labels.append(sg.last_labels)
     out = ev.finish(save_results=save_results)
@@ -297,6 +300,8 @@ def run_eval(model, dataset, dataset_path: str, J_regressor, smpl_path: str, par
         out.update(ev.uncert_summary())
         out.update(lk.finish())
     out.update(sg.finish(save_results))
+    if visibility is not None:
+        out.update(visibility.finish(out["corr_x"], out["corr_y"]))
     model.check_status()
     out["segm_summary"] = np.array([out["val_segm_ce"], out["val_segm_pixel_acc"], out["val_segm_miou"], out["val_segm_miou_fg"]], np.float64)
     out["imgname"] = np.asarray(dataset.imgname)
