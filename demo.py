@@ -50,6 +50,14 @@ solved matrix taken back onto SO(3); betas and orig_cam are smoothed with the ro
 (poco_amd/usmooth.py, csrc/track_smooth.hip).  The result gains smooth_shift [T,24] (degrees) and pose_net /
 betas_net / orig_cam_net; var stays as regressed.  After --infill it works on the in-filled pose.  Not with --smooth (two
 smoothers) and not with --gpus N > 1.
+--kp_refit LAMBDA (video mode, keypoint tracks) refits the joints the model doubts to the track's own BODY_25 keypoints on the GPU:
+per frame a Levenberg-Marquardt fit of the 24 joint rotations and the weak-perspective camera to the 14 body keypoints above
+--kp_vis_thresh, the network's pose being the prior and each joint held by its precision LAMBDA (--kp_refit_ref / var)^2, residuals in
+fractions of the box side under a Geman-McClure robustifier of width --kp_refit_rho (<= 0: off), --kp_refit_iters steps; shape is
+kept, every fitted frame is re-posed (poco_amd/refit.py, csrc/kp_refit.hip).  It runs first, on the finished
+unsmoothed tracks; --infill, then --smooth_uncert or --smooth take what it left.  The result gains refit_shift [T,24] (degrees),
+refit_cost [T,2], refit_flag [T] (0 fitted, 1 too few keypoints, 2 non-finite input) and pose_net / betas_net / orig_cam_net; var
+stays as regressed.  Not with folder, directory or webcam mode, --cfg2 or --gpus N > 1.
 --cfg2 FILE --ckpt2 FILE [--inf_model2 best] [--select crop|joint] [--select_scale S] runs a second model on the same crops on the
 same GPU and lets the uncertainty choose (poco_amd/select.py, csrc/select_regressor.hip): per crop the model
 whose global uncertainty (the reference's get_global_uncert of its own head) is lower, S times the second model's against the
@@ -201,6 +209,15 @@ def parse_args(argv=None):
                    help="--smooth_uncert: the uncertainty (`var`) at which a frame's weight is 1")
     p.add_argument("--smooth_uncert_max_gap", type=int, default=30,
                    help="--smooth_uncert: curvature is not penalised across a hole of more than this many frames")
+    p.add_argument("--kp_refit", type=float, default=None, metavar="LAMBDA",
+                   help="video mode, keypoint tracks: refit every frame's joint rotations and camera to the track's BODY_25 keypoints "
+                        "(made on the GPU, before --infill and the smoothers); LAMBDA > 0 weighs the prior, the network's own pose, each "
+                        "joint by its precision; the result gains refit_shift, refit_cost, refit_flag, pose_net, betas_net and "
+                        "orig_cam_net")
+    p.add_argument("--kp_refit_ref", type=float, default=0.3, help="--kp_refit: the uncertainty (`var`) at which a joint's prior weight is LAMBDA")
+    p.add_argument("--kp_refit_rho", type=float, default=0.1,
+                   help="--kp_refit: width of the Geman-McClure robustifier in fractions of the box side (<= 0: plain least squares)")
+    p.add_argument("--kp_refit_iters", type=int, default=10, help="--kp_refit: Levenberg-Marquardt steps per frame, 1..32")
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
@@ -326,6 +343,14 @@ def _check_smooth_uncert(args) -> None:
         sys.exit(f"--smooth_uncert_max_gap must be >= 1, got {gap}")
 
 
+def _check_kp_refit(args) -> None:
+    """--kp_refit and its three companions: refuse what cannot work before the engine is built."""
+    from poco_amd.refit import flag_error
+    msg = flag_error(args, "demo")
+    if msg:
+        sys.exit(msg)
+
+
 def _check_segm(args) -> None:
     """--save_segm: refuse video mode, a head without a segmentation mask, a body model without triangles and an unreadable
     --part_mapping before the engine is built."""
@@ -372,6 +397,7 @@ def main(args):
     _check_segm(args)
     _check_infill(args)
     _check_smooth_uncert(args)
+    _check_kp_refit(args)
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")
@@ -404,6 +430,11 @@ def main(args):
             tracking = load_tracking(tracking, **tracking_options(args))
         except ValueError as e:
             sys.exit(str(e))
+    if getattr(args, "kp_refit", None) is not None:                       # every track needs BODY_25 keypoints: a box track ends here
+        from poco_amd.refit import tracking_error
+        msg = tracking_error(tracking)
+        if msg:
+            sys.exit(msg)
     tester = POCOTester(args)
     out_dir = os.path.join(args.output_folder, stem + "_")
     if args.mode == "video":

@@ -53,6 +53,14 @@ visibility per joint, Pearson's and Spearman's Corr(1 - visibility, uncertainty)
 self-occlusion and object occlusion, Corr(1 - visibility, per-joint error), and uncertainty and error over K visibility bins (default
 5); the .npz gains vis_counts, vis, vis_summary, vis_joint and vis_bins.  Needs `pose`, `shape` and `part`; works for every model and
 with --crop dataset, --aug_*, --augment, --segm and --part_mapping.  Not with --cfg2, --tta, --sequences, --rank_metrics or --likelihood.
+--kp_refit LAMBDA [--kp_refit_ref 0.3] [--kp_refit_rho 0.1] [--kp_refit_iters 10] [--kp_vis_thresh 0.3] asks what the keypoint
+refit of demo.py's video mode does to the error against ground truth: per batch every row's joint rotations and camera are refitted
+on the GPU to the dataset's `openpose` [N,25,3] BODY_25 keypoints (the pseudo-GT files of demo.py --save_dataset carry them), the
+network's pose being the prior and each joint held by its precision LAMBDA (ref / var)^2 (poco_amd/refit.py, csrc/kp_refit.hip,
+DESIGN.md section 31); camera and norm come from pred_cam, center and scale; the refitted pose is re-posed and the raw prediction
+and the refit are scored side by side: the usual lines for each, their difference, the mean shift and r(shift, var).  The .npz
+gains mpjpe_raw / pampjpe_raw / v2v_raw / val_*_raw, refit_shift, refit_cost and refit_flag.  Not with --cfg2, --tta, --segm,
+--likelihood, --sequences, --rank_metrics, --visibility, --aug_* or --augment.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -155,6 +163,16 @@ def parse_args(argv=None):
                    help="with --visibility: pixels around the crop in which the body still counts, 0..res (default res / 2); it bounds "
                         "the truncation that can be measured")
     p.add_argument("--vis_bins", type=int, default=None, metavar="K", help="with --visibility: bins of the table, 2..20 (default 5)")
+    p.add_argument("--kp_refit", type=float, default=None, metavar="LAMBDA",
+                   help="also refit every row's joint rotations and camera to the dataset's `openpose` BODY_25 keypoints on the GPU "
+                        "(poco_amd/refit.py, csrc/kp_refit.hip), the network's pose being the prior, each joint held by its precision "
+                        "LAMBDA (ref / var)^2, and score the raw prediction and the refit side by side; the .npz gains *_raw, "
+                        "refit_shift, refit_cost and refit_flag")
+    p.add_argument("--kp_refit_ref", type=float, default=0.3, help="--kp_refit: the uncertainty at which a joint's prior weight is LAMBDA")
+    p.add_argument("--kp_refit_rho", type=float, default=0.1,
+                   help="--kp_refit: width of the Geman-McClure robustifier in fractions of the box side (<= 0: plain least squares)")
+    p.add_argument("--kp_refit_iters", type=int, default=10, help="--kp_refit: Levenberg-Marquardt steps per row, 1..32")
+    p.add_argument("--kp_vis_thresh", type=float, default=0.3, help="--kp_refit: the confidence a keypoint needs to count")
     p.add_argument("--min_cutoff", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 0.004)")
     p.add_argument("--beta", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 1.5)")
     return p.parse_args(argv)
@@ -306,6 +324,23 @@ def check_tta(args) -> None:
         sys.exit(msg)
 
 
+def check_kp_refit(args) -> None:
+    """--kp_refit and its companions: refuse what cannot work before an engine is built - the flags it excludes, options out of
+    range, a dataset file without `openpose`."""
+    from poco_amd.refit import flag_error
+    msg = flag_error(args, "eval")
+    if msg:
+        sys.exit(msg)
+    if getattr(args, "kp_refit", None) is not None and os.path.isfile(args.dataset):
+        import numpy as np
+        with np.load(args.dataset, allow_pickle=False) as z:
+            if "openpose" not in z.files:
+                sys.exit(f"{args.dataset}: --kp_refit fits the rows to their 2-D keypoints, but the file has no `openpose` [N,25,3] "
+                         "(demo.py --save_dataset writes it)")
+            if z["openpose"].shape[1:] != (25, 3):
+                sys.exit(f"{args.dataset}: --kp_refit maps BODY_25 keypoints only, but `openpose` is {tuple(z['openpose'].shape)}, not [N,25,3]")
+
+
 def check_sequences(args) -> None:
     """--sequences / --seq_*: refuse what cannot work before an engine is built - the flags it excludes, an unreadable --seq_post,
     and a dataset whose image names do not group into tracks."""
@@ -358,6 +393,7 @@ def main(args):
     check_select(args)
     check_tta(args)
     check_rank(args)
+    check_kp_refit(args)
     check_dataset_file(args.dataset)
     aug = augmentation_spec(args)
     occ = occlusion_spec(args)
@@ -415,6 +451,12 @@ def main(args):
     elif tester.pair is not None:
         res = evaluate.run_eval_pair(tester.pair, ds, J, batch_size=max(int(args.batch_size), 1),
                                      kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
+    elif getattr(args, "kp_refit", None) is not None:
+        from poco_amd import refit
+        res = evaluate.run_eval_refit(tester.model, ds, J, refit.joint_tables(args.smpl), float(args.kp_refit), float(args.kp_refit_ref),
+                                      float(args.kp_refit_rho), float(args.kp_vis_thresh), int(args.kp_refit_iters),
+                                      batch_size=max(int(args.batch_size), 1), kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT),
+                                      save_results=args.save_results)
     elif getattr(args, "sequences", False):
         from poco_amd.sequences import parse_pipelines
         opt = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)   # noqa: E731
@@ -434,6 +476,8 @@ def main(args):
     lines = evaluate.pair_report_lines(res, tester.pair.mode) if tester.pair is not None else evaluate.report_lines(res)
     if tester.tta is not None:
         lines = evaluate.tta_report_lines(res)
+    if getattr(args, "kp_refit", None) is not None:
+        lines = evaluate.refit_report_lines(res)
     for line in (evaluate.likelihood_lines(res) if args.likelihood else []) + lines:
         print(line)
     if getattr(args, "segm", False):

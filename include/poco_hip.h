@@ -1228,6 +1228,53 @@ int poco_op_track_smooth(const float* d_pose, const float* d_u, const int32_t* d
                          const float* d_lin, int L, double lam, double u_ref, int max_gap, double* d_scratch, float* d_pose_out,
                          float* d_lin_out, float* d_shift, int max_blocks, void* stream);
 
+/* ---- the keypoint refit: uncertain joints follow the row's 2-D keypoints, the network's own pose is the prior --------------------------
+ * demo.py --mode video --kp_refit LAMBDA, eval.py --kp_refit LAMBDA; csrc/kp_refit.hip; poco_amd/refit.py; DESIGN.md section 31;
+ * tests/refit_np.py restates it in float64 numpy with dense matrices and numpy.linalg.cholesky.  No counterpart in the reference
+ * (its demo keeps VIBE's smplify_runner, whose TemporalSMPLify is not in its tree).
+ *
+ * poco_op_kp_refit: N independent rows (frames of any tracks, crops of any images).  Device inputs: d_pose [N,24,3,3] (the network's
+ *   local joint rotations), d_u [N,24] (the post-processed uncertainty), d_jrest [N,24,3] (the rest-pose joints J(beta) of the row's
+ *   shape; betas are not optimised), d_kp [N,K,3] (x, y, confidence, any pixel frame), d_cam [N,5] = (a, tx, ty, px, py) with
+ *   u = a (X + tx) + px, v = a (Y + ty) + py, d_norm [N] (the box side: residuals are fractions of it).  HOST arrays: kp_joint int32
+ *   [K], 1 <= K <= POCO_REFIT_MAX_KP (the kinematic joint a keypoint observes, -1 = none), parents int32 [24] (parents[0] < 0,
+ *   0 <= parents[j] < j).  Scalars: lam > 0, u_ref > 0, rho (<= 0: no robustifier), cam_prior > 0, conf_thresh, min_kp >= 2,
+ *   iters in 1..POCO_REFIT_MAX_ITERS, all finite.
+ *   Unknowns  delta_j in R^3 per joint, applied as R_j <- R_j exp(delta_j) (exp: Rodrigues; |delta| < 1e-8: the series 1 - t^2 / 6,
+ *             1 / 2 - t^2 / 24), and (kappa, dtx, dty) applied as a <- a exp(kappa), tx <- tx + dtx, ty <- ty + dty: 75 in all.
+ *   Model     G_0 = R_0, p_0 = J_0; G_j = G_parent R_j, p_j = p_parent + G_parent (J_j - J_parent); keypoint k observes p_(kp_joint[k]).
+ *             d p_k / d delta_j = -[p_k - p_j]x G_j for j a PROPER ancestor of kp_joint[k] (a joint's own rotation does not move it)
+ *             and zero otherwise; d r / d kappa = (u - px, v - py) / norm, d r / d (dtx, dty) = a / norm on the diagonal.
+ *   Cost      F = sum_k gm(c_k |r_k|^2) + sum_j w_j |q_j|^2 + cam_prior (kappa^2 + dtx^2 + dty^2), the camera terms being the totals
+ *             since the start; r_k = (proj(p_k) - kp_k) / norm; c_k = the confidence if it exceeds conf_thresh and kp_joint[k] >= 0,
+ *             else 0; gm(s) = rho^2 s / (rho^2 + s) (Geman-McClure; s itself for rho <= 0); w_j = lam clamp((u_ref / max(u_j,
+ *             1e-6))^2, 1e-6, 1e6), a non-finite u_j giving lam 1e-6 (poco_op_track_smooth's rule); q_j = Log(Rnet_j^T R_j): half the
+ *             skew part of the matrix times angle / |half skew|, angle = atan2(|half skew|, (trace - 1) / 2), the half skew part
+ *             itself below 1e-8.  The sum runs over k, then j, then the camera, in ascending order.
+ *   Step      `iters` Levenberg-Marquardt steps from the network's values, every row all of them (no early exit).  A = J^T W J +
+ *             diag(w_j, cam_prior) with the IRLS weights W_k = c_k (rho^2 / (rho^2 + s_k))^2 at the current point, g = J^T W r +
+ *             (w_j q_j, cam_prior (kappa, dtx, dty)): the prior's Jacobian with respect to delta_j is taken as the identity (first
+ *             order in q_j).  (A + mu diag(A)) d = -g by root-free Cholesky (L D L^T) without pivoting: A is positive definite
+ *             whatever the data, every w_j and cam_prior being positive.  F at the trial point: lower = accepted, mu <- max(mu / 3,
+ *             1e-12); otherwise (a NaN included) the point is kept and mu <- min(3 mu, 1e12); mu starts at 1e-3.
+ *   Skipped   a row with a non-finite value in pose, jrest, kp, cam or norm, or norm <= 0: flag 2; else a row with fewer than min_kp
+ *             keypoints of non-zero c_k: flag 1.  Its pose and (a, tx, ty) are copied through bit for bit, its shift, cost and
+ *             accepted steps are 0.
+ *   Outputs (every element is written; none may overlap an input or another output): d_pose_out [N,24,3,3], d_cam_out [N,3] =
+ *   (a, tx, ty), d_shift [N,24] (degrees between Rnet_j and R_j, poco_op_track_smooth's formula), d_cost [N,2] (F before, after),
+ *   d_info int32 [N,2] (accepted steps, flag: 0 fitted, 1 too few keypoints, 2 non-finite input).
+ *   Arithmetic: fp64 throughout, rounded once to fp32 on store.  One launch on `stream` (a block per row at a time, the row in LDS);
+ *   max_blocks > 0 caps the grid (tests).  No allocation, no synchronisation, no atomics: a row's bits do not depend on the other
+ *   rows, on the grid or on max_blocks, and two runs give the same bits.
+ *   POCO_ERR_ARG before any GPU work: a null pointer, N < 1, 216 N >= 2^31, K outside 1..32, a kp_joint entry outside -1..23, a
+ *   parents table that is not a tree rooted at 0 with parent < child, a scalar out of range, max_blocks < 0, overlapping buffers. */
+#define POCO_REFIT_MAX_KP 32
+#define POCO_REFIT_MAX_ITERS 32
+int poco_op_kp_refit(const float* d_pose, const float* d_u, const float* d_jrest, const float* d_kp, const float* d_cam,
+                     const float* d_norm, int N, int K, const int32_t* kp_joint, const int32_t* parents, double lam, double u_ref,
+                     double rho, double cam_prior, double conf_thresh, int min_kp, int iters, float* d_pose_out, float* d_cam_out,
+                     float* d_shift, float* d_cost, int32_t* d_info, int max_blocks, void* stream);
+
 /* ---- eval.py --sequences: the acceleration and the acceleration error of every row of a ragged buffer of tracks --------------------
  * eval.py --sequences [--seq_post LIST]; csrc/track_accel.hip; poco_amd/sequences.py; tests/accel_np.py
  * restates it in float64 with plain loops.  The acceleration error is compute_error_accel of the VIBE line of work (not in the

@@ -337,6 +337,20 @@ void launch_track_smooth(const float* pose, const float* u, const int* frames, c
                          double lam, double u_ref, int max_gap, double* scratch, float* pose_out, float* lin_out, float* shift,
                          int max_blocks, hipStream_t s);
 
+// ---- the keypoint refit of demo.py / eval.py --kp_refit (kp_refit.hip) ---------------------------------------------------------------
+// include/poco_hip.h poco_op_kp_refit: N independent rows; pose [N,24,3,3], u [N,24], jrest [N,24,3], kp [N,K,3], cam [N,5], norm [N];
+// kp_joint [K] and parents [24] are HOST arrays (checked by the caller: -1..23, parents[j] in [0, j) for j >= 1); outputs pose_out,
+// cam_out [N,3], shift [N,24], cost [N,2], info int32 [N,2].  Rows are dealt to at most KP_REFIT_MAX_BLOCKS blocks of KP_REFIT_THREADS
+// (max_blocks > 0: at most that many) by a grid-stride loop; a block keeps its row in 41 KB of LDS.
+constexpr int KP_REFIT_MAX_BLOCKS = 4096;
+constexpr int KP_REFIT_THREADS = 128;
+constexpr int KP_REFIT_MAX_KP = 32;
+constexpr int KP_REFIT_MAX_ITERS = 32;
+void launch_kp_refit(const float* pose, const float* u, const float* jrest, const float* kp, const float* cam, const float* norm, int N,
+                     int K, const int* kp_joint, const int* parents, double lam, double u_ref, double rho, double cam_prior,
+                     double conf_thresh, int min_kp, int iters, float* pose_out, float* cam_out, float* shift, float* cost, int* info,
+                     int max_blocks, hipStream_t s);
+
 // ---- the temporal metric of eval.py --sequences: acceleration and acceleration error per row (track_accel.hip) -------------------
 // include/poco_hip.h poco_op_track_accel: P tracks = rows [offsets[p], offsets[p + 1]) of N; pred / gt [N,M,3] at a row stride in
 // floats (gt nullable); scratch = TRACK_ACCEL_ROW_DOUBLES doubles per row (acceleration error, acceleration, valid: the fp64 terms

@@ -1180,6 +1180,48 @@ extern "C" int poco_op_track_smooth(const float* d_pose, const float* d_u, const
   return POCO_OK;
 }
 
+// ---- the keypoint refit of demo.py / eval.py --kp_refit (kp_refit.hip) --------------------------------------------------------------
+static_assert(POCO_REFIT_MAX_KP == KP_REFIT_MAX_KP && POCO_REFIT_MAX_ITERS == KP_REFIT_MAX_ITERS,
+              "include/poco_hip.h and csrc/kernels.h disagree on the keypoint refit");
+extern "C" int poco_op_kp_refit(const float* d_pose, const float* d_u, const float* d_jrest, const float* d_kp, const float* d_cam,
+                                const float* d_norm, int N, int K, const int32_t* kp_joint, const int32_t* parents, double lam,
+                                double u_ref, double rho, double cam_prior, double conf_thresh, int min_kp, int iters, float* d_pose_out,
+                                float* d_cam_out, float* d_shift, float* d_cost, int32_t* d_info, int max_blocks, void* stream) {
+  const char* who = "poco_op_kp_refit";
+  if (!d_pose || !d_u || !d_jrest || !d_kp || !d_cam || !d_norm || !kp_joint || !parents || !d_pose_out || !d_cam_out || !d_shift ||
+      !d_cost || !d_info)
+    return op_bad(who, "null pointer (every input, both tables and every output are needed)");
+  if (N < 1 || (long long)N * 216 >= (1LL << 31)) return op_bad(who, "needs N >= 1 and fewer than 2^31 floats of pose");
+  if (K < 1 || K > POCO_REFIT_MAX_KP) return op_bad(who, "K must be in 1..32");
+  for (int k = 0; k < K; ++k)
+    if (kp_joint[k] < -1 || kp_joint[k] > 23) return op_bad(who, "a kp_joint entry must be in -1..23");
+  if (parents[0] >= 0) return op_bad(who, "parents must be a tree rooted at joint 0 (parents[0] < 0)");
+  for (int j = 1; j < 24; ++j)
+    if (parents[j] < 0 || parents[j] >= j) return op_bad(who, "parents must be a tree rooted at joint 0 with parent < child");
+  if (!std::isfinite(lam) || !(lam > 0.0)) return op_bad(who, "lambda must be finite and > 0");
+  if (!std::isfinite(u_ref) || !(u_ref > 0.0)) return op_bad(who, "u_ref must be finite and > 0");
+  if (!std::isfinite(rho)) return op_bad(who, "rho must be finite (<= 0 turns the robustifier off)");
+  if (!std::isfinite(cam_prior) || !(cam_prior > 0.0)) return op_bad(who, "cam_prior must be finite and > 0");
+  if (!std::isfinite(conf_thresh)) return op_bad(who, "conf_thresh must be finite");
+  if (min_kp < 2) return op_bad(who, "min_kp must be >= 2");
+  if (iters < 1 || iters > POCO_REFIT_MAX_ITERS) return op_bad(who, "iters must be in 1..32");
+  if (max_blocks < 0) return op_bad(who, "max_blocks must be >= 0");
+  // [begin, end) in bytes: six inputs, then five outputs, none of which may overlap anything before it
+  const size_t n = (size_t)N;
+  const struct { const void* p; size_t bytes; } buf[11] = {
+      {d_pose, n * 864}, {d_u, n * 96}, {d_jrest, n * 288}, {d_kp, n * (size_t)K * 12}, {d_cam, n * 20}, {d_norm, n * 4},
+      {d_pose_out, n * 864}, {d_cam_out, n * 12}, {d_shift, n * 96}, {d_cost, n * 8}, {d_info, n * 8}};
+  for (int o = 6; o < 11; ++o)
+    for (int i = 0; i < o; ++i) {
+      const uintptr_t a0 = (uintptr_t)buf[o].p, a1 = a0 + buf[o].bytes, b0 = (uintptr_t)buf[i].p, b1 = b0 + buf[i].bytes;
+      if (a0 < b1 && b0 < a1) return op_bad(who, "an output may not overlap an input or another output");
+    }
+  launch_kp_refit(d_pose, d_u, d_jrest, d_kp, d_cam, d_norm, N, K, kp_joint, parents, lam, u_ref, rho, cam_prior, conf_thresh, min_kp,
+                  iters, d_pose_out, d_cam_out, d_shift, d_cost, d_info, max_blocks, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
 // ---- eval.py --sequences: acceleration and acceleration error per row (track_accel.hip) ----------------------------------------
 static_assert(POCO_ACCEL_MAX_JOINTS == TRACK_ACCEL_MAX_JOINTS && POCO_ACCEL_SCRATCH_DOUBLES(1) == TRACK_ACCEL_ROW_DOUBLES,
               "include/poco_hip.h and csrc/kernels.h disagree on the acceleration operator");

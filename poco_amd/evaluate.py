@@ -322,6 +322,8 @@ class EvalDataset:
             raise ValueError("the dataset file has no `img` crops: --img_dir must name the folder its imgname entries are relative to")
         for k in ("gender", "person_id"):
             setattr(self, k, np.asarray(z[k]) if k in z.files else None)
+        # eval.py --kp_refit: the BODY_25 keypoints (x, y, confidence in image pixels) the pseudo-GT files carry
+        self.openpose = np.asarray(z["openpose"], np.float32).reshape(n, 25, 3) if "openpose" in z.files else None
         if crop == "dataset":
             self._init_dataset_crop(z, augment)
 
@@ -769,6 +771,92 @@ def tta_report_lines(res: Dict[str, object]):
     return lines + [f"Corr(view spread, pose distance): {res['val_corr_spread']}"]
 
 
+REFIT_SCALARS = tuple(k + "_raw" for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")) + ("refit_mean_shift", "refit_corr_shift_var")
+
+
+@torch.no_grad()
+def run_eval_refit(model, dataset: EvalDataset, J_regressor, tables, lam: float, u_ref: float = 0.3, rho: float = 0.1,
+                   conf_thresh: float = 0.3, iters: int = 10, batch_size: int = 64, kinematic: bool = True,
+                   sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False) -> Dict[str, object]:
+    """run_eval with the keypoint refit (eval.py --kp_refit): per batch the forward, then refit.refit_rows on the
+    batch's pose, processed uncertainty (trailing axes averaged, accumulated along the tree when `kinematic`) and shape against the
+    dataset's `openpose` keypoints - camera a = s h / 2 from pred_cam, (px, py) = the box centre, norm = h = 200 scale - then LBS of
+    the refitted pose (a row that was not fitted keeps the network's mesh), and two Evaluators stepped against the same ground truth
+    on the same stream: the raw prediction and the refit.  tables = refit.joint_tables(the body model).  Returns the refit's result
+    under run_eval's keys, the raw prediction's mpjpe / pampjpe / v2v and val_* with suffix _raw, refit_shift [N,24], refit_cost
+    [N,2], refit_flag [N], refit_mean_shift and refit_corr_shift_var (Pearson r of shift and processed uncertainty over the fitted
+    rows)."""
+    from . import ops, refit
+    from .synth import SMPL_PARENTS
+    if dataset.openpose is None:
+        raise ValueError("the keypoint refit needs `openpose` [N,25,3] in the dataset file (demo.py --save_dataset writes it)")
+    dev, n = model.device, len(dataset)
+    kw = dict(capacity=n, sel_uncert_part=sel_uncert_part, kinematic=kinematic, device=dev)
+    evs = [Evaluator(J_regressor, joint_map(dataset.name), **kw), Evaluator(J_regressor, joint_map(dataset.name), **kw)]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+    shift = torch.zeros(n, 24, dtype=torch.float32, device=dev)
+    cost = torch.zeros(n, 2, dtype=torch.float32, device=dev)
+    flag = torch.zeros(n, dtype=torch.int32, device=dev)
+    uvar = torch.zeros(n, 24, dtype=torch.float32, device=dev)
+    for lo in range(0, n, batch_size):
+        hi = min(lo + batch_size, n)
+        batch = dataset.batch(lo, hi, dev)
+        out = model(batch, want_segm=False)
+        var = out["var_pose"].float()
+        while var.dim() > 2:
+            var = var.mean(-1)
+        var = var.clone()
+        if kinematic:
+            for j in range(1, 24):
+                var[:, j] += var[:, int(SMPL_PARENTS[j])]
+        h = batch["scale"].reshape(-1).float() * 200.0
+        pc = out["pred_cam"].float()
+        cam = torch.stack([pc[:, 0] * h * 0.5, pc[:, 1], pc[:, 2], batch["center"][:, 0], batch["center"][:, 1]], 1).contiguous()
+        fit = refit.refit_rows(tables, out["pred_pose"], var, out["pred_shape"], t(dataset.openpose[lo:hi]), cam, h.contiguous(), lam, u_ref,
+                               rho, conf_thresh, iters)
+        verts, _ = model.smpl_lbs(out["pred_shape"].contiguous(), fit["pose"])
+        fitted = (fit["info"][:, 1] == 0)
+        refitted = dict(out)
+        refitted["pred_pose"] = fit["pose"]
+        refitted["smpl_vertices"] = torch.where(fitted[:, None, None], verts, out["smpl_vertices"]).contiguous()
+        shift[lo:hi].copy_(fit["shift"])
+        cost[lo:hi].copy_(fit["cost"])
+        flag[lo:hi].copy_(fit["info"][:, 1])
+        uvar[lo:hi].copy_(var)
+        gt_pose = t(dataset.pose[lo:hi])
+        if dataset.gt_form == "smpl":
+            gt = {"gt_vertices": model.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))[0]}
+        else:
+            gt = {"gt_joints": t(dataset.joints[lo:hi])}
+        evs[0].step(out, gt_pose, **gt)
+        evs[1].step(refitted, gt_pose, **gt)
+    raw = evs[0].finish()
+    res = evs[1].finish(save_results=save_results)
+    res.update({k + "_raw": raw[k] for k in ("mpjpe", "pampjpe", "v2v", "val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")})
+    res["refit_shift"], res["refit_cost"], res["refit_flag"] = shift.cpu().numpy(), cost.cpu().numpy(), flag.cpu().numpy()
+    ok = res["refit_flag"] == 0
+    res["refit_mean_shift"] = float(res["refit_shift"][ok].mean()) if ok.any() else 0.0
+    res["refit_corr_shift_var"] = refit._pearson(res["refit_shift"][ok].astype(np.float64).reshape(-1),
+                                                 uvar.cpu().numpy()[ok].astype(np.float64).reshape(-1))
+    model.check_status()
+    res["imgname"] = np.asarray(dataset.imgname)
+    for ev in evs:
+        ev.close()
+    return res
+
+
+def refit_report_lines(res: Dict[str, object]):
+    """The reference's lines for the raw prediction and for the refit, their difference, and what moved."""
+    lines = [f"Raw MPJPE: {res['val_mpjpe_raw']}", f"Raw PA-MPJPE: {res['val_pampjpe_raw']}", f"Raw V2V (mm): {res['val_v2v_raw']}",
+             f"Raw Uncert Error Correlation: {res['val_corr_raw']}"]
+    lines += [f"Refit {line}" for line in report_lines(res)]
+    lines.append("Refit - raw: " + ", ".join(f"{name} {res[k] - res[k + '_raw']:+.4f}" for name, k in
+                                             (("MPJPE", "val_mpjpe"), ("PA-MPJPE", "val_pampjpe"), ("V2V", "val_v2v"))))
+    n_fit = int((res["refit_flag"] == 0).sum())
+    return lines + [f"Refit shift: mean {res['refit_mean_shift']:.3f} deg over {n_fit} fitted of {len(res['refit_flag'])} rows, "
+                    f"Pearson r(shift, var) {res['refit_corr_shift_var']:+.3f}"]
+
+
 def check_occlusion_keys(files) -> None:
     """Synthetic occluders are centred on the ground-truth 2-D keypoints: refuse a dataset file without `part` or with ready-made
     `img` crops (ValueError)."""
@@ -826,6 +914,7 @@ def save_npz(path: str, res: Dict[str, object], dataset_name: str) -> None:
     pair = PAIR_SCALARS + tuple(k + tag for tag in ("_m1", "_m2") for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr"))
     keep.update({k: np.float64(res[k]) for k in pair if k in res})           # eval.py --cfg2 --ckpt2 (run_eval_pair)
     keep.update({k: np.float64(res[k]) for k in TTA_SCALARS if k in res})        # eval.py --tta (run_eval_tta)
+    keep.update({k: np.float64(res[k]) for k in REFIT_SCALARS if k in res})      # eval.py --kp_refit (run_eval_refit)
     keep.update({k: res[k] for k in ("seq_track_names", "seq_pipelines") if k in res})   # eval.py --sequences (run_eval_sequences)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     np.savez(path, **keep)

@@ -885,6 +885,64 @@ def track_smooth(pose: torch.Tensor, u: torch.Tensor, frames: torch.Tensor, offs
     return tuple(out)
 
 
+# ---- the keypoint refit (include/poco_hip.h; poco_amd/refit.py is the user's side) -------------------------------------------------
+REFIT_MAX_KP = 32                 # POCO_REFIT_MAX_KP
+REFIT_MAX_ITERS = 32              # POCO_REFIT_MAX_ITERS
+
+
+def kp_refit(pose: torch.Tensor, u: torch.Tensor, jrest: torch.Tensor, kp: torch.Tensor, cam: torch.Tensor, norm: torch.Tensor, kp_joint,
+             parents, lam: float, u_ref: float = 0.3, rho: float = 0.1, cam_prior: float = 1.0, conf_thresh: float = 0.3, min_kp: int = 4,
+             iters: int = 10, *, out=None, max_blocks: int = 0) -> dict:
+    """poco_op_kp_refit on device tensors: pose [N,24,3,3], u [N,24], jrest [N,24,3], kp [N,K,3], cam [N,5] = (a, tx, ty, px, py),
+    norm [N], all fp32; kp_joint [K] and parents [24] host integers -> dict(pose [N,24,3,3], cam [N,3], shift [N,24] in degrees, cost
+    [N,2], info int32 [N,2] = (accepted steps, flag)).  out = the same dict of contiguous tensors to write into (tests: poisoned
+    buffers); max_blocks > 0 caps the grid.  Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"kp_refit: {what}")
+    for name, t in (("pose", pose), ("u", u), ("jrest", jrest), ("kp", kp), ("cam", cam), ("norm", norm)):
+        need(torch.is_tensor(t) and t.is_cuda, f"{name} must be a CUDA tensor")
+        need(t.dtype == torch.float32, f"{name} must be float32, got {t.dtype}")
+    need(pose.dim() == 4 and tuple(pose.shape[1:]) == (24, 3, 3) and pose.shape[0] >= 1, f"pose must be [N,24,3,3], got {tuple(pose.shape)}")
+    N = int(pose.shape[0])
+    need(kp.dim() == 3 and kp.shape[0] == N and kp.shape[2] == 3, f"kp must be [{N},K,3], got {tuple(kp.shape)}")
+    K = int(kp.shape[1])
+    need(1 <= K <= REFIT_MAX_KP, f"K = {K} is outside 1..{REFIT_MAX_KP}")
+    for name, t, shp in (("u", u, (N, 24)), ("jrest", jrest, (N, 24, 3)), ("cam", cam, (N, 5)), ("norm", norm, (N,))):
+        need(tuple(t.shape) == shp, f"{name} must be {list(shp)}, got {tuple(t.shape)}")
+    kpj = np.ascontiguousarray(np.asarray(kp_joint).reshape(-1), np.int32)
+    par = np.ascontiguousarray(np.asarray(parents).reshape(-1).astype(np.int64).astype(np.int32))
+    need(kpj.shape == (K,) and bool(((kpj >= -1) & (kpj <= 23)).all()), f"kp_joint must hold {K} joints in -1..23")
+    need(par.shape == (24,) and par[0] < 0 and bool(((par[1:] >= 0) & (par[1:] < np.arange(1, 24))).all()),
+         "parents must be a tree of 24 joints rooted at joint 0 with parent < child")
+    lam, u_ref, rho, cam_prior, conf_thresh = float(lam), float(u_ref), float(rho), float(cam_prior), float(conf_thresh)
+    need(np.isfinite(lam) and lam > 0.0, f"lambda must be finite and > 0, got {lam!r}")
+    need(np.isfinite(u_ref) and u_ref > 0.0, f"u_ref must be finite and > 0, got {u_ref!r}")
+    need(np.isfinite(rho), f"rho must be finite, got {rho!r}")
+    need(np.isfinite(cam_prior) and cam_prior > 0.0, f"cam_prior must be finite and > 0, got {cam_prior!r}")
+    need(np.isfinite(conf_thresh), f"conf_thresh must be finite, got {conf_thresh!r}")
+    need(isinstance(min_kp, (int, np.integer)) and min_kp >= 2, f"min_kp must be an integer >= 2, got {min_kp!r}")
+    need(isinstance(iters, (int, np.integer)) and 1 <= iters <= REFIT_MAX_ITERS, f"iters must be an integer in 1..{REFIT_MAX_ITERS}, got {iters!r}")
+    need(isinstance(max_blocks, (int, np.integer)) and max_blocks >= 0, f"max_blocks must be an integer >= 0, got {max_blocks!r}")
+    dev = pose.device
+    shapes = {"pose": ((N, 24, 3, 3), torch.float32), "cam": ((N, 3), torch.float32), "shift": ((N, 24), torch.float32),
+              "cost": ((N, 2), torch.float32), "info": ((N, 2), torch.int32)}
+    if out is None:
+        out = {k: torch.empty(s, device=dev, dtype=dt) for k, (s, dt) in shapes.items()}
+    for k, (shp, dt) in shapes.items():
+        t = out.get(k)
+        need(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt,
+             f"out[{k!r}] must be a contiguous CUDA {dt} {shp}")
+    p = lambda t: C.c_void_p(t.data_ptr())                                    # noqa: E731
+    ins = [t.contiguous() for t in (pose, u, jrest, kp, cam, norm)]
+    with torch.cuda.device(dev):
+        check(lib().poco_op_kp_refit(*[p(t) for t in ins], N, K, C.c_void_p(kpj.ctypes.data), C.c_void_p(par.ctypes.data), C.c_double(lam),
+                                     C.c_double(u_ref), C.c_double(rho), C.c_double(cam_prior), C.c_double(conf_thresh), int(min_kp),
+                                     int(iters), p(out["pose"]), p(out["cam"]), p(out["shift"]), p(out["cost"]), p(out["info"]),
+                                     int(max_blocks), current_stream()), "poco_op_kp_refit")
+    return {k: out[k] for k in shapes}
+
+
 ACCEL_MAX_JOINTS = 32             # POCO_ACCEL_MAX_JOINTS
 
 

@@ -114,6 +114,7 @@ class POCOTester:
                 if "faces" in z.files:
                     self.faces = np.asarray(z["faces"], np.int64)
         self._renderer = None
+        self._refit_tables = None               # --kp_refit: (Jt, Jd, parents) of the body-model file, made at first use
         self._pseudo_src = []                   # --save_dataset: the label of every crop offered to the labeler
 
     def _build_engine(self, model_cfg, ckpt, inf_model, min_batch: int = 1):
@@ -566,6 +567,8 @@ class POCOTester:
         if raw:
             return stacked
         lam = getattr(self.args, "smooth_uncert", None)
+        if getattr(self.args, "kp_refit", None) is not None:
+            return self._finish_tracks_refitted(tracking_results, stacked, orig_width, orig_height)
         if getattr(self.args, "infill", None) is not None:
             res = self._finish_tracks_infilled(tracking_results, stacked, orig_width, orig_height)
             return res if lam is None else self._smooth_tracks_uncert(res, lam)
@@ -573,6 +576,41 @@ class POCOTester:
             return self._smooth_tracks_uncert({pid: self._finish_track(tr, stacked[pid], orig_width, orig_height, smooth=False)
                                                for pid, tr in tracking_results.items()}, lam)
         return {pid: self._finish_track(tr, stacked[pid], orig_width, orig_height) for pid, tr in tracking_results.items()}
+
+    def _finish_tracks_refitted(self, tracking_results: dict, stacked: dict, orig_width: int, orig_height: int) -> dict:
+        """--kp_refit LAMBDA: the tracks are finished unsmoothed, then ONE call of refit.refit_tracks over all of them refits pose and
+        orig_cam to the tracks' keypoints and re-poses the fitted frames.  Each result gains `refit_shift` [T,24], `refit_cost` [T,2],
+        `refit_flag` [T] and `pose_net` / `betas_net` / `orig_cam_net`, the network's values; var, var_global, pred_cam and
+        smpl_joints2d stay those of the raw prediction.  --infill, then --smooth_uncert or --smooth, work on what the refit left."""
+        from . import refit
+        res = {pid: self._finish_track(tr, stacked[pid], orig_width, orig_height, smooth=False) for pid, tr in tracking_results.items()}
+        if self._refit_tables is None:
+            self._refit_tables = refit.joint_tables(self.args.smpl)
+        a = self.args
+        thr = float(getattr(a, "kp_vis_thresh", 0.3))
+        fit = refit.refit_tracks(self.model, res, float(a.kp_refit), float(getattr(a, "kp_refit_ref", 0.3)), float(getattr(a, "kp_refit_rho", 0.1)),
+                                 thr, int(getattr(a, "kp_refit_iters", 10)), tables=self._refit_tables, img_w=orig_width, img_h=orig_height)
+        print(refit.summary_line(fit, res, self._refit_tables, orig_width, orig_height, thr))
+        for pid, r in res.items():
+            for net, k in (("pose_net", "pose"), ("betas_net", "betas"), ("orig_cam_net", "orig_cam")):
+                r.setdefault(net, r[k])
+            for k in ("pose", "orig_cam", "verts", "smpl_joints3d", "refit_shift", "refit_cost", "refit_flag"):
+                r[k] = fit[pid][k]
+        if getattr(a, "infill", None) is not None:
+            from . import infill
+            filled = infill.infill_tracks(self.model, res, float(a.infill), int(getattr(a, "infill_max_gap", 30)))
+            for pid, r in res.items():
+                for k in ("pose", "betas", "orig_cam", "verts", "smpl_joints3d", "infill"):
+                    r[k] = filled[pid][k]
+            print(infill.summary_line(filled))
+        if getattr(a, "smooth_uncert", None) is not None:
+            return self._smooth_tracks_uncert(res, a.smooth_uncert)
+        if getattr(a, "smooth", False):
+            from .smooth import smooth_pose
+            for r in res.values():
+                r["verts"], r["pose"], r["smpl_joints3d"] = smooth_pose(self.model, r["pose"], r["betas"], getattr(a, "min_cutoff", 0.004),
+                                                                        getattr(a, "beta", 1.5))
+        return res
 
     def _smooth_tracks_uncert(self, res: dict, lam: float) -> dict:
         """--smooth_uncert LAMBDA on finished, unsmoothed tracks (after --infill where that is given: its output is what is
