@@ -125,7 +125,14 @@ int poco_num_tensors(poco_handle_t h);
 int poco_tensor_info(poco_handle_t h, int i, char* name, size_t name_cap, int64_t* shape6, int* rank,
                      int* required);
 /* Copy one tensor (host fp32) into the engine.  Strict: unknown names and wrong element counts are
- * errors (the reference's silent strict->non-strict fallback, train_utils.py:118-124, is not kept). */
+ * errors (the reference's silent strict->non-strict fallback, train_utils.py:118-124, is not kept).
+ * The body model's three index tables are range-checked here, because the SMPL kernels index with them unchecked:
+ *   smpl.parents           for i >= 1 an integer with 0 <= parents[i] < i (a joint's parent comes before it); entry 0, the root's
+ *                          marker (-1, or the 4294967295 of an SMPL pickle's uint32), is neither read nor checked
+ *   smpl.joint_map         integers in [0, 54): 24 chain joints | 21 vertex picks | 9 regressed joints
+ *   smpl.extra_vertex_ids  integers in [0, 6890)
+ * A value that is not finite, not integral or out of its range is POCO_ERR_ARG; the message names the tensor, the index and the
+ * value, and nothing is stored (a table loaded earlier under that name stays). */
 int poco_load_tensor(poco_handle_t h, const char* name, const float* host_data, const int64_t* shape,
                      int rank);
 /* BN folding, MFMA weight packing, upload, workspace planning + allocation.  Needs the GPU. */
@@ -173,7 +180,10 @@ int poco_get_conv_cfg(poco_handle_t h, int op_index, int B, int* cfg7);
 
 /* SMPL linear blend skinning with the engine's loaded body model: replaces
  * smplx.SMPL.forward(pose2rot=False) as wrapped by pocolib/models/head/smpl_head.py:22-34.
- * d_betas [B,10], d_rotmat [B,24,3,3] -> d_verts [B,6890,3], d_joints49 [B,49,3]. */
+ * d_betas [B,10], d_rotmat [B,24,3,3] -> d_verts [B,6890,3], d_joints49 [B,49,3].
+ * The rotations need not be orthonormal (smoothed and blended matrices are used as they are).  The kernels index with
+ * smpl.parents, smpl.joint_map and smpl.extra_vertex_ids without a range check: poco_load_tensor has refused any table that
+ * would index outside the 24 joints, the 54 joint sources or the 6890 vertices. */
 int poco_smpl_lbs(poco_handle_t h, int B, const float* d_betas, const float* d_rotmat, float* d_verts,
                   float* d_joints49, void* stream);
 /* RealNVP with the engine's flow_head.flow.* weights (pocolib/models/layers/real_nvp.py):

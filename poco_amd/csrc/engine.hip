@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -1739,6 +1740,24 @@ extern "C" int poco_load_tensor(poco_handle_t h, const char* name, const float* 
     auto fmt = [](const int64_t* v, size_t m) { std::string t = "["; for (size_t k = 0; k < m; ++k) t += (k ? "," : "") + std::to_string(v[k]); return t + "]"; };
     poco_set_error(std::string("shape mismatch for ") + name + ": got " + fmt(shape, (size_t)rank) + ", expected " + fmt(d.shape.data(), d.shape.size()));
     return POCO_ERR_SHAPE;
+  }
+  // the body model's index tables are read by the SMPL kernels without a range check (kernels_smpl.hip: parents indexes the chain's
+  // LDS rows, joint_map the 54 joint sources, extra_vertex_ids a crop's vertices): a value outside its range is refused here
+  {
+    const std::string nm(name);
+    const bool par = nm == "smpl.parents", jm = nm == "smpl.joint_map", ev = nm == "smpl.extra_vertex_ids";
+    if (par || jm || ev)
+      for (size_t i = par ? 1 : 0; i < n; ++i) {       // parents[0] is the root's marker (-1, or 2^32 - 1 in SMPL pickles): never read
+        const double x = host_data[i];
+        const double hi = par ? (double)i : jm ? 54.0 : 6890.0;
+        if (!(std::isfinite(x) && x == std::floor(x) && x >= 0.0 && x < hi)) {
+          char val[48];
+          std::snprintf(val, sizeof val, "%.9g", x);
+          poco_set_error("poco_load_tensor: " + nm + "[" + std::to_string(i) + "] = " + val + " is not an integer in [0, " +
+                         std::to_string((long long)hi) + ")" + (par ? " (a joint's parent must come before it)" : ""));
+          return POCO_ERR_ARG;
+        }
+      }
   }
   HostParam p;
   p.shape.assign(shape, shape + rank);

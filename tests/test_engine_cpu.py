@@ -83,6 +83,90 @@ def test_strict_loading_errors():
         _lib.check(m._L.poco_finalize(m._h), "poco_finalize")
 
 
+def _load_table(m, name, values):
+    arr = np.ascontiguousarray(values, np.float32)
+    shp = (C.c_int64 * 1)(arr.size)
+    rc = m._L.poco_load_tensor(m._h, ("smpl." + name).encode(), C.c_void_p(arr.ctypes.data), shp, 1)
+    return rc, m._L.poco_last_error().decode()
+
+
+def _stored(m):
+    """names the engine holds a tensor for: poco_finalize lists the required ones it still misses"""
+    m._L.poco_finalize(m._h)
+    missing = m._L.poco_last_error().decode()
+    assert "missing required tensors" in missing
+    return {n for n, _, req in m.expected_tensors() if req and n + " " not in missing}
+
+
+POCO_ERR_ARG = 1                                # poco_amd/csrc/common.h
+SMPL_TABLES = {"parents": synth.SMPL_PARENTS, "joint_map": synth.JOINT_MAP_49, "extra_vertex_ids": synth.SMPL_EXTRA_VERTEX_IDS}
+BAD_TABLES = [
+    # tensor, index, value, how the message prints the value
+    ("parents", 1, 1, "1"), ("parents", 5, 5, "5"), ("parents", 5, 23, "23"), ("parents", 23, 24, "24"), ("parents", 3, -1, "-1"),
+    ("parents", 9, 4294967295, "4.2949673e+09"), ("parents", 2, 0.5, "0.5"), ("parents", 7, np.nan, "nan"),
+    ("joint_map", 0, 54, "54"), ("joint_map", 48, 54, "54"), ("joint_map", 20, -1, "-1"), ("joint_map", 20, 1e9, "1e+09"),
+    ("joint_map", 3, 44.5, "44.5"), ("joint_map", 3, np.inf, "inf"), ("joint_map", 3, -np.inf, "-inf"),
+    ("extra_vertex_ids", 0, 6890, "6890"), ("extra_vertex_ids", 20, 6890, "6890"), ("extra_vertex_ids", 11, -1, "-1"),
+    ("extra_vertex_ids", 11, 3e9, "3e+09"), ("extra_vertex_ids", 4, 331.25, "331.25"), ("extra_vertex_ids", 4, np.nan, "nan"),
+]
+
+
+@pytest.mark.parametrize("name,index,value,shown", BAD_TABLES)
+def test_smpl_index_tables_refused(name, index, value, shown):
+    """poco_load_tensor refuses an smpl.* index table that would make the SMPL kernels read outside the joints, the joint sources
+    or the vertices; the message names the tensor, the index and the value, and nothing is stored."""
+    m = POCO(backbone="resnet50-cliff", num_flow_layers=1, max_batch=1)
+    table = SMPL_TABLES[name].astype(np.float64)
+    table[index] = value
+    rc, msg = _load_table(m, name, table)
+    assert rc == POCO_ERR_ARG, (rc, msg)
+    assert f"smpl.{name}[{index}] = {shown} " in msg, msg
+    assert "smpl." + name not in _stored(m)
+    rc, msg = _load_table(m, name, SMPL_TABLES[name])                            # the good table still loads afterwards ...
+    assert rc == 0, msg
+    rc, _ = _load_table(m, name, table)                                          # ... and a later bad one does not replace it
+    assert rc == POCO_ERR_ARG and "smpl." + name in _stored(m)
+
+
+def test_smpl_index_tables_accepted():
+    m = POCO(backbone="resnet50-cliff", num_flow_layers=1, max_batch=1)
+    for name, table in SMPL_TABLES.items():
+        rc, msg = _load_table(m, name, table)
+        assert rc == 0, msg
+    for root in (-1, 4294967295, 0, 77, np.nan):                                  # entry 0 is neither read nor checked
+        p = synth.SMPL_PARENTS.astype(np.float64)
+        p[0] = root
+        rc, msg = _load_table(m, "parents", p)
+        assert rc == 0, (root, msg)
+    # the edges of each range
+    assert _load_table(m, "parents", [-1] + list(range(23)))[0] == 0             # the deepest tree: parents[i] = i - 1
+    assert _load_table(m, "parents", [-1] + [0] * 23)[0] == 0
+    assert _load_table(m, "joint_map", np.arange(49) % 54 + 5)[0] == 0            # 5 .. 53
+    assert _load_table(m, "joint_map", np.zeros(49))[0] == 0
+    assert _load_table(m, "extra_vertex_ids", [0, 6889] * 10 + [6889])[0] == 0
+    assert {"smpl.parents", "smpl.joint_map", "smpl.extra_vertex_ids"} <= _stored(m)
+    # the other smpl.* tensors are data, not indices: no range applies
+    m.load_smpl(synth.synth_smpl(7))
+
+
+def test_load_smpl_refuses_bad_tables():
+    """the Python loader raises with the library's message; a body model read from an SMPL pickle (uint32 parents) loads"""
+    m = POCO(backbone="resnet50-cliff", num_flow_layers=1, max_batch=1)
+    good = synth.synth_smpl(7)
+    pickled = dict(good, parents=good["parents"].astype(np.uint32))
+    assert pickled["parents"][0] == 4294967295
+    m.load_smpl(pickled)
+    for name, index, value, shown in [("joint_map", 7, 54, "54"), ("extra_vertex_ids", 20, 6890, "6890"), ("parents", 4, 4, "4")]:
+        bad = {k: v.copy() for k, v in good.items()}
+        bad[name][index] = value
+        with pytest.raises(_lib.PocoHipError) as ei:
+            m.load_smpl(bad)
+        rc, msg = _load_table(m, name, bad[name])
+        assert rc == POCO_ERR_ARG and msg in str(ei.value) and f"smpl.{name}[{index}] = {shown} " in msg, (msg, str(ei.value))
+        with pytest.raises(_lib.PocoHipError, match=r"smpl\." + name):
+            POCO(backbone="resnet50-cliff", num_flow_layers=1, max_batch=1, smpl=bad)
+
+
 def test_state_dict_round_trip():
     """the mirror class offers state_dict() under the reference's keys."""
     from tests import util
