@@ -58,6 +58,13 @@ kept, every fitted frame is re-posed (poco_amd/refit.py, csrc/kp_refit.hip, DESI
 unsmoothed tracks; --infill, then --smooth_uncert or --smooth take what it left.  The result gains refit_shift [T,24] (degrees),
 refit_cost [T,2], refit_flag [T] (0 fitted, 1 too few keypoints, 2 non-finite input) and pose_net / betas_net / orig_cam_net; var
 stays as regressed.  Not with folder, directory or webcam mode, --cfg2 or --gpus N > 1.
+--tracker sort (video mode) builds the tracks itself from the per-frame person boxes of --detections - the file folder mode reads -
+where the reference runs multi_person_tracker's SORT behind its detector: a constant-velocity Kalman filter per person and one optimal
+IoU assignment per frame, all frames of the clip in one launch (poco_amd/sort.py, csrc/sort_tracks.hip).
+--track_iou, --track_max_age and --track_min_hits are SORT's three parameters (0.3, 1, 3); --track_boxes filtered crops with the
+filter's boxes instead of the file's; --track_backfill gives a reported person the frames before --track_min_hits was reached.  The
+tracks go through the same path as a --tracking file's (and are written as <out>/tracking_results_sort.json, which --tracking reads
+back).  Not with --tracking or --kp_refit (box tracks have no keypoints); at most 64 people per frame; no detector, no appearance model.
 --cfg2 FILE --ckpt2 FILE [--inf_model2 best] [--select crop|joint] [--select_scale S] runs a second model on the same crops on the
 same GPU and lets the uncertainty choose (poco_amd/select.py, csrc/select_regressor.hip): per crop the model
 whose global uncertainty (the reference's get_global_uncert of its own head) is lower, S times the second model's against the
@@ -221,6 +228,18 @@ def parse_args(argv=None):
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
+    p.add_argument("--tracker", default="none", choices=["none", "sort"],
+                   help="video mode: sort = build the tracks from the per-frame person boxes of --detections on the GPU (SORT: a "
+                        "Kalman filter per person, one optimal IoU assignment per frame; at most 64 people per frame) instead of "
+                        "reading them from --tracking; <out>/tracking_results_sort.json is written for a later --tracking run")
+    p.add_argument("--track_iou", type=float, default=0.3, help="--tracker sort: the least IoU of a detection with a predicted box, in (0, 1)")
+    p.add_argument("--track_max_age", type=int, default=1, help="--tracker sort: frames a person may go undetected before the track ends")
+    p.add_argument("--track_min_hits", type=int, default=3,
+                   help="--tracker sort: consecutive detections before a person who enters after the first frames is reported")
+    p.add_argument("--track_boxes", default="detection", choices=["detection", "filtered"],
+                   help="--tracker sort: crop with the file's own boxes (default: what folder mode cuts) or with the Kalman filter's")
+    p.add_argument("--track_backfill", action="store_true",
+                   help="--tracker sort: a reported person's track also takes the frames before --track_min_hits was reached")
     p.add_argument("--gpus", type=int, default=1,
                    help="video mode: one process per GPU, whole tracks sharded across the ranks, ONE all-gather of the "
                         "packed SMPL records (RCCL over xGMI); `demo.py --gpus N` starts the N ranks itself")
@@ -351,6 +370,32 @@ def _check_kp_refit(args) -> None:
         sys.exit(msg)
 
 
+def _check_tracker(args) -> None:
+    """--tracker and its --track_* companions: refuse what cannot work before the engine is built."""
+    from poco_amd.sort import flag_error
+    msg = flag_error(args)
+    if msg:
+        sys.exit(msg)
+
+
+def _build_sort_tracks(args, folder: str, out_dir: str):
+    """--tracker sort: the tracks from --detections, and <out>/tracking_results_sort.json (rank 0 writes it)."""
+    from poco_amd import sort
+    from poco_amd.tester import load_detections
+    try:
+        names = sort.frame_names(folder)
+        tracks = sort.build_tracks(load_detections(args.detections), names, iou_thresh=args.track_iou, max_age=args.track_max_age,
+                                   min_hits=args.track_min_hits, boxes=args.track_boxes, backfill=args.track_backfill)
+    except ValueError as e:
+        sys.exit(str(e))
+    if not tracks:
+        sys.exit(f"--tracker sort: no track of at least {sort.MIN_NUM_FRAMES} frames in {args.detections}")
+    if int(os.environ.get("RANK", "0")) == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        sort.write_tracking(os.path.join(out_dir, "tracking_results_sort.json"), tracks)
+    return tracks
+
+
 def _check_segm(args) -> None:
     """--save_segm: refuse video mode, a head without a segmentation mask, a body model without triangles and an unreadable
     --part_mapping before the engine is built."""
@@ -397,6 +442,7 @@ def main(args):
     _check_segm(args)
     _check_infill(args)
     _check_smooth_uncert(args)
+    _check_tracker(args)
     _check_kp_refit(args)
     if args.gpus > 1:
         if args.mode != "video":
@@ -435,8 +481,10 @@ def main(args):
         msg = tracking_error(tracking)
         if msg:
             sys.exit(msg)
-    tester = POCOTester(args)
     out_dir = os.path.join(args.output_folder, stem + "_")
+    if args.mode == "video" and getattr(args, "tracker", "none") == "sort":
+        tracking = _build_sort_tracks(args, folder, out_dir)
+    tester = POCOTester(args)
     if args.mode == "video":
         stats = tester.run_on_video_folder(folder, tracking, out_dir)
     else:

@@ -1323,6 +1323,58 @@ int poco_op_track_accel(const float* d_pred, const float* d_gt, int stride, int 
  * POCO_ERR_STATE. */
 int poco_evaluator_copy_records(poco_evaluator_t e, const int32_t* d_order, int64_t n, float* d_out, void* stream);
 
+/* ---- SORT: the tracks of video mode from per-frame person boxes (Bewley et al. 2016) ------------------------------------------------
+ * demo.py --mode video --detections FILE --tracker sort; csrc/sort_tracks.hip; poco_amd/sort.py; DESIGN.md section 32;
+ * tests/sort_np.py restates it in float64 numpy with plain loops and scipy's assignment.  It replaces the association half of the
+ * reference's POCOTester.run_tracking (pocolib/core/tester.py), which calls multi_person_tracker: a detector followed by SORT.  The
+ * detector is not part of this library: its boxes are the input.
+ *
+ * poco_op_sort_tracks: C clips concatenated: d_clip_offsets int32 [C+1] over frames (0 = first, F = last), d_frame_offsets int32
+ *   [F+1] over detections (0 = first, N = last), both non-decreasing (a frame may hold no detection, a clip no frame); d_dets fp64
+ *   [N,4] = (cx, cy, w, h), w, h > 0, at most POCO_SORT_MAX per frame.  The CALLER checks the tables and the boxes (they are device
+ *   memory); the kernel clamps what it reads to the buffers and ends a clip with status 2 at a frame whose range is not inside
+ *   [0, N], runs backwards or holds more than 64 detections.  iou_thresh in (0, 1), max_age >= 0, min_hits >= 0, max_trackers in
+ *   1..POCO_SORT_MAX (SORT's published defaults: 0.3, 1, 3).
+ *   A tracker: x = [u, v, s, r, u', v', s'] (s = area, r = w / h), a symmetric 7 x 7 covariance P of which the elements row >= column
+ *   are computed and the others are their copies, and the counters time_since_update, hit_streak.  The matrices are those of the
+ *   published sort.py (KalmanBoxTracker.__init__): F = I + E(0,4) + E(1,5) + E(2,6); H = [I4 | 0]; R = diag(1, 1, 10, 10);
+ *   Q = diag(1, 1, 1, 1, 0.01, 0.01, 0.0001); P0 = diag(10, 10, 10, 10, 1e4, 1e4, 1e4).  Per clip, frame by frame, in fp64 without
+ *   contraction (no fused multiply-add):
+ *   1 predict  every live tracker: if s + s' <= 0 then s' = 0; x <- F x; P <- F P F^T + Q (each element the sum of at most four
+ *              elements of P, as (P[i][j] + P[i+4][j]) + (P[i][j+4] + P[i+4][j+4]), then + Q on the diagonal); hit_streak = 0 if
+ *              time_since_update > 0; time_since_update += 1.
+ *   2 gate     boxes as corners: a detection is (cx - w/2, cy - h/2, cx + w/2, cy + h/2), a tracker the same of (u, v, w, h) with
+ *              w = sqrt(s r), h = s / w.  o = wh / ((area_d + area_t) - wh), wh = max(0, xx2 - xx1) max(0, yy2 - yy1);
+ *              g[d][k] = o if o >= iou_thresh, else 0 (a NaN: 0).  A tracker with a non-finite u, v, w or h or with w <= 0 or h <= 0
+ *              has g = 0 against everything.
+ *   3 assign   a matching that maximises the sum of g; pairs with g = 0 are no matches.  Shortest augmenting paths with potentials
+ *              (the Hungarian method) on the max(D, K) square whose missing entries cost 0: a true optimum; where it is not unique
+ *              (equal totals) any optimum may come back.  Loops: at most 64 rows, 65 steps per row, 65 steps per path.
+ *   4 update   a matched tracker with z = (cx, cy, w h, w / h): y = z - x[:4]; S = P[:4,:4] + R = L D L^T (no pivoting, the sums in
+ *              ascending k, v - L[i][k] (L[j][k] D[k])); K = P[:,:4] S^-1 row by row (L w = b, w / D, L^T k = w); x <- x + K y;
+ *              AP = P - K P[:4,:]; P <- (AP - AP[:,:4] K^T) + (K R) K^T (the Joseph form); every sum over c = 0..3 starts from the
+ *              c = 0 product and adds the others in ascending c.  time_since_update = 0, hit_streak += 1.
+ *     birth    every unmatched detection, in detection order, starts a tracker with x = (cx, cy, w h, w / h, 0, 0, 0), P = P0,
+ *              both counters 0 and the clip's next id (ids count from 0 in creation order).
+ *   5 emit     a tracker is emitted in this frame if time_since_update == 0 and (hit_streak >= min_hits or the 1-based number of
+ *              the frame in its clip <= min_hits); then the trackers with time_since_update > max_age are removed, the others
+ *              keeping their order.
+ *   Outputs (every element is written): d_tracker int32 [N] (the id of the tracker the detection ended up in), d_id int32 [N] (the
+ *   same where that tracker was emitted in that frame, else -1), d_box fp64 [N,4] (u, v, sqrt(s r), s / sqrt(s r) of that tracker after
+ *   its update or birth), d_count int32 [C] (trackers created), d_status int32 [C]: 0 ok; 1 = at some frame the live trackers plus
+ *   the births would have exceeded max_trackers: nothing of that frame is applied and the detections of it and of every later frame
+ *   of the clip get d_tracker = d_id = -1 and a NaN box; 2 = the same ending at a frame the kernel could not read (above).
+ *   One launch on `stream`: a block of one wave per clip, the frames a sequential loop inside it, the phases of a frame separated by
+ *   block barriers; 58 KB of LDS per block (the 64 x 64 fp64 matrix, 64 packed covariances).  No allocation, no synchronisation, no
+ *   atomics: a clip's outputs do not depend on the other clips and repeat bit for bit from run to run.
+ *   POCO_ERR_ARG before any GPU work: C < 1, F < 0, N < 0, C > 2^24, F > 2^30, N > 2^28 (the int32 plans), a null offset table,
+ *   d_count or d_status, a null d_dets, d_tracker, d_id or d_box with N > 0, iou_thresh outside (0, 1) or not finite, max_age < 0,
+ *   min_hits < 0, max_trackers outside 1..64. */
+#define POCO_SORT_MAX 64
+int poco_op_sort_tracks(const double* d_dets, const int32_t* d_frame_offsets, const int32_t* d_clip_offsets, int64_t C, int64_t F,
+                        int64_t N, double iou_thresh, int max_age, int min_hits, int max_trackers, int32_t* d_tracker, int32_t* d_id,
+                        double* d_box, int32_t* d_count, int32_t* d_status, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

@@ -363,3 +363,14 @@ constexpr int TRACK_ACCEL_MAX_JOINTS = 32;
 constexpr int TRACK_ACCEL_ROW_DOUBLES = 3;
 void launch_track_accel(const float* pred, const float* gt, int stride, int M, const int* frames, const int* offsets, int P, int N,
                         double* scratch, float* accel, float* accel_err, double* track_sums, double* total, int max_blocks, hipStream_t s);
+
+// ---- SORT: tracks from per-frame detections, video mode's --tracker sort (sort_tracks.hip) -------------------------------------------
+// include/poco_hip.h poco_op_sort_tracks: C clips = frames [clip_offsets[c], clip_offsets[c + 1]) of F, a frame = detections
+// [frame_offsets[f], frame_offsets[f + 1]) of N; dets fp64 [N,4] (cx, cy, w, h); outputs tracker / id int32 [N], box fp64 [N,4],
+// count / status int32 [C].  One block of SORT_THREADS (one wave) per clip, the frames a sequential loop inside it; at most
+// SORT_MAX people (detections of a frame, live trackers).
+constexpr int SORT_THREADS = 64;
+constexpr int SORT_MAX = 64;
+void launch_sort_tracks(const double* dets, const int* frame_offsets, const int* clip_offsets, int C, int F, int N, double iou_thresh,
+                        int max_age, int min_hits, int max_trackers, int* tracker, int* id, double* box, int* count, int* status,
+                        hipStream_t s);

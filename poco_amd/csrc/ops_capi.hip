@@ -1240,3 +1240,24 @@ extern "C" int poco_op_track_accel(const float* d_pred, const float* d_gt, int s
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- SORT: tracks from per-frame detections, video mode's --tracker sort (sort_tracks.hip) -----------------------------------------
+static_assert(POCO_SORT_MAX == SORT_MAX, "include/poco_hip.h and csrc/kernels.h disagree on the tracker");
+extern "C" int poco_op_sort_tracks(const double* d_dets, const int32_t* d_frame_offsets, const int32_t* d_clip_offsets, int64_t C,
+                                   int64_t F, int64_t N, double iou_thresh, int max_age, int min_hits, int max_trackers,
+                                   int32_t* d_tracker, int32_t* d_id, double* d_box, int32_t* d_count, int32_t* d_status, void* stream) {
+  const char* who = "poco_op_sort_tracks";
+  if (C < 1 || F < 0 || N < 0) return op_bad(who, "needs C >= 1, F >= 0 and N >= 0");
+  // the plans are int32: frame and detection indices, and 4 N doubles of boxes addressed from an int
+  if (C > (1LL << 24) || F > (1LL << 30) || N > (1LL << 28)) return op_bad(who, "needs C <= 2^24, F <= 2^30 and N <= 2^28 (the int32 plans)");
+  if (!d_frame_offsets || !d_clip_offsets || !d_count || !d_status) return op_bad(who, "null pointer (both offset tables, count and status are needed)");
+  if (N > 0 && (!d_dets || !d_tracker || !d_id || !d_box)) return op_bad(who, "null pointer (dets, tracker, id and box are needed when N > 0)");
+  if (!std::isfinite(iou_thresh) || !(iou_thresh > 0.0) || !(iou_thresh < 1.0)) return op_bad(who, "iou_thresh must be in (0, 1)");
+  if (max_age < 0) return op_bad(who, "max_age must be >= 0");
+  if (min_hits < 0) return op_bad(who, "min_hits must be >= 0");
+  if (max_trackers < 1 || max_trackers > POCO_SORT_MAX) return op_bad(who, "max_trackers must be in 1..64");
+  launch_sort_tracks(d_dets, d_frame_offsets, d_clip_offsets, (int)C, (int)F, (int)N, iou_thresh, max_age, min_hits, max_trackers,
+                     d_tracker, d_id, d_box, d_count, d_status, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

@@ -1009,6 +1009,77 @@ def track_accel(pred: torch.Tensor, gt, frames: torch.Tensor, offsets: torch.Ten
     return {"accel": out[0], "accel_err": out[1] if gt is not None else None, "track_sums": out[2], "total": out[3]}
 
 
+# ---- SORT: tracks from per-frame detections (include/poco_hip.h; poco_amd/sort.py is the user's side) ---------------------------------
+SORT_MAX = 64                     # POCO_SORT_MAX
+
+
+def sort_tracks(dets: torch.Tensor, frame_offsets, clip_offsets=None, *, iou_thresh: float = 0.3, max_age: int = 1, min_hits: int = 3,
+                max_trackers: int = 64, out=None) -> dict:
+    """poco_op_sort_tracks: dets fp64 [N,4] (cx, cy, w, h) on the device, frame_offsets int32 [F+1] over the detections and
+    clip_offsets int32 [C+1] over the frames (None: one clip), each a host array / list (taken as it is) or a tensor (a device tensor
+    is downloaded once for the checks) -> dict(tracker int32 [N], id int32 [N], box fp64 [N,4], count int32 [C], status int32 [C])
+    on the device.  out = the same dict of contiguous tensors to write into (tests: guarded buffers).  Refused with PocoHipError
+    before any GPU work, the frame named: a frame of more than 64 detections, offsets that are not monotone, a box that is not
+    finite or has w <= 0 or h <= 0 (the boxes are downloaded once for that check)."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"sort_tracks: {what}")
+
+    def table(t, name):
+        dev_t = t if torch.is_tensor(t) and t.is_cuda else None
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        need(a.ndim == 1 and a.size >= 1 and a.dtype.kind in "iu", f"{name} must be a 1-D integer table, got {a.dtype} {a.shape}")
+        need(bool((a >= 0).all()) and int(a.max()) < (1 << 31), f"{name} must hold int32 values >= 0")
+        return np.ascontiguousarray(a, np.int32), dev_t
+
+    need(torch.is_tensor(dets) and dets.dtype == torch.float64, "dets must be a float64 tensor")
+    need(dets.dim() == 2 and dets.shape[1] == 4, f"dets must be [N,4] (cx, cy, w, h), got {tuple(dets.shape)}")
+    N = int(dets.shape[0])
+    fo, fo_dev = table(frame_offsets, "frame_offsets")
+    F = int(fo.size) - 1
+    co, co_dev = table(np.array([0, F], np.int32) if clip_offsets is None else clip_offsets, "clip_offsets")
+    Cn = int(co.size) - 1
+    need(Cn >= 1, "clip_offsets must be [C+1] with C >= 1")
+    need(co[0] == 0 and co[-1] == F, f"clip_offsets must start at 0 and end at F = {F}")
+    bad = np.nonzero(np.diff(co) < 0)[0]
+    need(bad.size == 0, f"clip_offsets are not monotone at clip {int(bad[0]) if bad.size else 0}")
+    need(fo[0] == 0 and fo[-1] == N, f"frame_offsets must start at 0 and end at N = {N}")
+    per = np.diff(fo)
+    bad = np.nonzero(per < 0)[0]
+    need(bad.size == 0, f"frame_offsets are not monotone at frame {int(bad[0]) if bad.size else 0}")
+    bad = np.nonzero(per > SORT_MAX)[0]
+    need(bad.size == 0, f"frame {int(bad[0]) if bad.size else 0} holds {int(per[bad[0]]) if bad.size else 0} detections, more than {SORT_MAX}")
+    iou_thresh = float(iou_thresh)
+    need(np.isfinite(iou_thresh) and 0.0 < iou_thresh < 1.0, f"iou_thresh must be in (0, 1), got {iou_thresh!r}")
+    for name, v, lo, hi in (("max_age", max_age, 0, None), ("min_hits", min_hits, 0, None), ("max_trackers", max_trackers, 1, SORT_MAX)):
+        need(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= lo and (hi is None or v <= hi) and v < (1 << 31),
+             f"{name} must be an integer {'>= ' + str(lo) if hi is None else 'in ' + str(lo) + '..' + str(hi)}, got {v!r}")
+    h = dets.detach().cpu().numpy()
+    ok = np.isfinite(h).all(1) & (h[:, 2] > 0) & (h[:, 3] > 0) if N else np.ones(0, bool)
+    if not ok.all():
+        i = int(np.nonzero(~ok)[0][0])
+        need(False, f"detection {i} of frame {int(np.searchsorted(fo, i, side='right')) - 1} is not a finite box with w, h > 0: {h[i].tolist()}")
+    need(dets.is_cuda, "dets must be a CUDA tensor")
+    dev = dets.device
+    shapes = {"tracker": ((N,), torch.int32), "id": ((N,), torch.int32), "box": ((N, 4), torch.float64), "count": ((Cn,), torch.int32),
+              "status": ((Cn,), torch.int32)}
+    if out is None:
+        out = {k: torch.empty(s, device=dev, dtype=dt) for k, (s, dt) in shapes.items()}
+    for k, (shp, dt) in shapes.items():
+        t = out.get(k)
+        need(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt,
+             f"out[{k!r}] must be a contiguous CUDA {dt} {shp}")
+    d_fo = fo_dev.to(torch.int32).contiguous() if fo_dev is not None else torch.from_numpy(fo).to(dev)
+    d_co = co_dev.to(torch.int32).contiguous() if co_dev is not None else torch.from_numpy(co).to(dev)
+    p = lambda t: C.c_void_p(t.data_ptr())                                      # noqa: E731
+    with torch.cuda.device(dev):
+        check(lib().poco_op_sort_tracks(p(dets.contiguous()), p(d_fo), p(d_co), C.c_int64(Cn), C.c_int64(F), C.c_int64(N),
+                                        C.c_double(iou_thresh), int(max_age), int(min_hits), int(max_trackers), p(out["tracker"]),
+                                        p(out["id"]), p(out["box"]), p(out["count"]), p(out["status"]), current_stream()),
+              "poco_op_sort_tracks")
+    return {k: out[k] for k in shapes}
+
+
 # ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
 # Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
 # that the caller can check `untouched`.
