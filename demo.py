@@ -228,6 +228,11 @@ def parse_args(argv=None):
     p.add_argument("--save_obj", action="store_true", help="save results as .obj files (meshes/<image|person>/<idx>.obj)")
     p.add_argument("--detections", type=str, default=None,
                    help="json {image name: [[cx,cy,w,h],...]} or the reference's detection_results.pkl (per-image list)")
+    p.add_argument("--calibration", type=str, default=None, metavar="FILE",
+                   help="a calibration file written by eval.py --calibrate: the final `var` of every person is mapped to the error "
+                        "observed on that dataset (one call on the GPU, after the uncertainty post-processing and every flag that changes "
+                        "`var`); the result gains err_pose [n,24] (per joint, the evaluator's pose distance) and err_mpjpe, err_pampjpe, "
+                        "err_v2v [n] (metres); the file's kinematic flag and head must be this run's")
     p.add_argument("--tracker", default="none", choices=["none", "sort"],
                    help="video mode: sort = build the tracks from the per-frame person boxes of --detections on the GPU (SORT: a "
                         "Kalman filter per person, one optimal IoU assignment per frame; at most 64 people per frame) instead of "
@@ -378,6 +383,22 @@ def _check_tracker(args) -> None:
         sys.exit(msg)
 
 
+def _check_calibration(args) -> None:
+    """--calibration: refuse --cfg2, an unreadable file and a file fitted for another head or kinematic flag before the engine is
+    built."""
+    from poco_amd import calibrate
+    msg = calibrate.demo_flag_error(args)
+    if msg:
+        sys.exit(msg)
+    if not getattr(args, "calibration", None):
+        return
+    from poco_amd.config import update_hparams
+    try:
+        calibrate.check_file(args.calibration, bool(getattr(args, "no_kinematic_uncert", True)), str(update_hparams(args.cfg).POCO.BACKBONE))
+    except (OSError, ValueError) as e:
+        sys.exit(f"--calibration: {e}")
+
+
 def _build_sort_tracks(args, folder: str, out_dir: str):
     """--tracker sort: the tracks from --detections, and <out>/tracking_results_sort.json (rank 0 writes it)."""
     from poco_amd import sort
@@ -444,6 +465,7 @@ def main(args):
     _check_smooth_uncert(args)
     _check_tracker(args)
     _check_kp_refit(args)
+    _check_calibration(args)
     if args.gpus > 1:
         if args.mode != "video":
             sys.exit("--gpus N shards whole tracks: video mode only (folder mode images are independent - run N demos)")

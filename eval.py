@@ -36,6 +36,12 @@ rho is printed beside Pearson's r, then AUSE / AURG (area of the sparsification 
 MPJPE, PA-MPJPE, V2V and the pose distance, then per kept fraction the uncertainty threshold and the errors of the crops kept; the
 .npz gains rank_spars_*, rank_oracle_*, rank_reliab_*, rank_thresholds and rank_summary.  Not with --cfg2, --tta, --segm or
 --likelihood.
+--calibrate OUT.npz [--calib_split half|parity|none] [--calib_bins K] fits monotone maps from the uncertainty to the observed error by
+isotonic regression on the GPU (csrc/isotonic.hip, poco_amd/calibrate.py): crop_mpjpe, crop_pampjpe, crop_v2v,
+joint_all and joint_0 .. joint_23, all in one call from the evaluator's records; printed per map: rows, blocks and the held-out ENCE,
+bias and 1 - SSE / SSE_const; OUT.npz is what demo.py --calibration reads, and the .npz gains calib_summary.  Allowed beside
+--rank_metrics; not with --segm, --likelihood, --cfg2, --tta, --sequences, --kp_refit, --visibility, --aug_* or --augment.
+
 --sequences treats the dataset's rows as the consecutive frames they are in 3DPW and Human3.6M: the rows are grouped into tracks by
 folder, person and frame number (poco_amd/sequences.py) and the records are scored on the GPU for Accel, the prediction's own
 jitter, and Accel error, the acceleration error of the video papers, both in mm / frame^2 (csrc/track_accel.hip, DESIGN.md section
@@ -140,6 +146,15 @@ def parse_args(argv=None):
                         "rank_thresholds and rank_summary")
     p.add_argument("--rank_bins", type=int, default=None, metavar="K",
                    help="with --rank_metrics: cuts of the sparsification curves = bins of the tables, 1..1024 (default 20)")
+    p.add_argument("--calibrate", type=str, default=None, metavar="OUT.npz",
+                   help="also fit monotone maps from the uncertainty to the observed error by isotonic regression on the GPU "
+                        "(poco_amd/calibrate.py, csrc/isotonic.hip): per crop for MPJPE, PA-MPJPE and V2V, per joint pooled and for each "
+                        "of the 24 joints; writes them to OUT.npz for demo.py --calibration and prints their held-out scores; the .npz "
+                        "gains calib_summary; allowed beside --rank_metrics")
+    p.add_argument("--calib_split", default=None, choices=["half", "parity", "none"],
+                   help="with --calibrate: score held out on first / second half of the rows (default), even / odd rows, or not at all")
+    p.add_argument("--calib_bins", type=int, default=None, metavar="K",
+                   help="with --calibrate: equal-count bins of the prediction for the calibration error, 1..1024 (default 20)")
     p.add_argument("--sequences", action="store_true",
                    help="the dataset's rows are consecutive frames: group them into tracks by folder, person and frame number and "
                         "also print Accel and Accel error (mm / frame^2), scored on the GPU (poco_amd/sequences.py, "
@@ -316,6 +331,14 @@ def check_rank(args) -> None:
         sys.exit(msg)
 
 
+def check_calibrate(args) -> None:
+    """--calibrate / --calib_split / --calib_bins: refuse what cannot work before an engine is built."""
+    from poco_amd.calibrate import flag_error
+    msg = flag_error(args)
+    if msg:
+        sys.exit(msg)
+
+
 def check_tta(args) -> None:
     """--tta / --tta_weight: refuse what cannot work before an engine is built."""
     from poco_amd.tta import flag_error
@@ -387,7 +410,17 @@ def check_visibility(args) -> None:
                      "its triangles)")
 
 
+def calibrate_spec(args, tester):
+    """run_eval's `calibrate` argument from --calibrate / --calib_split / --calib_bins, or None."""
+    if not getattr(args, "calibrate", None):
+        return None
+    from poco_amd.calibrate import make_meta
+    return {"split": getattr(args, "calib_split", None) or "half", "bins": getattr(args, "calib_bins", None) or 20,
+            "meta": make_meta(args.dataset_name, bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), str(tester.model_cfg.POCO.BACKBONE))}
+
+
 def main(args):
+    check_calibrate(args)
     check_visibility(args)
     check_sequences(args)
     check_select(args)
@@ -472,7 +505,8 @@ def main(args):
         res = evaluate.run_eval(tester.model, ds, J, batch_size=max(int(args.batch_size), 1),
                                 kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
                                 likelihood=args.likelihood,
-                                rank_metrics=(args.rank_bins or 20) if getattr(args, "rank_metrics", False) else None, **vis_kw)
+                                rank_metrics=(args.rank_bins or 20) if getattr(args, "rank_metrics", False) else None,
+                                calibrate=calibrate_spec(args, tester), **vis_kw)
     lines = evaluate.pair_report_lines(res, tester.pair.mode) if tester.pair is not None else evaluate.report_lines(res)
     if tester.tta is not None:
         lines = evaluate.tta_report_lines(res)
@@ -486,6 +520,11 @@ def main(args):
     if getattr(args, "rank_metrics", False):
         for line in evaluate.rank_lines(res):
             print(line)
+    if getattr(args, "calibrate", None):
+        from poco_amd import calibrate
+        for line in calibrate.summary_lines(res["calibration"]):
+            print(line)
+        calibrate.save(args.calibrate, res["calibration"])
     if getattr(args, "sequences", False):
         for line in evaluate.sequence_lines(res):
             print(line)

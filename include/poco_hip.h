@@ -1375,6 +1375,54 @@ int poco_op_sort_tracks(const double* d_dets, const int32_t* d_frame_offsets, co
                         int64_t N, double iou_thresh, int max_age, int min_hits, int max_trackers, int32_t* d_tracker, int32_t* d_id,
                         double* d_box, int32_t* d_count, int32_t* d_status, void* stream);
 
+/* ---- calibrating the uncertainty: isotonic regression of the error on the uncertainty, and evaluating the fitted maps ------------------
+ * eval.py --calibrate OUT.npz, demo.py --calibration FILE; csrc/isotonic.hip; poco_amd/calibrate.py; DESIGN.md section 33;
+ * tests/calib_np.py restates both operators with plain loops and a stack.  No counterpart in the reference's code.
+ *
+ * poco_op_isotonic: S independent segments in one ragged buffer.  d_key, d_y fp32 [M] in row order; d_order int32 [N], entries in
+ *   [0, M); d_seg_offsets int32 [S+1], non-decreasing from 0 to N (the CALLER checks both: they are device memory; the kernels clamp
+ *   every index they take from them).  Positions [seg_offsets[s], seg_offsets[s+1]) of d_order list segment s's rows in ascending
+ *   order of the canonical key of poco_op_rank_curve (-0.0 = +0.0; no NaN keys): d_order of poco_op_rank_curve plus a base offset.
+ *   A row may appear in several segments; a segment may be empty.  1 <= S <= POCO_ISO_MAX_SEGS, 0 <= N <= POCO_ISO_MAX_N,
+ *   0 <= M <= POCO_ISO_MAX_N and M >= 1 if N >= 1.  y must be finite (else: unspecified values, nothing out of bounds, every loop
+ *   a `for` bounded by the sizes).
+ *   The fit is the least-squares non-decreasing fit with ties pooled first:
+ *     units   within a segment, maximal runs of positions with equal canonical key; weight = rows, sum = sum of y.
+ *     blocks  the unique partition of the segment's units into consecutive blocks whose means (sum of y / rows) increase strictly
+ *             from block to block and of which none can be split into a left part whose mean is strictly below the right part's:
+ *             two neighbours pool when mean_left >= mean_right, decided as sum_l * rows_r >= sum_r * rows_l in fp64.
+ *   d_block int32 [N]: for every position the first position of its block (exact).
+ *   d_fit fp64 [N]: the block's mean at every position, summed in a final pass from the block's own rows in fp64 (a segmented scan
+ *     over tiles of POCO_ISO_TILE positions; the tree is a function of the block's extent alone) and divided once by the rows:
+ *     |value - fsum(block) / rows| <= 2^-52 * sum_block |y|.  No fused multiply-add.
+ *   d_seg_blocks int32 [S+1]: block offsets per segment; d_knots fp64 [B_total,4], compacted in order: per block the lowest and
+ *     the highest canonical key, the value and the rows.  Capacity N rows; rows past B_total are not written.
+ *   d_scratch: poco_op_isotonic_scratch_bytes(N, S) bytes (0 = N or S out of range; 256 when N = 0), 8-byte aligned.
+ *   max_blocks: 0 = the default grid, > 0 bounds it; every output is bitwise independent of it and equal from run to run.
+ *   12 + max(0, ceil(log2 N) - 11) launches on `stream` (2 when N = 0); the inputs are only read; no allocation, no synchronisation,
+ *   no floating-point atomic, no spin-wait, no grid barrier.
+ *   POCO_ERR_ARG before any GPU work: a null pointer (the [N] and [M] buffers and d_knots may be NULL only with N = 0), S, N or M
+ *   out of range, max_blocks < 0, a scratch buffer that is too small or misaligned, misaligned buffers, outputs or scratch that
+ *   overlap an input or each other.
+ *
+ * poco_op_calib_apply: d_out[r][c] = f_m(d_x[r][c]) with m = d_map_ids[c] (clamped to [0, P)), for d_x fp32 [R,S] row-major.
+ *   Map m = rows [d_map_offsets[m], d_map_offsets[m+1]) (clamped to [0, B]) of d_knots fp64 [B,4] as written by poco_op_isotonic:
+ *   blocks b = 0 .. n-1 with lo_b <= hi_b < lo_(b+1) and values v_b.  f(NaN) = NaN; an empty map gives NaN; v_0 for x <= lo_0;
+ *   v_(n-1) for x >= hi_(n-1); v_b for lo_b <= x <= hi_b; between hi_b and lo_(b+1):
+ *   v_b + (v_(b+1) - v_b) * ((x - hi_b) / (lo_(b+1) - hi_b)) in fp64 in exactly that order without contraction, rounded to fp32
+ *   once.  One lane per element, a binary search of at most 32 steps.  One launch on `stream`.
+ *   POCO_ERR_ARG before any GPU work: a null pointer (d_knots may be NULL only with B = 0), R outside 1..2^26, S outside 1..4096,
+ *   R * S > 2^30, P outside 1..4096, B outside 0..2^26, max_blocks < 0, misaligned buffers, d_out overlapping an input. */
+#define POCO_ISO_TILE 2048
+#define POCO_ISO_MAX_N (1 << 26)
+#define POCO_ISO_MAX_SEGS 4096
+size_t poco_op_isotonic_scratch_bytes(int64_t N, int S);
+int poco_op_isotonic(const float* d_key, const float* d_y, int64_t M, const int32_t* d_order, int64_t N, const int32_t* d_seg_offsets,
+                     int S, void* d_scratch, size_t scratch_bytes, int32_t* d_block, double* d_fit, int32_t* d_seg_blocks,
+                     double* d_knots, int max_blocks, void* stream);
+int poco_op_calib_apply(const float* d_x, int64_t R, int S, const int32_t* d_map_ids, const int32_t* d_map_offsets, int P,
+                        const double* d_knots, int64_t B, float* d_out, int max_blocks, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

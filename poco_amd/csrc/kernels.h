@@ -374,3 +374,23 @@ constexpr int SORT_MAX = 64;
 void launch_sort_tracks(const double* dets, const int* frame_offsets, const int* clip_offsets, int C, int F, int N, double iou_thresh,
                         int max_age, int min_hits, int max_trackers, int* tracker, int* id, double* box, int* count, int* status,
                         hipStream_t s);
+
+// ---- calibration: isotonic regression over ragged segments, and the fitted maps evaluated (isotonic.hip) --------------------------------
+// include/poco_hip.h poco_op_isotonic / poco_op_calib_apply.  Everything works on tiles of ISO_TILE consecutive POSITIONS of the
+// ragged buffer (segments are told apart by flags, so many small segments and one large one load the device alike), dealt to at
+// most ISO_MAX_BLOCKS blocks of ISO_THREADS (max_blocks > 0: at most that many) by grid-stride loops.  The scratch buffer is the
+// caller's: iso_scratch_layout gives the byte offset of every part of it (each a multiple of 256) and the total.
+constexpr int ISO_TILE = 2048;
+constexpr int ISO_THREADS = 256;
+constexpr int ISO_MAX_BLOCKS = 1024;
+constexpr int ISO_MAX_SEGS = 4096;
+constexpr long long ISO_MAX_N = 1 << 26;
+struct IsoScratch {
+  int NT;                                                  // tiles
+  size_t ys, ukey, flags, sum, lsum, len, head, nh, cp, after, fh, lh, fwd, bwd, nheads, hbase, total, bytes;
+};
+IsoScratch iso_scratch_layout(long long N);
+void launch_isotonic(const float* key, const float* y, int M, const int* order, int N, const int* seg_offsets, int S, void* scratch,
+                     int* block, double* fit, int* seg_blocks, double* knots, int max_blocks, hipStream_t s);
+void launch_calib_apply(const float* x, long long R, int S, const int* map_ids, const int* map_offsets, int P, const double* knots,
+                        int B, float* out, int max_blocks, hipStream_t s);

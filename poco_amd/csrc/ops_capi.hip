@@ -1261,3 +1261,71 @@ extern "C" int poco_op_sort_tracks(const double* d_dets, const int32_t* d_frame_
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- calibration: isotonic regression over ragged segments, the fitted maps evaluated (isotonic.hip) ---------------------------------
+static_assert(POCO_ISO_TILE == ISO_TILE && POCO_ISO_MAX_N == ISO_MAX_N && POCO_ISO_MAX_SEGS == ISO_MAX_SEGS,
+              "include/poco_hip.h and csrc/kernels.h disagree on the isotonic fit");
+static bool iso_shape_ok(int64_t N, int S) { return N >= 0 && N <= POCO_ISO_MAX_N && S >= 1 && S <= POCO_ISO_MAX_SEGS; }
+
+extern "C" size_t poco_op_isotonic_scratch_bytes(int64_t N, int S) {
+  return iso_shape_ok(N, S) ? iso_scratch_layout(N).bytes : 0;
+}
+
+extern "C" int poco_op_isotonic(const float* d_key, const float* d_y, int64_t M, const int32_t* d_order, int64_t N,
+                                const int32_t* d_seg_offsets, int S, void* d_scratch, size_t scratch_bytes, int32_t* d_block,
+                                double* d_fit, int32_t* d_seg_blocks, double* d_knots, int max_blocks, void* stream) {
+  const char* who = "poco_op_isotonic";
+  if (!iso_shape_ok(N, S)) return op_bad(who, "N must be in 0..2^26 and S in 1..4096");
+  if (M < 0 || M > POCO_ISO_MAX_N || (N > 0 && M < 1)) return op_bad(who, "M must be in 0..2^26, and >= 1 when N >= 1");
+  if (max_blocks < 0) return op_bad(who, "max_blocks must be >= 0");
+  if (!d_seg_offsets || !d_scratch || !d_seg_blocks) return op_bad(who, "null pointer (seg_offsets, scratch and seg_blocks are needed)");
+  if (N > 0 && (!d_key || !d_y || !d_order || !d_block || !d_fit || !d_knots))
+    return op_bad(who, "null pointer (key, y, order, block, fit and knots are needed when N > 0)");
+  if (!aligned_to(d_scratch, 8) || !aligned_to(d_fit, 8) || !aligned_to(d_knots, 8) || !aligned_to(d_key, 4) || !aligned_to(d_y, 4) ||
+      !aligned_to(d_order, 4) || !aligned_to(d_seg_offsets, 4) || !aligned_to(d_block, 4) || !aligned_to(d_seg_blocks, 4))
+    return op_bad(who, "scratch, fit and knots must be 8-byte aligned, the fp32 and int32 buffers 4-byte aligned");
+  const size_t need = iso_scratch_layout(N).bytes;
+  if (scratch_bytes < need)
+    return op_bad(who, "the scratch buffer holds " + std::to_string(scratch_bytes) + " bytes, poco_op_isotonic_scratch_bytes asks for " +
+                           std::to_string(need));
+  // [begin, end) in bytes: the four inputs, then the scratch and the four outputs, none of which may overlap anything before it
+  const size_t n = (size_t)N, m = (size_t)M, segs = (size_t)S + 1;
+  const struct { const void* p; size_t bytes; } buf[9] = {{d_key, m * 4}, {d_y, m * 4}, {d_order, n * 4}, {d_seg_offsets, segs * 4},
+                                                          {d_scratch, need}, {d_block, n * 4}, {d_fit, n * 8}, {d_seg_blocks, segs * 4},
+                                                          {d_knots, n * 32}};
+  for (int o = 4; o < 9; ++o)
+    for (int i = 0; i < o; ++i) {
+      if (!buf[i].bytes || !buf[o].bytes) continue;
+      const uintptr_t a0 = (uintptr_t)buf[o].p, a1 = a0 + buf[o].bytes, b0 = (uintptr_t)buf[i].p, b1 = b0 + buf[i].bytes;
+      if (a0 < b1 && b0 < a1) return op_bad(who, "the scratch and the outputs may not overlap an input or each other");
+    }
+  launch_isotonic(d_key, d_y, (int)M, d_order, (int)N, d_seg_offsets, S, d_scratch, d_block, d_fit, d_seg_blocks, d_knots, max_blocks,
+                  (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
+extern "C" int poco_op_calib_apply(const float* d_x, int64_t R, int S, const int32_t* d_map_ids, const int32_t* d_map_offsets, int P,
+                                   const double* d_knots, int64_t B, float* d_out, int max_blocks, void* stream) {
+  const char* who = "poco_op_calib_apply";
+  if (R < 1 || R > POCO_ISO_MAX_N || S < 1 || S > POCO_ISO_MAX_SEGS || R * S > (1LL << 30))
+    return op_bad(who, "R must be in 1..2^26, S in 1..4096 and R * S at most 2^30");
+  if (P < 1 || P > POCO_ISO_MAX_SEGS) return op_bad(who, "P must be in 1..4096");
+  if (B < 0 || B > POCO_ISO_MAX_N) return op_bad(who, "B must be in 0..2^26");
+  if (max_blocks < 0) return op_bad(who, "max_blocks must be >= 0");
+  if (!d_x || !d_map_ids || !d_map_offsets || !d_out || (B > 0 && !d_knots))
+    return op_bad(who, "null pointer (x, map_ids, map_offsets and out are needed, and knots when B > 0)");
+  if (!aligned_to(d_knots, 8) || !aligned_to(d_x, 4) || !aligned_to(d_map_ids, 4) || !aligned_to(d_map_offsets, 4) || !aligned_to(d_out, 4))
+    return op_bad(who, "knots must be 8-byte aligned, the fp32 and int32 buffers 4-byte aligned");
+  const size_t n = (size_t)R * (size_t)S;
+  const struct { const void* p; size_t bytes; } in[4] = {{d_x, n * 4}, {d_map_ids, (size_t)S * 4}, {d_map_offsets, ((size_t)P + 1) * 4},
+                                                         {d_knots, (size_t)B * 32}};
+  for (int i = 0; i < 4; ++i) {
+    if (!in[i].bytes) continue;
+    const uintptr_t a0 = (uintptr_t)d_out, a1 = a0 + n * 4, b0 = (uintptr_t)in[i].p, b1 = b0 + in[i].bytes;
+    if (a0 < b1 && b0 < a1) return op_bad(who, "out may not overlap an input");
+  }
+  launch_calib_apply(d_x, R, S, d_map_ids, d_map_offsets, P, d_knots, (int)B, d_out, max_blocks, (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

@@ -435,7 +435,7 @@ class EvalDataset:
 @torch.no_grad()
 def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
              sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_records: bool = False,
-             likelihood: bool = False, rank_metrics: Optional[int] = None, visibility=None) -> Dict[str, object]:
+             likelihood: bool = False, rank_metrics: Optional[int] = None, visibility=None, calibrate=None) -> Dict[str, object]:
     """trainer.py:298-336 over a whole dataset: forward, then the metrics of every batch (the ragged last one included) on the
     device.  SMPL ground truth: gt_vertices = POCO.smpl_lbs(shape, poco_op_rodrigues(pose)) (base_dataset.py:353-366, neutral
     model), also on the device.  Returns Evaluator.finish() plus `imgname`.  likelihood=True (needs `pose` in the dataset and
@@ -445,7 +445,9 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
     ranking.RANK_NPZ_KEYS arrays; everything else is what it is without the argument.
     visibility (eval.py --visibility): a visibility.VisibilityEval from visibility.prepare(); behind the metrics of every batch, on
     the same stream, it counts the visible pixels of every body part of the ground-truth mesh; the result gains the
-    visibility.NPZ_KEYS arrays and `vis_stats`.  Needs SMPL ground truth; without the argument nothing changes."""
+    visibility.NPZ_KEYS arrays and `vis_stats`.  Needs SMPL ground truth; without the argument nothing changes.
+    calibrate (eval.py --calibrate): dict(split, bins, meta); the result gains `calibration` (the calibrate.NPZ_KEYS arrays, for
+    calibrate.save) and the array `calib_summary`; everything else is what it is without the argument."""
     from . import ops
     dev = model.device
     ev = Evaluator(J_regressor, joint_map(dataset.name), capacity=len(dataset), sel_uncert_part=sel_uncert_part, kinematic=kinematic,
@@ -476,6 +478,10 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
         res.update(RankMetrics(ev, int(rank_metrics)).result)
     if visibility is not None:
         res.update(visibility.finish(res["corr_x"], res["corr_y"]))
+    if calibrate is not None:
+        from . import calibrate as calib
+        res["calibration"] = calib.calibrate(ev, calibrate.get("split", "half"), int(calibrate.get("bins", 20)), calibrate.get("meta"))
+        res["calib_summary"] = res["calibration"]["calib_summary"]
     model.check_status()
     res["imgname"] = np.asarray(dataset.imgname)
     ev.close()

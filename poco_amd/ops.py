@@ -830,6 +830,110 @@ def pearson64(x: torch.Tensor, y: torch.Tensor, max_blocks: int = 0, *, out=None
     return out
 
 
+# ---- calibration: isotonic regression over ragged segments, fitted maps evaluated (include/poco_hip.h; poco_amd/calibrate.py) -------
+ISO_TILE = 2048                   # POCO_ISO_TILE: positions per tile of the fit (tests sit on its edges)
+ISO_MAX_N, ISO_MAX_SEGS = 1 << 26, 4096
+ISOTONIC_ARGTYPES = ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t] +
+                     [C.c_void_p] * 4 + [C.c_int, C.c_void_p])
+CALIB_APPLY_ARGTYPES = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                        C.c_void_p]
+
+
+def isotonic_scratch_bytes(N: int, S: int) -> int:
+    """poco_op_isotonic_scratch_bytes: the bytes of scratch poco_op_isotonic needs for N positions in S segments (0: out of range)."""
+    fn = lib().poco_op_isotonic_scratch_bytes
+    fn.argtypes, fn.restype = [C.c_int64, C.c_int], C.c_size_t
+    return int(fn(int(N), int(S)))
+
+
+def check_offsets(seg_offsets, N: int, what: str) -> np.ndarray:
+    """A table of offsets as a host int64 array (a device tensor is read back once), refused unless it runs from 0 to N without a
+    step down."""
+    off = seg_offsets.detach().cpu().numpy() if torch.is_tensor(seg_offsets) else np.asarray(seg_offsets)
+    if off.ndim != 1 or len(off) < 2 or not np.issubdtype(off.dtype, np.integer):
+        raise PocoHipError(f"{what} must be an integer vector of at least two entries")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != N or np.any(np.diff(off) < 0):
+        raise PocoHipError(f"{what} must be non-decreasing from 0 to {N}, got {off[:4].tolist()} .. {off[-2:].tolist()}")
+    return off
+
+
+def isotonic(key: torch.Tensor, y: torch.Tensor, order: torch.Tensor, seg_offsets, max_blocks: int = 0, *, out=None, scratch=None) -> dict:
+    """poco_op_isotonic on device tensors: key, y fp32 [M], order int32 [N] (entries in [0, M): segment s's rows in ascending order of
+    canonical key at positions [seg_offsets[s], seg_offsets[s+1])), seg_offsets int32 [S+1] (a device tensor is read back once for
+    the check, a host array is checked and uploaded) -> dict(block int32 [N], fit float64 [N], seg_blocks int32 [S+1], knots float64
+    [N,4] of which the first seg_blocks[S] rows are written).  out = a dict with the same keys to write into; scratch = a uint8 CUDA
+    tensor of at least isotonic_scratch_bytes(N, S) bytes.  Argument errors raise PocoHipError before any GPU work.  Rows with a
+    non-finite key or y must be taken out by the CALLER (calibrate.finite_rows drops and counts them): the kernels stay inside their
+    buffers on such rows, but the values are unspecified."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"isotonic: {what}")
+    for name, t, dt in (("key", key, torch.float32), ("y", y, torch.float32), ("order", order, torch.int32)):
+        need(torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == 1,
+             f"{name} must be a contiguous {dt} CUDA vector")
+    M, N = int(key.shape[0]), int(order.shape[0])
+    need(int(y.shape[0]) == M, f"key and y must have one length, got {M} and {int(y.shape[0])}")
+    need(N <= ISO_MAX_N and M <= ISO_MAX_N and (N == 0 or M >= 1), f"N and M must be at most 2^26 and M >= 1 when N >= 1, got N {N}, M {M}")
+    off = check_offsets(seg_offsets, N, "isotonic: seg_offsets")
+    S = len(off) - 1
+    need(1 <= S <= ISO_MAX_SEGS, f"S must be in 1..{ISO_MAX_SEGS}, got {S}")
+    dev = key.device
+    if torch.is_tensor(seg_offsets) and seg_offsets.is_cuda and seg_offsets.dtype == torch.int32 and seg_offsets.is_contiguous():
+        d_off = seg_offsets
+    else:
+        d_off = torch.from_numpy(off.astype(np.int32)).to(dev)
+    shapes = {"block": ((N,), torch.int32), "fit": ((N,), torch.float64), "seg_blocks": ((S + 1,), torch.int32),
+              "knots": ((N, 4), torch.float64)}
+    if out is None:
+        out = {k: torch.empty(s, device=dev, dtype=dt) for k, (s, dt) in shapes.items()}
+    for k, (shp, dt) in shapes.items():
+        t = out.get(k)
+        need(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt,
+             f"out[{k!r}] must be a contiguous CUDA {dt} {shp}")
+    nbytes = isotonic_scratch_bytes(N, S)
+    if scratch is None:
+        scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    need(torch.is_tensor(scratch) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous(),
+         "scratch must be a contiguous uint8 CUDA tensor")
+    p = lambda t: t.data_ptr() if t.numel() else None                          # noqa: E731
+    fn = lib().poco_op_isotonic
+    fn.argtypes = ISOTONIC_ARGTYPES
+    with torch.cuda.device(dev):
+        check(fn(p(key), p(y), M, p(order), N, d_off.data_ptr(), S, scratch.data_ptr(), int(scratch.numel()), p(out["block"]),
+                 p(out["fit"]), out["seg_blocks"].data_ptr(), p(out["knots"]), int(max_blocks), current_stream()), "poco_op_isotonic")
+    return out
+
+
+def calib_apply(x: torch.Tensor, map_ids: torch.Tensor, map_offsets: torch.Tensor, knots: torch.Tensor, max_blocks: int = 0, *,
+                out=None) -> torch.Tensor:
+    """poco_op_calib_apply on device tensors: x fp32 [R,S], map_ids int32 [S], map_offsets int32 [P+1], knots float64 [B,4] as
+    poco_op_isotonic writes them -> fp32 [R,S], out[r][c] = the map map_ids[c] at x[r][c].  Argument errors raise PocoHipError
+    before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"calib_apply: {what}")
+    for name, t, dt, nd in (("x", x, torch.float32, 2), ("map_ids", map_ids, torch.int32, 1), ("map_offsets", map_offsets, torch.int32, 1),
+                            ("knots", knots, torch.float64, 2)):
+        need(torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == nd,
+             f"{name} must be a contiguous {dt} CUDA tensor of {nd} dimension(s)")
+    R, S = (int(v) for v in x.shape)
+    P, B = int(map_offsets.shape[0]) - 1, int(knots.shape[0])
+    need(int(map_ids.shape[0]) == S, f"map_ids must have one entry per column, got {int(map_ids.shape[0])} for {S}")
+    need(int(knots.shape[1]) == 4, "knots must be [B,4]")
+    need(R >= 1 and 1 <= S <= ISO_MAX_SEGS and 1 <= P <= ISO_MAX_SEGS, f"needs R >= 1, S and P in 1..{ISO_MAX_SEGS}, got {R}, {S}, {P}")
+    if out is None:
+        out = torch.empty((R, S), device=x.device, dtype=torch.float32)
+    need(torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (R, S) and out.dtype == torch.float32,
+         f"out must be a contiguous CUDA float32 {(R, S)}")
+    fn = lib().poco_op_calib_apply
+    fn.argtypes = CALIB_APPLY_ARGTYPES
+    with torch.cuda.device(x.device):
+        check(fn(x.data_ptr(), R, S, map_ids.data_ptr(), map_offsets.data_ptr(), P, knots.data_ptr() if B else None, B, out.data_ptr(),
+                 int(max_blocks), current_stream()), "poco_op_calib_apply")
+    return out
+
+
 # ---- video mode's uncertainty-weighted smoother (include/poco_hip.h; poco_amd/usmooth.py is the user's side) --------------------
 SMOOTH_MAX_LIN = 16
 SMOOTH_MAX_LAMBDA = 1e4

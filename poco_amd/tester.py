@@ -113,6 +113,10 @@ class POCOTester:
             with np.load(args.smpl) as z:
                 if "faces" in z.files:
                     self.faces = np.asarray(z["faces"], np.int64)
+        self.calibration = None                 # --calibration FILE: the final var -> err_pose, err_mpjpe, err_pampjpe, err_v2v
+        if getattr(args, "calibration", None):
+            from .calibrate import Calibration
+            self.calibration = Calibration(args.calibration, self.device, bool(self.model_cfg.POCO.KINEMATIC_UNCERT), str(self.backbone))
         self._renderer = None
         self._refit_tables = None               # --kp_refit: (Jt, Jd, parents) of the body-model file, made at first use
         self._pseudo_src = []                   # --save_dataset: the label of every crop offered to the labeler
@@ -419,6 +423,8 @@ class POCOTester:
         res["smpl_joints2d"] = np.concatenate([j2d, np.ones((len(dets), 49, 1), np.float32)], -1)
         res["var"], res["var_global"] = postproc.folder_uncert(output["var_pose"], self.backbone,
                                                                self.model_cfg.POCO.KINEMATIC_UNCERT)   # tester.py:242-245
+        if self.calibration is not None:
+            res.update(self.calibration.apply(res["var"]))
         return res
 
     @torch.no_grad()
@@ -938,6 +944,9 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
             return f"{vstem}/{f:06d}" if reader is not None else (names[f] if 0 <= f < len(names) else f"{f:06d}")
 
         dataset = self.pseudo_finish(frame_name, lambda x: int(x[0]) if str(x[0]).lstrip("-").isdigit() else order[x[0]])
+    if self.calibration is not None:                                   # after everything that changes `var`
+        for r in results.values():
+            r.update(self.calibration.apply(r["var"]))
     torch.cuda.synchronize()
     dt = time.time() - t0
     if rank != 0:
