@@ -67,6 +67,15 @@ DESIGN.md section 31); camera and norm come from pred_cam, center and scale; the
 and the refit are scored side by side: the usual lines for each, their difference, the mean shift and r(shift, var).  The .npz
 gains mpjpe_raw / pampjpe_raw / v2v_raw / val_*_raw, refit_shift, refit_cost and refit_flag.  Not with --cfg2, --tta, --segm,
 --likelihood, --sequences, --rank_metrics, --visibility, --aug_* or --augment.
+--bootstrap B [--boot_unit crop|track] [--boot_level 0.95] [--boot_seed 0] puts an interval on every headline number: the crops (or
+the tracks sequences.group_tracks finds: the rows of 3DPW are consecutive frames of about 60 clips) are resampled B times with
+replacement on the GPU (csrc/bootstrap.hip, poco_amd/bootstrap.py) and MPJPE, PA-MPJPE, V2V, the uncertainty /
+pose-error correlation and the per-crop Corr(uncertainty, MPJPE) are printed as `name  point  +- se  [lo, hi]  (valid/B)`: the point
+estimate, the bootstrap standard error and the percentile interval.  With --cfg2 (Model 1, Model 2, Selected), --tta (Base view,
+Fused) and --kp_refit (Raw, Refit) every label gets its lines and every label after the first its paired difference to the first, from
+the same draws.  The .npz gains boot_names, boot_summary [S,5], boot_spec (B, units, level, seed) and with --save_results
+boot_replicates [B,S].  Allowed beside --rank_metrics, --calibrate, --uncert_threshold, --crop dataset and --aug_*; not with --segm,
+--likelihood, --sequences or --visibility.
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -188,6 +197,14 @@ def parse_args(argv=None):
                    help="--kp_refit: width of the Geman-McClure robustifier in fractions of the box side (<= 0: plain least squares)")
     p.add_argument("--kp_refit_iters", type=int, default=10, help="--kp_refit: Levenberg-Marquardt steps per row, 1..32")
     p.add_argument("--kp_vis_thresh", type=float, default=0.3, help="--kp_refit: the confidence a keypoint needs to count")
+    p.add_argument("--bootstrap", type=int, default=None, metavar="B",
+                   help="also a cluster bootstrap of B replicates (1..65536) on the GPU (poco_amd/bootstrap.py, csrc/bootstrap.hip): point "
+                        "estimate, standard error and percentile interval of MPJPE, PA-MPJPE, V2V and the correlations, and with --cfg2, "
+                        "--tta or --kp_refit of the paired differences; the .npz gains boot_names, boot_summary and boot_spec")
+    p.add_argument("--boot_unit", default=None, choices=["crop", "track"],
+                   help="with --bootstrap: resample crops (default) or the tracks the image names group into (folder, person, frame number)")
+    p.add_argument("--boot_level", type=float, default=None, help="with --bootstrap: level of the percentile interval (default 0.95)")
+    p.add_argument("--boot_seed", type=int, default=None, help="with --bootstrap: seed of the draws, 0..2^53-1 (default 0)")
     p.add_argument("--min_cutoff", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 0.004)")
     p.add_argument("--beta", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 1.5)")
     return p.parse_args(argv)
@@ -410,6 +427,31 @@ def check_visibility(args) -> None:
                      "its triangles)")
 
 
+def check_bootstrap(args) -> None:
+    """--bootstrap / --boot_*: refuse what cannot work before an engine is built - the flags it excludes, options out of range, and
+    with --boot_unit track a dataset whose image names do not group into tracks."""
+    from poco_amd.bootstrap import flag_error
+    msg = flag_error(args)
+    if msg:
+        sys.exit(msg)
+    if getattr(args, "bootstrap", None) is not None and getattr(args, "boot_unit", None) == "track" and os.path.isfile(args.dataset):
+        import numpy as np
+        from poco_amd.sequences import group_tracks
+        with np.load(args.dataset, allow_pickle=False) as z:
+            rows = z
+            if getattr(args, "uncert_threshold", None) is not None:
+                from poco_amd.evaluate import select_confident
+                try:
+                    rows = select_confident(z, args.uncert_threshold, args.dataset)     # the tracks of the rows that are evaluated
+                except ValueError:
+                    return                                                              # check_uncert_threshold names what is wrong
+            if "imgname" in rows.files:
+                try:
+                    group_tracks(rows["imgname"], rows["person_id"] if "person_id" in rows.files else None)
+                except ValueError as e:
+                    sys.exit(f"{args.dataset}: --boot_unit track: {e}")
+
+
 def calibrate_spec(args, tester):
     """run_eval's `calibrate` argument from --calibrate / --calib_split / --calib_bins, or None."""
     if not getattr(args, "calibrate", None):
@@ -420,6 +462,7 @@ def calibrate_spec(args, tester):
 
 
 def main(args):
+    check_bootstrap(args)
     check_calibrate(args)
     check_visibility(args)
     check_sequences(args)
@@ -457,6 +500,10 @@ def main(args):
         print(f"Confident rows (uncertainty < {args.uncert_threshold}): {len(ds)} of {ds.total}")
     J = np.load(args.j_regressor).astype(np.float32)
     tester = POCOTester(args)                       # builds the engine from --cfg / --ckpt / --smpl exactly as demo.py does
+    boot_kw = {}
+    if getattr(args, "bootstrap", None) is not None:
+        from poco_amd import bootstrap
+        boot_kw["bootstrap"] = bootstrap.spec_from_args(args)
     vis_kw = {}
     if getattr(args, "visibility", False):
         from poco_amd import visibility
@@ -480,16 +527,16 @@ def main(args):
     elif tester.tta is not None:
         print(f"Test-time views: {tester.tta_text} ({tester.tta.weight} weights)")
         res = evaluate.run_eval_tta(tester.tta, ds, J, batch_size=max(int(args.batch_size), 1),
-                                    kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
+                                    kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results, **boot_kw)
     elif tester.pair is not None:
         res = evaluate.run_eval_pair(tester.pair, ds, J, batch_size=max(int(args.batch_size), 1),
-                                     kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results)
+                                     kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results, **boot_kw)
     elif getattr(args, "kp_refit", None) is not None:
         from poco_amd import refit
         res = evaluate.run_eval_refit(tester.model, ds, J, refit.joint_tables(args.smpl), float(args.kp_refit), float(args.kp_refit_ref),
                                       float(args.kp_refit_rho), float(args.kp_vis_thresh), int(args.kp_refit_iters),
                                       batch_size=max(int(args.batch_size), 1), kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT),
-                                      save_results=args.save_results)
+                                      save_results=args.save_results, **boot_kw)
     elif getattr(args, "sequences", False):
         from poco_amd.sequences import parse_pipelines
         opt = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)   # noqa: E731
@@ -506,7 +553,7 @@ def main(args):
                                 kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results,
                                 likelihood=args.likelihood,
                                 rank_metrics=(args.rank_bins or 20) if getattr(args, "rank_metrics", False) else None,
-                                calibrate=calibrate_spec(args, tester), **vis_kw)
+                                calibrate=calibrate_spec(args, tester), **vis_kw, **boot_kw)
     lines = evaluate.pair_report_lines(res, tester.pair.mode) if tester.pair is not None else evaluate.report_lines(res)
     if tester.tta is not None:
         lines = evaluate.tta_report_lines(res)
@@ -525,6 +572,9 @@ def main(args):
         for line in calibrate.summary_lines(res["calibration"]):
             print(line)
         calibrate.save(args.calibrate, res["calibration"])
+    if boot_kw:
+        for line in bootstrap.report_lines(res):
+            print(line)
     if getattr(args, "sequences", False):
         for line in evaluate.sequence_lines(res):
             print(line)

@@ -1423,6 +1423,50 @@ int poco_op_isotonic(const float* d_key, const float* d_y, int64_t M, const int3
 int poco_op_calib_apply(const float* d_x, int64_t R, int S, const int32_t* d_map_ids, const int32_t* d_map_offsets, int P,
                         const double* d_knots, int64_t B, float* d_out, int max_blocks, void* stream);
 
+/* ---- the cluster bootstrap: fp64 moments per unit and B resamples of the units with replacement, every sum in a fixed order -----------
+ * eval.py --bootstrap B; csrc/bootstrap.hip; poco_amd/bootstrap.py; tests/boot_np.py restates it with plain
+ * loops and math.fsum.  No counterpart in the reference's code, which reports point estimates only.
+ *
+ * poco_op_bootstrap: d_planes fp32 [E][n] on the device, 1 <= E <= POCO_BOOT_MAX_PLANES, 1 <= n <= POCO_BOOT_MAX_N.  pairs int32
+ *   [P][2] on the HOST (read before the launch; NULL if P = 0), 0 <= P <= POCO_BOOT_MAX_PAIRS, entries in [0, E); a pair may name
+ *   one plane twice.  d_unit_offsets int32 [U+1] on the device: unit u = rows [offsets[u], offsets[u+1]), non-decreasing from 0 to n,
+ *   empty units allowed, 1 <= U <= n (the CALLER checks the values: they are device memory; the kernel clamps every offset into
+ *   [0, n] and never reads outside d_planes).  NULL = every row is its own unit; then U must equal n.  0 <= B <= POCO_BOOT_MAX_B.
+ *   M = 1 + E + P.
+ *   d_center fp64 [E]: the mean of each plane over all n rows (tiles of 4096 rows: lane-strided sums and a halving tree over 256
+ *     lanes per tile, the same over the tiles' sums, one division).
+ *   d_unit_mom fp64 [U][M], per unit: column 0 = its rows, columns 1..E = the sums of the raw values, columns E+1..E+P = the sums of
+ *     (v_a - center_a) * (v_b - center_b) of each pair, each factor and the product rounded to fp64 before the addition (no fused
+ *     multiply-add).  The products are centred so that a correlation formed from them does not cancel; Pearson's r does not change
+ *     under a shift.  A wave per unit: lane l adds rows l, l + 64, ... of the unit in order, then a halving tree over the 64 lanes.
+ *   d_out fp64 [B+1][M]: row 0 = the sum of unit_mom over the units 0 .. U-1, each once (the full sample, by the arithmetic of the
+ *     replicates); row b >= 1 = the sum of unit_mom[idx(b, j)] over the draws j = 0 .. U-1.
+ *   The draws: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; ten rounds), key = (seed
+ *     low word, seed high word), counter = (q, 0, b, 0); its four output words, in order, are draws 4q .. 4q+3 of replicate b.
+ *     idx = ((uint64_t)word * U) >> 32.  A unit is drawn with a probability that is off from 1 / U by at most 2^-32: relative to
+ *     1 / U that is U 2^-32 = 8e-6 at U = 35 515 (3DPW's crops) and 2^-8 at U = 2^24.  Stateless: a draw depends on (seed, b, j, U).
+ *   The sum of a replicate: a block of 256 lanes; lane t owns the counters q = t, t + 256, ... and adds the rows of their draws
+ *     4q .. 4q+3 (those below U) in that order, column by column; then a halving tree over the 64 lanes of each wave and
+ *     ((wave 0 + wave 1) + wave 2) + wave 3.  Which additions form an output word, and their order, is fixed by (n, E, P, the
+ *     offsets, seed, b): not by the grid, max_blocks, B or the order in which blocks finish.  No floating-point atomics.
+ *   d_draw_counts uint32 [B][U], or NULL to skip: how often replicate b + 1 drew unit u (zeroed by a launch, then integer atomics).
+ *   d_scratch: poco_op_bootstrap_scratch_bytes(n, E, P, U) bytes (0 = an argument out of range), 8-byte aligned.
+ *   max_blocks: 0 = the default grid, > 0 bounds it; every output is bitwise independent of it and equal from run to run.
+ *   4 launches on `stream` (5 with d_draw_counts and B > 0); the inputs are only read; no allocation, no synchronisation.
+ *   A NaN or an infinity in a plane reaches center, hence every centred product of that plane; in the raw columns it reaches exactly
+ *   the replicates that drew its unit.
+ *   POCO_ERR_ARG before any GPU work: a null pointer (pairs may be NULL only with P = 0; d_unit_offsets only with U = n), n, E, P,
+ *   U or B out of range, max_blocks < 0, a pair entry outside [0, E), a scratch buffer that is too small, misaligned buffers,
+ *   scratch or outputs that overlap an input or each other. */
+#define POCO_BOOT_MAX_N (1 << 24)
+#define POCO_BOOT_MAX_PLANES 16
+#define POCO_BOOT_MAX_PAIRS 16
+#define POCO_BOOT_MAX_B 65536
+size_t poco_op_bootstrap_scratch_bytes(int64_t n, int E, int P, int64_t U);
+int poco_op_bootstrap(const float* d_planes, int64_t n, int E, const int32_t* pairs, int P, const int32_t* d_unit_offsets, int64_t U,
+                      int64_t B, uint64_t seed, void* d_scratch, size_t scratch_bytes, double* d_center, double* d_unit_mom,
+                      double* d_out, uint32_t* d_draw_counts, int max_blocks, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

@@ -394,3 +394,26 @@ void launch_isotonic(const float* key, const float* y, int M, const int* order, 
                      int* block, double* fit, int* seg_blocks, double* knots, int max_blocks, hipStream_t s);
 void launch_calib_apply(const float* x, long long R, int S, const int* map_ids, const int* map_offsets, int P, const double* knots,
                         int B, float* out, int max_blocks, hipStream_t s);
+
+// ---- the cluster bootstrap of eval.py --bootstrap: unit moments and B resamples of the units (bootstrap.hip) ----------------------------
+// include/poco_hip.h poco_op_bootstrap: planes fp32 [E][n], pairs int32 [P][2] on the HOST (checked by the caller), unit_offsets int32
+// [U + 1] on the device or null (every row its own unit); outputs center fp64 [E], unit_mom fp64 [U][M], out fp64 [B + 1][M] with
+// M = 1 + E + P, draw_counts uint32 [B][U] or null.  Tiles of BOOT_TILE rows, units (a wave each) and replicates (a block each) are dealt
+// to at most BOOT_MAX_BLOCKS blocks of BOOT_THREADS (max_blocks > 0: at most that many) by grid-stride loops.  The scratch buffer is the
+// caller's: boot_scratch_layout gives its one part (the per-tile partial sums of the planes) and the total.
+constexpr int BOOT_TILE = 4096;
+constexpr int BOOT_THREADS = 256;
+constexpr int BOOT_MAX_BLOCKS = 4096;
+constexpr int BOOT_MAX_PLANES = 16;
+constexpr int BOOT_MAX_PAIRS = 16;
+constexpr int BOOT_MAX_M = 1 + BOOT_MAX_PLANES + BOOT_MAX_PAIRS;
+constexpr long long BOOT_MAX_N = 1 << 24;
+constexpr long long BOOT_MAX_B = 65536;
+struct BootScratch {
+  int NT;                                                  // tiles
+  size_t partial, bytes;
+};
+BootScratch boot_scratch_layout(long long n, int E);
+void launch_bootstrap(const float* planes, long long n, int E, const int* pairs, int P, const int* unit_offsets, long long U, long long B,
+                      unsigned long long seed, void* scratch, double* center, double* unit_mom, double* out, unsigned* draw_counts,
+                      int max_blocks, hipStream_t s);

@@ -1329,3 +1329,52 @@ extern "C" int poco_op_calib_apply(const float* d_x, int64_t R, int S, const int
   POCO_HIP_CHECK(hipGetLastError());
   return POCO_OK;
 }
+
+// ---- the cluster bootstrap of eval.py --bootstrap: unit moments and resamples (bootstrap.hip) -----------------------------------------
+static_assert(POCO_BOOT_MAX_N == BOOT_MAX_N && POCO_BOOT_MAX_PLANES == BOOT_MAX_PLANES && POCO_BOOT_MAX_PAIRS == BOOT_MAX_PAIRS &&
+                  POCO_BOOT_MAX_B == BOOT_MAX_B,
+              "include/poco_hip.h and csrc/kernels.h disagree on the bootstrap");
+static bool boot_shape_ok(int64_t n, int E, int P, int64_t U) {
+  return n >= 1 && n <= POCO_BOOT_MAX_N && E >= 1 && E <= POCO_BOOT_MAX_PLANES && P >= 0 && P <= POCO_BOOT_MAX_PAIRS && U >= 1 && U <= n;
+}
+
+extern "C" size_t poco_op_bootstrap_scratch_bytes(int64_t n, int E, int P, int64_t U) {
+  return boot_shape_ok(n, E, P, U) ? boot_scratch_layout(n, E).bytes : 0;
+}
+
+extern "C" int poco_op_bootstrap(const float* d_planes, int64_t n, int E, const int32_t* pairs, int P, const int32_t* d_unit_offsets,
+                                 int64_t U, int64_t B, uint64_t seed, void* d_scratch, size_t scratch_bytes, double* d_center,
+                                 double* d_unit_mom, double* d_out, uint32_t* d_draw_counts, int max_blocks, void* stream) {
+  const char* who = "poco_op_bootstrap";
+  if (!boot_shape_ok(n, E, P, U)) return op_bad(who, "n must be in 1..2^24, E in 1..16, P in 0..16 and U in 1..n");
+  if (B < 0 || B > POCO_BOOT_MAX_B) return op_bad(who, "B must be in 0..65536");
+  if (max_blocks < 0) return op_bad(who, "max_blocks must be >= 0");
+  if (!d_unit_offsets && U != n) return op_bad(who, "without unit_offsets every row is its own unit: U must equal n");
+  if (!d_planes || !d_scratch || !d_center || !d_unit_mom || !d_out || (P > 0 && !pairs))
+    return op_bad(who, "null pointer (planes, scratch, center, unit_mom and out are needed, and pairs if P > 0)");
+  for (int k = 0; k < 2 * P; ++k)
+    if (pairs[k] < 0 || pairs[k] >= E) return op_bad(who, "a pair names a plane outside 0..E-1");
+  if (!aligned_to(d_scratch, 8) || !aligned_to(d_center, 8) || !aligned_to(d_unit_mom, 8) || !aligned_to(d_out, 8) ||
+      !aligned_to(d_planes, 4) || !aligned_to(d_unit_offsets, 4) || !aligned_to(d_draw_counts, 4))
+    return op_bad(who, "scratch, center, unit_mom and out must be 8-byte aligned, the fp32, int32 and uint32 buffers 4-byte aligned");
+  const size_t need = boot_scratch_layout(n, E).bytes;
+  if (scratch_bytes < need)
+    return op_bad(who, "the scratch buffer holds " + std::to_string(scratch_bytes) + " bytes, poco_op_bootstrap_scratch_bytes asks for " +
+                           std::to_string(need));
+  // [begin, end) in bytes: the two inputs, then the scratch and the four outputs, none of which may overlap anything before it
+  const size_t N = (size_t)n, Us = (size_t)U, M = (size_t)(1 + E + P);
+  const struct { const void* p; size_t bytes; } buf[7] = {{d_planes, (size_t)E * N * 4}, {d_unit_offsets, d_unit_offsets ? (Us + 1) * 4 : 0},
+                                                          {d_scratch, need}, {d_center, (size_t)E * 8}, {d_unit_mom, Us * M * 8},
+                                                          {d_out, ((size_t)B + 1) * M * 8},
+                                                          {d_draw_counts, d_draw_counts ? (size_t)B * Us * 4 : 0}};
+  for (int o = 2; o < 7; ++o)
+    for (int i = 0; i < o; ++i) {
+      if (!buf[i].bytes || !buf[o].bytes) continue;
+      const uintptr_t a0 = (uintptr_t)buf[o].p, a1 = a0 + buf[o].bytes, b0 = (uintptr_t)buf[i].p, b1 = b0 + buf[i].bytes;
+      if (a0 < b1 && b0 < a1) return op_bad(who, "the scratch and the outputs may not overlap an input or each other");
+    }
+  launch_bootstrap(d_planes, n, E, pairs, P, d_unit_offsets, U, B, seed, d_scratch, d_center, d_unit_mom, d_out, d_draw_counts, max_blocks,
+                   (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}

@@ -435,7 +435,7 @@ class EvalDataset:
 @torch.no_grad()
 def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
              sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_records: bool = False,
-             likelihood: bool = False, rank_metrics: Optional[int] = None, visibility=None, calibrate=None) -> Dict[str, object]:
+             likelihood: bool = False, rank_metrics: Optional[int] = None, visibility=None, calibrate=None, bootstrap=None) -> Dict[str, object]:
     """trainer.py:298-336 over a whole dataset: forward, then the metrics of every batch (the ragged last one included) on the
     device.  SMPL ground truth: gt_vertices = POCO.smpl_lbs(shape, poco_op_rodrigues(pose)) (base_dataset.py:353-366, neutral
     model), also on the device.  Returns Evaluator.finish() plus `imgname`.  likelihood=True (needs `pose` in the dataset and
@@ -447,7 +447,9 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
     the same stream, it counts the visible pixels of every body part of the ground-truth mesh; the result gains the
     visibility.NPZ_KEYS arrays and `vis_stats`.  Needs SMPL ground truth; without the argument nothing changes.
     calibrate (eval.py --calibrate): dict(split, bins, meta); the result gains `calibration` (the calibrate.NPZ_KEYS arrays, for
-    calibrate.save) and the array `calib_summary`; everything else is what it is without the argument."""
+    calibrate.save) and the array `calib_summary`; everything else is what it is without the argument.
+    bootstrap (eval.py --bootstrap): a bootstrap.BootSpec; the result gains the bootstrap.NPZ_KEYS arrays (and boot_replicates with
+    save_results), computed from the records after finish(); everything else is what it is without the argument."""
     from . import ops
     dev = model.device
     ev = Evaluator(J_regressor, joint_map(dataset.name), capacity=len(dataset), sel_uncert_part=sel_uncert_part, kinematic=kinematic,
@@ -482,10 +484,18 @@ def run_eval(model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kin
         from . import calibrate as calib
         res["calibration"] = calib.calibrate(ev, calibrate.get("split", "half"), int(calibrate.get("bins", 20)), calibrate.get("meta"))
         res["calib_summary"] = res["calibration"]["calib_summary"]
+    if bootstrap is not None:
+        res.update(_bootstrap([("", ev)], bootstrap, dataset, save_results))
     model.check_status()
     res["imgname"] = np.asarray(dataset.imgname)
     ev.close()
     return res
+
+
+def _bootstrap(evaluators, spec, dataset: "EvalDataset", save_replicates: bool) -> Dict[str, object]:
+    """bootstrap.bootstrap_evaluators on the run's evaluators, after their finish() calls (eval.py --bootstrap)."""
+    from .bootstrap import bootstrap_evaluators
+    return bootstrap_evaluators(evaluators, spec, imgname=dataset.imgname, person_id=dataset.person_id, save_replicates=save_replicates)
 
 
 SEQ_NPZ_KEYS = ("seq_track", "seq_frame", "seq_accel", "seq_accel_err", "seq_track_names", "seq_pipelines", "seq_summary")
@@ -655,12 +665,14 @@ def selection_summary(crop_mpjpe, crop_pampjpe, select) -> Dict[str, float]:
 
 @torch.no_grad()
 def run_eval_pair(pair, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
-                  sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False) -> Dict[str, object]:
+                  sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, bootstrap=None) -> Dict[str, object]:
     """run_eval with a second model (eval.py --cfg2 --ckpt2): per batch RegressorPair.forward_all, then three
     Evaluators - model 1, model 2, selected - stepped against the same ground truth on the same stream; the choices are kept in
     device buffers, so nothing goes to the host between the forward and the three finish() calls.  Returns the selected result
     under run_eval's keys, the two models' mpjpe / pampjpe / v2v and val_* with suffixes _m1 and _m2, their per-crop record values
-    crop_mpjpe_m* / crop_pampjpe_m* [N], select [N,24] uint8, select_score [N,2] and selection_summary of them."""
+    crop_mpjpe_m* / crop_pampjpe_m* [N], select [N,24] uint8, select_score [N,2] and selection_summary of them.
+    bootstrap: a bootstrap.BootSpec; the result gains the bootstrap.NPZ_KEYS arrays for Model 1, Model 2 and Selected, the latter two
+    also as paired differences to Model 1; nothing else changes."""
     from . import ops
     dev, n = pair.device, len(dataset)
     evs = [Evaluator(J_regressor, joint_map(dataset.name), capacity=n, sel_uncert_part=sel_uncert_part, kinematic=kinematic, device=dev)
@@ -688,6 +700,8 @@ def run_eval_pair(pair, dataset: EvalDataset, J_regressor, batch_size: int = 64,
     res["select"], res["select_score"] = select.cpu().numpy(), score.cpu().numpy()
     res.update(selection_summary((res["crop_mpjpe_m1"], res["crop_mpjpe_m2"]), (res["crop_pampjpe_m1"], res["crop_pampjpe_m2"]),
                                  res["select"]))
+    if bootstrap is not None:
+        res.update(_bootstrap(list(zip(("Model 1", "Model 2", "Selected"), evs)), bootstrap, dataset, save_results))
     pair.check_status()
     res["imgname"] = np.asarray(dataset.imgname)
     for ev in evs:
@@ -712,14 +726,17 @@ TTA_OUTPUT_KEYS = ("pred_pose", "var_pose", "pred_shape", "smpl_vertices", "smpl
 
 @torch.no_grad()
 def run_eval_tta(tta_model, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
-                 sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_outputs: bool = False) -> Dict[str, object]:
+                 sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_outputs: bool = False,
+                 bootstrap=None) -> Dict[str, object]:
     """run_eval with test-time views (eval.py --tta, DESIGN.md section 26): per batch of b = max(1, batch_size // K) crops the K * b
     views are cut in one launch (tta.dataset_batch), TTAModel.forward_all regresses and fuses them, and three Evaluators are
     stepped against the base frame's ground truth on the same stream: the base view, the fused result, and the fused result with
     var_pose := tta_spread and kinematic off, whose correlation is Corr(view spread, pose distance).  Nothing goes to the host
     between the forward and the three finish() calls.  Returns the fused result under run_eval's keys, the base view's mpjpe /
     pampjpe / v2v and val_* with suffix _base, val_corr_spread, tta_spread [N,24] and tta_views [K,3] (flip, rot, scale).
-    return_outputs (tests): also `outputs` = per batch (the K per-view dicts, the fused dict) of host arrays."""
+    return_outputs (tests): also `outputs` = per batch (the K per-view dicts, the fused dict) of host arrays.
+    bootstrap: a bootstrap.BootSpec; the result gains the bootstrap.NPZ_KEYS arrays for Base view and Fused and their paired
+    difference; nothing else changes."""
     from . import ops, tta
     if dataset.crop != "dataset":
         raise ValueError("run_eval_tta cuts its views with the dataset crop: the dataset needs crop='dataset'")
@@ -758,6 +775,8 @@ def run_eval_tta(tta_model, dataset: EvalDataset, J_regressor, batch_size: int =
     res["tta_spread"] = spread.cpu().numpy()
     res["tta_views"] = np.asarray([[float(v.flip), float(v.rot), float(v.scale)] for v in views], np.float64)
     res["tta_weight"] = tta_model.weight
+    if bootstrap is not None:
+        res.update(_bootstrap([("Base view", evs[0]), ("Fused", evs[1])], bootstrap, dataset, save_results))
     if return_outputs:
         res["outputs"] = outputs
     tta_model.check_status()
@@ -783,7 +802,7 @@ REFIT_SCALARS = tuple(k + "_raw" for k in ("val_mpjpe", "val_pampjpe", "val_v2v"
 @torch.no_grad()
 def run_eval_refit(model, dataset: EvalDataset, J_regressor, tables, lam: float, u_ref: float = 0.3, rho: float = 0.1,
                    conf_thresh: float = 0.3, iters: int = 10, batch_size: int = 64, kinematic: bool = True,
-                   sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False) -> Dict[str, object]:
+                   sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, bootstrap=None) -> Dict[str, object]:
     """run_eval with the keypoint refit (eval.py --kp_refit): per batch the forward, then refit.refit_rows on the
     batch's pose, processed uncertainty (trailing axes averaged, accumulated along the tree when `kinematic`) and shape against the
     dataset's `openpose` keypoints - camera a = s h / 2 from pred_cam, (px, py) = the box centre, norm = h = 200 scale - then LBS of
@@ -791,7 +810,8 @@ def run_eval_refit(model, dataset: EvalDataset, J_regressor, tables, lam: float,
     on the same stream: the raw prediction and the refit.  tables = refit.joint_tables(the body model).  Returns the refit's result
     under run_eval's keys, the raw prediction's mpjpe / pampjpe / v2v and val_* with suffix _raw, refit_shift [N,24], refit_cost
     [N,2], refit_flag [N], refit_mean_shift and refit_corr_shift_var (Pearson r of shift and processed uncertainty over the fitted
-    rows)."""
+    rows).  bootstrap: a bootstrap.BootSpec; the result gains the bootstrap.NPZ_KEYS arrays for Raw and Refit and their paired
+    difference; nothing else changes."""
     from . import ops, refit
     from .synth import SMPL_PARENTS
     if dataset.openpose is None:
@@ -844,6 +864,8 @@ def run_eval_refit(model, dataset: EvalDataset, J_regressor, tables, lam: float,
     res["refit_mean_shift"] = float(res["refit_shift"][ok].mean()) if ok.any() else 0.0
     res["refit_corr_shift_var"] = refit._pearson(res["refit_shift"][ok].astype(np.float64).reshape(-1),
                                                  uvar.cpu().numpy()[ok].astype(np.float64).reshape(-1))
+    if bootstrap is not None:
+        res.update(_bootstrap([("Raw", evs[0]), ("Refit", evs[1])], bootstrap, dataset, save_results))
     model.check_status()
     res["imgname"] = np.asarray(dataset.imgname)
     for ev in evs:
@@ -922,5 +944,6 @@ def save_npz(path: str, res: Dict[str, object], dataset_name: str) -> None:
     keep.update({k: np.float64(res[k]) for k in TTA_SCALARS if k in res})        # eval.py --tta (run_eval_tta)
     keep.update({k: np.float64(res[k]) for k in REFIT_SCALARS if k in res})      # eval.py --kp_refit (run_eval_refit)
     keep.update({k: res[k] for k in ("seq_track_names", "seq_pipelines") if k in res})   # eval.py --sequences (run_eval_sequences)
+    keep.update({k: res[k] for k in ("boot_names",) if k in res})                        # eval.py --bootstrap (poco_amd/bootstrap.py)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     np.savez(path, **keep)

@@ -934,6 +934,81 @@ def calib_apply(x: torch.Tensor, map_ids: torch.Tensor, map_offsets: torch.Tenso
     return out
 
 
+# ---- the cluster bootstrap: unit moments and resamples (include/poco_hip.h; poco_amd/bootstrap.py is the user's side) ---------------
+BOOT_MAX_N, BOOT_MAX_PLANES, BOOT_MAX_PAIRS, BOOT_MAX_B = 1 << 24, 16, 16, 65536
+BOOTSTRAP_ARGTYPES = ([C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p,
+                       C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p])
+
+
+def bootstrap_scratch_bytes(n: int, E: int, P: int, U: int) -> int:
+    """poco_op_bootstrap_scratch_bytes: the bytes of scratch poco_op_bootstrap needs (0: an argument out of range)."""
+    fn = lib().poco_op_bootstrap_scratch_bytes
+    fn.argtypes, fn.restype = [C.c_int64, C.c_int, C.c_int, C.c_int64], C.c_size_t
+    return int(fn(int(n), int(E), int(P), int(U)))
+
+
+def bootstrap(planes: torch.Tensor, pairs=(), unit_offsets=None, B: int = 0, seed: int = 0, max_blocks: int = 0, *, out=None,
+              scratch=None, draw_counts: bool = False) -> dict:
+    """poco_op_bootstrap on device tensors: planes fp32 [E,n], pairs = up to 16 (a, b) plane indices (host), unit_offsets int32 [U+1]
+    (None: every row is its own unit; a device tensor is read back once for the check, a host array is checked and uploaded), B
+    replicates, seed in 0..2^64-1 -> dict(center float64 [E], unit_mom float64 [U,M], out float64 [B+1,M], M = 1 + E + P, and with
+    draw_counts=True or out["draw_counts"] given: draw_counts int32 [B,U], the bits of the header's uint32).  out = a dict with the
+    same keys to write into; scratch = a uint8 CUDA tensor of at least bootstrap_scratch_bytes(n, E, P, U) bytes.  max_blocks > 0
+    bounds the grid (the result does not depend on it).  Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"bootstrap: {what}")
+    need(torch.is_tensor(planes) and planes.is_cuda and planes.dtype == torch.float32 and planes.is_contiguous() and planes.dim() == 2,
+         "planes must be a contiguous float32 CUDA [E,n]")
+    E, n = (int(v) for v in planes.shape)
+    need(1 <= E <= BOOT_MAX_PLANES and 1 <= n <= BOOT_MAX_N, f"E must be in 1..{BOOT_MAX_PLANES} and n in 1..2^24, got E {E}, n {n}")
+    try:
+        pr = np.ascontiguousarray(np.asarray(list(pairs), np.int64).reshape(-1, 2))
+    except (TypeError, ValueError):
+        pr = None
+    need(pr is not None and len(pr) <= BOOT_MAX_PAIRS, f"pairs must be at most {BOOT_MAX_PAIRS} (a, b) plane indices")
+    P = len(pr)
+    need(P == 0 or (pr.min() >= 0 and pr.max() < E), f"a pair names a plane outside 0..{E - 1}")
+    pr = np.ascontiguousarray(pr.astype(np.int32))
+    need(isinstance(B, (int, np.integer)) and 0 <= B <= BOOT_MAX_B, f"B must be in 0..{BOOT_MAX_B}, got {B}")
+    need(isinstance(seed, (int, np.integer)) and 0 <= int(seed) < 1 << 64, f"seed must be in 0..2^64-1, got {seed}")
+    dev = planes.device
+    d_off = None
+    U = n
+    if unit_offsets is not None:
+        off = check_offsets(unit_offsets, n, "bootstrap: unit_offsets")
+        U = len(off) - 1
+        need(U <= n, f"at most n = {n} units, got {U}")
+        if torch.is_tensor(unit_offsets) and unit_offsets.is_cuda and unit_offsets.dtype == torch.int32 and unit_offsets.is_contiguous():
+            d_off = unit_offsets
+        else:
+            d_off = torch.from_numpy(off.astype(np.int32)).to(dev)
+    M = 1 + E + P
+    shapes = {"center": ((E,), torch.float64), "unit_mom": ((U, M), torch.float64), "out": ((int(B) + 1, M), torch.float64)}
+    if draw_counts or (out is not None and out.get("draw_counts") is not None):
+        shapes["draw_counts"] = ((int(B), U), torch.int32)
+    if out is None:
+        out = {k: torch.empty(s, device=dev, dtype=dt) for k, (s, dt) in shapes.items()}
+    for k, (shp, dt) in shapes.items():
+        t = out.get(k)
+        need(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt,
+             f"out[{k!r}] must be a contiguous CUDA {dt} {shp}")
+    nbytes = bootstrap_scratch_bytes(n, E, P, U)
+    if scratch is None:
+        scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    need(torch.is_tensor(scratch) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous(),
+         "scratch must be a contiguous uint8 CUDA tensor")
+    counts = out.get("draw_counts") if "draw_counts" in shapes else None
+    fn = lib().poco_op_bootstrap
+    fn.argtypes = BOOTSTRAP_ARGTYPES
+    with torch.cuda.device(dev):
+        check(fn(planes.data_ptr(), n, E, pr.ctypes.data if P else None, P, None if d_off is None else d_off.data_ptr(), U, int(B),
+                 int(seed), scratch.data_ptr(), int(scratch.numel()), out["center"].data_ptr(), out["unit_mom"].data_ptr(),
+                 out["out"].data_ptr(), counts.data_ptr() if counts is not None and counts.numel() else None, int(max_blocks),
+                 current_stream()), "poco_op_bootstrap")
+    return out
+
+
 # ---- video mode's uncertainty-weighted smoother (include/poco_hip.h; poco_amd/usmooth.py is the user's side) --------------------
 SMOOTH_MAX_LIN = 16
 SMOOTH_MAX_LAMBDA = 1e4
