@@ -17,6 +17,7 @@
 //   counts     draw_counts is zeroed by a launch of its own, then filled with integer atomics (their result has no order).
 //
 // No floating-point atomics, no spin-wait, no grid barrier.  LDS: boot_center 2 KB, boot_resample 4 x BOOT_MAX_M x 8 = 1056 bytes.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -53,20 +54,6 @@ __device__ __forceinline__ double wave_tree(double v) {
   return v;                                                             // lane 0 holds the sum
 }
 
-// the sum of the block's 256 values, returned to every lane: a halving tree in LDS
-__device__ __forceinline__ double block_tree(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int o = BT_TH / 2; o > 0; o >>= 1) {
-    if (t < o) red[t] = red[t] + red[t + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(BT_TH) void boot_center_tiles(BootDev a) {
   __shared__ double red[BT_TH];
   const long long items = (long long)a.E * a.NT;
@@ -76,7 +63,7 @@ __global__ __launch_bounds__(BT_TH) void boot_center_tiles(BootDev a) {
     const float* p = a.planes + (size_t)e * (size_t)a.n;
     double acc = 0.0;
     for (long long r = r0 + threadIdx.x; r < r1; r += BT_TH) acc = acc + (double)p[r];
-    acc = block_tree(acc, red);
+    acc = block_tree_sum<BT_TH>(acc, red);
     if (threadIdx.x == 0) a.partial[it] = acc;
   }
 }
@@ -87,7 +74,7 @@ __global__ __launch_bounds__(BT_TH) void boot_center_final(BootDev a) {
     const double* p = a.partial + (size_t)e * a.NT;
     double acc = 0.0;
     for (int i = threadIdx.x; i < a.NT; i += BT_TH) acc = acc + p[i];
-    acc = block_tree(acc, red);
+    acc = block_tree_sum<BT_TH>(acc, red);
     if (threadIdx.x == 0) a.center[e] = acc / (double)a.n;
   }
 }

@@ -12,6 +12,7 @@
 //   flow_epilogue_kernel   one wave per crop: log sigma, mean_9(bar), the per-crop sum over the joints in joint order (fp64), zeros
 //                          for an invalid crop (a select, so a NaN in an invalid crop's inputs does not leak).
 // The reductions are one block each, fp64, strided then tree: a fixed order, no atomics - two runs give the same bits.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 #include "rodrigues.h"
@@ -75,19 +76,6 @@ __global__ __launch_bounds__(64) void flow_epilogue_kernel(const float* __restri
   }
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int o = RED_THREADS / 2; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // summary[4] = {valid crops, mean log phi, mean log sigma, loss_nf}; means over valid crops x 24 joints (0 / 0 = NaN without one)
 __global__ __launch_bounds__(RED_THREADS) void flow_nll_reduce_kernel(const float* __restrict__ rec, long long N, double* __restrict__ summary) {
   __shared__ double red[RED_THREADS];
@@ -101,7 +89,8 @@ __global__ __launch_bounds__(RED_THREADS) void flow_nll_reduce_kernel(const floa
       lp += p; ls += s; df += s - p;
     }
   }
-  cnt = block_sum(cnt, red); lp = block_sum(lp, red); ls = block_sum(ls, red); df = block_sum(df, red);
+  cnt = block_tree_sum<RED_THREADS>(cnt, red); lp = block_tree_sum<RED_THREADS>(lp, red);
+  ls = block_tree_sum<RED_THREADS>(ls, red); df = block_tree_sum<RED_THREADS>(df, red);
   if (threadIdx.x == 0) {
     const double terms = 24.0 * cnt;
     summary[0] = cnt; summary[1] = lp / terms; summary[2] = ls / terms; summary[3] = df / terms;
@@ -121,7 +110,7 @@ __global__ __launch_bounds__(RED_THREADS) void eval_uncert_summary_kernel(const 
     q += (double)r[off_mpjpe] / (m + 1e-9);
     v += m;
   }
-  q = block_sum(q, red); v = block_sum(v, red);
+  q = block_tree_sum<RED_THREADS>(q, red); v = block_tree_sum<RED_THREADS>(v, red);
   if (threadIdx.x == 0) { summary[0] = q / (double)N; summary[1] = v / (double)N; }
 }
 

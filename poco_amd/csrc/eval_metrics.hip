@@ -17,9 +17,11 @@
 // latency-bound): the records are the fp32 roundings of fp64 results, so they do not depend on the slice count or the batching.
 // The processed uncertainty alone is fp32, in the order of poco_amd/postproc.py, so that it equals the host's values.
 // No atomics: every output word has one writer and every sum a fixed order - two runs give the same bits.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 #include "rodrigues.h"
+#include "rotation_fit.h"
 #include "../../include/poco_hip.h"
 
 #include <algorithm>
@@ -33,7 +35,6 @@ constexpr int EV_CHUNK = 1024;                         // vertices per block of 
 constexpr int EV_PART_V2V = 2 * EV_MAXJ * 3;           // partial: [pred joints 96 | gt joints 96 | distance sum | pad]
 constexpr int EV_PSTRIDE = EV_PART_V2V + 2;
 constexpr int EV_MAX_SUB = 256;                        // crops per launch pair (bounds the partial scratch)
-constexpr int EV_JACOBI_SWEEPS = 10;                   // cyclic sweeps of the 4x4 solve: see DESIGN.md "Evaluation"
 constexpr int EV_FIN_THREADS = 1024;
 // record offsets (include/poco_hip.h)
 constexpr int R_MPJPE = 0, R_PA = 1, R_V2V = 2, R_MPJPE_J = 4, R_PA_J = 36, R_POSE = 68, R_UNC = 92, R_PRED = 116, R_GT = 212,
@@ -116,8 +117,9 @@ __global__ __launch_bounds__(256) void eval_partial(EvalDev d, const float* __re
   if (tid == 0) out[EV_PART_V2V] = (wred[0] + wred[1]) + (wred[2] + wred[3]);
 }
 
-// One Jacobi rotation of the symmetric 4x4 `a` in the (p, q) plane, accumulated into the eigenvector matrix `v` (columns).
-__device__ __forceinline__ void jacobi_rotate(double (&a)[4][4], double (&v)[4][4], int p, int q) {
+// jacobi_rotate of rotation_fit.h with the file's default contraction: eval_crop is one latency-bound wave per crop, and the
+// shared, uncontracted solve measured 3 us (5 %) slower per step.  Its multiply-adds fuse, so the last bits differ from the header's.
+__device__ __forceinline__ void jacobi_rotate_fused(double (&a)[4][4], double (&v)[4][4], int p, int q) {
   const double apq = a[p][q];
   if (!(apq != 0.0)) return;                       // zero (or NaN: nothing to gain): a branch, not a loop
   const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
@@ -212,23 +214,14 @@ __global__ __launch_bounds__(64) void eval_crop(EvalDev d, int b0, long long fir
   // argmax over SO(3) of tr(R K) = the unit quaternion that maximises q^T N q (Horn 1987); the reference's U, V and Z sign fix
   // (eval_utils.py:39-45) select the same rotation
   double N[4][4], E[4][4];
-  N[0][0] = K[0][0] + K[1][1] + K[2][2];
-  N[1][1] = K[0][0] - K[1][1] - K[2][2];
-  N[2][2] = -K[0][0] + K[1][1] - K[2][2];
-  N[3][3] = -K[0][0] - K[1][1] + K[2][2];
-  N[0][1] = N[1][0] = K[1][2] - K[2][1];
-  N[0][2] = N[2][0] = K[2][0] - K[0][2];
-  N[0][3] = N[3][0] = K[0][1] - K[1][0];
-  N[1][2] = N[2][1] = K[0][1] + K[1][0];
-  N[1][3] = N[3][1] = K[2][0] + K[0][2];
-  N[2][3] = N[3][2] = K[1][2] + K[2][1];
+  horn_matrix(K, N);
   #pragma unroll
   for (int r = 0; r < 4; ++r)
     #pragma unroll
     for (int c = 0; c < 4; ++c) E[r][c] = r == c ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < EV_JACOBI_SWEEPS; ++sweep) {
-    jacobi_rotate(N, E, 0, 1); jacobi_rotate(N, E, 0, 2); jacobi_rotate(N, E, 0, 3);
-    jacobi_rotate(N, E, 1, 2); jacobi_rotate(N, E, 1, 3); jacobi_rotate(N, E, 2, 3);
+  for (int sweep = 0; sweep < ROT_JACOBI_SWEEPS; ++sweep) {
+    jacobi_rotate_fused(N, E, 0, 1); jacobi_rotate_fused(N, E, 0, 2); jacobi_rotate_fused(N, E, 0, 3);
+    jacobi_rotate_fused(N, E, 1, 2); jacobi_rotate_fused(N, E, 1, 3); jacobi_rotate_fused(N, E, 2, 3);
   }
   double qw = E[0][0], qx = E[1][0], qy = E[2][0], qz = E[3][0], best = N[0][0];
   #pragma unroll
@@ -298,19 +291,6 @@ __global__ __launch_bounds__(64) void eval_crop(EvalDev d, int b0, long long fir
   }
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int o = EV_FIN_THREADS / 2; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // summary[8] = {N, 1000 mean MPJPE, 1000 mean PA-MPJPE, 1000 mean V2V, Pearson r, number of (x, y) pairs, 0, 0}
 __global__ __launch_bounds__(EV_FIN_THREADS) void eval_finish(EvalDev d, long long N, double* __restrict__ summary) {
   __shared__ double red[EV_FIN_THREADS];
@@ -321,8 +301,8 @@ __global__ __launch_bounds__(EV_FIN_THREADS) void eval_finish(EvalDev d, long lo
     a += r[R_MPJPE]; p += r[R_PA]; v += r[R_V2V];
     for (int k = 0; k < d.nsel; ++k) { sx += r[R_POSE + d.sel[k]]; sy += r[R_UNC + d.sel[k]]; }
   }
-  a = block_sum(a, red); p = block_sum(p, red); v = block_sum(v, red);
-  sx = block_sum(sx, red); sy = block_sum(sy, red);
+  a = block_tree_sum<EV_FIN_THREADS>(a, red); p = block_tree_sum<EV_FIN_THREADS>(p, red); v = block_tree_sum<EV_FIN_THREADS>(v, red);
+  sx = block_tree_sum<EV_FIN_THREADS>(sx, red); sy = block_tree_sum<EV_FIN_THREADS>(sy, red);
   const double n = (double)N, terms = n * (double)d.nsel;
   const double mx = sx / terms, my = sy / terms;
   double cxx = 0, cyy = 0, cxy = 0;
@@ -333,7 +313,8 @@ __global__ __launch_bounds__(EV_FIN_THREADS) void eval_finish(EvalDev d, long lo
       cxx += x * x; cyy += y * y; cxy += x * y;
     }
   }
-  cxx = block_sum(cxx, red); cyy = block_sum(cyy, red); cxy = block_sum(cxy, red);
+  cxx = block_tree_sum<EV_FIN_THREADS>(cxx, red); cyy = block_tree_sum<EV_FIN_THREADS>(cyy, red);
+  cxy = block_tree_sum<EV_FIN_THREADS>(cxy, red);
   if (t == 0) {
     double r = cxy / (sqrt(cxx) * sqrt(cyy));
     r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);                       // scipy.stats.pearsonr clips; a NaN stays a NaN

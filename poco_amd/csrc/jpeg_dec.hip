@@ -18,6 +18,7 @@
 // A state is (byte, bit) in the STUFFED stream + block within the MCU + zigzag index.  Every loop is bounded by a constant or by a
 // count the host validated; every read of the stream is clamped to its interval, every store is guarded by its own index.  No
 // global atomics: every word has one writer, except the status words, to which every writer stores a non-zero value.
+#include "block_prims.h"
 #include "common.h"
 #include "jpeg_dec_internal.h"
 #include "../../include/poco_hip.h"
@@ -232,29 +233,6 @@ __global__ __launch_bounds__(64) void jdec_fix(const unsigned char* __restrict__
   wg_out[im->wg_off + w] = exits[(size_t)im->sub_off + min(j0 + JD_THREADS - 1, nsub - 1)];
 }
 
-// Exclusive prefix sum over the block's threads (and the total): wave scans through __shfl_up, wave totals through LDS.
-__device__ __forceinline__ int block_exscan(int v, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-  #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-  #pragma unroll
-  for (int w = 0; w < JD_THREADS / 64; ++w) {
-    const int t = wsum[w];
-    if (w < wv) base += t;
-    tot += t;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
 __global__ __launch_bounds__(JD_THREADS) void jdec_scan(const DImg* __restrict__ imgs, const DSeg* __restrict__ segs_g,
                                                         const unsigned* __restrict__ count, const int* __restrict__ seg_of,
                                                         unsigned* __restrict__ prefix, unsigned* __restrict__ base,
@@ -267,7 +245,7 @@ __global__ __launch_bounds__(JD_THREADS) void jdec_scan(const DImg* __restrict__
   for (int j0 = 0; j0 < nsub; j0 += JD_THREADS) {
     const int j = j0 + tid;
     int tot;
-    const int ex = block_exscan(j < nsub ? (int)count[g0 + j] : 0, wsum, &tot);
+    const int ex = block_exscan<JD_THREADS / 64>(j < nsub ? (int)count[g0 + j] : 0, wsum, &tot);
     if (j < nsub) prefix[g0 + j] = (unsigned)(carry + ex);
     carry += tot;
   }
@@ -327,7 +305,7 @@ __global__ __launch_bounds__(JD_THREADS) void jdec_dc(const DImg* __restrict__ i
     const bool ok = t < total && blk < blk_end;
     const int v = ok ? (int)coef[(size_t)blk * 64] : 0;
     int tot;
-    const int ex = block_exscan(v, wsum, &tot);
+    const int ex = block_exscan<JD_THREADS / 64>(v, wsum, &tot);
     if (ok) coef[(size_t)blk * 64] = (short)(carry + ex + v);
     carry += tot;
   }

@@ -11,6 +11,7 @@
 //   jpeg_compact    per interval: prefix sum of the lengths (+ 2 marker bytes each), copy behind the header, RSTm / EOI, total length
 // The restart interval is what makes the bit stream parallel: DC prediction and bit alignment restart at every MCU row, so rows
 // are coded independently and concatenated.  No global atomics: every output word has one writer.
+#include "block_prims.h"
 #include "common.h"
 #include "../../include/poco_hip.h"
 
@@ -221,29 +222,6 @@ constexpr int EN_CF_STRIDE = 66;                              // int16 per stage
 constexpr int EN_BITS_WORDS = EN_THREADS * (JPEG_BLOCK_BITS / 32) + 2;   // worst case of a round + the carried byte + one spare
 constexpr size_t EN_LDS_BYTES = (size_t)EN_BITS_WORDS * 4 + (size_t)EN_THREADS * EN_CF_STRIDE * 2 + HUFF_WORDS * 4 + 8 * 4;
 
-// Exclusive prefix sum over the block's threads (and the total): wave scans through __shfl_up, wave totals through LDS.
-__device__ __forceinline__ unsigned block_exscan(unsigned v, unsigned* wsum, unsigned* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned inc = v;
-  #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  unsigned base = 0, tot = 0;
-  #pragma unroll
-  for (int w = 0; w < EN_THREADS / 64; ++w) {
-    const unsigned t = wsum[w];
-    if (w < wv) base += t;
-    tot += t;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
 // MSB-first bit writer into the round's LDS buffer from bit position `pos`.  The first and the last word of a lane's string are
 // shared with its neighbours (LDS atomic OR into zeroed words); the words in between are its own (plain stores).
 struct BitWriter {
@@ -343,7 +321,7 @@ __global__ __launch_bounds__(EN_THREADS) void jpeg_entropy(const short* __restri
       len = cnt.n;
     }
     unsigned total;
-    const unsigned ex = block_exscan(len, wsum, &total);
+    const unsigned ex = block_exscan<EN_THREADS / 64>(len, wsum, &total);
     unsigned T = carry_bits + total;
     const bool last = c0 + EN_THREADS >= nblk;
     const unsigned fill = last ? (0u - T) & 7 : 0;            // the interval ends padded with 1-bits to a byte boundary
@@ -367,7 +345,7 @@ __global__ __launch_bounds__(EN_THREADS) void jpeg_entropy(const short* __restri
       unsigned ff = 0;
       for (unsigned b = 0; b < nb; ++b) ff += ((w >> (24 - 8 * b)) & 0xFF) == 0xFF;
       unsigned tot;
-      unsigned o = out_pos + tid * 4 + block_exscan(ff, wsum, &tot);       // out_pos already counts the rounds before
+      unsigned o = out_pos + tid * 4 + block_exscan<EN_THREADS / 64>(ff, wsum, &tot);       // out_pos already counts the rounds before
       for (unsigned b = 0; b < nb; ++b) {
         const unsigned char byte = (unsigned char)(w >> (24 - 8 * b));
         out[o++] = byte;

@@ -19,8 +19,10 @@
 //   solve     backward substitution, right-looking, the running sum in the lane's register; one barrier per column.
 //   trial     R_j exp(d_j), one lane per joint, into the other of two point buffers; evaluate; accept = flip the buffers.
 // Every value is a function of its own row alone and of no lane count: the bits do not depend on the other rows or on the grid.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
+#include "rotation_fit.h"
 
 #include <cstdint>
 
@@ -33,11 +35,8 @@ constexpr int TRI = NR * (NR + 1) / 2;                                // 2926 do
 constexpr int MAXK = KP_REFIT_MAX_KP;
 constexpr int MAXC = 72;                                              // columns of a keypoint's Jacobian: 3 x ancestors + 3; any tree of 24
                                                                       // joints has at most 23 (a chain), SMPL at most 7 (24 columns)
-constexpr double RF_W_MIN = 1e-6, RF_W_MAX = 1e6, RF_U_MIN = 1e-6;    // track_smooth.hip's rule
 constexpr double RF_MU0 = 1e-3, RF_MU_MIN = 1e-12, RF_MU_MAX = 1e12;
 constexpr double RF_SMALL = 1e-8;
-
-__device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }    // i >= j
 
 // one evaluated point: what the Jacobian and the accept test need
 struct Point {
@@ -61,15 +60,6 @@ struct RefitDev {
   double lam, u_ref, rho, cam_prior, conf_thresh;
   signed char kp_joint[MAXK], parent[NJ], depth[NJ], nanc[NJ], anc[NJ][NJ - 1];    // anc: proper ancestors, ascending
 };
-
-__device__ __forceinline__ double weight_of(float uf, double u_ref) {
-  #pragma clang fp contract(off)
-  if (!(fabsf(uf) <= 3.402823466e+38f)) return RF_W_MIN;
-  const double u = (double)uf;
-  const double r = u_ref / (u > RF_U_MIN ? u : RF_U_MIN);
-  const double w = r * r;
-  return w < RF_W_MIN ? RF_W_MIN : (w > RF_W_MAX ? RF_W_MAX : w);
-}
 
 __device__ __forceinline__ void mat3(const double* a, const double* b, double* c) {          // c = a b
   #pragma clang fp contract(off)
@@ -205,7 +195,7 @@ __global__ __launch_bounds__(KP_REFIT_THREADS) void kp_refit_rows(RefitDev d) {
       S.c[tid] = c;
       counts = c != 0.0;
     }
-    if (tid < NJ) S.w[tid] = d.lam * weight_of(d.u[(size_t)row * NJ + tid], d.u_ref);
+    if (tid < NJ) S.w[tid] = d.lam * uncert_weight(d.u[(size_t)row * NJ + tid], d.u_ref);
     const float a0f = camr[0], tx0f = camr[1], ty0f = camr[2], pxf = camr[3], pyf = camr[4], normf = d.norm[row];
     bad |= !finite(a0f) || !finite(tx0f) || !finite(ty0f) || !finite(pxf) || !finite(pyf) || !finite(normf) || !(normf > 0.f);
     if (tid < 3) S.pt[0].x[tid] = 0.0;

@@ -25,6 +25,7 @@
 //   png_compact  per segment: prefix sum of the lengths, IDAT header, copy, CRC; the first writes signature + IHDR, the last the
 //                Adler-32, IEND and the total length
 // No global atomics: every output byte has one writer.
+#include "block_prims.h"
 #include "common.h"
 #include "../../include/poco_hip.h"
 
@@ -128,32 +129,9 @@ struct HuffWork {
   unsigned* misc;     // [64]  counts per length [0..15], first code per length [16..31], wave sums [32..47], scalars [48..]
 };
 
-// Exclusive prefix sum over the block's threads (and the total): wave scans through __shfl_up, wave totals through LDS.
-__device__ __forceinline__ unsigned block_exscan(unsigned v, unsigned* wsum, unsigned* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned inc = v;
-  #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  unsigned base = 0, tot = 0;
-  #pragma unroll
-  for (int w = 0; w < SG_WAVES; ++w) {
-    const unsigned t = wsum[w];
-    if (w < wv) base += t;
-    tot += t;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
 __device__ __forceinline__ unsigned block_sum(unsigned v, unsigned* wsum) {
   unsigned total;
-  (void)block_exscan(v, wsum, &total);
+  (void)block_exscan<SG_WAVES>(v, wsum, &total);
   return total;
 }
 
@@ -310,7 +288,7 @@ __device__ __forceinline__ void emit_round(Emit emit, unsigned* bits, unsigned* 
   emit(cnt);
   if (closing && tid == closer) cnt.put(0, 3);
   unsigned total;
-  const unsigned ex = block_exscan(cnt.n, wsum, &total);
+  const unsigned ex = block_exscan<SG_WAVES>(cnt.n, wsum, &total);
   unsigned T = *carry_bits + total;
   const unsigned pad = closing ? (0u - T) & 7 : 0;
   const unsigned T_end = T + (closing ? pad + 32 : 0);

@@ -25,6 +25,7 @@
 //
 // LDS: rank_scatter holds 4 x 256 wave counters and a 256-entry scan line, 5 KB; nothing else exceeds 8 KB.  No floating-point
 // atomics anywhere; the only additions into shared counters are integer ones made by one lane per digit and wave.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -387,19 +388,6 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_cuts(CurveDev a, double* __
 }
 
 // ---- Pearson's r of two fp64 arrays: one block, two walks (means, then centred sums), fixed order --------------------------------
-__device__ __forceinline__ double block_tree(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int o = RK_SCAN_THREADS / 2; o > 0; o >>= 1) {
-    if (t < o) red[t] = red[t] + red[t + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(RK_SCAN_THREADS) void pearson64_kernel(const double* __restrict__ x, const double* __restrict__ y, long long n,
                                                                     double* __restrict__ out) {
   #pragma clang fp contract(off)
@@ -418,14 +406,15 @@ __global__ __launch_bounds__(RK_SCAN_THREADS) void pearson64_kernel(const double
   }
   if (!cx) flat[0] = 0;                                                // racing stores of the same value
   if (!cy) flat[1] = 0;
-  sx = block_tree(sx, red); sy = block_tree(sy, red);
+  sx = block_tree_sum<RK_SCAN_THREADS>(sx, red); sy = block_tree_sum<RK_SCAN_THREADS>(sy, red);
   const double mx = sx / (double)n, my = sy / (double)n;
   double cxx = 0.0, cyy = 0.0, cxy = 0.0;
   for (long long i = t; i < n; i += RK_SCAN_THREADS) {
     const double a = x[i] - mx, b = y[i] - my;
     cxx = cxx + a * a; cyy = cyy + b * b; cxy = cxy + a * b;
   }
-  cxx = block_tree(cxx, red); cyy = block_tree(cyy, red); cxy = block_tree(cxy, red);
+  cxx = block_tree_sum<RK_SCAN_THREADS>(cxx, red); cyy = block_tree_sum<RK_SCAN_THREADS>(cyy, red);
+  cxy = block_tree_sum<RK_SCAN_THREADS>(cxy, red);
   if (t == 0) {
     double r = cxy / (sqrt(cxx) * sqrt(cyy));
     r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);                         // a NaN stays a NaN

@@ -16,6 +16,7 @@
 //   E  lane k < K + births reads its tracker, a ballot over `time_since_update <= max_age` gives its new slot, and after a barrier
 //      it writes it there: the order of the trackers is kept.
 // LDS 58.4 KB (the matrix 32 KB, 64 packed covariances 14 KB, states, boxes, counters): two blocks fit a CU's 160 KB.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -48,7 +49,6 @@ struct Shared {
 };
 static_assert(sizeof(Shared) <= 60 * 1024, "sort_tracks: the block's LDS");
 
-__device__ __forceinline__ constexpr int tri(int r, int c) { return r * (r + 1) / 2 + c; }   // r >= c
 __device__ __forceinline__ double quiet_nan64() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 __device__ __forceinline__ void load_state(const Shared& S, int k, double (&x)[7], double (&P)[7][7]) {

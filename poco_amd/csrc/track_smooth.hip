@@ -13,13 +13,14 @@
 //             it substitutes backward and leaves the fp64 solution in its scratch column (the linear columns go straight out).
 //             A step is 3000 of them for a long track: the inputs of the next SM_CHUNK rows are loaded while this chunk is computed.
 //   project   all four waves, one lane per (row, joint) of the group: the nine solved doubles -> the nearest rotation (Horn's
-//             quaternion, cyclic Jacobi with the fixed sweep count of tta_fuse.hip and eval_metrics.hip, restated here so those
-//             files stay as they are) -> nine floats and the angle to the input.
+//             quaternion, cyclic Jacobi with a fixed sweep count: nearest_rotation of rotation_fit.h, shared with tta_fuse.hip and
+//             eval_metrics.hip) -> nine floats and the angle to the input.
 // The two __syncthreads between the phases order the scratch writes of one lane before the reads of another.  Every output word
 // has exactly one writer and every value is a function of its own track alone: the bits do not depend on the other tracks or on
 // the grid ((track, group) pairs are dealt to the blocks by a grid-stride loop).
 #include "common.h"
 #include "kernels.h"
+#include "rotation_fit.h"
 
 #include <cstdint>
 
@@ -29,8 +30,6 @@ constexpr int NJ = 24;
 constexpr int SM_GROUP = 7;                                           // joints of a block: 7 x 9 = 63 lanes of wave 0
 constexpr int SM_GROUPS = 4;                                          // 7 + 7 + 7 + 3
 constexpr int SM_CHUNK = 8;                                           // rows whose inputs are in flight together
-constexpr int SM_JACOBI_SWEEPS = 10;                                  // TTA_JACOBI_SWEEPS of tta_fuse.hip
-constexpr double SM_W_MIN = 1e-6, SM_W_MAX = 1e6, SM_U_MIN = 1e-6;
 
 struct SmoothDev {
   const float *pose, *u, *lin;
@@ -40,77 +39,6 @@ struct SmoothDev {
   int P, N, L, max_gap;
   double lam, u_ref;
 };
-
-// jacobi_rotate and nearest_rotation of tta_fuse.hip, restated
-__device__ __forceinline__ void jacobi_rotate(double (&a)[4][4], double (&v)[4][4], int p, int q) {
-  #pragma clang fp contract(off)
-  const double apq = a[p][q];
-  if (!(apq != 0.0)) return;
-  const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  #pragma unroll
-  for (int k = 0; k < 4; ++k) {                                       // A <- A G
-    const double akp = a[k][p], akq = a[k][q];
-    a[k][p] = c * akp - s * akq;
-    a[k][q] = s * akp + c * akq;
-  }
-  #pragma unroll
-  for (int k = 0; k < 4; ++k) {                                       // A <- G^T A
-    const double apk = a[p][k], aqk = a[q][k];
-    a[p][k] = c * apk - s * aqk;
-    a[q][k] = s * apk + c * aqk;
-  }
-  #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double vkp = v[k][p], vkq = v[k][q];
-    v[k][p] = c * vkp - s * vkq;
-    v[k][q] = s * vkp + c * vkq;
-  }
-}
-
-__device__ __forceinline__ void nearest_rotation(const double (&M)[9], double (&R)[9]) {
-  #pragma clang fp contract(off)
-  double N[4][4], E[4][4];
-  const double k00 = M[0], k01 = M[3], k02 = M[6], k10 = M[1], k11 = M[4], k12 = M[7], k20 = M[2], k21 = M[5], k22 = M[8];
-  N[0][0] = k00 + k11 + k22;
-  N[1][1] = k00 - k11 - k22;
-  N[2][2] = -k00 + k11 - k22;
-  N[3][3] = -k00 - k11 + k22;
-  N[0][1] = N[1][0] = k12 - k21;
-  N[0][2] = N[2][0] = k20 - k02;
-  N[0][3] = N[3][0] = k01 - k10;
-  N[1][2] = N[2][1] = k01 + k10;
-  N[1][3] = N[3][1] = k20 + k02;
-  N[2][3] = N[3][2] = k12 + k21;
-  #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    #pragma unroll
-    for (int c = 0; c < 4; ++c) E[r][c] = r == c ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < SM_JACOBI_SWEEPS; ++sweep) {
-    jacobi_rotate(N, E, 0, 1); jacobi_rotate(N, E, 0, 2); jacobi_rotate(N, E, 0, 3);
-    jacobi_rotate(N, E, 1, 2); jacobi_rotate(N, E, 1, 3); jacobi_rotate(N, E, 2, 3);
-  }
-  double qw = E[0][0], qx = E[1][0], qy = E[2][0], qz = E[3][0], best = N[0][0];
-  #pragma unroll
-  for (int k = 1; k < 4; ++k)
-    if (N[k][k] > best) { best = N[k][k]; qw = E[0][k]; qx = E[1][k]; qy = E[2][k]; qz = E[3][k]; }
-  const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-  qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-  R[0] = qw * qw + qx * qx - qy * qy - qz * qz; R[1] = 2.0 * (qx * qy - qw * qz); R[2] = 2.0 * (qx * qz + qw * qy);
-  R[3] = 2.0 * (qx * qy + qw * qz); R[4] = qw * qw - qx * qx + qy * qy - qz * qz; R[5] = 2.0 * (qy * qz - qw * qx);
-  R[6] = 2.0 * (qx * qz - qw * qy); R[7] = 2.0 * (qy * qz + qw * qx); R[8] = qw * qw - qx * qx - qy * qy + qz * qz;
-}
-
-// w = clamp((u_ref / max(u, 1e-6))^2, 1e-6, 1e6); a NaN or an infinity of either sign gives 1e-6
-__device__ __forceinline__ double weight_of(float uf, double u_ref) {
-  #pragma clang fp contract(off)
-  if (!(fabsf(uf) <= 3.402823466e+38f)) return SM_W_MIN;
-  const double u = (double)uf;
-  const double r = u_ref / (u > SM_U_MIN ? u : SM_U_MIN);
-  const double w = r * r;
-  return w < SM_W_MIN ? SM_W_MIN : (w > SM_W_MAX ? SM_W_MAX : w);
-}
 
 // Row t of D, the second divided difference over frames (f0, f1, f2) at columns t - 1, t, t + 1, and g = lambda * omega_t; all
 // zero when a spacing exceeds max_gap (or is not positive: the caller's frames must increase strictly; such a row is dropped).
@@ -178,7 +106,7 @@ __global__ __launch_bounds__(TRACK_SMOOTH_THREADS) void track_smooth_blocks(Smoo
         for (int k = 0; k < SM_CHUNK; ++k) {
           const int i = i0 + k;
           if (i >= T) break;
-          const double w = weight_of(cur[k].u, d.u_ref);
+          const double w = uncert_weight(cur[k].u, d.u_ref);
           const int fc = cur[k].f2;
           const PenRow rp = i + 1 <= T - 2 ? pen_row(fa, fb, fc, d.max_gap, d.lam) : PenRow{0, 0, 0, 0};
           const double diag = w + ((rp.g * rp.a * rp.a + r0.g * r0.b * r0.b) + rm.g * rm.c * rm.c);
@@ -242,7 +170,7 @@ __global__ __launch_bounds__(TRACK_SMOOTH_THREADS) void track_smooth_blocks(Smoo
         M[i] = xs[i];
         A[i] = (double)Rin[i];
       }
-      nearest_rotation(M, R);
+      nearest_rotation<ROT_JACOBI_SWEEPS>(M, R);
       // the angle of A^T R: atan2 of half the norm of its skew part and (trace - 1) / 2, well conditioned at 0 and at pi
       double Q[9];
       #pragma unroll

@@ -9,20 +9,20 @@
 //   tta_fuse_rows   one lane per (crop, joint), lanes dealt by a grid-stride loop over the B * 24 entries.  A lane walks the K
 //                   views twice: the first pass forms M = sum w_k R_k, W and sum w_k v_k (the lane of joint 0 also the ten shape
 //                   sums), then the rotation nearest to M - Horn's quaternion form, the largest eigenvector of a symmetric 4x4 by
-//                   cyclic Jacobi with the fixed sweep count of eval_metrics.hip, restated here so that file stays as it is - and
+//                   cyclic Jacobi with a fixed sweep count: nearest_rotation of rotation_fit.h, which the evaluator shares - and
 //                   the second pass re-reads the K rotations (36 bytes each, in cache) for the spread instead of keeping 8 x 9
 //                   doubles live across the solve.  All arithmetic in fp64 with contraction off; every output is rounded once.
 // Every output word has exactly one writer and every value is a function of its own (crop, joint): the result does not depend on
 // the grid.  The loops run over K and fixed counts only; nothing iterates on the data.
 #include "common.h"
 #include "kernels.h"
+#include "rotation_fit.h"
 
 #include <cstdint>
 
 namespace {
 
 constexpr int NJ = 24;
-constexpr int TTA_JACOBI_SWEEPS = 10;                                 // EV_JACOBI_SWEEPS of eval_metrics.hip
 // pocolib/core/constants.py:104-111 (poco_amd/datacrop.py SMPL_JOINTS_FLIP_PERM)
 __constant__ int kFlipPerm[NJ] = {0, 2, 1, 3, 5, 4, 6, 8, 7, 9, 11, 10, 12, 14, 13, 15, 17, 16, 19, 18, 21, 20, 23, 22};
 
@@ -68,71 +68,6 @@ __device__ __forceinline__ double load_view(const TtaDev& a, int k, int b, int j
   return a.weight ? 1.0 / (v + 1e-9) : 1.0;
 }
 
-// One Jacobi rotation of the symmetric 4x4 `a` in the (p, q) plane, accumulated into the eigenvector matrix `v` (columns):
-// jacobi_rotate of eval_metrics.hip, restated.
-__device__ __forceinline__ void jacobi_rotate(double (&a)[4][4], double (&v)[4][4], int p, int q) {
-  #pragma clang fp contract(off)
-  const double apq = a[p][q];
-  if (!(apq != 0.0)) return;                                          // zero (or NaN: nothing to gain): a branch, not a loop
-  const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  #pragma unroll
-  for (int k = 0; k < 4; ++k) {                                       // A <- A G
-    const double akp = a[k][p], akq = a[k][q];
-    a[k][p] = c * akp - s * akq;
-    a[k][q] = s * akp + c * akq;
-  }
-  #pragma unroll
-  for (int k = 0; k < 4; ++k) {                                       // A <- G^T A
-    const double apk = a[p][k], aqk = a[q][k];
-    a[p][k] = c * apk - s * aqk;
-    a[q][k] = s * apk + c * aqk;
-  }
-  #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double vkp = v[k][p], vkq = v[k][q];
-    v[k][p] = c * vkp - s * vkq;
-    v[k][q] = s * vkp + c * vkq;
-  }
-}
-
-// argmax over SO(3) of tr(R^T M) = the unit quaternion that maximises q^T N q (Horn 1987) with N built from K = M^T, as
-// eval_crop builds it from its K.  A singular M (views half a turn apart) still yields a rotation: whichever eigenvector the
-// sweeps leave under the largest diagonal entry.
-__device__ __forceinline__ void nearest_rotation(const double (&M)[9], double (&R)[9]) {
-  #pragma clang fp contract(off)
-  double N[4][4], E[4][4];
-  const double k00 = M[0], k01 = M[3], k02 = M[6], k10 = M[1], k11 = M[4], k12 = M[7], k20 = M[2], k21 = M[5], k22 = M[8];
-  N[0][0] = k00 + k11 + k22;
-  N[1][1] = k00 - k11 - k22;
-  N[2][2] = -k00 + k11 - k22;
-  N[3][3] = -k00 - k11 + k22;
-  N[0][1] = N[1][0] = k12 - k21;
-  N[0][2] = N[2][0] = k20 - k02;
-  N[0][3] = N[3][0] = k01 - k10;
-  N[1][2] = N[2][1] = k01 + k10;
-  N[1][3] = N[3][1] = k20 + k02;
-  N[2][3] = N[3][2] = k12 + k21;
-  #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    #pragma unroll
-    for (int c = 0; c < 4; ++c) E[r][c] = r == c ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < TTA_JACOBI_SWEEPS; ++sweep) {
-    jacobi_rotate(N, E, 0, 1); jacobi_rotate(N, E, 0, 2); jacobi_rotate(N, E, 0, 3);
-    jacobi_rotate(N, E, 1, 2); jacobi_rotate(N, E, 1, 3); jacobi_rotate(N, E, 2, 3);
-  }
-  double qw = E[0][0], qx = E[1][0], qy = E[2][0], qz = E[3][0], best = N[0][0];
-  #pragma unroll
-  for (int k = 1; k < 4; ++k)
-    if (N[k][k] > best) { best = N[k][k]; qw = E[0][k]; qx = E[1][k]; qy = E[2][k]; qz = E[3][k]; }
-  const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-  qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-  R[0] = qw * qw + qx * qx - qy * qy - qz * qz; R[1] = 2.0 * (qx * qy - qw * qz); R[2] = 2.0 * (qx * qz + qw * qy);
-  R[3] = 2.0 * (qx * qy + qw * qz); R[4] = qw * qw - qx * qx + qy * qy - qz * qz; R[5] = 2.0 * (qy * qz - qw * qx);
-  R[6] = 2.0 * (qx * qz - qw * qy); R[7] = 2.0 * (qy * qz + qw * qx); R[8] = qw * qw - qx * qx - qy * qy + qz * qz;
-}
-
 __global__ __launch_bounds__(TTA_THREADS) void tta_fuse_rows(TtaDev a) {
   #pragma clang fp contract(off)
   const int K = a.views.count;
@@ -171,7 +106,7 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_fuse_rows(TtaDev a) {
       continue;
     }
     double Rp[9];
-    nearest_rotation(M, Rp);
+    nearest_rotation<ROT_JACOBI_SWEEPS>(M, Rp);
     double acc = 0.0;
     for (int k = 0; k < K; ++k) {
       double R[9], v;
