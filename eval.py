@@ -76,6 +76,17 @@ Fused) and --kp_refit (Raw, Refit) every label gets its lines and every label af
 the same draws.  The .npz gains boot_names, boot_summary [S,5], boot_spec (B, units, level, seed) and with --save_results
 boot_replicates [B,S].  Allowed beside --rank_metrics, --calibrate, --uncert_threshold, --crop dataset and --aug_*; not with --segm,
 --likelihood, --sequences or --visibility.
+--corrupt LEVELS [--corrupt_seed S] (with --crop dataset) asks what happens to the error and to the uncertainty as the picture itself
+gets worse: LEVELS is a comma-separated list of levels, each a '+'-joined chain of at most four of gaussian_blur:<sigma>,
+motion_blur:<L>:<degrees>, pixelate:<f>, contrast:<c>, gamma:<g>, gaussian_noise:<sigma> and jpeg:<quality>, e.g.
+gaussian_blur:1,gaussian_blur:2+jpeg:30; the clean crop is always level 0, at most 8 levels in all.  The raw crops (after --aug_* /
+--aug_occlude) are degraded on the GPU (csrc/corrupt.hip, poco_amd/corrupt.py; jpeg goes through the device's
+encoder and decoder), the K versions of max(1, batch_size // K) crops go through ONE forward and every level is scored side by
+side.  Printed per level: the usual lines, mean and median var and the differences to the clean crop; then Pearson's and Spearman's
+Corr(delta var, delta MPJPE) over crops x levels.  The .npz holds level 0 under the usual keys and gains corrupt_levels,
+corrupt_summary and the per-crop mpjpe_l<k>, pampjpe_l<k>, v2v_l<k>, var_l<k>.  Allowed beside --bootstrap (every level, and its
+paired difference to level 0) and --save_results; not with --tta, --cfg2, --segm, --likelihood, --sequences, --visibility,
+--kp_refit, --calibrate or --rank_metrics.  These are not ImageNet-C's definitions (those need cv2 and skimage).
 Not computed: gendered SMPL models,
 multi-GPU evaluation (DESIGN.md "Evaluation").
 """
@@ -205,6 +216,13 @@ def parse_args(argv=None):
                    help="with --bootstrap: resample crops (default) or the tracks the image names group into (folder, person, frame number)")
     p.add_argument("--boot_level", type=float, default=None, help="with --bootstrap: level of the percentile interval (default 0.95)")
     p.add_argument("--boot_seed", type=int, default=None, help="with --bootstrap: seed of the draws, 0..2^53-1 (default 0)")
+    p.add_argument("--corrupt", type=str, default=None, metavar="LEVELS",
+                   help="degrade the raw crops on the GPU and score every level side by side (poco_amd/corrupt.py, csrc/corrupt.hip): "
+                        "comma-separated levels, each a '+'-joined chain of at most four of gaussian_blur:<sigma>, motion_blur:<L>:<degrees>, "
+                        "pixelate:<f>, contrast:<c>, gamma:<g>, gaussian_noise:<sigma>, jpeg:<quality> (e.g. gaussian_blur:1,gaussian_blur:2+jpeg:30; "
+                        "at most 8 with the clean crop, which is always level 0); needs --crop dataset; a forward takes the levels of "
+                        "max(1, batch_size // K) crops")
+    p.add_argument("--corrupt_seed", type=int, default=None, help="with --corrupt: seed of gaussian_noise, 0..2^64-1 (default 0)")
     p.add_argument("--min_cutoff", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 0.004)")
     p.add_argument("--beta", type=float, default=None, help="with --seq_post: one-euro filter of `smooth` (default 1.5)")
     return p.parse_args(argv)
@@ -452,6 +470,14 @@ def check_bootstrap(args) -> None:
                     sys.exit(f"{args.dataset}: --boot_unit track: {e}")
 
 
+def check_corrupt(args) -> None:
+    """--corrupt / --corrupt_seed: refuse what cannot work before an engine is built."""
+    from poco_amd.corrupt import flag_error
+    msg = flag_error(args)
+    if msg:
+        sys.exit(msg)
+
+
 def calibrate_spec(args, tester):
     """run_eval's `calibrate` argument from --calibrate / --calib_split / --calib_bins, or None."""
     if not getattr(args, "calibrate", None):
@@ -462,6 +488,7 @@ def calibrate_spec(args, tester):
 
 
 def main(args):
+    check_corrupt(args)
     check_bootstrap(args)
     check_calibrate(args)
     check_visibility(args)
@@ -524,6 +551,11 @@ def main(args):
                                 uncert_threshold=getattr(args, "uncert_threshold", None), res=tester.model_cfg.DATASET.IMG_RES, **vis_kw)
         except ValueError as e:
             sys.exit(str(e))
+    elif tester.corrupt is not None:
+        from poco_amd import corrupt
+        print(f"Corruption levels: {corrupt.levels_text(tester.corrupt.levels)}")
+        res = evaluate.run_eval_corrupt(tester.corrupt, ds, J, batch_size=max(int(args.batch_size), 1),
+                                        kinematic=bool(tester.model_cfg.POCO.KINEMATIC_UNCERT), save_results=args.save_results, **boot_kw)
     elif tester.tta is not None:
         print(f"Test-time views: {tester.tta_text} ({tester.tta.weight} weights)")
         res = evaluate.run_eval_tta(tester.tta, ds, J, batch_size=max(int(args.batch_size), 1),
@@ -559,6 +591,8 @@ def main(args):
         lines = evaluate.tta_report_lines(res)
     if getattr(args, "kp_refit", None) is not None:
         lines = evaluate.refit_report_lines(res)
+    if tester.corrupt is not None:
+        lines = evaluate.corrupt_report_lines(res)
     for line in (evaluate.likelihood_lines(res) if args.likelihood else []) + lines:
         print(line)
     if getattr(args, "segm", False):

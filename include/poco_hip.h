@@ -1467,6 +1467,56 @@ int poco_op_bootstrap(const float* d_planes, int64_t n, int E, const int32_t* pa
                       int64_t B, uint64_t seed, void* d_scratch, size_t scratch_bytes, double* d_center, double* d_unit_mom,
                       double* d_out, uint32_t* d_draw_counts, int max_blocks, void* stream);
 
+/* ---- image degradation of raw crops: blur, pixelation, contrast, gamma, noise and the rounding before a JPEG round trip -----------------
+ * eval.py --corrupt LEVELS; csrc/corrupt.hip; poco_amd/corrupt.py; tests/corrupt_np.py restates it with plain
+ * float64 loops.  The reference's only pixel-level augmentation is the per-channel factor of poco_dataset_crop's `pn`; the kinds here
+ * are the common ones of corruption benchmarks, defined below and NOT ImageNet-C's (those need cv2 and skimage).
+ *
+ * poco_op_corrupt: d_in fp32 [N,3,res,res], raw crops in [0, 255] as poco_dataset_crop(..., normalize = 0) writes them; per crop a chain
+ *   of chain_len records, d_steps [N][chain_len] on the device and h_steps, the host copy they were uploaded from (the ranges below are
+ *   checked on it; nothing compares the two, as for poco_dataset_crop).  A chain ends at its first POCO_CORRUPT_NONE record; crops of
+ *   one call may carry different chains.  The steps at positions pos_begin <= p < pos_end are applied, one launch per position over all
+ *   crops (none in the range: one launch that copies), ping-pong between d_tmp and d_out, both fp32 [N,3,res,res]; the last launch
+ *   writes d_out: raw, or with normalize != 0 mapped by (x / 255 - mean) / std in float32 as oracle/crop_np.normalize_np.  d_tmp's
+ *   content afterwards is unspecified.  The caller that composes a JPEG round trip between two positions calls once per position.
+ *   Every step reads fp32, evaluates in fp64 without contraction, clamps to [0, 255] and rounds once to fp32 on the store.  A tap
+ *   outside the plane is mirrored without repeating the edge (scipy.ndimage mode='mirror'), as often as needed; res = 1 maps every
+ *   index to 0.  x = column, y = row, v = the fp32 input of the step as fp64:
+ *     GAUSSIAN_BLUR  p0 = sigma in (0, 5].  r = int(3 sigma + 0.5); w_k = exp(-k^2 / (2 sigma^2)), k = -r .. r, divided by their sum taken
+ *                    in that order; h(y, x) = sum_k w_k v(y, x + k), then out(y, x) = sum_k w_k h(y + k, x), both in the order k = -r .. r,
+ *                    h kept in fp64.  Yardstick: scipy.ndimage.gaussian_filter(float64, sigma, mode='mirror', truncate=3.0).
+ *     MOTION_BLUR    ival = L odd in 3..31, (p0, p1) = unit direction (dx, dy), computed on the host.  The mean of the L bilinear samples at
+ *                    (x + k p0, y + k p1), k = -(L-1)/2 .. (L-1)/2 in that order; a sample = (1-fy) ((1-fx) v00 + fx v01) + fy ((1-fx) v10 +
+ *                    fx v11) with (fx, fy) the fractions above floor.
+ *     PIXELATE       ival = f in 2..32.  The mean over each f x f cell anchored at (0, 0), partial at the far edges, written to every pixel
+ *                    of the cell: per column the sum over the cell's rows top to bottom, those sums left to right, one division by the count.
+ *     CONTRAST       p0 = c in [0, 2].  mean + c (v - mean), mean per crop and channel: 256 lane-strided sums of the row-major plane, the
+ *                    halving tree of csrc/block_prims.h, one division.
+ *     GAMMA          p0 = g in [0.2, 5].  255 (v / 255)^g.
+ *     GAUSSIAN_NOISE p0 = sigma in [0, 255] pixel units.  Philox4x32-10 as poco_op_bootstrap's, key = seed, counter = (e / 4, 0, stream,
+ *                    chain position) for element e of the crop's [3,res,res] block; words (w0, w1) and (w2, w3) give two Box-Muller pairs,
+ *                    u1 = (w + 1) 2^-32, u2 = w 2^-32, z = sqrt(-2 ln u1) (cos, sin)(2 pi u2): z of elements 4q, 4q+1 | 4q+2, 4q+3.
+ *                    out = v + sigma z.  `stream` is the caller's name of the crop (eval.py: the dataset row), so a crop's noise does not
+ *                    depend on its place in the batch.
+ *     JPEG           ival = quality 1..100.  floor(v + 0.5): the bytes a JPEG encoder is given.  The round trip itself is composed by the
+ *                    caller (poco_amd/corrupt.py: poco_jpeg_encode, then poco_jpeg_decode, one picture per crop).
+ *   Enqueued on `stream`: no allocation, no synchronisation, any N.  POCO_ERR_ARG before any launch: a null pointer, N < 1, res outside
+ *   1..4096, chain_len outside 1..POCO_CORRUPT_MAX_STEPS, a position range outside 0 <= pos_begin <= pos_end <= chain_len, buffers that
+ *   are not three different ones, and - read from h_steps - an unknown kind, a step after an empty one, a parameter outside the ranges
+ *   above or not finite.  The kernel reads d_steps only and clamps the kind and every index it derives from a record. */
+#define POCO_CORRUPT_MAX_STEPS 4
+enum { POCO_CORRUPT_NONE = 0, POCO_CORRUPT_GAUSSIAN_BLUR = 1, POCO_CORRUPT_MOTION_BLUR = 2, POCO_CORRUPT_PIXELATE = 3,
+       POCO_CORRUPT_CONTRAST = 4, POCO_CORRUPT_GAMMA = 5, POCO_CORRUPT_GAUSSIAN_NOISE = 6, POCO_CORRUPT_JPEG = 7 };
+typedef struct {
+  int32_t kind;       /* POCO_CORRUPT_*                                                   */
+  int32_t ival;       /* motion_blur: L; pixelate: f; jpeg: quality                       */
+  float p0, p1;       /* sigma | (dx, dy) | c | g | noise sigma                           */
+  uint32_t seed[2];   /* gaussian_noise: the Philox key                                   */
+  uint32_t stream;    /* gaussian_noise: counter word 2, the caller's name of the crop    */
+} poco_corrupt_step_t;
+int poco_op_corrupt(const float* d_in, const poco_corrupt_step_t* d_steps, const poco_corrupt_step_t* h_steps, int N, int chain_len,
+                    int pos_begin, int pos_end, int res, int normalize, float* d_tmp, float* d_out, void* stream);
+
 /* Time `ncfg` tile configurations (cfgs7 = ncfg x SEVEN ints {MT,NT,WM,WN,R,NI,ALG} each, csrc/common.h CONV_CFG_INTS;
  * MT<=0 = heuristic) for one conv shape on random data; ms_out[i] < 0 = configuration invalid for this shape.  NULL cfgs7 /
  * ms_out, ncfg < 1 or channel counts that are not multiples of 16 are POCO_ERR_ARG.  iters < 0: |iters| launches of the RESIDUAL form (the

@@ -20,6 +20,7 @@
 #include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
+#include "philox.h"
 
 #include <cstdint>
 
@@ -119,19 +120,6 @@ __global__ __launch_bounds__(BT_TH) void boot_unit_mom(BootDev a) {
 __global__ __launch_bounds__(BT_TH) void boot_zero_counts(uint32_t* counts, unsigned long long words) {
   for (unsigned long long i = (unsigned long long)blockIdx.x * BT_TH + threadIdx.x; i < words; i += (unsigned long long)gridDim.x * BT_TH)
     counts[i] = 0u;
-}
-
-struct Philox4 { uint32_t w[4]; };
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-  #pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return Philox4{{c0, c1, c2, c3}};
 }
 
 // MM: the compile-time bound of the accumulators (a.M <= MM), so that they stay in registers.

@@ -297,6 +297,9 @@ class EvalDataset:
         # want_occ_mask: set by the visibility step; with occluders, batch() then leaves the batch's mask uint8 [n,res,res] of the
         # pixels they touched in last_occ_mask (None without occluders), on the device
         self.want_occ_mask, self.last_occ_mask = False, None
+        # raw_crop: set by run_eval_corrupt; batch() then hands out `img` as the raw float crop in [0, 255] (poco_dataset_crop with
+        # normalize = 0), which poco_op_corrupt degrades and normalises
+        self.raw_crop = False
         z = np.load(path, allow_pickle=False)
         self.gt_form = check_dataset_keys(z.files)
         if occlude is not None:
@@ -387,15 +390,15 @@ class EvalDataset:
         self.last_occ_mask = None
         if self.occlude is not None and self.want_occ_mask:
             # eval.py --visibility: the same crops and cover from the launch that also writes the per-pixel mask
-            img, cover, self.last_occ_mask = datacrop.dataset_crop(images, idx, params, self.res, True, want_mask=True,
+            img, cover, self.last_occ_mask = datacrop.dataset_crop(images, idx, params, self.res, not self.raw_crop, want_mask=True,
                                                                    occlusion=(self.occlude.atlas(device), self.occ_records[lo:hi]))
             self._occ_pending.append((lo, hi, cover))
         elif self.occlude is not None:
-            img, cover = datacrop.dataset_crop(images, idx, params, self.res, True,
+            img, cover = datacrop.dataset_crop(images, idx, params, self.res, not self.raw_crop,
                                                occlusion=(self.occlude.atlas(device), self.occ_records[lo:hi]))
             self._occ_pending.append((lo, hi, cover))
         else:
-            img = datacrop.dataset_crop(images, idx, params, self.res, True)
+            img = datacrop.dataset_crop(images, idx, params, self.res, not self.raw_crop)
         shapes = np.asarray([frames[k].shape[:2] for k in idx], np.float32)
         center, scale = self.center[lo:hi], self.scale_eff[lo:hi].astype(np.float32)      # float32, as the file's scale is held here
         info = np.stack([calculate_bbox_info(c, s, hw) for c, s, hw in zip(center, scale, shapes)])
@@ -796,6 +799,95 @@ def tta_report_lines(res: Dict[str, object]):
     return lines + [f"Corr(view spread, pose distance): {res['val_corr_spread']}"]
 
 
+CORRUPT_SUMMARY_FIELDS = ("mpjpe", "pampjpe", "v2v", "corr", "var_mean", "var_median", "d_mpjpe", "d_pampjpe", "d_v2v", "d_var")
+CORRUPT_SCALARS = ("val_corr_dvar_dmpjpe", "val_spearman_dvar_dmpjpe")
+
+
+@torch.no_grad()
+def run_eval_corrupt(cmodel, dataset: EvalDataset, J_regressor, batch_size: int = 64, kinematic: bool = True,
+                     sel_uncert_part: Optional[Sequence[int]] = None, save_results: bool = False, return_outputs: bool = False,
+                     bootstrap=None) -> Dict[str, object]:
+    """run_eval under image degradation (eval.py --corrupt, DESIGN.md section 35): per batch of b = max(1, batch_size // K) crops the
+    dataset crop hands over the raw crops (after --aug_* / --aug_occlude), corrupt.CorruptModel makes their K level-major versions -
+    level 0 the clean crop - and regresses them in one forward, and K Evaluators are stepped against the same ground truth on the
+    same stream.  Returns level 0 under run_eval's keys; per level k the per-crop arrays mpjpe_l<k> / pampjpe_l<k> [N,M], v2v_l<k>
+    and var_l<k> [N] (the mean of the crop's 24 processed uncertainties); corrupt_summary [K, 10] (CORRUPT_SUMMARY_FIELDS: the
+    headline numbers, mean and median var, and the differences to level 0 in mm and in var); corrupt_levels; and over crops x
+    levels >= 1 Pearson's and Spearman's Corr(var_k - var_0, MPJPE_k - MPJPE_0) through ops.pearson64 / ops.rank_curve.
+    return_outputs (tests): also `outputs` = per batch the K per-level dicts of host arrays and `level_imgs` = the K * b crops the
+    forward was given.  bootstrap: a bootstrap.BootSpec; every level gets its lines and every level after the first its paired
+    difference to level 0."""
+    from . import corrupt, ops
+    if dataset.crop != "dataset":
+        raise ValueError("run_eval_corrupt degrades the raw crops of the dataset crop: the dataset needs crop='dataset'")
+    dev, n, levels, K = cmodel.device, len(dataset), cmodel.levels, cmodel.K
+    b = max(1, min(int(batch_size) // K, cmodel.max_batch))
+    evs = [Evaluator(J_regressor, joint_map(dataset.name), capacity=n, sel_uncert_part=sel_uncert_part, kinematic=kinematic, device=dev)
+           for _ in range(K)]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+    outputs = []
+    dataset.raw_crop = True
+    try:
+        for lo in range(0, n, b):
+            hi = min(lo + b, n)
+            lb = cmodel.level_batch(dataset.batch(lo, hi, dev), range(lo, hi))
+            outs = cmodel.forward_rows(lb)
+            gt_pose = t(dataset.pose[lo:hi])
+            if dataset.gt_form == "smpl":
+                gt = {"gt_vertices": cmodel.smpl_lbs(t(dataset.shape[lo:hi]), ops.rodrigues(gt_pose))[0]}
+            else:
+                gt = {"gt_joints": t(dataset.joints[lo:hi])}
+            for ev, out in zip(evs, outs):
+                ev.step(out, gt_pose, **gt)
+            if return_outputs:
+                outputs.append(dict(level_imgs=lb["img"].cpu().numpy(),
+                                    levels=[{k: o[k].cpu().numpy() for k in TTA_OUTPUT_KEYS if k in o} for o in outs]))
+    finally:
+        dataset.raw_crop = False
+    res = evs[0].finish(save_results=save_results, return_records=True)
+    per = [res] + [ev.finish(return_records=True) for ev in evs[1:]]
+    summ = np.zeros((K, len(CORRUPT_SUMMARY_FIELDS)))
+    crop_var = [r["records"][:, R_UNC:R_UNC + 24].astype(np.float64).mean(axis=1) for r in per]
+    crop_err = [r["records"][:, R_MPJPE].astype(np.float64) for r in per]
+    for k, r in enumerate(per):
+        res[f"mpjpe_l{k}"], res[f"pampjpe_l{k}"], res[f"v2v_l{k}"] = r["mpjpe"].copy(), r["pampjpe"].copy(), r["v2v"].copy()
+        res[f"var_l{k}"] = crop_var[k]
+        summ[k, :6] = r["val_mpjpe"], r["val_pampjpe"], r["val_v2v"], r["val_corr"], crop_var[k].mean(), np.median(crop_var[k])
+        summ[k, 6:9] = summ[k, :3] - summ[0, :3]
+        summ[k, 9] = summ[k, 4] - summ[0, 4]
+    res.pop("records")
+    res["corrupt_summary"], res["corrupt_levels"] = summ, np.asarray([corrupt.describe(lv) for lv in levels])
+    dvar = torch.from_numpy(np.concatenate([crop_var[k] - crop_var[0] for k in range(1, K)])).to(dev)
+    derr = torch.from_numpy(np.concatenate([crop_err[k] - crop_err[0] for k in range(1, K)])).to(dev)
+    res["val_corr_dvar_dmpjpe"] = float(ops.pearson64(dvar, derr).item())
+    ranks = [ops.rank_curve(v.to(torch.float32).contiguous(), None, 1)["rank"] for v in (dvar, derr)]
+    res["val_spearman_dvar_dmpjpe"] = float(ops.pearson64(ranks[0], ranks[1]).item())
+    if bootstrap is not None:
+        res.update(_bootstrap([(f"Level {k} ({corrupt.describe(lv)})", ev) for k, (lv, ev) in enumerate(zip(levels, evs))], bootstrap, dataset,
+                              save_results))
+    if return_outputs:
+        res["outputs"] = outputs
+    cmodel.check_status()
+    res["imgname"] = np.asarray(dataset.imgname)
+    for ev in evs:
+        ev.close()
+    return res
+
+
+def corrupt_report_lines(res: Dict[str, object]):
+    """Per level the usual lines, mean and median var and the differences to the clean crop; then the two correlations."""
+    lines = []
+    for k, (name, row) in enumerate(zip(res["corrupt_levels"], np.asarray(res["corrupt_summary"]))):
+        s = dict(zip(CORRUPT_SUMMARY_FIELDS, row))
+        label = f"Level {k} ({name})"
+        lines += [f"{label} MPJPE: {s['mpjpe']}", f"{label} PA-MPJPE: {s['pampjpe']}", f"{label} V2V (mm): {s['v2v']}",
+                  f"{label} Uncert Error Correlation: {s['corr']}", f"{label} var mean / median: {s['var_mean']} / {s['var_median']}"]
+        if k:
+            lines.append(f"{label} - clean: MPJPE {s['d_mpjpe']:+}, PA-MPJPE {s['d_pampjpe']:+}, V2V {s['d_v2v']:+} (mm), var {s['d_var']:+}")
+    return lines + [f"N: {res['N']}", f"Corr(delta var, delta MPJPE) over crops x levels: Pearson {res['val_corr_dvar_dmpjpe']}, "
+                                       f"Spearman {res['val_spearman_dvar_dmpjpe']}"]
+
+
 REFIT_SCALARS = tuple(k + "_raw" for k in ("val_mpjpe", "val_pampjpe", "val_v2v", "val_corr")) + ("refit_mean_shift", "refit_corr_shift_var")
 
 
@@ -943,6 +1035,8 @@ def save_npz(path: str, res: Dict[str, object], dataset_name: str) -> None:
     keep.update({k: np.float64(res[k]) for k in pair if k in res})           # eval.py --cfg2 --ckpt2 (run_eval_pair)
     keep.update({k: np.float64(res[k]) for k in TTA_SCALARS if k in res})        # eval.py --tta (run_eval_tta)
     keep.update({k: np.float64(res[k]) for k in REFIT_SCALARS if k in res})      # eval.py --kp_refit (run_eval_refit)
+    keep.update({k: np.float64(res[k]) for k in CORRUPT_SCALARS if k in res})    # eval.py --corrupt (run_eval_corrupt)
+    keep.update({k: res[k] for k in ("corrupt_levels",) if k in res})
     keep.update({k: res[k] for k in ("seq_track_names", "seq_pipelines") if k in res})   # eval.py --sequences (run_eval_sequences)
     keep.update({k: res[k] for k in ("boot_names",) if k in res})                        # eval.py --bootstrap (poco_amd/bootstrap.py)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)

@@ -1384,3 +1384,94 @@ def mlp_chain(layers, rows, stages, bufs, B, max_blocks=256):
     rc = lib().poco_op_mlp_chain(arr(li), nl, wp, bp, arr(ri), nr, arr(si), ns, dp, sizes, nb, int(B), int(max_blocks), current_stream())
     check(rc, "poco_op_mlp_chain")
     return rc
+
+
+# ---- image degradation of raw crops (include/poco_hip.h poco_op_corrupt; poco_amd/corrupt.py is the user's side) ------------------
+CORRUPT_MAX_STEPS = 4
+CORRUPT_KINDS = ("none", "gaussian_blur", "motion_blur", "pixelate", "contrast", "gamma", "gaussian_noise", "jpeg")
+CORRUPT_JPEG = CORRUPT_KINDS.index("jpeg")
+# poco_corrupt_step_t
+CORRUPT_STEP = np.dtype([("kind", np.int32), ("ival", np.int32), ("p0", np.float32), ("p1", np.float32), ("seed", np.uint32, (2,)),
+                         ("stream", np.uint32)])
+assert CORRUPT_STEP.itemsize == 28
+_corrupt_codecs = {}
+
+
+def _corrupt_codec(device, res: int):
+    """The JPEG encoder and decoder of res x res crops on `device`, made once."""
+    from . import jpeg
+    key = (str(device), int(res))
+    if key not in _corrupt_codecs:
+        # quality 100 on a noisy crop: the stream can approach the encoder's worst case, far above the decoder's default room
+        _corrupt_codecs[key] = (jpeg.JpegEncoder(device, res, res),
+                                jpeg.JpegDecoder(device, res, res, 1, max_bytes=jpeg.worst_case_bytes(res, res)))
+    return _corrupt_codecs[key]
+
+
+def _corrupt_jpeg_round_trip(buf: torch.Tensor, crops, qualities) -> None:
+    """buf fp32 [N,3,res,res] holding whole numbers in [0, 255] in the crops named: each goes through poco_jpeg_encode and the
+    decoder as a picture of its own (4:2:0 fancy upsampling looks across a seam of stacked pictures), in place.  The decoder
+    parses the stream on the host, so every picture costs one read-back of its bytes."""
+    enc, dec = _corrupt_codec(buf.device, int(buf.shape[-1]))
+    for n, q in zip(crops, qualities):
+        frame = buf[n].permute(1, 2, 0).to(torch.uint8).contiguous()
+        pix, status = dec.decode([enc.encode(frame, int(q))], return_status=True)
+        if status[0] != 0:
+            raise PocoHipError(f"corrupt: the decoder refused the encoder's stream of crop {n} (status {status[0]})")
+        buf[n].copy_(pix[0].permute(2, 0, 1))
+
+
+def corrupt(x: torch.Tensor, steps: np.ndarray, normalize: bool = False, *, out: torch.Tensor = None, tmp: torch.Tensor = None) -> torch.Tensor:
+    """poco_op_corrupt on raw crops: x fp32 [N,3,res,res] in [0, 255] on the device, steps = a host array [N,L] of CORRUPT_STEP
+    records (L <= 4; a chain ends at its first `none`) -> fp32 [N,3,res,res], raw or with normalize=True mapped as
+    oracle/crop_np.normalize_np.  out and tmp: the two buffers the launches ping-pong between (made here if not given; x is only
+    read).  Chains without a jpeg step are one call: no allocation beyond the buffers, no synchronisation.  With a jpeg step the
+    chain positions are run one by one and the crops whose step at that position is jpeg take the round trip through the
+    encoder and the decoder in between (this reads their bytes back).  Argument errors raise PocoHipError before any GPU work."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"corrupt: {what}")
+    need(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+         and x.shape[2] == x.shape[3], "x must be a contiguous float32 CUDA [N,3,res,res]")
+    N, res = int(x.shape[0]), int(x.shape[2])
+    need(isinstance(steps, np.ndarray) and steps.dtype == CORRUPT_STEP and steps.ndim == 2 and steps.shape[0] == N,
+         f"steps must be a numpy array [{N},L] of ops.CORRUPT_STEP records")
+    L = int(steps.shape[1])
+    need(1 <= L <= CORRUPT_MAX_STEPS, f"a chain holds 1..{CORRUPT_MAX_STEPS} steps, got {L}")
+    steps = np.ascontiguousarray(steps)
+    bufs = {}
+    for name, b in (("out", out), ("tmp", tmp)):
+        if b is None:
+            b = torch.empty_like(x)
+        need(torch.is_tensor(b) and b.is_cuda and b.device == x.device and b.dtype == torch.float32 and b.is_contiguous() and b.shape == x.shape,
+             f"{name} must be a contiguous float32 CUDA tensor of x's shape on x's device")
+        bufs[name] = b
+    out, tmp = bufs["out"], bufs["tmp"]
+    need(len({x.data_ptr(), out.data_ptr(), tmp.data_ptr()}) == 3, "x, out and tmp must be three buffers")
+    d_steps = torch.from_numpy(steps.view(np.uint8).reshape(-1)).to(x.device)
+    fn = lib().poco_op_corrupt
+    fn.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 3
+
+    def call(src, lo, hi, norm, scratch, dst):
+        with torch.cuda.device(x.device):
+            check(fn(src.data_ptr(), d_steps.data_ptr(), steps.ctypes.data, N, L, lo, hi, res, int(bool(norm)), scratch.data_ptr(),
+                     dst.data_ptr(), current_stream()), "poco_op_corrupt")
+    kinds = steps["kind"]
+    if not (kinds == CORRUPT_JPEG).any():
+        call(x, 0, L, normalize, tmp, out)
+        return out
+    # with a jpeg step: one call per position, the round trips in between.  Every call is a single launch src -> dst (its scratch
+    # buffer is not written), the targets alternate so that the last one is `out`: the last position's, or the normalising copy's.
+    P = int((kinds != 0).sum(1).max())
+    spare = torch.empty_like(x)
+    last = tmp if normalize else out
+    src = x
+    for p in range(P):
+        dst = last if (P - 1 - p) % 2 == 0 else (out if last is tmp else tmp)
+        call(src, p, p + 1, False, spare, dst)
+        jp = np.nonzero(kinds[:, p] == CORRUPT_JPEG)[0]
+        _corrupt_jpeg_round_trip(dst, jp.tolist(), steps["ival"][jp, p].tolist())
+        src = dst
+    if normalize:
+        call(src, L, L, True, spare, out)
+    return out

@@ -75,6 +75,7 @@ class POCOTester:
     _pseudo = None                      # --save_dataset: the device-side labeler of the current run (pseudo_begin), else None
     pair = None                         # --cfg2 / --ckpt2: the RegressorPair that stands where self.model is used for forwards, else None
     tta = None                          # --tta: the TTAModel that stands where self.model is used for forwards, else None
+    corrupt = None                      # eval.py --corrupt: the CorruptModel around self.model (which stays the engine), else None
 
     def __init__(self, args):
         self.args = args
@@ -91,8 +92,15 @@ class POCOTester:
         if getattr(args, "tta", None):
             from . import tta
             views = tta.parse_views(args.tta)
-        # --tta: a forward takes the K views of max(1, batch_size // K) crops, so the engine holds at least the K views of one crop
-        self.model = self._build_engine(self.model_cfg, args.ckpt, getattr(args, "inf_model", "best"), min_batch=len(views) if views else 1)
+        levels = None
+        if getattr(args, "corrupt", None):
+            from . import corrupt
+            levels = corrupt.parse_levels(args.corrupt)
+        # --tta / --corrupt: a forward takes the K views (levels) of max(1, batch_size // K) crops, so the engine holds at least the K of one crop
+        self.model = self._build_engine(self.model_cfg, args.ckpt, getattr(args, "inf_model", "best"),
+                                        min_batch=len(views) if views else (len(levels) if levels else 1))
+        if levels:
+            self.corrupt = corrupt.CorruptModel(self.model, levels, int(getattr(args, "corrupt_seed", None) or 0))
         if views:
             self.model = self.tta = tta.TTAModel(self.model, views, getattr(args, "tta_weight", None) or "uncert")
             self.tta_text = tta.views_text(views)
