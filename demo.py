@@ -65,6 +65,15 @@ IoU assignment per frame, all frames of the clip in one launch (poco_amd/sort.py
 filter's boxes instead of the file's; --track_backfill gives a reported person the frames before --track_min_hits was reached.  The
 tracks go through the same path as a --tracking file's (and are written as <out>/tracking_results_sort.json, which --tracking reads
 back).  Not with --tracking or --kp_refit (box tracks have no keypoints); at most 64 people per frame; no detector, no appearance model.
+--track_stitch (video mode) rejoins what an occlusion broke: after the forward, the tracks (SORT's or a --tracking file's; those of at
+least --stitch_min_frag frames now reach the forward) are fragments, and one optimal assignment per clip on the GPU decides which
+fragment continues which - from the regressed body shape, averaged with the model's own precision, and the motion of the boxes
+extrapolated from both sides to the middle of the hole of at most --stitch_max_gap frames (poco_amd/stitch.py, csrc/track_stitch.hip,
+DESIGN.md section 36).  The frames of a hole get interpolated boxes and go through the forward (--stitch_no_fill leaves them out), chains
+under 25 frames are dropped, and --infill, --smooth_uncert and --smooth see one long track.  The result gains stitch [T] (1 = a row that
+fills a hole) and stitch_frag [T]; <out>/tracking_results_stitched.json holds the chains for a later --tracking run.  The defaults of
+--stitch_motion_tol and --stitch_shape_tol are guesses, not measured on real video.  Not with keypoint tracks, --kp_refit,
+--save_dataset or --gpus N > 1.
 --cfg2 FILE --ckpt2 FILE [--inf_model2 best] [--select crop|joint] [--select_scale S] runs a second model on the same crops on the
 same GPU and lets the uncertainty choose (poco_amd/select.py, csrc/select_regressor.hip): per crop the model
 whose global uncertainty (the reference's get_global_uncert of its own head) is lower, S times the second model's against the
@@ -245,6 +254,28 @@ def parse_args(argv=None):
                    help="--tracker sort: crop with the file's own boxes (default: what folder mode cuts) or with the Kalman filter's")
     p.add_argument("--track_backfill", action="store_true",
                    help="--tracker sort: a reported person's track also takes the frames before --track_min_hits was reached")
+    p.add_argument("--track_stitch", action="store_true",
+                   help="video mode: after the forward, join the tracks an occlusion broke into chains - by the regressed body shape "
+                        "(weighted by the model's own uncertainty) and the extrapolated motion of the boxes, one optimal assignment "
+                        "on the GPU - run the frames of the holes through the forward with interpolated boxes, and hand the chains to "
+                        "--infill / --smooth_uncert / --smooth as single tracks; the result gains stitch and stitch_frag, "
+                        "<out>/tracking_results_stitched.json is written for a later --tracking run")
+    p.add_argument("--stitch_max_gap", type=int, default=30,
+                   help="--track_stitch: the most missing frames between two joined tracks (the default of --infill_max_gap)")
+    p.add_argument("--stitch_fit_len", type=int, default=8,
+                   help="--track_stitch: the rows at a track's end and start through which its motion is fitted, 1..32")
+    p.add_argument("--stitch_motion_tol", type=float, default=0.5,
+                   help="--track_stitch: the largest mismatch of the two extrapolated boxes, in body heights per square root of the "
+                        "frames apart; the default is a guess that nobody has measured on real video")
+    p.add_argument("--stitch_shape_tol", type=float, default=1.0,
+                   help="--track_stitch: the largest distance of the two mean shapes in units of their pooled spread (with a floor of "
+                        "0.05 per beta); the default and the floor are guesses that nobody has measured on real video")
+    p.add_argument("--stitch_shape", type=float, default=1.0,
+                   help="--track_stitch: the weight of the shape term against the motion term; 0 switches the shape term off")
+    p.add_argument("--stitch_min_frag", type=int, default=5,
+                   help="--track_stitch: tracks of at least this many frames reach the forward (instead of 25); the 25-frame rule is "
+                        "applied to the chains")
+    p.add_argument("--stitch_no_fill", action="store_true", help="--track_stitch: join the ids and leave the holes")
     p.add_argument("--gpus", type=int, default=1,
                    help="video mode: one process per GPU, whole tracks sharded across the ranks, ONE all-gather of the "
                         "packed SMPL records (RCCL over xGMI); `demo.py --gpus N` starts the N ranks itself")
@@ -383,6 +414,14 @@ def _check_tracker(args) -> None:
         sys.exit(msg)
 
 
+def _check_stitch(args) -> None:
+    """--track_stitch and its --stitch_* companions: refuse what cannot work before the engine is built."""
+    from poco_amd.stitch import flag_error
+    msg = flag_error(args)
+    if msg:
+        sys.exit(msg)
+
+
 def _check_calibration(args) -> None:
     """--calibration: refuse --cfg2, an unreadable file and a file fitted for another head or kinematic flag before the engine is
     built."""
@@ -405,12 +444,14 @@ def _build_sort_tracks(args, folder: str, out_dir: str):
     from poco_amd.tester import load_detections
     try:
         names = sort.frame_names(folder)
+        min_frames = args.stitch_min_frag if getattr(args, "track_stitch", False) else sort.MIN_NUM_FRAMES
         tracks = sort.build_tracks(load_detections(args.detections), names, iou_thresh=args.track_iou, max_age=args.track_max_age,
-                                   min_hits=args.track_min_hits, boxes=args.track_boxes, backfill=args.track_backfill)
+                                   min_hits=args.track_min_hits, boxes=args.track_boxes, backfill=args.track_backfill,
+                                   min_frames=min_frames)
     except ValueError as e:
         sys.exit(str(e))
     if not tracks:
-        sys.exit(f"--tracker sort: no track of at least {sort.MIN_NUM_FRAMES} frames in {args.detections}")
+        sys.exit(f"--tracker sort: no track of at least {min_frames} frames in {args.detections}")
     if int(os.environ.get("RANK", "0")) == 0:
         os.makedirs(out_dir, exist_ok=True)
         sort.write_tracking(os.path.join(out_dir, "tracking_results_sort.json"), tracks)
@@ -464,6 +505,7 @@ def main(args):
     _check_infill(args)
     _check_smooth_uncert(args)
     _check_tracker(args)
+    _check_stitch(args)
     _check_kp_refit(args)
     _check_calibration(args)
     if args.gpus > 1:
@@ -493,11 +535,17 @@ def main(args):
     elif not folder or not os.path.isdir(folder):
         sys.exit(f"input folder not found: {folder}")
     tracking = args.tracking
-    if args.mode == "video" and tracking:                                 # read before the engine is built: a bad file ends here
+    stitching = bool(getattr(args, "track_stitch", False))
+    if args.mode == "video" and tracking:                               # read before the engine is built: a bad file ends here
         try:
-            tracking = load_tracking(tracking, **tracking_options(args))
+            tracking = load_tracking(tracking, **tracking_options(args), **({"min_frames": args.stitch_min_frag} if stitching else {}))
         except ValueError as e:
             sys.exit(str(e))
+    if stitching:                                                         # gap rows have no keypoints: a keypoint track ends here
+        from poco_amd.stitch import tracking_error as stitch_tracking_error
+        msg = stitch_tracking_error(tracking)
+        if msg:
+            sys.exit(msg)
     if getattr(args, "kp_refit", None) is not None:                       # every track needs BODY_25 keypoints: a box track ends here
         from poco_amd.refit import tracking_error
         msg = tracking_error(tracking)

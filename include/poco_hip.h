@@ -1375,6 +1375,60 @@ int poco_op_sort_tracks(const double* d_dets, const int32_t* d_frame_offsets, co
                         int64_t N, double iou_thresh, int max_age, int min_hits, int max_trackers, int32_t* d_tracker, int32_t* d_id,
                         double* d_box, int32_t* d_count, int32_t* d_status, void* stream);
 
+/* ---- track stitching: the fragments an occlusion left of one person joined into chains, by body shape and box motion ------------------
+ * demo.py --mode video --track_stitch; csrc/track_stitch.hip; poco_amd/stitch.py; tests/stitch_np.py restates
+ * it in float64 numpy with plain loops and scipy's assignment.  No counterpart in the reference's code: its tracker's ids are final.
+ *
+ * poco_op_track_stitch: C clips concatenated: d_clip_offsets int32 [C+1] over fragments (0 = first, P = last), d_frag_offsets int32
+ *   [P+1] over rows (0 = first, N = last), at most POCO_STITCH_MAX_FRAGS fragments in a clip (a clip may hold none), at least one row
+ *   in a fragment; d_frames int32 [N], strictly increasing inside a fragment; d_boxes fp64 [N,4] = (cx, cy, w, h), w, h > 0; d_betas
+ *   fp32 [N,10]; d_var fp32 [N,24], >= 0.  The CALLER checks the tables and the rows (they are device memory); the kernels clamp
+ *   every index they take from a table, and a clip whose range or one of whose fragments' ranges is not inside the buffers, is empty
+ *   or runs backwards, or which holds more than 256 fragments, ends with status 2.
+ *   max_gap >= 0, fit_len in 1..POCO_STITCH_MAX_FIT, u_ref, motion_tol, shape_tol, shape_floor > 0, shape_w >= 0 (0: no shape term).
+ *   All of it in fp64 without contraction (no fused multiply-add), in this order:
+ *   1 describe  fragment p, rows i = 0..T-1, first frame s, last frame e.  u_i = (var[i][0] + ... + var[i][23]) / 24 in ascending
+ *               joint order; w_i = r r with r = u_ref / max(u_i, 1e-6).  W = sum w_i, W2 = sum w_i^2, bbar_k = (sum w_i beta_ik) / W,
+ *               sig2 = ((sum_i w_i d_i) / W) / 10 with d_i = sum_k (beta_ik - bbar_k)^2 in ascending k.  Every sum over the rows is
+ *               the same tree, a function of T alone: slot l of 64 adds its rows l, l + 64, ... in ascending order to 0, then a
+ *               halving tree over the slots (slot t += slot t + o for o = 32, 16, .., 1).
+ *               tail fit: the last m = min(fit_len, T) rows, t_j = frame_j - e, each of q = (cx, cy, log h): tbar = (sum t_j) / m,
+ *               qbar = (sum q_j) / m, Stt = sum (t_j - tbar)^2, Stq = sum (t_j - tbar)(q_j - qbar), all in ascending j from 0;
+ *               velocity = Stq / Stt, state = qbar - velocity * tbar; with m = 1 (or Stt = 0) velocity = 0 and state = qbar.
+ *               head fit: the same over the first m rows with t_j = frame_j - s.
+ *   2 pair      (a -> b), a != b in one clip, D = s_b - e_a in 1..max_gap + 1 (else gain 0): h = D / 2; pa = tail state(a) +
+ *               tail velocity(a) * h, pb = head state(b) - head velocity(b) * h;
+ *               c_m = sqrt((dx dx + dy dy) / (exp(pa.l) exp(pb.l)) + dl dl) / (motion_tol sqrt(D)) with (dx, dy, dl) = pa - pb;
+ *               c_s = sqrt((sum_k (bbar_ak - bbar_bk)^2) / 10) / sqrt((sig2_a + sig2_b) + shape_floor^2) / shape_tol;
+ *               gain 0 if c_m > 1, if shape_w > 0 and c_s > 1, or if either is not finite; else
+ *               gain = 1 - (c_m c_m + shape_w (c_s c_s)) / (1 + shape_w).
+ *   3 assign    per clip a matching of tails to heads that maximises the sum of the gains; pairs of gain 0 are no links.  Shortest
+ *               augmenting paths with potentials on the n x n square of costs -gain (poco_op_sort_tracks' step 3 on up to 256
+ *               columns): a true optimum; where it is not unique any optimum may come back.  Loops: at most 256 rows, 257 steps
+ *               per row, 257 steps per path.  D >= 1 makes every chain run forward in time: no cycle, no overlap inside a chain.
+ *   Outputs (every element is written): d_succ, d_pred int32 [P] (fragment index inside the call, -1 = none), d_chain int32 [P]
+ *   (chains numbered per clip from 0 in the order of their FIRST fragments' indices), d_gain fp64 [P] (the gain of the link to the
+ *   successor, 0 without one), d_desc fp64 [P,POCO_STITCH_DESC] = bbar[10], sig2, W, W2, T, tail state[3], tail velocity[3], head
+ *   state[3], head velocity[3], s, e (zeros for a fragment the kernel cannot read), d_status int32 [C]: 0, or 2 (above): then the
+ *   clip's fragments get succ = pred = -1, their own chain and gain 0.
+ *   d_scratch: POCO_STITCH_SCRATCH_DOUBLES(P) doubles, caller-owned, set and consumed by the call (per fragment its row of the
+ *   clip's gain matrix).  Three launches on `stream` (a block of one wave per fragment; a block of 256 per fragment, a lane per
+ *   pair; a block of 256 per clip, a lane per column); no allocation, no synchronisation, no atomics, no grid barrier, no spin-wait:
+ *   a clip's outputs do not depend on the other clips and repeat bit for bit from run to run.
+ *   POCO_ERR_ARG before any GPU work: C < 1, P < 0, N < 0, C > 2^24, P > 2^22, N > 2^24 (the int32 plans), a null offset table or
+ *   d_status, a null d_frames, d_boxes, d_betas or d_var with N > 0, a null d_scratch, d_succ, d_pred, d_chain, d_gain or d_desc with
+ *   P > 0, max_gap outside 0..2^30, fit_len outside 1..32, u_ref, motion_tol, shape_tol or shape_floor not finite or <= 0, shape_w
+ *   not finite or < 0. */
+#define POCO_STITCH_MAX_FRAGS 256
+#define POCO_STITCH_MAX_FIT 32
+#define POCO_STITCH_DESC 28
+#define POCO_STITCH_SCRATCH_DOUBLES(P) ((size_t)(P) * 256)
+int poco_op_track_stitch(const int32_t* d_clip_offsets, const int32_t* d_frag_offsets, const int32_t* d_frames, const double* d_boxes,
+                         const float* d_betas, const float* d_var, int64_t C, int64_t P, int64_t N, int max_gap, int fit_len,
+                         double u_ref, double motion_tol, double shape_tol, double shape_floor, double shape_w, double* d_scratch,
+                         int32_t* d_succ, int32_t* d_pred, int32_t* d_chain, double* d_gain, double* d_desc, int32_t* d_status,
+                         void* stream);
+
 /* ---- calibrating the uncertainty: isotonic regression of the error on the uncertainty, and evaluating the fitted maps ------------------
  * eval.py --calibrate OUT.npz, demo.py --calibration FILE; csrc/isotonic.hip; poco_amd/calibrate.py; DESIGN.md section 33;
  * tests/calib_np.py restates both operators with plain loops and a stack.  No counterpart in the reference's code.

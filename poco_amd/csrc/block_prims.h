@@ -45,5 +45,30 @@ __device__ __forceinline__ T block_exscan(T v, T* wsum, T* total) {
   return base + inc - v;
 }
 
+// The least of the 64 * WAVES values of a block and the index that came with it, returned to every lane; of equal values the lower
+// index wins, so the result does not depend on the order of the lanes.  Butterflies inside the waves, the waves' results through LDS
+// (sval[WAVES], sidx[WAVES]).  Ends with a barrier, so both may be reused at once.
+template <int WAVES>
+__device__ __forceinline__ void block_argmin(double& v, int& idx, double* sval, int* sidx) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  #pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double ov = __shfl_xor(v, off);
+    const int oi = __shfl_xor(idx, off);
+    if (ov < v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+  }
+  if (lane == 0) { sval[wv] = v; sidx[wv] = idx; }
+  __syncthreads();
+  v = sval[0];
+  idx = sidx[0];
+  #pragma unroll
+  for (int w = 1; w < WAVES; ++w) {
+    const double ov = sval[w];
+    const int oi = sidx[w];
+    if (ov < v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+  }
+  __syncthreads();
+}
+
 // Index of (r, c), r >= c, in a lower triangle packed row by row.
 __device__ __forceinline__ constexpr int tri(int r, int c) { return r * (r + 1) / 2 + c; }

@@ -375,6 +375,22 @@ void launch_sort_tracks(const double* dets, const int* frame_offsets, const int*
                         int max_age, int min_hits, int max_trackers, int* tracker, int* id, double* box, int* count, int* status,
                         hipStream_t s);
 
+// ---- video mode's --track_stitch: fragments of tracks joined into chains by shape and motion (track_stitch.hip) ------------------------
+// include/poco_hip.h poco_op_track_stitch: C clips = fragments [clip_offsets[c], clip_offsets[c + 1]) of P, a fragment = rows
+// [frag_offsets[p], frag_offsets[p + 1]) of N; frames int32 [N], boxes fp64 [N,4], betas fp32 [N,10], var fp32 [N,24]; scratch =
+// STITCH_MAX_FRAGS doubles per fragment (its row of the clip's gain matrix); outputs succ / pred / chain int32 [P], gain fp64 [P],
+// desc fp64 [P,STITCH_DESC], status int32 [C].  A block of STITCH_ROW_THREADS per fragment, then blocks of STITCH_THREADS per
+// fragment and per clip; at most STITCH_MAX_FRAGS fragments in a clip.
+constexpr int STITCH_THREADS = 256;
+constexpr int STITCH_ROW_THREADS = 64;
+constexpr int STITCH_MAX_FRAGS = 256;
+constexpr int STITCH_MAX_FIT = 32;
+constexpr int STITCH_DESC = 28;
+void launch_track_stitch(const int* clip_offsets, const int* frag_offsets, const int* frames, const double* boxes, const float* betas,
+                         const float* var, int C, int P, int N, int max_gap, int fit_len, double u_ref, double motion_tol,
+                         double shape_tol, double shape_floor, double shape_w, double* scratch, int* succ, int* pred, int* chain,
+                         double* gain, double* desc, int* status, hipStream_t s);
+
 // ---- calibration: isotonic regression over ragged segments, and the fitted maps evaluated (isotonic.hip) --------------------------------
 // include/poco_hip.h poco_op_isotonic / poco_op_calib_apply.  Everything works on tiles of ISO_TILE consecutive POSITIONS of the
 // ragged buffer (segments are told apart by flags, so many small segments and one large one load the device alike), dealt to at

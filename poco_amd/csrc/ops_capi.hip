@@ -1262,6 +1262,37 @@ extern "C" int poco_op_sort_tracks(const double* d_dets, const int32_t* d_frame_
   return POCO_OK;
 }
 
+// ---- video mode's --track_stitch: fragments joined into chains by shape and motion (track_stitch.hip) ---------------------------------
+static_assert(POCO_STITCH_MAX_FRAGS == STITCH_MAX_FRAGS && POCO_STITCH_MAX_FIT == STITCH_MAX_FIT && POCO_STITCH_DESC == STITCH_DESC &&
+                  POCO_STITCH_SCRATCH_DOUBLES(1) == STITCH_MAX_FRAGS,
+              "include/poco_hip.h and csrc/kernels.h disagree on the stitcher");
+extern "C" int poco_op_track_stitch(const int32_t* d_clip_offsets, const int32_t* d_frag_offsets, const int32_t* d_frames,
+                                    const double* d_boxes, const float* d_betas, const float* d_var, int64_t C, int64_t P, int64_t N,
+                                    int max_gap, int fit_len, double u_ref, double motion_tol, double shape_tol, double shape_floor,
+                                    double shape_w, double* d_scratch, int32_t* d_succ, int32_t* d_pred, int32_t* d_chain,
+                                    double* d_gain, double* d_desc, int32_t* d_status, void* stream) {
+  const char* who = "poco_op_track_stitch";
+  if (C < 1 || P < 0 || N < 0) return op_bad(who, "needs C >= 1, P >= 0 and N >= 0");
+  // the plans are int32: 256 P doubles of scratch and 24 N floats of var addressed from an int
+  if (C > (1LL << 24) || P > (1LL << 22) || N > (1LL << 24)) return op_bad(who, "needs C <= 2^24, P <= 2^22 and N <= 2^24 (the int32 plans)");
+  if (!d_clip_offsets || !d_frag_offsets || !d_status) return op_bad(who, "null pointer (both offset tables and status are needed)");
+  if (N > 0 && (!d_frames || !d_boxes || !d_betas || !d_var)) return op_bad(who, "null pointer (frames, boxes, betas and var are needed when N > 0)");
+  if (P > 0 && (!d_scratch || !d_succ || !d_pred || !d_chain || !d_gain || !d_desc))
+    return op_bad(who, "null pointer (scratch, succ, pred, chain, gain and desc are needed when P > 0)");
+  if (max_gap < 0 || max_gap > (1 << 30)) return op_bad(who, "max_gap must be in 0..2^30");
+  if (fit_len < 1 || fit_len > POCO_STITCH_MAX_FIT) return op_bad(who, "fit_len must be in 1..32");
+  if (!std::isfinite(u_ref) || !(u_ref > 0.0)) return op_bad(who, "u_ref must be finite and > 0");
+  if (!std::isfinite(motion_tol) || !(motion_tol > 0.0)) return op_bad(who, "motion_tol must be finite and > 0");
+  if (!std::isfinite(shape_tol) || !(shape_tol > 0.0)) return op_bad(who, "shape_tol must be finite and > 0");
+  if (!std::isfinite(shape_floor) || !(shape_floor > 0.0)) return op_bad(who, "shape_floor must be finite and > 0");
+  if (!std::isfinite(shape_w) || !(shape_w >= 0.0)) return op_bad(who, "shape_w must be finite and >= 0");
+  launch_track_stitch(d_clip_offsets, d_frag_offsets, d_frames, d_boxes, d_betas, d_var, (int)C, (int)P, (int)N, max_gap, fit_len, u_ref,
+                      motion_tol, shape_tol, shape_floor, shape_w, d_scratch, d_succ, d_pred, d_chain, d_gain, d_desc, d_status,
+                      (hipStream_t)stream);
+  POCO_HIP_CHECK(hipGetLastError());
+  return POCO_OK;
+}
+
 // ---- calibration: isotonic regression over ragged segments, the fitted maps evaluated (isotonic.hip) ---------------------------------
 static_assert(POCO_ISO_TILE == ISO_TILE && POCO_ISO_MAX_N == ISO_MAX_N && POCO_ISO_MAX_SEGS == ISO_MAX_SEGS,
               "include/poco_hip.h and csrc/kernels.h disagree on the isotonic fit");

@@ -1259,6 +1259,107 @@ def sort_tracks(dets: torch.Tensor, frame_offsets, clip_offsets=None, *, iou_thr
     return {k: out[k] for k in shapes}
 
 
+# ---- track stitching: fragments joined into chains (include/poco_hip.h; poco_amd/stitch.py is the user's side) -------------------------
+STITCH_MAX_FRAGS = 256            # POCO_STITCH_MAX_FRAGS
+STITCH_DESC = 28                  # POCO_STITCH_DESC
+STITCH_DEFAULTS = {"max_gap": 30, "fit_len": 8, "u_ref": 0.3, "motion_tol": 0.5, "shape_tol": 1.0, "shape_floor": 0.05, "shape_w": 1.0}
+
+
+def track_stitch(clip_offsets, frag_offsets, frames: torch.Tensor, boxes: torch.Tensor, betas: torch.Tensor, var: torch.Tensor, *,
+                 max_gap: int = 30, fit_len: int = 8, u_ref: float = 0.3, motion_tol: float = 0.5, shape_tol: float = 1.0,
+                 shape_floor: float = 0.05, shape_w: float = 1.0, out=None) -> dict:
+    """poco_op_track_stitch: clip_offsets int32 [C+1] over the fragments (None: one clip) and frag_offsets int32 [P+1] over the rows,
+    each a host array / list or a tensor (a device tensor is downloaded once for the checks); frames int32 [N], boxes fp64 [N,4]
+    (cx, cy, w, h), betas fp32 [N,10], var fp32 [N,24] on the device -> dict(succ, pred, chain int32 [P], gain fp64 [P], desc fp64
+    [P,28], status int32 [C]) on the device.  out = the same dict of contiguous tensors to write into (tests: guarded buffers).
+    Refused with PocoHipError before any GPU work, the fragment named: more than 256 fragments in a clip, an empty fragment, frames
+    that do not increase strictly, offsets that are not monotone, a box that is not finite or has w <= 0 or h <= 0, betas or var
+    that are not finite, a negative var (the rows are downloaded once for these checks)."""
+    def need(ok, what):
+        if not ok:
+            raise PocoHipError(f"track_stitch: {what}")
+
+    def table(t, name):
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        need(a.ndim == 1 and a.size >= 1 and a.dtype.kind in "iu", f"{name} must be a 1-D integer table, got {a.dtype} {a.shape}")
+        need(bool((a >= 0).all()) and int(a.max()) < (1 << 31), f"{name} must hold int32 values >= 0")
+        return np.ascontiguousarray(a, np.int32)
+
+    for name, t, dt, cols in (("frames", frames, torch.int32, None), ("boxes", boxes, torch.float64, 4), ("betas", betas, torch.float32, 10),
+                              ("var", var, torch.float32, 24)):
+        need(torch.is_tensor(t) and t.dtype == dt, f"{name} must be a {str(dt).replace('torch.', '')} tensor")
+        need(t.dim() == 1 if cols is None else (t.dim() == 2 and t.shape[1] == cols),
+             f"{name} must be [N]" if cols is None else f"{name} must be [N,{cols}], got {tuple(t.shape)}")
+    N = int(frames.shape[0])
+    need(boxes.shape[0] == N and betas.shape[0] == N and var.shape[0] == N, f"boxes, betas and var must hold N = {N} rows like frames")
+    fo = table(frag_offsets, "frag_offsets")
+    P = int(fo.size) - 1
+    co = table(np.array([0, P], np.int32) if clip_offsets is None else clip_offsets, "clip_offsets")
+    Cn = int(co.size) - 1
+    need(Cn >= 1, "clip_offsets must be [C+1] with C >= 1")
+    need(co[0] == 0 and co[-1] == P, f"clip_offsets must start at 0 and end at P = {P}")
+    per = np.diff(co)
+    bad = np.nonzero(per < 0)[0]
+    need(bad.size == 0, f"clip_offsets are not monotone at clip {int(bad[0]) if bad.size else 0}")
+    bad = np.nonzero(per > STITCH_MAX_FRAGS)[0]
+    need(bad.size == 0, f"clip {int(bad[0]) if bad.size else 0} holds {int(per[bad[0]]) if bad.size else 0} fragments, more than {STITCH_MAX_FRAGS}")
+    need(fo[0] == 0 and fo[-1] == N, f"frag_offsets must start at 0 and end at N = {N}")
+    rows = np.diff(fo)
+    bad = np.nonzero(rows < 0)[0]
+    need(bad.size == 0, f"frag_offsets are not monotone at fragment {int(bad[0]) if bad.size else 0}")
+    bad = np.nonzero(rows == 0)[0]
+    need(bad.size == 0, f"fragment {int(bad[0]) if bad.size else 0} is empty")
+    for name, v, lo, hi in (("max_gap", max_gap, 0, 1 << 30), ("fit_len", fit_len, 1, 32)):
+        need(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and lo <= v <= hi, f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+    real = {}
+    for name, v, strict in (("u_ref", u_ref, True), ("motion_tol", motion_tol, True), ("shape_tol", shape_tol, True),
+                            ("shape_floor", shape_floor, True), ("shape_w", shape_w, False)):
+        ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v) and (v > 0 if strict else v >= 0)
+        need(ok, f"{name} must be finite and {'> 0' if strict else '>= 0'}, got {v!r}")
+        real[name] = float(v)
+    frag_of = lambda i: int(np.searchsorted(fo, i, side="right")) - 1               # noqa: E731
+    if N:
+        fr = frames.detach().cpu().numpy()
+        step = np.diff(fr.astype(np.int64)) > 0
+        step[fo[1:-1] - 1] = True                                                   # between two fragments: anything goes
+        if not step.all():
+            i = int(np.nonzero(~step)[0][0]) + 1
+            need(False, f"the frames of fragment {frag_of(i)} do not increase strictly at row {i} ({int(fr[i - 1])} then {int(fr[i])})")
+        h = boxes.detach().cpu().numpy()
+        ok = np.isfinite(h).all(1) & (h[:, 2] > 0) & (h[:, 3] > 0)
+        if not ok.all():
+            i = int(np.nonzero(~ok)[0][0])
+            need(False, f"row {i} of fragment {frag_of(i)} is not a finite box with w, h > 0: {h[i].tolist()}")
+        for name, t in (("betas", betas), ("var", var)):
+            a = t.detach().cpu().numpy()
+            ok = np.isfinite(a).all(1) & ((a >= 0).all(1) if name == "var" else True)
+            if not ok.all():
+                i = int(np.nonzero(~ok)[0][0])
+                need(False, f"row {i} of fragment {frag_of(i)}: {name} must be finite{' and >= 0' if name == 'var' else ''}")
+    for name, t in (("frames", frames), ("boxes", boxes), ("betas", betas), ("var", var)):
+        need(t.is_cuda, f"{name} must be a CUDA tensor")
+    dev = frames.device
+    shapes = {"succ": ((P,), torch.int32), "pred": ((P,), torch.int32), "chain": ((P,), torch.int32), "gain": ((P,), torch.float64),
+              "desc": ((P, STITCH_DESC), torch.float64), "status": ((Cn,), torch.int32)}
+    if out is None:
+        out = {k: torch.empty(s, device=dev, dtype=dt) for k, (s, dt) in shapes.items()}
+    for k, (shp, dt) in shapes.items():
+        t = out.get(k)
+        need(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shp and t.dtype == dt,
+             f"out[{k!r}] must be a contiguous CUDA {dt} {shp}")
+    d_fo, d_co = torch.from_numpy(fo).to(dev), torch.from_numpy(co).to(dev)
+    scratch = torch.empty((max(P, 1) * STITCH_MAX_FRAGS,), device=dev, dtype=torch.float64)
+    p = lambda t: C.c_void_p(t.data_ptr())                                      # noqa: E731
+    with torch.cuda.device(dev):
+        check(lib().poco_op_track_stitch(p(d_co), p(d_fo), p(frames.contiguous()), p(boxes.contiguous()), p(betas.contiguous()),
+                                         p(var.contiguous()), C.c_int64(Cn), C.c_int64(P), C.c_int64(N), int(max_gap), int(fit_len),
+                                         C.c_double(real["u_ref"]), C.c_double(real["motion_tol"]), C.c_double(real["shape_tol"]),
+                                         C.c_double(real["shape_floor"]), C.c_double(real["shape_w"]), p(scratch), p(out["succ"]),
+                                         p(out["pred"]), p(out["chain"]), p(out["gain"]), p(out["desc"]), p(out["status"]),
+                                         current_stream()), "poco_op_track_stitch")
+    return {k: out[k] for k in shapes}
+
+
 # ---- head kernels on their own, at any stride (include/poco_hip.h; tests/test_head_kernels_gpu.py) ------------------------------
 # Every operand lies in a NaN-filled Rows buffer, every output between poisoned guard bands; the output buffers are returned so
 # that the caller can check `untouched`.

@@ -580,6 +580,8 @@ class POCOTester:
         self.select_summary()
         if raw:
             return stacked
+        if getattr(self.args, "track_stitch", False):
+            tracking_results, stacked = self._stitch_tracks(tracking_results, stacked, frames, orig_width, orig_height, bbox_scale)
         lam = getattr(self.args, "smooth_uncert", None)
         if getattr(self.args, "kp_refit", None) is not None:
             return self._finish_tracks_refitted(tracking_results, stacked, orig_width, orig_height)
@@ -590,6 +592,29 @@ class POCOTester:
             return self._smooth_tracks_uncert({pid: self._finish_track(tr, stacked[pid], orig_width, orig_height, smooth=False)
                                                for pid, tr in tracking_results.items()}, lam)
         return {pid: self._finish_track(tr, stacked[pid], orig_width, orig_height) for pid, tr in tracking_results.items()}
+
+    def _stitch_tracks(self, tracking_results: dict, stacked: dict, frames, orig_width: int, orig_height: int, bbox_scale: float):
+        """--track_stitch: ONE call of stitch.stitch_tracks joins the fragments into chains by their regressed shape and the motion of
+        their boxes; unless --stitch_no_fill, the frames of the holes between joined fragments get interpolated boxes and go through
+        the forward; chains under 25 frames are dropped.  The finishing branches then see each chain as one long track whose
+        uncertain rows sit in the middle: what --infill and --smooth_uncert were written for.  Every raw row gains `stitch` (0 an own
+        row, 1 a gap row) and `stitch_frag` (the index of the source fragment in the chain, -1 on a gap row), which _finish_track
+        hands on; the merged tracks are kept in self.stitched_tracking."""
+        from . import stitch
+        fill = not getattr(self.args, "stitch_no_fill", False)
+        merged, st, chains = stitch.stitch_tracks(tracking_results, stacked, None, fill=fill, device=self.device,
+                                                  **stitch.params_of(self.args))
+        gap = stitch.gap_tracks(merged, chains)
+        if gap:
+            if hasattr(frames, "plan"):
+                frames.plan(sorted({int(f) for v in gap.values() for f in v["frames"]}))
+            st = stitch.merge_gap_rows(st, self.run_on_video(gap, frames, orig_width, orig_height, bbox_scale, raw=True), chains)
+        merged, st, kept, dropped = stitch.drop_short(merged, st, chains)
+        for ch in kept:
+            st[ch["pid"]] = {**st[ch["pid"]], "stitch": ch["stitch"], "stitch_frag": ch["stitch_frag"]}
+        print(stitch.summary_line(len(tracking_results), chains, dropped))
+        self.stitched_tracking = merged
+        return merged, st
 
     def _finish_tracks_refitted(self, tracking_results: dict, stacked: dict, orig_width: int, orig_height: int) -> dict:
         """--kp_refit LAMBDA: the tracks are finished unsmoothed, then ONE call of refit.refit_tracks over all of them refits pose and
@@ -688,6 +713,8 @@ class POCOTester:
         else:
             var, var_global = postproc.video_uncert(st["var_pose"], self.backbone,
                                                     self.model_cfg.POCO.KINEMATIC_UNCERT)    # tester.py:416-419
+        if "stitch" in st:                      # --track_stitch: which rows filled a hole, and the fragment each other row came from
+            extra = {**extra, "stitch": st["stitch"], "stitch_frag": st["stitch_frag"]}
         return {
             **extra,
             "pred_cam": st["pred_cam"],
@@ -943,7 +970,13 @@ def _run_on_frames(self, frame_folder: str, tracking_path: Optional[str], output
         if isinstance(load, _GroupLoader):
             load.plan(sorted({int(f) for v in tracking.values() for f in v["frames"]}))
         self.pseudo_begin(sum(len(v["frames"]) for v in tracking.values()))
+        self.stitched_tracking = None
         results = self.run_on_video(tracking, load, W, H, bbox_scale)
+        if self.stitched_tracking is not None:                             # --track_stitch: the chains are the tracks from here on
+            from .sort import write_tracking
+            os.makedirs(output_path, exist_ok=True)
+            write_tracking(os.path.join(output_path, "tracking_results_stitched.json"), self.stitched_tracking)
+            tracking = self.stitched_tracking
         order = {pid: i for i, pid in enumerate(tracking)}
         vstem = os.path.splitext(os.path.basename(os.path.normpath(frame_folder)))[0]
 
@@ -1143,10 +1176,11 @@ def tracking_options(args) -> dict:
             "smooth_bbox": bool(getattr(args, "smooth_bbox", False))}
 
 
-def load_tracking(path: Optional[str], vis_thresh: float = 0.3, smooth_bbox: bool = False, method: str = "bbox") -> Optional[dict]:
+def load_tracking(path: Optional[str], vis_thresh: float = 0.3, smooth_bbox: bool = False, method: str = "bbox",
+                  min_frames: int = 25) -> Optional[dict]:
     """{person_id: {'bbox': [T,4] (cx,cy,w,h), 'frames': [T]}} from json or the reference's
-    `tracking_results_<method>.pkl` (demo.py:125-131); tracks shorter than MIN_NUM_FRAMES = 25 frames are dropped as in
-    tester.py:133-136.
+    `tracking_results_<method>.pkl` (demo.py:125-131); tracks shorter than min_frames = MIN_NUM_FRAMES = 25 frames are dropped as in
+    tester.py:133-136 (--track_stitch passes --stitch_min_frag: short fragments reach the forward, the rule is applied to the chains).
 
     The file's content decides how a track is read.  A track with `bbox` is read as it is; a `joints2d` array of the same length
     next to it is kept.  A track with `joints2d` [T,K,3] and no `bbox` - a pose tracker's output, the reference's
@@ -1169,9 +1203,9 @@ def load_tracking(path: Optional[str], vis_thresh: float = 0.3, smooth_bbox: boo
             if not len(tr["frames"]):
                 import sys
                 print(f"load_tracking: track {k!r} of {path} has no frame with a keypoint above {vis_thresh}: dropped", file=sys.stderr)
-            elif is_json or len(tr["frames"]) >= 25:
+            elif is_json or len(tr["frames"]) >= min_frames:
                 out[str(k)] = tr
-        elif is_json or frames.shape[0] >= 25:
+        elif is_json or frames.shape[0] >= min_frames:
             out[str(k)] = {"bbox": np.asarray(v["bbox"], np.float32).reshape(-1, 4), "frames": frames}
             if v.get("joints2d") is not None and len(v["joints2d"]) == frames.shape[0]:
                 try:
