@@ -137,6 +137,23 @@ def bilinear_tab_i():
 _TAB_I = None
 
 
+def warp_coords(M, res):
+    """warpAffine's fixed-point source coordinates of the res x res output: (sx, sy, fx, fy) int64 [res,res], indexed [y, x] - the
+    integer tap (saturated to int16) and the 5-bit fractions.  The same lines as warp_affine_u8 below, for the tests that have to
+    know which taps a pixel reads."""
+    Mi = invert_affine_cv(M)
+    AB = float(1 << AB_BITS)
+    xs = np.arange(res, dtype=np.float64)
+    adelta = np.rint(Mi[0] * xs * AB).astype(np.int64)
+    bdelta = np.rint(Mi[3] * xs * AB).astype(np.int64)
+    rd = (1 << AB_BITS) // TAB // 2
+    X0 = np.rint((Mi[1] * xs + Mi[2]) * AB).astype(np.int64) + rd
+    Y0 = np.rint((Mi[4] * xs + Mi[5]) * AB).astype(np.int64) + rd
+    X = (X0[:, None] + adelta[None, :]) >> (AB_BITS - INTER_BITS)
+    Y = (Y0[:, None] + bdelta[None, :]) >> (AB_BITS - INTER_BITS)
+    return np.clip(X >> INTER_BITS, -32768, 32767), np.clip(Y >> INTER_BITS, -32768, 32767), X & (TAB - 1), Y & (TAB - 1)
+
+
 def warp_affine_u8(img, M, res):
     """cv2.warpAffine(img uint8 [H,W,C], M 2x3 float64, (res,res), INTER_LINEAR, BORDER_CONSTANT 0) -> uint8 [res,res,C]."""
     global _TAB_I

@@ -1690,6 +1690,9 @@ extern "C" int poco_create(const char* variant, int max_batch, int num_flow_laye
 
 extern "C" int poco_create_ex(const char* variant, int max_batch, int num_flow_layers, const char* options, poco_handle_t* out) {
   if (!variant || !out || max_batch < 1) { poco_set_error("poco_create: bad arguments"); return POCO_ERR_ARG; }
+  // launches behind the engine put a count derived from the batch on gridDim.y (smpl_skin_kernel: one block row per 64 crops); the
+  // cap is the one the stand-alone operators use, far above any batch the workspace could hold
+  if (max_batch > 65535) { poco_set_error("poco_create: max_batch must be in 1..65535"); return POCO_ERR_ARG; }
   std::string v(variant);
   const size_t dash = v.find('-');
   if (dash == std::string::npos) { poco_set_error("variant must be '<backbone>-<head>' (poco.py:41)"); return POCO_ERR_ARG; }

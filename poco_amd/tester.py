@@ -38,19 +38,35 @@ def calculate_bbox_info(center, scale, orig_shape):
     return info.astype(np.float32)                            # image_utils.py:174-187
 
 
-def crop_normalize(frame_u8: torch.Tensor, boxes: torch.Tensor, bbox_scale: float = 1.0, res: int = 224) -> torch.Tensor:
+def crop_normalize(frame_u8: torch.Tensor, boxes: torch.Tensor, bbox_scale: float = 1.0, res: int = 224,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """frame uint8 [H,W,3] RGB cuda, boxes [N,4] (cx,cy,w,h) cuda float32 or float64 -> [N,3,res,res] fp32: the normalised
-    crop of get_single_image_crop_demo (vibe_image_utils.py:233-266), byte-exact with cv2's fixed-point warpAffine."""
-    assert frame_u8.is_cuda and frame_u8.dtype == torch.uint8 and frame_u8.is_contiguous()
-    assert boxes.is_cuda and boxes.dtype in (torch.float32, torch.float64) and boxes.shape[1:] == (4,)
+    crop of get_single_image_crop_demo (vibe_image_utils.py:233-266), byte-exact with cv2's fixed-point warpAffine.
+    out: a contiguous float32 [N,3,res,res] tensor on the frame's device to write into (made here if not given).
+    A ValueError, before any GPU work: a frame that is not a contiguous uint8 CUDA [H,W,3]; boxes that are not a contiguous
+    float32 / float64 [N,4] tensor on the frame's device with N >= 1; res < 1; an `out` of another form."""
+    if not (torch.is_tensor(frame_u8) and frame_u8.is_cuda and frame_u8.dtype == torch.uint8 and frame_u8.dim() == 3
+            and frame_u8.shape[2] == 3 and frame_u8.is_contiguous()):
+        raise ValueError("crop_normalize: the frame must be a contiguous uint8 CUDA tensor [H,W,3]")
+    if not (torch.is_tensor(boxes) and boxes.is_cuda and boxes.device == frame_u8.device and boxes.dtype in (torch.float32, torch.float64)
+            and boxes.dim() == 2 and boxes.shape[1] == 4 and boxes.shape[0] >= 1 and boxes.is_contiguous()):
+        raise ValueError("crop_normalize: boxes must be a contiguous float32 or float64 [N,4] tensor on the frame's device, N >= 1")
+    if isinstance(res, bool) or not isinstance(res, (int, np.integer)) or res < 1:
+        raise ValueError(f"crop_normalize: res must be an integer >= 1, got {res!r}")
+    res = int(res)
     H, W, _ = frame_u8.shape
     N = boxes.shape[0]
-    out = torch.empty(N, 3, res, res, device=frame_u8.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(N, 3, res, res, device=frame_u8.device, dtype=torch.float32)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.device == frame_u8.device and out.dtype == torch.float32 and out.is_contiguous()
+              and tuple(out.shape) == (N, 3, res, res)):
+        raise ValueError(f"crop_normalize: out must be a contiguous float32 [{N},3,{res},{res}] tensor on the frame's device")
     L = lib()
     fn = L.poco_crop_normalize if boxes.dtype == torch.float32 else L.poco_crop_normalize_f64
     fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
-    check(fn(frame_u8.data_ptr(), H, W, boxes.contiguous().data_ptr(), N, float(bbox_scale), res, out.data_ptr(),
-             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "poco_crop_normalize")
+    with torch.cuda.device(frame_u8.device):
+        check(fn(frame_u8.data_ptr(), H, W, boxes.data_ptr(), N, float(bbox_scale), res, out.data_ptr(),
+                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), "poco_crop_normalize")
     return out
 
 
